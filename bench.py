@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the SVAT hot path: cell-timesteps/s on the SVAT_benchmark grid.
 
-    python bench.py --gpus N --steps K --warmup W [--size NX NY]
+    python bench.py --gpus N --steps K --warmup W [--size NX NY] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` also writes what the timed
+steps computed (see `dump_context`), `--full` adds what the headline does not need: the CPU baseline, the device's clock
+readings and, for the default SVAT line, the `extras` child runs.
 
 One "step" is one model time step (adaptive dt: 24 h / 1 h / 10 min) of every column of the grid:
 the device-side user hooks, the predicate kernels and the fused per-column kernel.  The workload
@@ -27,8 +31,8 @@ region:
     the tau -> taum1 copies, so it moves fewer bytes than that; this figure can exceed the peak and is not a roofline
     fraction.
 
-The `cpu_baseline` entry times the oracle (a C port of the reference's NumPy step, OpenMP over the columns) on a bounded
-sample of the same workload.
+The `cpu_baseline` entry (`--full`) times the oracle (a C port of the reference's NumPy step, OpenMP over the columns) on a
+bounded sample of the same workload.
 """
 import argparse
 import json
@@ -74,6 +78,80 @@ def measured_traffic(key, n_cells):
     if not rec:
         return None, None
     return rec["hbm_bytes_per_launch"], rec
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SEED = 0                # the column sample of a dump larger than that
+
+
+def dump_sample(n, bytes_per_column):
+    """The columns a dump holds: every column where they fit into DUMP_MAX_BYTES (less 1 MB for the small arrays beside them), else a
+    fixed, seeded, sorted sample of as many as fit."""
+    import numpy as np
+
+    k = max(1, (DUMP_MAX_BYTES - (1 << 20)) // (bytes_per_column + 8))
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def write_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array, float64 (float32 stays float32)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32 if np.asarray(a).dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
+def scalars_row(s):
+    """The time-stepping scalars of a Context (RhScalars) as one float64 row, in the structure's field order."""
+    row = []
+    for k, _ in s._fields_:
+        v = getattr(s, k)
+        row += [float(x) for x in v] if hasattr(v, "__len__") else [float(v)]
+    return row
+
+
+def dump_context(out_dir, ctx):
+    """--dump-outputs of the SVAT / oneD / routed paths: what a caller of the timed steps receives -- every plane the context holds
+    (state, fluxes, diagnostics, parameters) over the columns of `dump_sample`, `column_index` (those columns) and `scalars`
+    (the time-stepping scalars after the last step)."""
+    held = [nm for i, (nm, _) in enumerate(ctx.planes) if i < getattr(ctx, "planes_held", len(ctx.planes))]
+    cols = dump_sample(ctx.n, 8 * len(held))
+    arrays = {nm: ctx.download(nm)[cols] for nm in held}
+    arrays.update(column_index=cols, scalars=scalars_row(ctx.get_scalars()))
+    write_outputs(out_dir, arrays)
+
+
+def dump_sas(out_dir, ctx):
+    """--dump-outputs of --model sas: every array the transport context holds but its inputs (the daily fluxes, the SAS parameters) after
+    the last timed day -- age distributions, concentrations, age statistics -- over the columns of `dump_sample`, and `column_index`."""
+    import numpy as np
+
+    from roger_amd._native import DAILY_INPUTS, NativeError
+
+    shapes = {}
+    for nm in ctx.names:
+        if nm in DAILY_INPUTS or nm.startswith("sas_params_"):
+            continue
+        try:
+            shapes[nm] = ctx.shape(nm)
+        except NativeError:   # not held by this context
+            continue
+    cols = dump_sample(ctx.n, 8 * sum(int(np.prod(s[1:])) for s in shapes.values()))
+    arrays = {}
+    for nm, s in shapes.items():
+        if len(s) == 1:
+            arrays[nm] = ctx.download(nm)[cols]
+        else:   # (n, ages): the sampled rows one by one, never the whole array on the host
+            arrays[nm] = np.concatenate([ctx.download_cells(nm, int(c), 1) for c in cols])
+    arrays["column_index"] = cols
+    write_outputs(out_dir, arrays)
 
 
 def prewarm(torch, device, ms):
@@ -209,6 +287,8 @@ def bench_sas(args, torch, dist, rank, local_rank, world, device):
     ctx.enable_timing(False)
     ctx.sync()   # raises if a column asked for an unsupported SAS family
     d18O = ctx.download("C_iso_q_ss")[:4]
+    if args.dump_outputs and rank == 0:
+        dump_sas(args.dump_outputs, ctx)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -280,7 +360,7 @@ def bench_sas(args, torch, dist, rank, local_rank, world, device):
                 "compute": compute,
             },
         }
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N = 1 only
             cells = max(8, min(n, int(args.cpu_cells) // 25))
             days = min(ndays_resident, args.steps + args.warmup, 4)
             v, secs, threads = cpu_baseline_sas(cells, days, args.ages, args.substeps, daily, args.sas_solver)
@@ -345,6 +425,8 @@ def bench_routed(args, torch, dist, rank, local_rank, world, device):
         elapsed = float(t.item())
     if s1.itt - s0.itt != args.steps:   # (the reference's water balance check fails on routed runs: sanity_ok is not asserted)
         raise SystemExit(f"bench: step bookkeeping failed (itt {s0.itt}->{s1.itt})")
+    if args.dump_outputs and rank == 0:
+        dump_context(args.dump_outputs, ctx)
     if rank == 0:
         census = json.load(open(os.path.join(REPO, "roger_amd", "csrc", "rh_step_bytes.json")))   # bytes per column from the ISA (tools/isa_census.py)
         # device-driven: the gathers are folded into the second and third pass (k_routed_bg / k_routed_cg), and every step of the call
@@ -503,6 +585,8 @@ def bench_setup(args, torch, device):
 
     run_days(args.warmup_days)
     elapsed, steps = run_days(args.days)
+    if args.dump_outputs:
+        dump_context(args.dump_outputs, ctx)
     n = nx * ny
     out = {
         "metric": "cell-timesteps/sec on SVAT_benchmark grid",
@@ -690,10 +774,15 @@ def main():
                     help="svat / oned, device stepping: untimed steps in FRONT of the warm-up that bring the model to the end of the forcing's "
                          "first heavy-rain event (step 112 with the default --warmup 5), so that the timed steps of even a 20-step run "
                          "cover all three step classes -- 5 ten-minute, 14 hourly and 1 daily step (SURVEY 8d: per dt-class; VERDICT r2 weak #8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true",
-                    help="one GPU, --model svat at the default size: do not add the `extras` object (SVAT at 3200 x 3125 and the SAS step at 10^5 "
-                         "columns, each from a child run of this script after the headline measurement); for profiling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline (`cpu_baseline`), the device's clock levels before and after the run "
+                         "(`clocks_mhz`) and, one GPU, --model svat at the default size, the `extras` object (SVAT at 3200 x 3125 and the SAS "
+                         "step at 10^5 columns, each from a child run of this script after the headline measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64; at most 64 MB in all, a fixed, seeded "
+                         "sample of the columns where the whole grid would be more; rank 0's slab on several GPUs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (and without `extras`)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the `extras` object; for profiling runs")
     ap.add_argument("--cpu-cells", type=int, default=1000000,
                     help="columns of the CPU baseline sample (svat / oned; sas uses 1/25 of it)")
     ap.add_argument("--stepping", choices=("device", "setup", "script", "hooks", "routines"), default="device",
@@ -819,7 +908,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
-    clocks0 = device_clocks() if rank == 0 else None   # (a child process that takes half a second: BEFORE the warm-up, not between it and the timed region)
+    clocks0 = device_clocks() if rank == 0 and args.full else None   # (a child process that takes half a second: BEFORE the warm-up, not between it and the timed region)
     run(args.spinup + args.warmup)
     s0 = ctx.get_scalars()
     prewarm(torch, device, args.prewarm_ms)
@@ -840,6 +929,8 @@ def main():
         elapsed = float(t.item())
     if s1.sanity_ok != 1 or s1.itt - s0.itt != args.steps:
         raise SystemExit(f"bench: step bookkeeping failed (sanity_ok={s1.sanity_ok}, itt {s0.itt}->{s1.itt})")
+    if args.dump_outputs and rank == 0:
+        dump_context(args.dump_outputs, ctx)
 
     if rank == 0:
         value = world * n_local * args.steps / elapsed
@@ -926,9 +1017,10 @@ def main():
                 "full_store_launch": full,   # the call's last step (stores every plane), or null when no step ran with sparse stores
                 "outside_kernel_us_per_step": (elapsed - kernel_ms / 1e3) / args.steps * 1e6,
             },
-            "clocks_mhz": {"before": clocks0, "after": device_clocks()},
         }
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N = 1 only
+        if args.full:
+            out["clocks_mhz"] = {"before": clocks0, "after": device_clocks()}
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N = 1 only
             cpu_steps = min(args.steps + args.warmup, 60)
             v, secs, threads = cpu_baseline(args.cpu_cells, cpu_steps, forcing)
             out["cpu_baseline"] = {
@@ -941,7 +1033,7 @@ def main():
             }
         plain = (world == 1 and args.model == "svat" and tuple(args.size) == (1000, 1000) and args.params == "uniform" and not args.station_weights
                  and not os.environ.get("RH_BENCH_FORCE_DIST") and not os.environ.get("RH_BENCH_FORCE_PHASED"))
-        if plain and not args.no_extras and not args.no_cpu_baseline:   # (--no-cpu-baseline marks the profiling / A-B runs of tools/*.sh)
+        if plain and args.full and not args.no_extras and not args.no_cpu_baseline:   # (--no-cpu-baseline marks the profiling / A-B runs of tools/*.sh)
             ctx.close()   # (the headline's arena is not needed any more)
             out["extras"] = bench_extras(torch, device)
         print(json.dumps(out))

@@ -46,8 +46,8 @@ if [ "$what" = all ] || [ "$what" = svat ]; then
   svat_pairs svat 80x53 4240
   unset RH_PMC_MODEL RH_PMC_SIZE
   cp $out/traffic.json profiles/   # the bench lines take roofline.traffic from the records just written
-  bench svat_1e6 --steps 200 --warmup 10
-  bench svat_1e6_default
+  bench svat_1e6 --steps 200 --warmup 10 --full
+  bench svat_1e6_default --full
   bench svat_1e6_dt_classes --steps 600 --warmup 10 --no-cpu-baseline
   bench svat_1e6_hetero --params hetero --steps 200 --warmup 10 --no-cpu-baseline
   bench svat_1e7 --size 3200 3125 --steps 60 --warmup 5 --no-cpu-baseline
@@ -57,7 +57,7 @@ if [ "$what" = all ] || [ "$what" = svat ]; then
   bench svat_80x53_station_weights --size 80 53 --params hetero --station-weights --steps 2000 --warmup 50 --no-cpu-baseline
   bench svat_1e6_station_weights --station-weights --steps 200 --warmup 10 --no-cpu-baseline
   RH_BENCH_FORCE_DIST=1 bench svat_1e6_rccl_one_rank --steps 200 --warmup 10 --no-cpu-baseline
-  bench svat_1e6_driver_command --gpus 1 --steps 20 --warmup 5
+  bench svat_1e6_driver_command --gpus 1 --steps 20 --warmup 5 --full
   RH_NO_SPARSE_STORES=1 bench svat_1e6_full_stores --steps 200 --warmup 10 --no-cpu-baseline
   # the benchmark as a RogerSetup script calling plain run(): stock hooks (on the device), a hook of the script's own in front of the physics (one native call per step) and the three-call step
   for st in setup script hooks routines; do
@@ -115,7 +115,7 @@ if [ "$what" = all ] || [ "$what" = sas ]; then
   valu rk4_ages1000_sub6 100000 2 6 1 RK4
   # the bench lines take roofline.traffic / roofline.compute from the records just written
   cp $out/traffic.json $out/sas_valu.json profiles/
-  bench sas_1e6 --model sas --steps 8 --warmup 2
+  bench sas_1e6 --model sas --steps 8 --warmup 2 --full
   # 10^5 columns: the size the counters below are collected at (bench.py fills roofline.traffic / roofline.compute from them on a later run)
   bench sas_1e5 --model sas --size 1000 100 --steps 20 --warmup 2 --no-cpu-baseline
   bench sas_1e5_euler --model sas --size 1000 100 --steps 10 --warmup 2 --sas-solver Euler --no-cpu-baseline
