@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 4   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4) */
+#define RH_ABI_VERSION 5   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -182,10 +182,12 @@ int rh_subsurface_runoff(rh_ctx *ctx);  /* calculate_subsurface_runoff (SVAT bra
  *   rh_surface_routing    = calculate_surface_runoff, core/surface_runoff.py:240-250 -> calc_surface_runoff_routing_1D :14-227
  *   rh_subsurface_routing = the routing part of calculate_subsurface_runoff, core/subsurface_runoff.py:1468-1469 ->
  *                           calc_subsurface_runoff_routing_1D :1158-1437 (call it after rh_subsurface_runoff)
- * Each is rh_route_out (per column: the outflow), the exchange of the edge columns with the x-neighbours over the context's RCCL
- * communicator when it has more than one rank (rh_comm_init / rh_set_comm; the reference itself never exchanges them: with MPI its
- * routed water is lost at the process boundaries), and rh_route_in (the gather from the eight neighbours + per column: the inflow).
- * The pieces are exported for drivers that exchange the halos themselves: rh_route_get_edges / rh_route_get_static_edges return the
+ * Each is rh_route_out (per column: the outflow), the exchange of the border cells with the up to eight neighbour ranks of the
+ * communicator's process grid (rh_comm_set_grid: the west / east columns, south / north rows and corner cells) over the context's
+ * RCCL communicator when it has more than one rank (rh_comm_init / rh_set_comm; the reference itself never exchanges them: with MPI
+ * its routed water is lost at the process boundaries), and rh_route_in (the gather from the eight neighbours + per column: the
+ * inflow).  The pieces are exported for drivers that exchange the west / east halos themselves (a grid split along x only; the
+ * y-neighbours' rows and the corners travel over RCCL only): rh_route_get_edges / rh_route_get_static_edges return the
  * rank's own edge columns x = 0 ("lo") and x = nx - 1 ("hi") (ny values each: q_out of the step; flow direction and mask, once),
  * rh_route_set_halo hands in the neighbour's column for side 0 (x = -1) or 1 (x = nx); q may be NULL when only the static part is
  * set, flow_dir / mask may be NULL afterwards.  `which`: 0 surface, 1 subsurface. */
@@ -306,7 +308,7 @@ int rh_predicates_expand(rh_ctx *ctx, int word, int32_t *dev_dst64);
 int rh_predicates_compress(rh_ctx *ctx, int word, const int32_t *dev_src64);
 
 /* ---- multi-GPU stepping without the host in the loop (SURVEY section 8b "rh_set_comm", 8e) -----------------------------------
- * One process per GPU, the grid split along x (roger/distributed.py:121-187); the only exchange of the SVAT / oneD step is the
+ * One process per GPU, the grid split into px x py blocks (roger/distributed.py:121-187); the only exchange of the SVAT / oneD step is the
  * OR of the ranks' summary words -- what the reference does per step by gathering 18 fields to rank 0, deciding dt there and
  * scattering them back (roger/core/adaptive_time_stepping_dist_safe.py:6-26).  rh_run_steps_dist enqueues, per step, on the
  * context's stream: ncclAllReduce(MAX, 64 x int32: the summary word the previous fused kernel's tail spread out) -> control kernel
@@ -315,10 +317,16 @@ int rh_predicates_compress(rh_ctx *ctx, int word, const int32_t *dev_src64);
  *   rh_comm_unique_id   rank 0 creates the 128-byte id (ncclGetUniqueId); the caller hands it to the other ranks
  *   rh_comm_init        every rank: ncclCommInitRank on the context's device (collective); owned by the context
  *   rh_set_comm         or: borrow a communicator the caller owns (an ncclComm_t); NULL detaches
+ *   rh_comm_set_grid    the process grid (px, py) of the communicator, ranks x-fastest as distributed.proc_rank_to_index: rank
+ *                       r holds block (r % px, r / px).  Default (nranks, 1), set again by rh_comm_init / rh_set_comm.  Only the
+ *                       routing's exchange depends on it: the neighbours west / east are x - 1 / x + 1, south / north y - 1 / y + 1
+ *                       (distributed.get_process_neighbors), and the corners.  RH_ERR_ARG unless px, py >= 1 and px * py = nranks;
+ *                       RH_ERR_STATE without a communicator.  The neighbours' flow direction and mask are exchanged again.
  * With one rank the all-reduce is a copy: rh_run_steps_dist then equals rh_run_steps bit for bit (tests/test_hip_comm.py). */
 int rh_comm_unique_id(void *id128);
 int rh_comm_init(rh_ctx *ctx, const void *id128, int nranks, int rank);
 int rh_set_comm(rh_ctx *ctx, void *nccl_comm);
+int rh_comm_set_grid(rh_ctx *ctx, int px, int py);
 /* ncclCommCount / ncclCommUserRank of the communicator the context holds, asked of RCCL itself (1 / 0 without a communicator). */
 int rh_comm_info(rh_ctx *ctx, int *nranks, int *rank);
 int rh_run_steps_dist(rh_ctx *ctx, int64_t nsteps);

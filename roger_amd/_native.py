@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 4   # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 5   # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -136,6 +136,7 @@ def load():
     lib.rh_comm_init.argtypes = [vp, vp, i32, i32]
     lib.rh_set_comm.argtypes = [vp, vp]
     lib.rh_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.rh_comm_set_grid.argtypes = [vp, i32, i32]
     lib.rh_run_steps_dist.argtypes = [vp, i64]
     lib.rh_step_routed.argtypes = [vp, i32]
     lib.rh_planes_held.argtypes = [vp]
@@ -402,7 +403,7 @@ DECLARED_SYMBOLS = (
     "rh_svat_step", "rh_svat_step_scalars", "rh_param_stats", "rh_predicate_words", "rh_timing_summary", "rh_timing_detail", "rh_enable_timing", "rh_set_forcing_series",
     "rh_hooks_phase", "rh_run_steps", "rh_predicates_expand", "rh_predicates_compress", "rh_step_core", "rh_calibrate_copy", "rh_debug_swap_arenas", "rh_selftest_pow", "rh_selftest_window_sum", "rh_set_lut_mlms", "rh_params_lateral",
     "rh_step_summary", "rh_step_finish", "rh_diag_set_interval", "rh_diag_slot_times", "rh_placement_report", "rh_step_summary_expand", "rh_step_finish_compress", "rh_diag_configure", "rh_diag_download", "rh_diag_device_ptr", "rh_diag_steps",
-    "rh_set_forcing_weights", "rh_adaptive_dt_finish", "rh_diag_upload", "rh_diag_set_slot_state", "rh_set_forcing_stations", "rh_step_mode", "rh_comm_unique_id", "rh_comm_init", "rh_set_comm", "rh_comm_info", "rh_plane_is_pure_output", "rh_sparse_steps", "rh_set_time_limit", "rh_run_steps_dist",
+    "rh_set_forcing_weights", "rh_adaptive_dt_finish", "rh_diag_upload", "rh_diag_set_slot_state", "rh_set_forcing_stations", "rh_step_mode", "rh_comm_unique_id", "rh_comm_init", "rh_set_comm", "rh_comm_info", "rh_comm_set_grid", "rh_plane_is_pure_output", "rh_sparse_steps", "rh_set_time_limit", "rh_run_steps_dist",
     "rh_surface_routing", "rh_subsurface_routing", "rh_step_routed", "rh_planes_held", "rh_route_out", "rh_route_in", "rh_route_get_edges", "rh_route_get_static_edges", "rh_route_set_halo",
 )
 
@@ -578,7 +579,7 @@ class Context:
         self._check(self._lib.rh_route_in(self._h, int(which)), "rh_route_in")
 
     def route_edges(self, which):
-        """(lo, hi): q_out of the rank's edge columns x = 0 and x = nx - 1 (what the x-neighbours' halos take)."""
+        """(lo, hi): q_out of the rank's edge columns x = 0 and x = nx - 1 (the west / east parts of what the neighbours' halos take)."""
         lo, hi = np.empty(self.ny), np.empty(self.ny)
         self._check(self._lib.rh_route_get_edges(self._h, int(which), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)),
                     "rh_route_get_edges")
@@ -715,6 +716,11 @@ class Context:
         n, r = C.c_int(), C.c_int()
         self._check(self._lib.rh_comm_info(self._h, C.byref(n), C.byref(r)), "rh_comm_info")
         return n.value, r.value
+
+    def comm_set_grid(self, px, py):
+        """The process grid (px, py) of the communicator, ranks x-fastest (distributed.proc_rank_to_index); (nranks, 1) until called.
+        The routing exchanges its halo with the neighbours in x and y (and the corners) of this grid."""
+        self._check(self._lib.rh_comm_set_grid(self._h, int(px), int(py)), "rh_comm_set_grid")
 
     def run_steps_dist(self, nsteps):
         self._check(self._lib.rh_run_steps_dist(self._h, int(nsteps)), "rh_run_steps_dist")

@@ -229,14 +229,17 @@ struct rh_ctx {
     int *exch_buf;
     bool exch_valid;      // exch_buf[0..63] holds the summary word of the columns as they are now (written by the last fused kernel's tail)
     int comm_nranks, comm_rank;
+    int grid_px, grid_py; // process grid of the communicator, ranks x-fastest (rh_comm_set_grid; default (nranks, 1))
     int planes_held;      // planes the arena has slots for: all of them for a routing context, otherwise all but the routing's (the last
                           // ones of rh_fields.def) -- the tile stride of the non-routing contexts stays what it was before the routing was
                           // added (at 10^6 columns the fused step ran 13 % slower with nine more slots per tile: 2.21 instead of 2.14 GB,
                           // A/B on one box)
-    // routing (settings.enable_routing_1D): edge columns of this rank and halo columns of its x-neighbours, ny values each
-    double *route_q;      // [0, 2 ny): own edges lo / hi of q_out; [2 ny, 4 ny): halo lo / hi
-    int *route_i;         // flow direction and mask: [0, 4 ny) own edges (fd lo, fd hi, mk lo, mk hi), [4 ny, 8 ny) halos (same order)
+    // routing (settings.enable_routing_1D): the rank's own border and the one-cell halo frame of its neighbours, both in the frame
+    // layout of F = 2 ny + 2 nx + 4 values (route_frame_parts: west / east columns, south / north rows, four corners)
+    double *route_q;      // q_out: [0, F) own border, [F, 2 F) halo frame
+    int *route_i;         // [0, F) own flow direction, [F, 2 F) own mask, [2 F, 3 F) halo flow direction, [3 F, 4 F) halo mask
     bool route_halo[2];   // a halo column is present on that side (rh_route_set_halo or the RCCL exchange)
+    bool route_frame;     // the halo frame holds a neighbour's data; the gathers read it (a part without a neighbour holds zeros)
     bool route_static_done;   // the neighbours' flow direction and mask have been exchanged over RCCL
     std::string err;
 };
@@ -2293,13 +2296,22 @@ __global__ __launch_bounds__(RH_BLOCK) void k_params_surface_if_monthly(Arena a,
 // code_d, q_out[s], 0) * maskCatch[s] with s = c - (dx_d, dy_d) an interior cell (surface_runoff.py:137-204; the reference scatters
 // into shifted slices, a cell next to the edge of the grid receives nothing from outside).  The reference's direction order
 // N, NE, E, SE, S, SW, W, NW and numpy's sum of 8 contiguous values, ((a0+a1)+(a2+a3)) + ((a4+a5)+(a6+a7)).
-// Several ranks (decomposition along x, the slow index): the neighbour ranks' edge columns -- q_out per step, flow direction and mask
-// once -- arrive in halo[0] (the column x = -1) and halo[1] (x = nx); null where the rank has no neighbour.
+// Several ranks (the grid split along x and y, num_proc = (px, py)): the neighbour ranks' border cells -- q_out per step, flow
+// direction and mask once -- arrive in a one-cell frame around the block.  Frame layout (F = 2 ny + 2 nx + 4 values): [0, ny) the
+// west column x = -1, [ny, 2 ny) the east column x = nx, [2 ny, 2 ny + nx) the south row y = -1, [2 ny + nx, 2 ny + 2 nx) the north
+// row y = ny, then the corners (-1, -1), (nx, -1), (-1, ny), (nx, ny).  A part without a neighbour holds zeros: the +0.0 contribution
+// of a source outside the grid.  Null pointers: no neighbour at all (one domain), nothing outside the block is read.
 struct RouteHalo {
-    const double *q[2];
-    const int *flow_dir[2];
-    const int *mask[2];
+    const double *q;
+    const int *flow_dir;
+    const int *mask;
 };
+// the frame index of a source cell outside the block (sx in [-1, nx], sy in [-1, ny], not both inside)
+RH_DEV int route_frame_index(int nx, int ny, int sx, int sy, bool x_in, bool y_in) {
+    if (y_in) return (sx < 0 ? 0 : ny) + sy;
+    if (x_in) return 2 * ny + (sy < 0 ? 0 : nx) + sx;
+    return 2 * ny + 2 * nx + (sx < 0 ? 0 : 1) + (sy < 0 ? 0 : 2);
+}
 RH_DEV double route_gather_value(const Arena &a, int nx, int ny, int src_plane, int64_t i, const RouteHalo &H) {
     const int ix = (int)(i / ny), iy = (int)(i % ny);
     const int CODE[8] = {64, 128, 1, 2, 4, 8, 16, 32};
@@ -2309,22 +2321,19 @@ RH_DEV double route_gather_value(const Arena &a, int nx, int ny, int src_plane, 
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
         const int sx = ix - DX[d], sy = iy - DY[d];
+        const bool x_in = sx >= 0 && sx < nx, y_in = sy >= 0 && sy < ny;
         double q = 0.0;
         int fd = 0, mk = 0;
-        if (sy >= 0 && sy < ny) {
-            if (sx >= 0 && sx < nx) {
-                const int64_t s = (int64_t)sx * ny + sy;
-                q = *rh_cell_any<const double>(a, src_plane, s);
-                fd = *rh_cell_any<const int>(a, RH_P_flow_dir_topo, s);
-                mk = *rh_cell_any<const int>(a, RH_P_maskCatch, s);
-            } else {
-                const int side = sx < 0 ? 0 : 1;
-                if (H.q[side]) {
-                    q = H.q[side][sy];
-                    fd = H.flow_dir[side][sy];
-                    mk = H.mask[side][sy];
-                }
-            }
+        if (x_in && y_in) {
+            const int64_t s = (int64_t)sx * ny + sy;
+            q = *rh_cell_any<const double>(a, src_plane, s);
+            fd = *rh_cell_any<const int>(a, RH_P_flow_dir_topo, s);
+            mk = *rh_cell_any<const int>(a, RH_P_maskCatch, s);
+        } else if (H.q) {
+            const int f = route_frame_index(nx, ny, sx, sy, x_in, y_in);
+            q = H.q[f];
+            fd = H.flow_dir[f];
+            mk = H.mask[f];
         }
         v[d] = (fd == CODE[d] ? q : 0.0) * (double)mk;
     }
@@ -2336,7 +2345,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_route_gather(Arena a, int nx, int 
     *rh_cell_any<double>(a, dst_plane, i) = route_gather_value(a, nx, ny, src_plane, i, H);
 }
 // Device-driven routed stepping: the second and third pass with the gather in front of them folded in -- a column reads its eight
-// neighbours' q_out (own columns from the arena, the x-neighbour ranks' edge columns from the halo buffers) instead of a q_in plane
+// neighbours' q_out (own columns from the arena, the neighbour ranks' border cells from the halo frame) instead of a q_in plane
 // that a kernel of its own wrote: 4 launches per step instead of 6 (k_ctrl, k_routed_a2, k_routed_bg, k_routed_cg[_after]).
 template <int P, int WHICH, typename T>
 RH_DEV void ld_or_gather(const Arena &a, int64_t i, T &dst, int nx, int ny, const RouteHalo &H) {
@@ -2386,13 +2395,26 @@ __global__ __launch_bounds__(RH_BLOCK, RH_STEP_WAVES) void k_routed_cg(Arena a, 
     }
     if (bad) atomicOr(&D->words[2], 1ull);
 }
-// the rank's own edge columns (x = 0 and x = nx - 1) of a plane into two contiguous rows of ny (what the neighbours' halos take)
+// the rank's own border of one or two planes in the frame layout (what the neighbours' frames take): the columns x = 0 / nx - 1, the
+// rows y = 0 / ny - 1 (strided in the arena), the corner cells (0, 0), (nx - 1, 0), (0, ny - 1), (nx - 1, ny - 1); only the parts set
+// in `parts` (bit p: part p of route_frame_parts).  out1 may be null.
 template <typename T>
-__global__ void k_route_edges(Arena a, int nx, int ny, int plane, T *lo, T *hi) {
-    const int iy = blockIdx.x * blockDim.x + threadIdx.x;
-    if (iy >= ny) return;
-    lo[iy] = *rh_cell_any<const T>(a, plane, iy);
-    hi[iy] = *rh_cell_any<const T>(a, plane, (int64_t)(nx - 1) * ny + iy);
+__global__ void k_route_pack(Arena a, int nx, int ny, unsigned parts, int plane0, T *out0, int plane1, T *out1) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    int part, x, y;
+    if (t < ny) part = 0, x = 0, y = t;
+    else if (t < 2 * ny) part = 1, x = nx - 1, y = t - ny;
+    else if (t < 2 * ny + nx) part = 2, x = t - 2 * ny, y = 0;
+    else if (t < 2 * ny + 2 * nx) part = 3, x = t - 2 * ny - nx, y = ny - 1;
+    else if (t < 2 * ny + 2 * nx + 4) {
+        const int k = t - 2 * ny - 2 * nx;
+        part = 4 + k, x = (k & 1) ? nx - 1 : 0, y = (k & 2) ? ny - 1 : 0;
+    } else
+        return;
+    if (!((parts >> part) & 1u)) return;
+    const int64_t s = (int64_t)x * ny + y;
+    out0[t] = *rh_cell_any<const T>(a, plane0, s);
+    if (out1) out1[t] = *rh_cell_any<const T>(a, plane1, s);
 }
 
 // max over the columns of slope_per (the trip count of the reference's look-up loop, soil.py:621)
@@ -2656,6 +2678,7 @@ static void release_comm(rh_ctx *ctx) {
     ctx->own_comm = false;
     ctx->comm_nranks = 1;
     ctx->comm_rank = 0;
+    ctx->grid_px = ctx->grid_py = 1;
     ctx->route_static_done = false;
 }
 #define NCCLCHK(ctx, call)                                                                                                   \
@@ -2774,9 +2797,11 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     ctx->exch_valid = false;
     ctx->comm_nranks = 1;
     ctx->comm_rank = 0;
+    ctx->grid_px = ctx->grid_py = 1;
     ctx->route_q = nullptr;
     ctx->route_i = nullptr;
     ctx->route_halo[0] = ctx->route_halo[1] = false;
+    ctx->route_frame = false;
     ctx->route_static_done = false;
     if (cfg->enable_routing_1D && !cfg->enable_lateral_flow) {
         delete ctx;
@@ -3256,13 +3281,36 @@ int rh_after_timestep(rh_ctx *ctx) {
 }
 
 // ---- settings.enable_routing_1D -------------------------------------------------------------------------------------------------
+static size_t route_frame_size(const rh_ctx *ctx) { return 2 * (size_t)ctx->cfg.ny + 2 * (size_t)ctx->cfg.nx + 4; }
+// the eight parts of the frame layout (k_route_pack, route_gather_value): west, east, south, north, then the corners south-west,
+// south-east, north-west, north-east -- offset and length of each, and where its neighbour sits in the process grid
+static const int ROUTE_PART_DX[8] = {-1, 1, 0, 0, -1, 1, -1, 1};
+static const int ROUTE_PART_DY[8] = {0, 0, -1, 1, -1, -1, 1, 1};
+static void route_frame_parts(const rh_ctx *ctx, size_t off[8], size_t len[8]) {
+    const size_t nx = (size_t)ctx->cfg.nx, ny = (size_t)ctx->cfg.ny;
+    const size_t o[8] = {0, ny, 2 * ny, 2 * ny + nx, 2 * ny + 2 * nx, 2 * ny + 2 * nx + 1, 2 * ny + 2 * nx + 2, 2 * ny + 2 * nx + 3};
+    const size_t l[8] = {ny, ny, nx, nx, 1, 1, 1, 1};
+    for (int p = 0; p < 8; ++p) off[p] = o[p], len[p] = l[p];
+}
+// the neighbour rank of every part (-1: none, the edge of the grid) from the communicator's process grid (ranks x-fastest,
+// distributed.get_process_neighbors); the bits of the parts that have one
+static unsigned route_neighbours(const rh_ctx *ctx, int peer[8]) {
+    const int px = ctx->grid_px, py = ctx->grid_py, ix = ctx->comm_rank % px, iy = ctx->comm_rank / px;
+    unsigned parts = 0;
+    for (int p = 0; p < 8; ++p) {
+        const int jx = ix + ROUTE_PART_DX[p], jy = iy + ROUTE_PART_DY[p];
+        peer[p] = jx >= 0 && jx < px && jy >= 0 && jy < py ? jx + jy * px : -1;
+        if (peer[p] >= 0) parts |= 1u << p;
+    }
+    return parts;
+}
 static int route_buffers(rh_ctx *ctx) {
     if (ctx->route_q) return RH_OK;
-    const size_t ny = (size_t)ctx->cfg.ny;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->route_q, 4 * ny * sizeof(double)));
-    HIPCHK(ctx, hipMalloc((void **)&ctx->route_i, 8 * ny * sizeof(int)));
-    HIPCHK(ctx, hipMemsetAsync(ctx->route_q, 0, 4 * ny * sizeof(double), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->route_i, 0, 8 * ny * sizeof(int), ctx->stream));
+    const size_t F = route_frame_size(ctx);
+    HIPCHK(ctx, hipMalloc((void **)&ctx->route_q, 2 * F * sizeof(double)));
+    HIPCHK(ctx, hipMalloc((void **)&ctx->route_i, 4 * F * sizeof(int)));
+    HIPCHK(ctx, hipMemsetAsync(ctx->route_q, 0, 2 * F * sizeof(double), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->route_i, 0, 4 * F * sizeof(int), ctx->stream));
     return RH_OK;
 }
 static int route_check(rh_ctx *ctx, int which, const char *who) {
@@ -3271,14 +3319,17 @@ static int route_check(rh_ctx *ctx, int which, const char *who) {
     if (which != 0 && which != 1) return fail(ctx, RH_ERR_ARG, std::string(who) + ": which must be 0 (surface) or 1 (subsurface)");
     return route_buffers(ctx);
 }
-static void route_pack_edges(rh_ctx *ctx, int plane, bool ints, int slot) {
+// the own border: q_out of the routing (which >= 0) into route_q, or flow direction and mask into route_i -- one launch
+static void route_pack(rh_ctx *ctx, int which, unsigned parts) {
     const int ny = (int)ctx->cfg.ny, nx = (int)ctx->cfg.nx;
-    const dim3 grid((ny + 255) / 256), block(256);
-    if (ints)
-        hipLaunchKernelGGL(k_route_edges<int>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, plane, ctx->route_i + (size_t)slot * ny,
-                           ctx->route_i + (size_t)(slot + 1) * ny);
+    const size_t F = route_frame_size(ctx);
+    const dim3 grid((unsigned)((F + 255) / 256)), block(256);
+    if (which < 0)
+        hipLaunchKernelGGL(k_route_pack<int>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, parts, (int)RH_P_flow_dir_topo, ctx->route_i,
+                           (int)RH_P_maskCatch, ctx->route_i + F);
     else
-        hipLaunchKernelGGL(k_route_edges<double>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, plane, ctx->route_q, ctx->route_q + ny);
+        hipLaunchKernelGGL(k_route_pack<double>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, parts,
+                           which == 0 ? (int)RH_P_q_sur_out : (int)RH_P_q_sub_out, ctx->route_q, 0, (double *)nullptr);
 }
 int rh_route_out(rh_ctx *ctx, int which) {
     int rc = route_check(ctx, which, "rh_route_out");
@@ -3288,12 +3339,13 @@ int rh_route_out(rh_ctx *ctx, int which) {
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
+// the west / east parts of the frame layout: [0, ny) and [ny, 2 ny)
 int rh_route_get_edges(rh_ctx *ctx, int which, double *q_lo, double *q_hi) {
     int rc = route_check(ctx, which, "rh_route_get_edges");
     if (rc) return rc;
     if (!q_lo || !q_hi) return fail(ctx, RH_ERR_ARG, "rh_route_get_edges: null pointer");
     const size_t ny = (size_t)ctx->cfg.ny;
-    route_pack_edges(ctx, which == 0 ? RH_P_q_sur_out : RH_P_q_sub_out, false, 0);
+    route_pack(ctx, which, 3u);
     CHECK_LAUNCH(ctx);
     HIPCHK(ctx, hipMemcpyAsync(q_lo, ctx->route_q, ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(q_hi, ctx->route_q + ny, ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -3304,12 +3356,12 @@ int rh_route_get_static_edges(rh_ctx *ctx, int32_t *fd_lo, int32_t *fd_hi, int32
     int rc = route_check(ctx, 0, "rh_route_get_static_edges");
     if (rc) return rc;
     if (!fd_lo || !fd_hi || !mk_lo || !mk_hi) return fail(ctx, RH_ERR_ARG, "rh_route_get_static_edges: null pointer");
-    const size_t ny = (size_t)ctx->cfg.ny;
-    route_pack_edges(ctx, RH_P_flow_dir_topo, true, 0);
-    route_pack_edges(ctx, RH_P_maskCatch, true, 2);
+    const size_t ny = (size_t)ctx->cfg.ny, F = route_frame_size(ctx);
+    route_pack(ctx, -1, 3u);
     CHECK_LAUNCH(ctx);
     int32_t *dst[4] = {fd_lo, fd_hi, mk_lo, mk_hi};
-    for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(dst[k], ctx->route_i + k * ny, ny * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    const size_t src[4] = {0, ny, F, F + ny};
+    for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(dst[k], ctx->route_i + src[k], ny * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
@@ -3317,29 +3369,24 @@ int rh_route_set_halo(rh_ctx *ctx, int side, const double *q, const int32_t *flo
     int rc = route_check(ctx, 0, "rh_route_set_halo");
     if (rc) return rc;
     if (side != 0 && side != 1) return fail(ctx, RH_ERR_ARG, "rh_route_set_halo: side must be 0 (x = -1) or 1 (x = nx)");
-    const size_t ny = (size_t)ctx->cfg.ny;
+    const size_t ny = (size_t)ctx->cfg.ny, F = route_frame_size(ctx);
     if (flow_dir && mask) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->route_i + (4 + side) * ny, flow_dir, ny * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->route_i + (6 + side) * ny, mask, ny * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->route_i + 2 * F + side * ny, flow_dir, ny * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->route_i + 3 * F + side * ny, mask, ny * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         ctx->route_halo[side] = true;
+        ctx->route_frame = true;
     }
     if (q) {
         if (!ctx->route_halo[side]) return fail(ctx, RH_ERR_STATE, "rh_route_set_halo: the side's flow direction and mask must be set first");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->route_q + (2 + side) * ny, q, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->route_q + F + side * ny, q, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
 static RouteHalo route_halo_of(rh_ctx *ctx) {
-    const size_t ny = (size_t)ctx->cfg.ny;
-    RouteHalo H;
-    for (int side = 0; side < 2; ++side) {
-        const bool have = ctx->route_halo[side];
-        H.q[side] = have ? ctx->route_q + (2 + side) * ny : nullptr;
-        H.flow_dir[side] = have ? ctx->route_i + (4 + side) * ny : nullptr;
-        H.mask[side] = have ? ctx->route_i + (6 + side) * ny : nullptr;
-    }
-    return H;
+    if (!ctx->route_frame) return RouteHalo{nullptr, nullptr, nullptr};
+    const size_t F = route_frame_size(ctx);
+    return RouteHalo{ctx->route_q + F, ctx->route_i + 2 * F, ctx->route_i + 3 * F};
 }
 static int rh_route_gather_only(rh_ctx *ctx, int which) {
     int rc = route_check(ctx, which, "rh_route_in");
@@ -3359,43 +3406,46 @@ int rh_route_in(rh_ctx *ctx, int which) {
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
-// the neighbours' edge columns over RCCL (decomposition along x: rank r - 1 holds x < 0, rank r + 1 holds x >= nx)
+// the neighbours' border cells over RCCL: one group per exchange, in it a send of the own part and a receive into the frame part per
+// present neighbour (west, east, south, north, the corners; counts ny, nx, 1) -- on a (N, 1) grid the west and east columns only.
+// Flow direction and mask go once (again after rh_comm_set_grid), q_out of the routing every time.
 static int route_exchange(rh_ctx *ctx, int which) {
     RcclApi *api = rccl_api();
     if (!api->ok) return fail(ctx, RH_ERR_STATE, "routing: " + api->why);
-    const size_t ny = (size_t)ctx->cfg.ny;
-    const int r = ctx->comm_rank, N = ctx->comm_nranks;
+    if (int rc = route_buffers(ctx)) return rc;   // (routed_core exchanges before its first gather allocates them)
+    const size_t F = route_frame_size(ctx);
+    size_t off[8], len[8];
+    int peer[8];
+    route_frame_parts(ctx, off, len);
+    const unsigned parts = route_neighbours(ctx, peer);
     if (!ctx->route_static_done) {
-        route_pack_edges(ctx, RH_P_flow_dir_topo, true, 0);
-        route_pack_edges(ctx, RH_P_maskCatch, true, 2);
+        // a part without a neighbour holds zeros (also what an earlier grid left there)
+        HIPCHK(ctx, hipMemsetAsync(ctx->route_q + F, 0, F * sizeof(double), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->route_i + 2 * F, 0, 2 * F * sizeof(int), ctx->stream));
+        route_pack(ctx, -1, parts);
         CHECK_LAUNCH(ctx);
         NCCLCHK(ctx, api->GroupStart());
         for (int k = 0; k < 2; ++k) {   // k = 0: flow direction, 1: mask
-            int *own = ctx->route_i + (size_t)(2 * k) * ny, *halo = ctx->route_i + (size_t)(4 + 2 * k) * ny;
-            if (r > 0) {
-                NCCLCHK(ctx, api->Send(own, ny, ncclInt32, r - 1, ctx->comm, ctx->stream));
-                NCCLCHK(ctx, api->Recv(halo, ny, ncclInt32, r - 1, ctx->comm, ctx->stream));
-            }
-            if (r < N - 1) {
-                NCCLCHK(ctx, api->Send(own + ny, ny, ncclInt32, r + 1, ctx->comm, ctx->stream));
-                NCCLCHK(ctx, api->Recv(halo + ny, ny, ncclInt32, r + 1, ctx->comm, ctx->stream));
+            int *own = ctx->route_i + (size_t)k * F, *halo = ctx->route_i + (size_t)(2 + k) * F;
+            for (int p = 0; p < 8; ++p) {
+                if (peer[p] < 0) continue;
+                NCCLCHK(ctx, api->Send(own + off[p], len[p], ncclInt32, peer[p], ctx->comm, ctx->stream));
+                NCCLCHK(ctx, api->Recv(halo + off[p], len[p], ncclInt32, peer[p], ctx->comm, ctx->stream));
             }
         }
         NCCLCHK(ctx, api->GroupEnd());
-        ctx->route_halo[0] = r > 0;
-        ctx->route_halo[1] = r < N - 1;
+        ctx->route_halo[0] = peer[0] >= 0;
+        ctx->route_halo[1] = peer[1] >= 0;
+        ctx->route_frame = parts != 0;
         ctx->route_static_done = true;
     }
-    route_pack_edges(ctx, which == 0 ? RH_P_q_sur_out : RH_P_q_sub_out, false, 0);
+    route_pack(ctx, which, parts);
     CHECK_LAUNCH(ctx);
     NCCLCHK(ctx, api->GroupStart());
-    if (r > 0) {
-        NCCLCHK(ctx, api->Send(ctx->route_q, ny, ncclDouble, r - 1, ctx->comm, ctx->stream));
-        NCCLCHK(ctx, api->Recv(ctx->route_q + 2 * ny, ny, ncclDouble, r - 1, ctx->comm, ctx->stream));
-    }
-    if (r < N - 1) {
-        NCCLCHK(ctx, api->Send(ctx->route_q + ny, ny, ncclDouble, r + 1, ctx->comm, ctx->stream));
-        NCCLCHK(ctx, api->Recv(ctx->route_q + 3 * ny, ny, ncclDouble, r + 1, ctx->comm, ctx->stream));
+    for (int p = 0; p < 8; ++p) {
+        if (peer[p] < 0) continue;
+        NCCLCHK(ctx, api->Send(ctx->route_q + off[p], len[p], ncclDouble, peer[p], ctx->comm, ctx->stream));
+        NCCLCHK(ctx, api->Recv(ctx->route_q + F + off[p], len[p], ncclDouble, peer[p], ctx->comm, ctx->stream));
     }
     NCCLCHK(ctx, api->GroupEnd());
     return RH_OK;
@@ -3796,7 +3846,7 @@ int rh_hooks_phase(rh_ctx *ctx) {
 // coupled twice (after the infiltration and after the lateral flow), so the step is eleven per-column passes with two gathers in
 // between instead of the fused kernel.  monthly: 1 / 0 = the caller's set_parameters decision, -1 = the device's (after the
 // device-side set_forcing hook, rh_run_steps).  Several ranks: the two predicate words of the adaptive time stepping are all-reduced
-// over the context's communicator (64 int32 each, as rh_run_steps_dist's summary word), the edge columns go to the x-neighbours.
+// over the context's communicator (64 int32 each, as rh_run_steps_dist's summary word), the border cells go to the neighbours.
 static int allreduce_word(rh_ctx *ctx, int word) {
     RcclApi *api = rccl_api();
     if (!api->ok) return fail(ctx, RH_ERR_STATE, "rh_step_routed: " + api->why);
@@ -4034,6 +4084,8 @@ int rh_comm_init(rh_ctx *ctx, const void *id128, int nranks, int rank) {
     ctx->own_comm = true;
     ctx->comm_nranks = nranks;
     ctx->comm_rank = rank;
+    ctx->grid_px = nranks;
+    ctx->grid_py = 1;
     return RH_OK;
 }
 int rh_set_comm(rh_ctx *ctx, void *nccl_comm) {
@@ -4045,7 +4097,19 @@ int rh_set_comm(rh_ctx *ctx, void *nccl_comm) {
         if (!api->ok) return fail(ctx, RH_ERR_STATE, "rh_set_comm: " + api->why);
         NCCLCHK(ctx, api->CommCount(ctx->comm, &ctx->comm_nranks));
         NCCLCHK(ctx, api->CommUserRank(ctx->comm, &ctx->comm_rank));
+        ctx->grid_px = ctx->comm_nranks;
+        ctx->grid_py = 1;
     }
+    return RH_OK;
+}
+int rh_comm_set_grid(rh_ctx *ctx, int px, int py) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->comm) return fail(ctx, RH_ERR_STATE, "rh_comm_set_grid: no communicator (rh_comm_init / rh_set_comm)");
+    if (px < 1 || py < 1 || (int64_t)px * py != ctx->comm_nranks)
+        return fail(ctx, RH_ERR_ARG, "rh_comm_set_grid: px * py must equal the communicator's " + std::to_string(ctx->comm_nranks) + " ranks");
+    ctx->grid_px = px;
+    ctx->grid_py = py;
+    ctx->route_static_done = false;   // new neighbours: their flow direction and mask are exchanged again
     return RH_OK;
 }
 int rh_comm_info(rh_ctx *ctx, int *nranks, int *rank) {
@@ -4068,7 +4132,7 @@ int rh_run_steps_dist(rh_ctx *ctx, int64_t nsteps) {
     bool over = false;
     if (int rc = limit_reached(ctx, &over)) return rc;
     if (over) return RH_OK;
-    if (ctx->cfg.enable_routing_1D) {   // the routed step exchanges its predicate words and edge columns itself
+    if (ctx->cfg.enable_routing_1D) {   // the routed step exchanges its predicate words and border cells itself
         for (int64_t k = 0; k < nsteps; ++k) {
             int rc;
             if (!ctx->per_cell && ctx->routed_device_ok)

@@ -2,11 +2,14 @@
 
 Decomposition API follows the reference (roger/distributed.py:121-187): `num_proc = (px, py)`,
 ranks laid out x-fastest, even divisibility required, chunk slices with or without the 2-cell
-overlap, process neighbours, `exchange_overlap` for the 2-cell ghost frame, global reductions.  On
-this path columns never read their neighbours, so no halo is exchanged; what the reference does per
-step -- gather 18 fields to rank 0, decide dt there, scatter back
-(adaptive_time_stepping_dist_safe.py:6-26) -- is replaced by one all-reduce of 64 predicate bits
-(as 64 int32, MAX) per step.
+overlap, process neighbours, `exchange_overlap` for the 2-cell ghost frame, global reductions.  The
+grid may be split in both directions.  On the SVAT / oneD path columns never read their neighbours, so
+no halo is exchanged; what the reference does per step -- gather 18 fields to rank 0, decide dt there,
+scatter back (adaptive_time_stepping_dist_safe.py:6-26) -- is replaced by one all-reduce of 64
+predicate bits (as 64 int32, MAX) per step, whatever the block shape.  The routing
+(settings.enable_routing_1D) exchanges a one-cell halo -- west / east columns, south / north rows,
+corners -- with the neighbours of `get_process_neighbors`, from C over RCCL (rh_comm_set_grid hands the
+context the process grid).
 """
 
 

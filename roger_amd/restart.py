@@ -11,7 +11,7 @@ roger/restart.py:32-67, 129-174), so that states can go back and forth between t
   the reference in both directions: tests/test_restart_interchange.py.
 * The device-side output accumulators (rh_diag_*) go into the group "hip_diag": a restart in the middle of an output interval keeps
   the partial sums.
-* Several ranks (num_proc = (N, 1)): the slabs are gathered to rank 0, which writes ONE file with the global arrays like the
+* Several ranks (num_proc = (px, py)): the blocks are gathered to rank 0, which writes ONE file with the global arrays like the
   reference's MPI-IO write (roger/restart.py:43-64); every rank reads its own chunk, ghost frame included (`get_chunk_slices(...,
   include_overlap=True)`, :20-24).
 * Container: h5py where it is installed; otherwise `roger_amd.h5lite`, a small classic-HDF5 writer / reader (contiguous datasets;

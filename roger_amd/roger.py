@@ -118,17 +118,14 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     setattr(state.settings, setting, value)
             settings_mod.check_setting_conflicts(state.settings)
             # against the REAL size of the process group (roger/roger.py:292, distributed.py:121-138): a run started on N ranks
-            # without num_proc=(N, 1) must fail here instead of stepping N uncoupled copies
+            # with a num_proc = (px, py) of other than N blocks must fail here instead of stepping N uncoupled copies
             distributed.validate_decomposition(state.settings.nx, state.settings.ny, rs.num_proc, rst.proc_num)
-            if rst.proc_num > 1 and rs.num_proc[1] != 1:
-                raise NotImplementedError("the hip backend splits the grid along x only: num_proc = (N, 1) (BASELINE.json north_star)")
             state.initialize_variables()
             offline = state.settings.enable_offline_transport
             if rst.proc_num > 1 and state.settings.enable_routing_1D and not offline:
-                # routed water crosses the rank boundaries: the edge columns travel over the context's communicator inside
+                # routed water crosses the rank boundaries: the border cells travel over the context's communicator inside
                 # rh_step_core / rh_step_routed (the reference never exchanges them, core/utilities.py:79 is not on this path)
-                state.backend_context.comm_init_torch()
-                self._comm_ready = True
+                self._comm_init(state.backend_context)
             self.set_grid(state)
             self.set_topography(state)
             self.set_look_up_tables(state)
@@ -434,6 +431,14 @@ class RogerSetup(metaclass=abc.ABCMeta):
         self._device_hooks = True
         self._per_cell_forcing = bool(self.state.settings.enable_distributed_input or not neutral)
 
+    def _comm_init(self, ctx):
+        """The context's communicator over the process group; with num_proc = (px, py > 1) also its process grid (the routing's
+        halo reaches the y-neighbours and corners; a (N, 1) grid is the default and makes no further call)."""
+        ctx.comm_init_torch()
+        if rs.num_proc[1] > 1:
+            ctx.comm_set_grid(*rs.num_proc)
+        self._comm_ready = True
+
     def _stepper(self, one_exchange):
         key = "_stepper_one" if one_exchange else "_stepper_three"
         if getattr(self, key, None) is None:
@@ -456,8 +461,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             # (rh_comm_init + rh_run_steps_dist), through torch.distributed otherwise
             if hasattr(ctx, "run_steps_dist"):
                 if not getattr(self, "_comm_ready", False):
-                    ctx.comm_init_torch()
-                    self._comm_ready = True
+                    self._comm_init(ctx)
                 ctx.run_steps_dist(nsteps)
             else:
                 self._stepper(one_exchange=True).run(nsteps)
