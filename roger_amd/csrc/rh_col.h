@@ -27,15 +27,11 @@ struct Col {
 #undef RH_DECL_I32_2
 };
 
-// RH_TILED = 1 (default): the arena is a sequence of tiles of 64 cells (one wavefront's columns); inside a tile every
+// The arena is a sequence of tiles of 64 cells (one wavefront's columns); inside a tile every
 // plane has a 512-byte slot (64 float64, or 64 int32 in its first half), slots in plane order.  Everything one
 // wavefront loads and stores during a step lies in ONE contiguous span of RH_NPLANES * 512 bytes (77 KB) instead of
 // RH_NPLANES addresses 8 MB apart: one or two address translations per wave instead of one per plane, and consecutive
 // plane accesses fall into the same DRAM pages.  A plane access is still one fully coalesced 512-byte request.
-// RH_TILED = 0: plane-major (plane p at base + p * stride), kept for experiments.
-#ifndef RH_TILED
-#define RH_TILED 1
-#endif
 // RH_TILE_CELLS: columns per tile, 64 (a wavefront's) or a multiple of it up to the workgroup's 256 -- then a plane's slot holds the
 // columns of 2 or 4 consecutive wavefronts of a workgroup (1 / 2 KiB contiguous per plane and workgroup instead of 512-byte pieces).
 // 256 since the end of round 3: with the kernel's arithmetic cut by rh_pow the longer pieces show a little -- alternating with the 64-column
@@ -51,54 +47,33 @@ static_assert(RH_TILE_CELLS == 64 || RH_TILE_CELLS == 128 || RH_TILE_CELLS == 25
 
 struct Arena {
     char *base;
-    size_t stride;  // tiled: bytes per tile (RH_NPLANES * RH_SLOT_BYTES); plane-major: bytes between planes
+    size_t stride;  // bytes per tile ((planes held + RH_STRIDE_PAD) * RH_SLOT_BYTES)
     int64_t n;      // cells
 };
 
-// Address of cell i of a plane.  Tiled: the tile index is uniform over the wavefront (every kernel maps lane l of a
+// Address of cell i of a plane.  The tile index is uniform over the wavefront (every kernel maps lane l of a
 // wave to cell 64 * k + l), so it is taken from the first active lane and the whole tile/plane part of the address is
 // scalar arithmetic; the per-lane part is lane * element size.
 template <typename T>
 RH_DEV T *rh_cell(const Arena &a, int plane, int64_t i) {
-#if RH_TILED
     // (uniform over the wavefront: the tile index and, inside a tile of several wavefronts, the wavefront's 64-column piece)
     const int tile = __builtin_amdgcn_readfirstlane((int)(i >> RH_TILE_SHIFT));
     const int piece = __builtin_amdgcn_readfirstlane((int)(i & (RH_TILE_CELLS - 1)) & ~63);
     return reinterpret_cast<T *>(a.base + (size_t)tile * a.stride + (size_t)plane * RH_SLOT_BYTES) + piece + (int)(i & 63);
-#else
-    return reinterpret_cast<T *>(a.base + (size_t)plane * a.stride) + i;
-#endif
 }
 // Address of ANY cell of a plane (the routing's gather reads the eight neighbours: the tile is not uniform over the wavefront).
 template <typename T>
 RH_DEV T *rh_cell_any(const Arena &a, int plane, int64_t i) {
-#if RH_TILED
     return reinterpret_cast<T *>(a.base + (size_t)(i >> RH_TILE_SHIFT) * a.stride + (size_t)plane * RH_SLOT_BYTES) + (int)(i & (RH_TILE_CELLS - 1));
-#else
-    return reinterpret_cast<T *>(a.base + (size_t)plane * a.stride) + i;
-#endif
 }
-// RH_NT: plane accesses as non-temporal (streaming) loads / stores -- every plane is touched once per kernel, nothing is worth
-// keeping in the caches.  bit 0: loads, bit 1: stores.  Measured on the fused step at 10^6 columns, alternating in one call
-// (tools/ab_variants.sh): 0.3158 ms plain, 0.3136 loads only, 0.3108 stores only, 0.3016 both (- 4.5 %); a plain copy with the
-// same access shape gains 3 - 5 % (tools/experiments/bw_probe.hip).
-#ifndef RH_NT
-#define RH_NT 3
-#endif
-RH_DEV void rh_ld(const Arena &a, int plane, int64_t i, double &dst) {
-    dst = (RH_NT & 1) ? __builtin_nontemporal_load(rh_cell<const double>(a, plane, i)) : *rh_cell<const double>(a, plane, i);
-}
-RH_DEV void rh_ld(const Arena &a, int plane, int64_t i, int &dst) {
-    dst = (RH_NT & 1) ? __builtin_nontemporal_load(rh_cell<const int>(a, plane, i)) : *rh_cell<const int>(a, plane, i);
-}
-RH_DEV void rh_st(const Arena &a, int plane, int64_t i, double v) {
-    if (RH_NT & 2) __builtin_nontemporal_store(v, rh_cell<double>(a, plane, i));
-    else *rh_cell<double>(a, plane, i) = v;
-}
-RH_DEV void rh_st(const Arena &a, int plane, int64_t i, int v) {
-    if (RH_NT & 2) __builtin_nontemporal_store(v, rh_cell<int>(a, plane, i));
-    else *rh_cell<int>(a, plane, i) = v;
-}
+// Plane accesses are non-temporal (streaming) loads / stores -- every plane is touched once per kernel, nothing is worth
+// keeping in the caches.  Measured on the fused step at 10^6 columns, alternating in one call (tools/ab_variants.sh):
+// 0.3158 ms plain, 0.3136 loads only, 0.3108 stores only, 0.3016 both (- 4.5 %); a plain copy with the same access shape
+// gains 3 - 5 % (tools/experiments/bw_probe.hip).
+RH_DEV void rh_ld(const Arena &a, int plane, int64_t i, double &dst) { dst = __builtin_nontemporal_load(rh_cell<const double>(a, plane, i)); }
+RH_DEV void rh_ld(const Arena &a, int plane, int64_t i, int &dst) { dst = __builtin_nontemporal_load(rh_cell<const int>(a, plane, i)); }
+RH_DEV void rh_st(const Arena &a, int plane, int64_t i, double v) { __builtin_nontemporal_store(v, rh_cell<double>(a, plane, i)); }
+RH_DEV void rh_st(const Arena &a, int plane, int64_t i, int v) { __builtin_nontemporal_store(v, rh_cell<int>(a, plane, i)); }
 
 // Settings that the kernels read (subset of rh_config, device copy).
 struct Consts {

@@ -349,14 +349,13 @@ int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
     }
     // smallest workgroup whose blocked layout covers the ages + 1 edges (rh_sas_kernels.h; the isotope and the anion kernels are
     // translation units of their own, rh_sas_det_iso.hip / rh_sas_det_anion.hip)
-    static const bool e4 = std::getenv("RH_SAS_E4") != nullptr;
 #ifdef RH_SAS_PHASES
     static unsigned long long *d_phases = nullptr;
     if (!d_phases) (void)hipMalloc((void **)&d_phases, 32 * sizeof(unsigned long long));
     (void)hipMemsetAsync(d_phases, 0, 32 * sizeof(unsigned long long), ctx->stream);
     args.phases = d_phases;
 #endif
-    const int lrc = (ctx->cfg.tracer != RH_SAS_TRACER_OXYGEN18 ? rh_sas_launch_det_anion : rh_sas_launch_det_iso)(ctx->stream, args, (unsigned)ctx->cfg.n_cells, c.ages + 1, e4);
+    const int lrc = (ctx->cfg.tracer != RH_SAS_TRACER_OXYGEN18 ? rh_sas_launch_det_anion : rh_sas_launch_det_iso)(ctx->stream, args, (unsigned)ctx->cfg.n_cells, c.ages + 1);
 #ifdef RH_SAS_PHASES
     {
         unsigned long long h[32];

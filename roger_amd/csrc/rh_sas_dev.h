@@ -11,27 +11,20 @@
 #include "roger_hip_sas.h"
 
 #define SAS_DEV __device__ __forceinline__
-// the workgroup barrier of the cross-wave reductions (-DRH_SAS_NO_BARRIER: timing experiments only, the results are then wrong)
-#ifdef RH_SAS_NO_BARRIER
-#define SAS_SYNC() ((void)0)
-#else
+// the workgroup barrier of the cross-wave reductions
 #define SAS_SYNC() __syncthreads()
-#endif
 
 // (SA / S) ** k of the power-law SAS function, the hot spot of the kernel: 5 * substeps * (ages + 1)
 // evaluations per column and day.  The device library's general pow() costs ~230 VALU instructions
 // here (measured: 2/3 of the kernel's instruction stream).  The argument range is narrow -- 0 < SA <= S,
 // k finite -- so (SA / S)**k = 2**(k * (log2 SA - log2 S)) is evaluated directly in ~50 instructions,
 // and the division goes away as well (log2 S is computed once per sub-step):
-//   sas_log2:  x = m * 2**e, m in [sqrt(1/2), sqrt(2));  s = (m - 1) / (m + 1);
-//              ln m = s * (2 + z * (2/3 + 2/5 z + ... + 2/19 z**8)), z = s*s <= 0.02944 (next term < 2.4e-17 rel.)
+//   sas_log2:  x = m * 2**e, m in [1, 2);  log2 m = log2 c_i + log2(1 + r) with c_i from a 64-entry table,
+//              |r| <= 1/128, log2(1 + r) by its series to r^8 (see below)
 //   sas_exp2:  y = n + r, |r| <= 1/2;  2**r = exp(r ln 2) by its Taylor series to degree 13 (remainder < 4e-18);
 //              result = ldexp(., n)
 // Error: the rounding of the logarithms dominates, ~|log2 SA| * 2**-53 * k * ln 2 relative, i.e. < 1e-14 * k for
-// SA / S > 1e-21; SA == S gives exactly 1 (Omega(S) = 1).  RH_SAS_POW=0 selects the library pow(SA / S, k).
-#ifndef RH_SAS_POW
-#define RH_SAS_POW 3
-#endif
+// SA / S > 1e-21; SA == S gives exactly 1 (Omega(S) = 1).
 // Division by a divisor that is uniform over many quotients (flux * h inside the sub-step loop): the compiler's
 // IEEE division is  rcp -> two Newton steps on the reciprocal -> q0 = a * r -> e = fma(-d, q0, a) -> fma(e, r, q0)
 // wrapped in v_div_scale / v_div_fixup for operands near the exponent limits.  With the refined reciprocal hoisted
@@ -103,37 +96,25 @@ SAS_DEV double pow_fifth(double r, int *e2) {
 // Polynomial coefficients live in constant memory so that they reach the FMAs as scalar-register
 // operands (one v_fma_f64 per Horner step); as immediates each step costs a 64-bit v_mov besides.
 #include "rh_sas_tables.inc"
-// RH_SAS_LOG: 1 = table-assisted log2 (64-entry table of {1/c, log2 c} in LDS, degree-8 log2(1 + r)); 0 = the
-// table-free version (s = (m - 1) / (m + 1), odd series to s^19)
-#ifndef RH_SAS_LOG
-#define RH_SAS_LOG 1
-#endif
+// the table-assisted log2: a 64-entry table of {1/c, log2 c} (copied to LDS by the step kernels), degree-8 log2(1 + r)
 static __constant__ double2 SAS_LOG_T[64] = {RH_SAS_LOG_TABLE};
 static __constant__ double SAS_LOG1P_C[8] = {RH_SAS_LOG1P_COEF};
-static __constant__ double SAS_LOG_C[9] = {2.0 / 19.0, 2.0 / 17.0, 2.0 / 15.0, 2.0 / 13.0, 2.0 / 11.0, 2.0 / 9.0, 2.0 / 7.0, 2.0 / 5.0, 2.0 / 3.0};
 static __constant__ double SAS_EXP_C[12] = {1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0,
                                      1.0 / 40320.0,      1.0 / 5040.0,      1.0 / 720.0,      1.0 / 120.0,     1.0 / 24.0,
                                      1.0 / 6.0,          0.5};
 struct PowConsts {
-    double lc[9], ec[12];
+    double lc[8], ec[12];
     const double2 *logt;  // the log2 table (LDS copy in the step kernel)
 };
 SAS_DEV PowConsts load_pow_consts(const double2 *logt) {
     PowConsts c;
     c.logt = logt;
-#if RH_SAS_LOG == 1
 #pragma unroll
     for (int i = 0; i < 8; ++i) c.lc[i] = SAS_LOG1P_C[i];
-    c.lc[8] = 0.0;
-#else
-#pragma unroll
-    for (int i = 0; i < 9; ++i) c.lc[i] = SAS_LOG_C[i];
-#endif
 #pragma unroll
     for (int i = 0; i < 12; ++i) c.ec[i] = SAS_EXP_C[i];
     return c;
 }
-#if RH_SAS_LOG == 1
 // log2 x = e + log2 c_i + log2(1 + r):  x = m * 2^e with m in [1, 2), i = the top six mantissa bits, c_i the centre of
 // that sixty-fourth, r = m / c_i - 1 by one fma on the tabulated reciprocal (|r| <= 1/128; the table's log2 c_i is
 // -log2 of that very reciprocal, so the split is exact), log2(1 + r) by its series to r^8.
@@ -148,27 +129,6 @@ SAS_DEV double sas_log2(const PowConsts &C, double x) {
     for (int k = 1; k < 8; ++k) p = __builtin_fma(p, r, C.lc[k]);
     return ((double)e + t.y) + p * r;
 }
-#else
-SAS_DEV double sas_log2(const PowConsts &C, double x) {
-    int e = __builtin_amdgcn_frexp_exp(x);
-    double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
-    const bool low = m < 0.70710678118654752440;
-    m = low ? m + m : m;
-    e = low ? e - 1 : e;
-    const double f = m - 1.0, d = m + 1.0;
-    double r = __builtin_amdgcn_rcp(d);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    double s = f * r;
-    s = __builtin_fma(__builtin_fma(-d, s, f), r, s);
-    const double z = s * s;
-    double p = C.lc[0];
-#pragma unroll
-    for (int i = 1; i < 9; ++i) p = __builtin_fma(p, z, C.lc[i]);
-    const double lnm = s * __builtin_fma(p, z, 2.0);
-    return __builtin_fma(lnm, 1.44269504088896340736, (double)e);
-}
-#endif
 // 2**y.  No range clamp is needed: v_cvt_i32_f64 saturates and v_ldexp_f64 under/overflows to 0 / inf.
 SAS_DEV double sas_exp2(const PowConsts &C, double y) {
     const double n = __builtin_rint(y);
@@ -182,11 +142,7 @@ SAS_DEV double sas_exp2(const PowConsts &C, double y) {
 }
 // (x / S) ** k for 0 < x <= S; log2S = sas_log2(S)
 SAS_DEV double sas_pow_ratio(const PowConsts &C, double x, double S, double log2S, double k) {
-#if RH_SAS_POW == 0
-    return pow(x / S, k);
-#else
     return sas_exp2(C, k * (sas_log2(C, x) - log2S));
-#endif
 }
 
 enum SasArr {
@@ -857,8 +813,8 @@ SAS_DEV void ageing(Blk<W> &B, int A, int base, double (&sa)[E], double (&msa)[E
 
 // the whole day (deterministic: the stages in args.stages) in one launch on `stream`, per kernel family:
 // launchers of the kernel translation units (host functions)
-int rh_sas_launch_det_iso(hipStream_t stream, const SasArgs &args, unsigned n_cells, int nages, bool e4);
-int rh_sas_launch_det_anion(hipStream_t stream, const SasArgs &args, unsigned n_cells, int nages, bool e4);
+int rh_sas_launch_det_iso(hipStream_t stream, const SasArgs &args, unsigned n_cells, int nages);
+int rh_sas_launch_det_anion(hipStream_t stream, const SasArgs &args, unsigned n_cells, int nages);
 int rh_sas_launch_euler_iso(hipStream_t stream, const SasArgs &args);
 int rh_sas_launch_euler_anion(hipStream_t stream, const SasArgs &args);
 int rh_sas_launch_rk4_iso(hipStream_t stream, const SasArgs &args);

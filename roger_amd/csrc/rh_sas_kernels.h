@@ -89,9 +89,7 @@ SAS_DEV void calc_tt(Blk<W> &B, const SasArgs &P, const double *p, double flux, 
     else if (code == 3 || (code >= 31 && code <= 37)) calc_tt_family<W, E, FAM_KUMARASWAMI>(B, P, p, flux, sa, mk, base, tt);
     else if (code == 2) calc_tt_family<W, E, FAM_DIRAC>(B, P, p, flux, sa, mk, base, tt);
     else if (code == 51) calc_tt_family<W, E, FAM_EXPONENTIAL>(B, P, p, flux, sa, mk, base, tt);
-#ifndef RH_SAS_NO_GAMMA  // (experiments: the kernel without the gamma family's code)
     else if (code == 4) calc_tt_family<W, E, FAM_GAMMA>(B, P, p, flux, sa, mk, base, tt);
-#endif
     else {
         // 52, the exponential with reversed age order (sas.py:186-190): Omega DEcreases from 1 to 0 along the age axis,
         // calc_tt clips every difference to 0 (:430-433) -- no water is selected, like Omega = 0.  Any other code is
@@ -382,17 +380,6 @@ __global__ __launch_bounds__(W * 64) SAS_OCCUPANCY void k_sas(const SasArgs P) {
 template <int W, bool ANION>
 __global__ __launch_bounds__(W * 64) SAS_OCCUPANCY_E8 void k_sas8(const SasArgs P) {
     sas_body<W, 8, ANION>(P);
-}
-// Sixteen age classes per thread, ONE wavefront per column (ages <= 1023): no workgroup barrier and no exchange through LDS at all, the
-// scans are the wave's DPP scan plus a running sum over the thread's own classes; the state of a column then takes the register file of
-// a whole SIMD (1 wave/SIMD, 512 registers: VGPRs + AGPRs).  -DRH_SAS_EXPERIMENT_E16 builds ONLY this shape (experiments).
-#ifndef RH_SAS_E16_WAVES
-#define RH_SAS_E16_WAVES 1
-#endif
-#define SAS_OCCUPANCY_E16 __attribute__((amdgpu_waves_per_eu(RH_SAS_E16_WAVES, RH_SAS_E16_WAVES)))
-template <bool ANION>
-__global__ __launch_bounds__(64) SAS_OCCUPANCY_E16 void k_sas16(const SasArgs P) {
-    sas_body<1, 16, ANION>(P);
 }
 template <int W, int E, bool ANION>
 __device__ __forceinline__ void sas_body(const SasArgs &P) {
@@ -699,32 +686,21 @@ __device__ __forceinline__ void sas_body(const SasArgs &P) {
 
 
 #ifdef RH_SAS_DET_ANION   // this unit's kernels: 0 = isotopes (oxygen-18, deuterium), 1 = anions (bromide, chloride, virtual tracer)
-// the whole day (or the stages in args.stages) in one launch; returns RH_ERR_ARG if the age axis fits no shape
-int RH_SAS_DET_NAME(hipStream_t stream, const SasArgs &args, unsigned n_cells, int nages, bool e4) {
+// the whole day (or the stages in args.stages) in one launch
+int RH_SAS_DET_NAME(hipStream_t stream, const SasArgs &args, unsigned n_cells, int nages) {
     constexpr bool AN = RH_SAS_DET_ANION != 0;
 #define RH_L4(W, E) hipLaunchKernelGGL((k_sas<W, E, AN>), dim3(n_cells), dim3(W * 64), 0, stream, args)
 #define RH_L8(W) hipLaunchKernelGGL((k_sas8<W, AN>), dim3(n_cells), dim3(W * 64), 0, stream, args)
-#ifdef RH_SAS_EXPERIMENT_E16
-    if (nages > 1024) return RH_ERR_ARG;
-    hipLaunchKernelGGL((k_sas16<AN>), dim3(n_cells), dim3(64), 0, stream, args);
-    return RH_OK;
-#else
-    // eight classes per thread from 257 age classes on (9.63 against 10.17 ms per day at 10^5 columns x 1000 ages); RH_SAS_E4=1: the
-    // four-class shapes for comparison
-    if (!e4 && nages > 256 && nages <= 4096) {
-        if (nages <= 512) RH_L8(1);
-        else if (nages <= 1024) RH_L8(2);
-        else if (nages <= 2048) RH_L8(4);
-        else RH_L8(8);
-    } else if (nages <= 64) RH_L4(1, 1);
+    // eight classes per thread from 257 age classes on (9.63 against 10.17 ms per day at 10^5 columns x 1000 ages with four)
+    if (nages <= 64) RH_L4(1, 1);
     else if (nages <= 128) RH_L4(1, 2);
     else if (nages <= 256) RH_L4(1, 4);
-    else if (nages <= 512) RH_L4(2, 4);
-    else if (nages <= 1024) RH_L4(4, 4);
-    else if (nages <= 2048) RH_L4(8, 4);
+    else if (nages <= 512) RH_L8(1);
+    else if (nages <= 1024) RH_L8(2);
+    else if (nages <= 2048) RH_L8(4);
+    else if (nages <= 4096) RH_L8(8);
     else RH_L4(16, 4);
     return RH_OK;
-#endif
 #undef RH_L4
 #undef RH_L8
 }

@@ -54,14 +54,6 @@
 #define RH_WSTRIDE 16       // words between two slots of the device-wide OR words (sumw, frontw, dayw): 128 bytes -- a slot per cache line
 #endif
 #define RH_SRC_SUMW 1        // ... in sumw[] (k_summary rebuilt it from the arena)
-#ifndef RH_STEP_PREFETCH
-// 0: a stage's planes are requested right in front of it.  1: the NEXT stage's planes are requested before the current stage computes
-// -- in the source; the compiler sinks the loads back to their first use (no difference measured).  2 (default since round 3): the same
-// with a scheduling barrier behind the requests (__builtin_amdgcn_sched_barrier), so that a stage's arithmetic runs under the next
-// stage's loads: 197 VGPRs as before, nothing spilled, 2 - 3 % per step (10^6 columns 0.2294 -> 0.2228 ms, 10^7 2.047 -> 2.000 ms, oneD
-// 0.2413 -> 0.2354 ms; library variants alternating inside one call, tools/ab_variants.sh).
-#define RH_STEP_PREFETCH 2
-#endif
 #ifndef RH_STEP_WAVES
 #define RH_STEP_WAVES 2     // waves per SIMD the fused kernel is compiled for (register budget 512 / waves)
 #endif
@@ -220,8 +212,6 @@ struct rh_ctx {
     size_t ev_used;
     int *dt_log_buf;
     std::vector<double> probe_ms;   // placement probing: streaming-kernel time per candidate arena, the chosen one first
-    char *arena_alloc;    // what hipMalloc returned for the arena (arena.base = arena_alloc + arena_offset)
-    size_t arena_offset, arena_pad = 0;
     void *stage_buf;      // one contiguous plane (n * 8 bytes): uploads and downloads pass through it
     // multi-GPU: RCCL communicator and the exchange buffers of the summary word (64 int32 sent, 64 received)
     ncclComm_t comm;
@@ -1720,7 +1710,6 @@ __global__ void k_words_compress(DevState *D, int w, const int *src) {
     for (int off = 32; off; off >>= 1) b |= __shfl_xor(b, off);
     if (threadIdx.x == 0) D->words[w] = b;
 }
-__global__ void k_zero_words(DevState *D) { D->words[0] = D->words[1] = D->words[2] = D->words[3] = 0; }
 
 // ---------------------------------------------------------------------------------------------
 // per-column kernels
@@ -1768,14 +1757,10 @@ RH_DEV void rh_ld_p(const Arena &a, int64_t i, T &dst, unsigned long long um) {
             if (um >> 63) return;
         }
         const bool uni = (um >> bit) & 1ull;
-#if RH_TILED
         const int tile = __builtin_amdgcn_readfirstlane((int)(i >> RH_TILE_SHIFT));
         const int piece = __builtin_amdgcn_readfirstlane((int)(i & (RH_TILE_CELLS - 1)) & ~63);
         const T *p = reinterpret_cast<const T *>(a.base + (size_t)tile * a.stride + (size_t)PLANE * RH_SLOT_BYTES) + piece + (uni ? 0 : (int)(i & 63));
-#else
-        const T *p = reinterpret_cast<const T *>(a.base + (size_t)PLANE * a.stride) + (uni ? (i & ~(int64_t)63) : i);
-#endif
-        dst = (RH_NT & 1) ? __builtin_nontemporal_load(p) : *p;
+        dst = __builtin_nontemporal_load(p);
     }
 }
 #define LDP(name) rh_ld_p<RH_P_##name, MK1>(a, i, c.name, um);
@@ -1872,12 +1857,11 @@ __global__ __launch_bounds__(RH_BLOCK) void k_param_mask(Arena a, DevState *D, u
     } else {                                                             \
         RH_SEQ_##seq##_STORE_##rt(ST) RH_SEQ_##seq##_ROT_##rt(ROT)       \
     }
-#if RH_STEP_PREFETCH
-#if RH_STEP_PREFETCH >= 2
+// the loads of the NEXT stage are requested before the current stage computes, with a scheduling barrier behind them, so that a
+// stage's arithmetic runs under the next stage's loads (round 3: 197 VGPRs as before, nothing spilled, 2 - 3 % per step against
+// requesting a stage's planes right in front of it -- 10^6 columns 0.2294 -> 0.2228 ms, 10^7 2.047 -> 2.000 ms, oneD 0.2413 -> 0.2354
+// ms; library variants alternating inside one call, tools/ab_variants.sh)
 #define RH_PIN __builtin_amdgcn_sched_barrier(0);
-#else
-#define RH_PIN
-#endif
 #ifdef RH_STEP_PHASES   // measurement builds (tools/step_phases.sh): wave cycles per stage of the step, by class of step length
 __device__ unsigned long long g_step_phases[256 * 64];   // 256 copies (one address would serialise the chip's atomics)
 #define RH_PH(k)                                                                          \
@@ -1889,6 +1873,8 @@ __device__ unsigned long long g_step_phases[256 * 64];   // 256 copies (one addr
 #else
 #define RH_PH(k)
 #endif
+// q_pt / q_sw: the column's summary values for the next step's predicates, sampled where they are final
+// (tools/gen_sets.py asserts that no later stage assigns them)
 #define RH_STEP_BODY(seq, mon_rt, MON_LOADS, MON_RUN, sub_rt, sub_call, ne_rt, ne_call, at_rt, at_call) \
     RH_LOADS(seq, rt_select_prec) RH_LOADS(seq, rt_select_pet) MON_LOADS RH_LOADS(seq, rt_interception) RH_PIN  \
     rt_select_prec(c, X, prec_s, ta_s); RH_STORES(seq, rt_select_prec)                                                \
@@ -1921,40 +1907,6 @@ __device__ unsigned long long g_step_phases[256 * 64];   // 256 copies (one addr
     RH_LOADS(seq, at_rt) RH_PIN                                                                                 \
     bad = ne_call; RH_STORES(seq, ne_rt) RH_PH(13)                                                                 \
     at_call; RH_STORES(seq, at_rt) RH_PH(14)
-#else
-#define RH_STAGE(seq, rt, call) RH_LOADS(seq, rt) call; RH_STORES(seq, rt)
-#ifdef RH_NO_SELSTAGE  // timing experiments only
-#define RH_DBG_SEL(x)
-#else
-#define RH_DBG_SEL(x) x
-#endif
-#ifdef RH_NO_SUMMARY
-#define RH_DBG_SUM(x)
-#else
-#define RH_DBG_SUM(x) x
-#endif
-// q_pt / q_sw: the column's summary values for the next step's predicates, sampled where they are final
-// (tools/gen_sets.py asserts that no later stage assigns them)
-#define RH_STEP_BODY(seq, mon_rt, MON_LOADS, MON_RUN, sub_rt, sub_call, ne_rt, ne_call, at_rt, at_call) \
-    RH_DBG_SEL(RH_STAGE(seq, rt_select_prec, rt_select_prec(c, X, prec_s, ta_s)))                                     \
-    RH_STAGE(seq, rt_select_pet, rt_select_pet(c, X, pet_v, ta_v))                                       \
-    RH_DBG_SUM(q = summary_bits_pt(c.prec, c.ta, K);)                                                    \
-    MON_LOADS MON_RUN                                                                                    \
-    RH_STAGE(seq, rt_interception, rt_interception(c, K))                                                \
-    RH_STAGE(seq, rt_evapotranspiration, RH_DERIVE(rt_evapotranspiration) rt_evapotranspiration(c, K))   \
-    RH_STAGE(seq, rt_snow, rt_snow(c, K, X))                                                             \
-    RH_DBG_SUM(q = summary_bits_sw(q, c.swe, c.swe_top); if (post) post_summary(D, q, dep);)             \
-    RH_STAGE(seq, rt_inf_events, rt_inf_events(c, K, X))                                                 \
-    RH_STAGE(seq, rt_inf_matrix, RH_DERIVE(rt_inf_matrix) rt_inf_matrix(c, K, X))                        \
-    RH_STAGE(seq, rt_inf_macropores, RH_DERIVE(rt_inf_macropores) rt_inf_macropores(c, K, X))            \
-    RH_STAGE(seq, rt_inf_cracks, rt_inf_cracks(c, K, X))                                                 \
-    RH_STAGE(seq, rt_inf_finish, rt_inf_finish(c, K, X))                                                 \
-    RH_STAGE(seq, sub_rt, RH_DERIVE(sub_rt) sub_call)                                                    \
-    RH_STAGE(seq, rt_capillary_rise, rt_capillary_rise(c, X))                                            \
-    RH_STAGE(seq, rt_storage, RH_DERIVE(rt_storage) rt_storage(c, X))                                    \
-    RH_STAGE(seq, ne_rt, bad = ne_call)                                                                  \
-    RH_STAGE(seq, at_rt, at_call)
-#endif
 
 // A wavefront's summary bits into the device-wide words, as soon as they are final (right after the snow stage: the latency of
 // the returning atomic hides behind the infiltration stages).  `dep` carries the returned value to the completion count at the end
@@ -2031,17 +1983,13 @@ __global__ __launch_bounds__(RH_BLOCK, RH_STEP_WAVES) void k_step(Arena a, DevSt
     // workgroup b to the column block  (b mod 8) * blocks_per_xcd + b / 8  lets every XCD walk ONE contiguous eighth of
     // the arena instead of every XCD touching every page.  Never slower; on one box 6 - 11 % faster at 10^7 columns (21 GB
     // arena: 3.87 -> 3.44 .. 3.64 ms per step; oneD 4.38 -> 4.12 ms), on another box and up to 4 x 10^6 columns the same
-    // (DESIGN.md section 5 on the speed levels of this kernel).  -DRH_XCD_ROUND_ROBIN: the plain mapping.
+    // (DESIGN.md section 5 on the speed levels of this kernel).
     // RH_TAIL_PRE: the last workgroup of the grid has no columns -- its first wavefront is pre_tail
     const unsigned nb = gridDim.x - ((flags & RH_TAIL_PRE) ? 1u : 0u);
     const bool extra = blockIdx.x >= nb;
-#ifndef RH_XCD_ROUND_ROBIN
     const unsigned x = blockIdx.x & 7u, base_cnt = nb >> 3, rem = nb & 7u;
     const unsigned blk = x * base_cnt + (x < rem ? x : rem) + (blockIdx.x >> 3);
     const int64_t i = extra ? a.n : (int64_t)blk * RH_BLOCK + threadIdx.x;
-#else
-    const int64_t i = extra ? a.n : (int64_t)blockIdx.x * RH_BLOCK + threadIdx.x;
-#endif
     __shared__ unsigned wg_done;      // wavefronts of this workgroup that are through
     __shared__ CtrlLds tail_lds;      // scratch of the tail and of pre_tail (one wavefront each of the whole grid)
     const StepCtx *Xp = (flags & RH_TAIL_USE_NEXT) ? &D->X_next : &D->X;
@@ -2094,9 +2042,8 @@ __global__ __launch_bounds__(RH_BLOCK, RH_STEP_WAVES) void k_step(Arena a, DevSt
     } else if (post) {
         post_summary(D, 0ull, dep);
     }
-    // (behind the column pipeline in the kernel's text: in front of it, the allocator spilled 36 - 63 of the pipeline's registers.
-    //  RH_X_NOPRE / RH_X_NOCOMPLETION / RH_X_NOTAIL: timing-only builds whose results are NOT valid -- profiles/r04_tail_phases.txt)
-#if !defined(RH_CENSUS) && !defined(RH_X_NOPRE)
+    // (behind the column pipeline in the kernel's text: in front of it, the allocator spilled 36 - 63 of the pipeline's registers)
+#ifndef RH_CENSUS
     if (__builtin_expect(extra && threadIdx.x < 64, 0)) pre_tail(D, tail_lds, flags, dep);
 #endif
     const bool any_bad = __any(bad);
@@ -2110,15 +2057,8 @@ __global__ __launch_bounds__(RH_BLOCK, RH_STEP_WAVES) void k_step(Arena a, DevSt
     if ((threadIdx.x & 63) == 0) {
         if (any_bad) dep |= (unsigned)(__hip_atomic_fetch_or(&D->words[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 63);
         const unsigned o = atomicAdd(&wg_done, dep);   // LDS; dep == 1
-        if (o == (RH_BLOCK / 64) - 1) {                // the last wave of the workgroup reports the workgroup
-#ifndef RH_X_NOCOMPLETION
-            last = grid_completion(D, n_groups);
-#endif
-        }
+        if (o == (RH_BLOCK / 64) - 1) last = grid_completion(D, n_groups);   // the last wave of the workgroup reports the workgroup
     }
-#ifdef RH_X_NOTAIL
-    last = false;
-#endif
 #ifndef RH_CENSUS   // tools/isa_census.py counts the per-column memory instructions of the kernel without its tail
     if (__shfl((int)last, 0)) step_tail(D, tail_lds, flags, dst64);
 #endif
@@ -2151,12 +2091,10 @@ RH_CELL_KERNEL(k_capillary_rise, rt_capillary_rise, rt_capillary_rise(c, X))
 RH_CELL_KERNEL(k_storage, rt_storage, rt_storage(c, X))
 RH_CELL_KERNEL(k_num_error, rt_num_error, if (rt_num_error(c, K)) atomicOr(&D->words[2], 1ull))
 RH_CELL_KERNEL(k_after_timestep, rt_after_timestep, rt_after_timestep(c))
-RH_CELL_KERNEL(k_step_core, rt_step_core, if (rt_step_core(c, K, X)) atomicOr(&D->words[2], 1ull))
 // oneD model variants
 RH_CELL_KERNEL(k_subsurface_runoff_lateral, rt_subsurface_runoff_lateral, rt_subsurface_runoff_lateral(c, K, X))
 RH_CELL_KERNEL(k_num_error_lateral, rt_num_error_lateral, if (rt_num_error_lateral(c, K)) atomicOr(&D->words[2], 1ull))
 RH_CELL_KERNEL(k_after_timestep_oned, rt_after_timestep_oned, rt_after_timestep_oned(c))
-RH_CELL_KERNEL(k_step_core_lateral, rt_step_core_lateral, if (rt_step_core_lateral(c, K, X)) atomicOr(&D->words[2], 1ull))
 RH_CELL_KERNEL(k_params_lateral, rt_params_lateral, rt_params_lateral(c, D->mlms, D->mlms_rows, D->max_slope_per))
 // settings.enable_routing_1D: the per-column parts of the D8 routing (rh_physics.h) ...
 RH_CELL_KERNEL(k_infiltration_routed, rt_infiltration_routed, rt_infiltration_routed(c, K, X))
@@ -2166,7 +2104,7 @@ RH_CELL_KERNEL(k_route_subsurface_out, rt_route_subsurface_out, rt_route_subsurf
 RH_CELL_KERNEL(k_route_subsurface_in, rt_route_subsurface_in, rt_route_subsurface_in(c))
 RH_CELL_KERNEL(k_num_error_routed, rt_num_error_routed, if (rt_num_error_routed(c, K)) atomicOr(&D->words[2], 1ull))
 // the step core in three passes, one kernel each (the infiltration's branch conditions come from the adaptive time stepping's
-// predicate word, as in k_step_core: global over the ranks)
+// predicate word: global over the ranks)
 // ... staged like the fused step (tools/gen_sets.py PLAIN_SEQUENCES): every plane is loaded right before the first stage that mentions it
 // and stored right after the last one that assigns it (short live ranges instead of all loads up front)
 #define RH_PSTAGE(seq, rt, call) RH_SEQ_##seq##_LOAD_##rt(LD) call; RH_SEQ_##seq##_STORE_##rt(ST)
@@ -2213,8 +2151,8 @@ RH_PASS_KERNEL(k_routed_c_after,
                RH_PSTAGE(routed_c_after, rt_num_error_routed, bad = rt_num_error_routed(c, K))
                RH_PSTAGE(routed_c_after, rt_after_timestep_oned, rt_after_timestep_oned(c)))
 // The step core of the hook-preserving flow (rh_step_core: RogerSetup.step() with the user hooks on the host) as ONE staged pass -- the
-// fused kernel's pipeline without its selection, rotation and control parts.  k_step_core / k_step_core_lateral, which load every
-// plane up front, need 256 VGPRs + 92 / 118 AGPRs and run at one wave per SIMD; kept for A/B (RH_STEP_CORE_UNSTAGED).
+// fused kernel's pipeline without its selection, rotation and control parts.  (Kernels that load every plane up front need 256 VGPRs
+// + 92 / 118 AGPRs and run at one wave per SIMD, VERDICT r2 weak #5.)
 #define RH_CORE_HEAD(seq)                                                                          \
     RH_PSTAGE(seq, rt_interception, rt_interception(c, K))                                         \
     RH_PSTAGE(seq, rt_evapotranspiration, rt_evapotranspiration(c, K))                             \
@@ -2756,8 +2694,6 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     ctx->dt_log_buf = nullptr;
     ctx->dev = nullptr;
     ctx->arena.base = nullptr;
-    ctx->arena_alloc = nullptr;
-    ctx->arena_offset = 0;
     ctx->rot_consistent = false;
     ctx->m1_stale = false;
     ctx->agg_daily_stale = true;
@@ -2780,14 +2716,9 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     ctx->diag_n = 0;
     ctx->diag_slots = 0;
     ctx->per_cell = false;
-#if RH_TILED
     const size_t n_tiles = ((size_t)ctx->n + RH_TILE_CELLS - 1) / RH_TILE_CELLS;
     ctx->planes_held = cfg->enable_routing_1D ? (int)RH_NPLANES : (int)RH_P_flow_dir_topo;
     const size_t stride = (size_t)(ctx->planes_held + RH_STRIDE_PAD) * RH_SLOT_BYTES, arena_bytes = n_tiles * stride;
-#else
-    ctx->planes_held = RH_NPLANES;
-    const size_t stride = (((size_t)ctx->n * sizeof(double)) + 255) / 256 * 256, arena_bytes = stride * RH_NPLANES;
-#endif
     ctx->arena.stride = stride;
     ctx->arena.n = ctx->n;
     ctx->stage_buf = nullptr;
@@ -2815,12 +2746,6 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     hipError_t e;
     if ((e = hipStreamCreate(&ctx->stream)) != hipSuccess) return bail(e, "hipStreamCreate");
     ctx->own_stream = true;
-    {   // experiments (tools/placement_diag*.py): RH_ARENA_OFFSET_KB shifts the arena inside a larger allocation
-        const char *off = std::getenv("RH_ARENA_OFFSET_KB");
-        ctx->arena_offset = off ? (size_t)std::atoll(off) * 1024 : 0;
-        const char *pad = std::getenv("RH_ARENA_PAD_KB");   // ... and RH_ARENA_PAD_KB pads the allocation behind the arena
-        ctx->arena_pad = pad ? (size_t)std::atoll(pad) * 1024 : 0;
-    }
     {
         // Placement probing (rh_config.placement_probes): candidates are allocated one after the other and held until
         // the choice is made, so that each lands somewhere else; a copy of 96 planes with the fused kernel's access
@@ -2836,23 +2761,23 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
             if (k > 0) {   // all candidates are held until the choice is made: never more than a quarter of the free memory in total
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) != hipSuccess ||
-                    (free_b + k * (arena_bytes + ctx->arena_offset + ctx->arena_pad)) / 4 < (k + 1) * (arena_bytes + ctx->arena_offset + ctx->arena_pad)) break;
+                    (free_b + k * arena_bytes) / 4 < (k + 1) * arena_bytes) break;
             }
             char *p = nullptr;
-            if ((e = hipMalloc((void **)&p, arena_bytes + ctx->arena_offset + ctx->arena_pad)) != hipSuccess) {
+            if ((e = hipMalloc((void **)&p, arena_bytes)) != hipSuccess) {
                 if (k == 0) return bail(e, "hipMalloc(arena)");
                 (void)hipGetLastError();
                 break;
             }
             cand.push_back(p);
-            if ((e = hipMemsetAsync(p + ctx->arena_offset, 0, arena_bytes, ctx->stream)) != hipSuccess) {
+            if ((e = hipMemsetAsync(p, 0, arena_bytes, ctx->stream)) != hipSuccess) {
                 for (char *q : cand) (void)hipFree(q);
                 return bail(e, "hipMemset");
             }
             double ms = 0;
             if (probes > 1) {
                 Arena probe = ctx->arena;
-                probe.base = p + ctx->arena_offset;
+                probe.base = p;
                 float best = 1e30f;
                 for (int rep = 0; rep < 4; ++rep) {   // the first repetition warms up
                     (void)hipEventRecord(ev0, ctx->stream);
@@ -2871,8 +2796,7 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
         size_t pick = 0;
         for (size_t k = 1; k < cand.size(); ++k)
             if (cand_ms[k] < cand_ms[pick]) pick = k;
-        ctx->arena_alloc = cand[pick];
-        ctx->arena.base = cand[pick] + ctx->arena_offset;
+        ctx->arena.base = cand[pick];
         if (probes > 1) {
             ctx->probe_ms.push_back(cand_ms[pick]);
             for (size_t k = 0; k < cand.size(); ++k)
@@ -2989,7 +2913,7 @@ void rh_destroy(rh_ctx *ctx) {
     if (ctx->mlms_buf) (void)hipFree(ctx->mlms_buf);
     if (ctx->diag_buf) (void)hipFree(ctx->diag_buf);
     if (ctx->diag_steps_buf) (void)hipFree(ctx->diag_steps_buf);
-    if (ctx->arena_alloc) (void)hipFree(ctx->arena_alloc);
+    if (ctx->arena.base) (void)hipFree(ctx->arena.base);
     if (ctx->stage_buf) (void)hipFree(ctx->stage_buf);
     if (ctx->exch_buf) (void)hipFree(ctx->exch_buf);
     if (ctx->route_q) (void)hipFree(ctx->route_q);
@@ -3081,11 +3005,7 @@ void *rh_plane_device_ptr(rh_ctx *ctx, int plane) {
         return nullptr;
     }
     planes_touched(ctx);  // the caller may write through the pointer
-#if RH_TILED
     return ctx->arena.base + (size_t)plane * RH_SLOT_BYTES;   // cell i: + (i / 64) * tile_bytes + (i % 64) * element size
-#else
-    return ctx->arena.base + (size_t)plane * ctx->arena.stride;
-#endif
 }
 
 int rh_set_scalars(rh_ctx *ctx, const rh_scalars *s) {
@@ -3254,14 +3174,10 @@ static int routed_core(rh_ctx *ctx, bool with_after);
 int rh_step_core(rh_ctx *ctx) {
     if (!ctx) return RH_ERR_ARG;
     if (ctx->cfg.enable_routing_1D) return routed_core(ctx, false);   // the columns are coupled: routine by routine with the two gathers
-    static const bool unstaged = std::getenv("RH_STEP_CORE_UNSTAGED") != nullptr;   // A/B, tests: the single-function kernels
-    if (ctx->cfg.enable_lateral_flow) {
-        if (unstaged) LAUNCH_CELLS(ctx, k_step_core_lateral);
-        else LAUNCH_CELLS(ctx, k_core_staged_lateral);
-    } else {
-        if (unstaged) LAUNCH_CELLS(ctx, k_step_core);
-        else LAUNCH_CELLS(ctx, k_core_staged);
-    }
+    if (ctx->cfg.enable_lateral_flow)
+        LAUNCH_CELLS(ctx, k_core_staged_lateral);
+    else
+        LAUNCH_CELLS(ctx, k_core_staged);
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, ctx->stream, ctx->dev);
     // the output accumulators follow every step, also in the hook-preserving flow (itt / time were just advanced)
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, 0);
@@ -3485,7 +3401,7 @@ static int timing_pair(rh_ctx *ctx, hipEvent_t *ev0, hipEvent_t *ev1) {
 static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst64 = nullptr) {
     // Timing: the event pair rides on the kernel's own dispatch (hipExtLaunchKernelGGL: start / stop are taken from the
     // dispatch's completion signal) instead of two hipEventRecord packets around it, which cost 5 us per step at 10^6
-    // columns.  -DRH_EVENT_RECORD: the hipEventRecord pair.
+    // columns.
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ctx->timing) {
         if (ctx->ev_used + 2 > 2 * (size_t)RH_DT_LOG_CAP)
@@ -3497,20 +3413,12 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
         }
         ev0 = ctx->events[ctx->ev_used];
         ev1 = ctx->events[ctx->ev_used + 1];
-#ifdef RH_EVENT_RECORD
-        HIPCHK(ctx, hipEventRecord(ev0, ctx->stream));
-#endif
     }
-    // a launch whose tail forms the next step's control part gets one workgroup more: pre_tail (RH_NO_PRE_TAIL=1: the tail does it all)
-    static const bool pre_ok = std::getenv("RH_NO_PRE_TAIL") == nullptr;
-    if ((flags & RH_TAIL_CTRL) && pre_ok) flags |= RH_TAIL_PRE;
+    // a launch whose tail forms the next step's control part gets one workgroup more: pre_tail
+    if (flags & RH_TAIL_CTRL) flags |= RH_TAIL_PRE;
     const dim3 grid(grid_for(ctx->n) + ((flags & RH_TAIL_PRE) ? 1u : 0u)), block(RH_BLOCK);
     const bool lat = ctx->cfg.enable_lateral_flow != 0;
-#ifdef RH_EVENT_RECORD
-#define RH_LAUNCH_K(K) hipLaunchKernelGGL(K, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, flags, ctx->n_groups, dst64)
-#else
 #define RH_LAUNCH_K(K) hipExtLaunchKernelGGL(K, grid, block, 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev, flags, ctx->n_groups, dst64)
-#endif
     // lazy rotation: the planes were last touched by a complete fused step (X_m1 == X) and nobody who reads X_m1 planes
     // follows inside this call (the accumulator kernel may, if it was given an X_m1 plane)
     const bool lazy = ctx->lazy_ok && ctx->rot_consistent && !ctx->diag_reads_m1;
@@ -3552,12 +3460,7 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
 #undef RH_LAUNCH_STEP
 #undef RH_LAUNCH_K
     CHECK_LAUNCH(ctx);
-    if (ctx->timing) {
-#ifdef RH_EVENT_RECORD
-        HIPCHK(ctx, hipEventRecord(ev1, ctx->stream));
-#endif
-        ctx->ev_used += 2;
-    }
+    if (ctx->timing) ctx->ev_used += 2;
     ctx->summary_valid = !(flags & RH_TAIL_SKIP);  // the fused kernel's tail leaves the summary word of the state it wrote (words[3])
     ctx->pending_valid = (flags & RH_TAIL_CTRL) != 0;
     ctx->pre_valid = (flags & RH_TAIL_PRE) && !(flags & RH_TAIL_CTRL);
@@ -3894,7 +3797,7 @@ static int routed_core(rh_ctx *ctx, bool with_after) {
 static int routed_step_device(rh_ctx *ctx, bool sparse_wanted = false) {
     int rc;
     // sparse stores: another step of the same rh_run_steps call follows and no accumulator reads the planes in between
-    const bool sparse = sparse_wanted && ctx->sparse_ok && !ctx->diag_n && std::getenv("RH_ROUTED_SEPARATE_GATHERS") == nullptr;
+    const bool sparse = sparse_wanted && ctx->sparse_ok && !ctx->diag_n;
     RcclApi *api = nullptr;
     const bool ranks = ctx->comm && ctx->comm_nranks > 1;
     if (ctx->comm) {
@@ -3921,30 +3824,22 @@ static int routed_step_device(rh_ctx *ctx, bool sparse_wanted = false) {
         else hipExtLaunchKernelGGL(k_routed_a2<false>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev);
         if (ctx->timing) ctx->ev_used += 2;
     }
-    static const bool separate_gathers = std::getenv("RH_ROUTED_SEPARATE_GATHERS") != nullptr;   // A/B, tests: the 6-launch step
     const dim3 grid(grid_for(ctx->n)), block(RH_BLOCK);
     const int nx = (int)ctx->cfg.nx, ny = (int)ctx->cfg.ny;
     if ((rc = route_check(ctx, 0, "routed step"))) return rc;
     if (ranks && (rc = route_exchange(ctx, 0))) return rc;
-    if (separate_gathers) {
-        if ((rc = rh_route_gather_only(ctx, 0))) return rc;
-        LAUNCH_CELLS(ctx, k_routed_b);
-    } else if (sparse)
+    if (sparse)
         hipLaunchKernelGGL(k_routed_bg<true>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
     else
         hipLaunchKernelGGL(k_routed_bg<false>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
     if (ranks && (rc = route_exchange(ctx, 1))) return rc;
-    if (separate_gathers && (rc = rh_route_gather_only(ctx, 1))) return rc;
     // (the control kernel has advanced itt / time and rotated the scalars, scalars_update; the sanity word stays in words[2], where
     // rh_get_scalars reads it)
     if (ctx->diag_n) {   // the accumulators read the planes between the numerics and the rotation
-        if (separate_gathers) LAUNCH_CELLS(ctx, k_routed_c);
-        else hipLaunchKernelGGL((k_routed_cg<false, false>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
+        hipLaunchKernelGGL((k_routed_cg<false, false>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
         hipLaunchKernelGGL(k_diag, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, 0);
         LAUNCH_CELLS(ctx, k_after_timestep_oned);
-    } else if (separate_gathers)
-        LAUNCH_CELLS(ctx, k_routed_c_after);
-    else if (sparse)
+    } else if (sparse)
         hipLaunchKernelGGL((k_routed_cg<true, true>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
     else
         hipLaunchKernelGGL((k_routed_cg<true, false>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
@@ -4162,18 +4057,13 @@ int rh_run_steps_dist(rh_ctx *ctx, int64_t nsteps) {
             LAUNCH_WG(ctx, k_summary_reduce, ctx->dev, 0, send, src);
             CHECK_LAUNCH(ctx);
         }
-        static const bool copy_only = std::getenv("RH_DIST_COPY_ONLY") != nullptr;   // timing experiment (one rank): the exchange as a plain copy
-        if (copy_only && ctx->comm_nranks == 1)
-            HIPCHK(ctx, hipMemcpyAsync(recv, send, 64 * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-        else
-            NCCLCHK(ctx, api->AllReduce(send, recv, 64, ncclInt32, ncclMax, ctx->comm, ctx->stream));
+        NCCLCHK(ctx, api->AllReduce(send, recv, 64, ncclInt32, ncclMax, ctx->comm, ctx->stream));
         // the fused launch in front of the exchange formed the columns-independent half of this control part (pre_tail): the kernel behind
         // the exchange keeps the decisions
         LAUNCH_ONE(ctx, k_ctrl, ctx->dev, 1, RH_SRC_WORD3, (const int *)recv, ctx->pre_valid ? 1 : 0);
         CHECK_LAUNCH(ctx);
         ctx->sparse_next = ctx->sparse_ok && k + 1 < nsteps;
-        static const bool pre_ok = std::getenv("RH_NO_PRE_TAIL") == nullptr;
-        int rc = launch_fused_kernel(ctx, -1, pre_ok ? (RH_TAIL_PRE | RH_TAIL_HOOKS) : 0, send);   // the tail spreads the next step's summary word into `send`
+        int rc = launch_fused_kernel(ctx, -1, RH_TAIL_PRE | RH_TAIL_HOOKS, send);   // the tail spreads the next step's summary word into `send`
         if (rc) return rc;
     }
     return RH_OK;
@@ -4330,13 +4220,7 @@ int rh_calibrate_copy(rh_ctx *ctx, int src_plane0, int dst_plane0, int nplanes) 
     for (int p = 0; p < nplanes; ++p)
         if (PLANE_IS_INT[src_plane0 + p] || PLANE_IS_INT[dst_plane0 + p]) return fail(ctx, RH_ERR_ARG, "calibration planes must be float64");
     planes_touched(ctx);
-    Arena probe = ctx->arena;
-    if (const char *sh = std::getenv("RH_CALIB_SHIFT_KB")) {   // experiment (tools/arena_phase.py): the same copy shifted inside the allocation's padding
-        const size_t shift = (size_t)std::atoll(sh) * 1024;
-        if (shift > ctx->arena_pad) return fail(ctx, RH_ERR_ARG, "RH_CALIB_SHIFT_KB exceeds RH_ARENA_PAD_KB");
-        probe.base = ctx->arena.base + shift;
-    }
-    hipLaunchKernelGGL(k_calib_copy, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, probe, src_plane0, dst_plane0, nplanes);
+    hipLaunchKernelGGL(k_calib_copy, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, src_plane0, dst_plane0, nplanes);
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -4348,9 +4232,6 @@ int rh_debug_swap_arenas(rh_ctx *a, rh_ctx *b) {
     HIPCHK(a, hipStreamSynchronize(a->stream));
     HIPCHK(b, hipStreamSynchronize(b->stream));
     std::swap(a->arena.base, b->arena.base);
-    std::swap(a->arena_alloc, b->arena_alloc);
-    std::swap(a->arena_offset, b->arena_offset);
-    std::swap(a->arena_pad, b->arena_pad);
     a->pmask_valid = b->pmask_valid = false;   // (the wave words describe the planes of the arena a context steps on)
     return RH_OK;
 }
