@@ -58,9 +58,19 @@ def _object_header(messages):
     return struct.pack("<BxHII4x", 1, len(messages), 1, len(data)) + data
 
 
+class Deferred:
+    """A contiguous dataset whose data `create` leaves to be written block by block (`StreamFile.put`)."""
+
+    def __init__(self, shape, dtype):
+        self.shape = tuple(int(d) for d in shape)
+        self.dtype = np.dtype(_DTYPES[np.dtype(dtype).name][0])
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+
+
 class _Writer:
     def __init__(self):
         self.buf = bytearray()
+        self.deferred = []   # (Deferred, position of its address field)
 
     def alloc(self, data, align=8):
         while len(self.buf) % align:
@@ -70,6 +80,14 @@ class _Writer:
         return addr
 
     def dataset(self, arr):
+        if isinstance(arr, Deferred):   # header now, data region at the end of the file (`create`)
+            space = struct.pack("<BBB5x", 1, len(arr.shape), 0) + b"".join(struct.pack("<Q", int(d)) for d in arr.shape)
+            msgs = [_message(0x0001, space), _message(0x0003, _datatype_message(arr.dtype)), _message(0x0005, bytes([2, 2, 0, 0])),
+                    _message(0x0008, struct.pack("<BBQQ", 3, 1, UNDEF, arr.nbytes))]
+            hdr = self.alloc(_object_header(msgs))
+            # where the layout message's address field lies: header prefix, the three messages before it, its own 8-byte prefix, 2 B
+            self.deferred.append((arr, hdr + 16 + sum(len(m) for m in msgs[:3]) + 8 + 2))
+            return hdr
         arr = np.asarray(arr)
         if arr.dtype == np.bool_:
             arr = arr.astype(np.int8)
@@ -113,6 +131,17 @@ class _Writer:
 
 def write(path, groups):
     """groups: {group name: {dataset name: array}} -> an HDF5 file with those groups under the root."""
+    _layout(path, groups)
+
+
+def create(path, groups):
+    """As `write`, where datasets may be `Deferred(shape, dtype)`: everything else is written now, the file is extended to its full
+    length (the data regions of the deferred datasets are holes until written) and a `StreamFile` writes their data by element
+    offset -- a dataset larger than the host's memory is written block by block."""
+    return StreamFile(path, _layout(path, groups), "r+b")
+
+
+def _layout(path, groups):
     n_max = max([len(groups)] + [len(v) for v in groups.values()] + [1])
     leaf_k = max(4, (n_max + 1) // 2)
     w = _Writer()
@@ -122,13 +151,63 @@ def write(path, groups):
         entries = {name: w.dataset(arr) for name, arr in dsets.items()}
         top[gname] = w.group(entries, leaf_k)[0]
     root_hdr, root_tree, root_heap = w.group(top, leaf_k)
+    end = _pad8(len(w.buf)) if w.deferred else len(w.buf)   # (a file without deferred data: exactly the metadata and data above)
+    where = {}
+    for d, pos in w.deferred:   # the data of the deferred datasets goes behind the metadata, in declaration order
+        w.buf[pos:pos + 8] = struct.pack("<Q", end)
+        where[id(d)] = (end, d)
+        end = _pad8(end + d.nbytes)
     sb = SIG + bytes([0, 0, 0, 0, 0, 8, 8, 0]) + struct.pack("<HHI", leaf_k, 16, 0)
-    sb += struct.pack("<QQQQ", 0, UNDEF, len(w.buf), UNDEF)
+    sb += struct.pack("<QQQQ", 0, UNDEF, end, UNDEF)
     sb += struct.pack("<QQII", 0, root_hdr, 1, 0) + struct.pack("<QQ", root_tree, root_heap)
     assert len(sb) == 96
     w.buf[:96] = sb
     with open(path, "wb") as f:
-        f.write(bytes(w.buf))
+        f.write(w.buf)
+        if end > len(w.buf):
+            f.truncate(end)
+    return {(g, k): where[id(a)] for g, dsets in groups.items() for k, a in dsets.items() if isinstance(a, Deferred)}
+
+
+class StreamFile:
+    """Element-addressed access to the contiguous datasets of a file: `put` / `get` of `count` elements from element `first` of the
+    flattened (C order) dataset, through the file descriptor -- no more of the file is held in memory than the block asked for."""
+
+    def __init__(self, path, where, mode):
+        self._f = open(path, mode)
+        self._where = where   # (group, name) -> (data address, Deferred-like with shape / dtype)
+
+    def shape(self, group, name):
+        return self._where[(group, name)][1].shape
+
+    def _span(self, group, name, first, count):
+        addr, d = self._where[(group, name)]
+        total = d.nbytes // d.dtype.itemsize
+        if first < 0 or count < 0 or first + count > total:
+            raise IndexError(f"h5lite: elements [{first}, {first + count}) of {group}/{name} (size {total})")
+        return addr + first * d.dtype.itemsize, d.dtype
+
+    def put(self, group, name, first, data):
+        off, dt = self._span(group, name, int(first), int(np.size(data)))
+        self._f.seek(off)
+        self._f.write(memoryview(np.ascontiguousarray(data, dtype=dt)).cast("B"))
+
+    def get(self, group, name, first, count):
+        off, dt = self._span(group, name, int(first), int(count))
+        out = np.empty(int(count), dtype=dt)
+        self._f.seek(off)
+        if self._f.readinto(memoryview(out).cast("B")) != out.nbytes:
+            raise ValueError(f"h5lite: {group}/{name} is truncated")
+        return out.astype(dt.newbyteorder("="), copy=False)
+
+    def close(self):
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -210,7 +289,9 @@ class _Reader:
         assert self.d[heap_addr:heap_addr + 4] == b"HEAP"
         data_addr = struct.unpack_from("<Q", self.d, heap_addr + 24)[0]
         start = data_addr + off
-        end = self.d.index(b"\0", start)
+        end = self.d.find(b"\0", start)   # (find: a memory map has no index)
+        if end < 0:
+            raise ValueError("h5lite: unterminated name in a local heap")
         return self.d[start:end].decode()
 
     def _tree_leaves(self, addr):
@@ -355,6 +436,21 @@ class _Reader:
             raise ValueError(f"h5lite: datatype class {cls} is not supported")
         return np.dtype((">" if big else "<") + kind + str(size))
 
+    def contiguous(self, hdr_addr):
+        """(data address, Deferred-like description) of a contiguous dataset, None for any other layout."""
+        msgs = dict(self.messages(hdr_addr))
+        lay = msgs.get(0x0008)
+        if lay is None or lay[0] != 3 or lay[1] != 1 or 0x000B in msgs:
+            return None
+        b = msgs[0x0001]
+        pos = 8 if b[0] == 1 else 4
+        shape = tuple(struct.unpack_from("<Q", b, pos + 8 * i)[0] for i in range(b[1]))
+        addr = struct.unpack_from("<Q", lay, 2)[0]
+        d = Deferred.__new__(Deferred)
+        d.shape, d.dtype = shape, self._dtype(msgs[0x0003])
+        d.nbytes = int(np.prod(shape, dtype=np.int64)) * d.dtype.itemsize
+        return (addr, d) if addr != UNDEF else None
+
     def dataset(self, hdr_addr):
         msgs = self.messages(hdr_addr)
         shape = dtype = layout = None
@@ -445,6 +541,33 @@ def read_root(path):
 def is_hdf5(path):
     with open(path, "rb") as f:
         return f.read(8) == SIG
+
+
+def open_blocks(path, streamed=()):
+    """({group: {name: array}} of the datasets, StreamFile over the contiguous ones named in `streamed`) -- those are not read: the
+    metadata is parsed through a memory map, their data is read block by block (`StreamFile.get`)."""
+    import mmap
+
+    with open(path, "rb") as f:
+        m = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    try:
+        r = _Reader(m)
+        small, where = {}, {}
+        for gname, addr in r.group(r.root).items():
+            if not r.is_group(addr):
+                continue
+            small[gname] = {}
+            for k, a in r.group(addr).items():
+                if r.is_group(a):
+                    continue
+                c = r.contiguous(a)
+                if c is not None and k in streamed:
+                    where[(gname, k)] = c
+                else:
+                    small[gname][k] = r.dataset(a)
+        return small, StreamFile(path, where, "rb")
+    finally:
+        m.close()
 
 
 def read(path):

@@ -20,7 +20,28 @@ roger/restart.py:32-67, 129-174), so that states can go back and forth between t
 Driven like the reference: `settings.restart_input_filename` is read at the end of `setup()` (roger/roger.py:324-326),
 `settings.restart_output_filename` (Python format syntax over the variables and settings, :156-158) is written every
 `settings.restart_frequency` seconds at the start of a step (:385-386) and, with `settings.write_restart`, at the end of `run()`
-(:578-579); `runtime_settings.diskless_mode` suppresses writing (:134)."""
+(:578-579); `runtime_settings.diskless_mode` suppresses writing (:134).
+
+Offline transport (settings.enable_offline_transport, the SAS model) -- same settings, same groups, its own contents:
+* "core": the names of `REFERENCE_RESTART_VARIABLES` the transport registry has (the grid, the clock, the storages of the SVAT run it
+  reads); "hip_core": the rest of what the next day step reads -- the per-cell variables of the SAS context (concentrations, solute
+  masses, age statistics, parameters) and of the host (the snow signal and the other time levels the hooks read back), `ages` /
+  `nages`, `warmup_done` (0-d) and the tracer / solver codes of the run (`sas_tracer`: index in `_TRACERS`, `sas_solver`:
+  _native.SAS_SOLVERS), against which `read_restart` checks the model -- and the age-resolved storages sa_rz, sa_ss, msa_rz, msa_ss, sa_s,
+  msa_s as (nx, ny, ages) datasets: the interior of time level tau, the only level the device holds (both levels agree after a step).
+* Left out: the forcing series (x, y, t) that set_forcing_setup rebuilds (PREC_DIST_DAILY, INF_*, C_IN, C_ISO_IN ...), the
+  distributions tt_*, mtt_*, TT_* (every step rewrites them before anything reads them) and the host-side age diagnostics SA_*,
+  csa_* (set by the script's initial conditions, never touched by the step): at 10^6 columns x 1000 ages each of these is 8 GB.
+* The age-resolved storages never exist on the host in full: they are streamed between the SAS context and the file in blocks of
+  `BLOCK_BYTES` (rh_sas_download_cells / rh_sas_upload_cells), so a write holds one block of them at a time.  Several ranks: rank 0
+  writes the file; the other ranks send their blocks to it one at a time over the process group (torch.distributed send / recv), so
+  no rank holds more than a block either (verified over gloo; the send / recv of device tensors under NCCL / RCCL is not tested).  Each
+  rank reads its own cells back.  Nothing on the write path reads an age-resolved `vs.<name>`: that would download the whole array
+  into its host mirror (`_restart_filename` picks the scalars by their metadata for that reason).
+* Container: h5py where it is installed, otherwise h5lite's block-wise writer / reader (`h5lite.create`, `h5lite.open_blocks`).
+* Not claimed: that the reference's reader accepts a transport file.  No restart file of the reference's transport models is
+  available to check against; what is checked is that an interrupted run continues bit for bit
+  (tests/test_host_package_sas_restart.py, tests/test_hip_sas_restart.py)."""
 import os
 
 import numpy as np
@@ -103,8 +124,12 @@ def _read_file(path):
 
 
 def _restart_filename(state, template):
+    """The template formatted with the scalars and the settings.  The scalars are picked by their metadata (no dims): an array is never
+    read here -- for the transport model that would download every age-resolved variable a step left newer on the device."""
     statedict = {}
-    for key in state.var_meta:
+    for key, var in state.var_meta.items():
+        if var.dims is not None:
+            continue
         try:
             v = np.asarray(getattr(state.variables, key))
         except Exception:   # noqa: BLE001
@@ -175,6 +200,249 @@ def collect(state):
     return groups
 
 
+# ---- offline transport ----------------------------------------------------------------------------------------------------------------
+AGE_STATE = ("sa_rz", "sa_ss", "msa_rz", "msa_ss", "sa_s", "msa_s")   # streamed (nx, ny, ages) datasets
+BLOCK_BYTES = 64 << 20   # age-resolved data per block of columns (upload / download / file / process group)
+_TRACERS = ("oxygen18", "deuterium", "bromide", "chloride", "virtualtracer")   # the codes of `sas_tracer` in a file
+
+
+def _transport_small(state):
+    """{group: {name: array}} of everything but the age-resolved storages (global arrays on rank 0, None on the other ranks)."""
+    vs, settings = state.variables, state.settings
+    multi = rst.proc_num > 1
+    core, more = {}, {}
+    for key, var in state.var_meta.items():
+        dims = tuple(var.dims or ())
+        if key in _NOT_STATE or key in AGE_STATE or "t" in dims or (dims[:2] == ("x", "y") and ("ages" in dims or "nages" in dims)):
+            continue
+        if var.sas is not None and not _held(state.sas_context, var.sas):
+            continue   # (a variable of the registry whose array this tracer's context does not allocate, e.g. M_evap_soil)
+        val = np.asarray(getattr(vs, key))
+        if multi and dims[:2] == ("x", "y"):
+            val = _gather_global(state, key, val)
+        elif multi and dims in (("x",), ("y",)):
+            val = _gather_coordinate(state, key, val)
+        (core if key in REFERENCE_RESTART_VARIABLES else more)[key] = val
+    from . import _native
+
+    more["warmup_done"] = np.array(int(bool(settings.warmup_done)), dtype=np.int64)
+    more["sas_tracer"] = np.array(_TRACERS.index(state.sas_context.tracer), dtype=np.int64)
+    more["sas_solver"] = np.array(_native.SAS_SOLVERS[state.sas_context.solver], dtype=np.int64)
+    return {"core": core, MORE_GROUP: more}
+
+
+def _held(sas, name):
+    try:
+        sas.shape(name)
+    except (KeyError, RuntimeError):
+        return False
+    return True
+
+
+def _block_cells(sas):
+    return max(1, BLOCK_BYTES // (8 * sas.ages))
+
+
+def _row_runs(nx, ny, rank, first, count):
+    """The runs of cells [first, first + count) of a rank's block (C order over its (nxl, nyl) cells) along the global grid's rows:
+    (offset in the block, global x, global y of the run's first cell, length)."""
+    (gx, gy), _ = distributed.get_chunk_slices(nx, ny, rs.num_proc, rank)
+    nyl = gy.stop - gy.start
+    c = first
+    while c < first + count:
+        i, j = divmod(c, nyl)
+        n = min(nyl - j, first + count - c)
+        yield c - first, gx.start + i, gy.start + j, n
+        c += n
+
+
+def _p2p_device():
+    """Where point-to-point blocks travel from: host memory over gloo, the rank's device over NCCL / RCCL.  Only the gloo path is
+    exercised by the tests (tests/test_host_package_sas_restart.py, two CPU ranks); the NCCL / RCCL path is not verified."""
+    import torch
+    import torch.distributed as dist
+
+    return torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+
+
+def _gather_coordinate(state, key, local):
+    """The global (x,) / (y,) coordinate of a grid split over several ranks, on rank 0; None elsewhere."""
+    import torch.distributed as dist
+
+    world, rank = rst.proc_num, rst.proc_rank
+    parts = [None] * world if rank == 0 else None
+    dist.gather_object(np.asarray(local), parts, dst=0)
+    if rank != 0:
+        return None
+    axis = state.var_meta[key].dims[0]
+    nx, ny = state.settings.nx, state.settings.ny
+    out = np.zeros((nx if axis == "x" else ny) + 4, dtype=local.dtype)
+    for r, part in enumerate(parts):
+        g, l = distributed.get_chunk_slices(nx, ny, rs.num_proc, r, include_overlap=True)
+        k = 0 if axis == "x" else 1
+        out[g[k]] = part[l[k]]
+    return out
+
+
+class _H5pyBlocks:
+    """The block-wise file of `_write_transport` / `_read_transport` over h5py."""
+
+    def __init__(self, path, groups, mode):
+        import h5py
+
+        self.f = h5py.File(path, mode)
+        if mode == "w":
+            for gname, dsets in groups.items():
+                g = self.f.require_group(gname)
+                for k, a in dsets.items():
+                    if isinstance(a, h5lite.Deferred):
+                        g.create_dataset(k, shape=a.shape, dtype=a.dtype)
+                    else:
+                        a = np.asarray(a)
+                        g.create_dataset(k, data=a.astype(np.int8) if a.dtype == np.bool_ else a)
+
+    def has(self, group, name):
+        return group in self.f and name in self.f[group]
+
+    def shape(self, group, name):
+        return self.f[group][name].shape
+
+    def put_row(self, group, name, x, y, rows):
+        self.f[group][name][x, y:y + len(rows)] = rows
+
+    def get_row(self, group, name, x, y, n):
+        return self.f[group][name][x, y:y + n]
+
+    def close(self):
+        self.f.close()
+
+
+class _LiteBlocks:
+    """The same over h5lite's StreamFile (contiguous (nx, ny, ages) datasets: a row run is one contiguous range)."""
+
+    def __init__(self, stream):
+        self.s = stream
+
+    def has(self, group, name):
+        return (group, name) in self.s._where
+
+    def shape(self, group, name):
+        return self.s.shape(group, name)
+
+    def put_row(self, group, name, x, y, rows):
+        nx, ny, ages = self.s.shape(group, name)
+        self.s.put(group, name, (x * ny + y) * ages, rows)
+
+    def get_row(self, group, name, x, y, n):
+        nx, ny, ages = self.s.shape(group, name)
+        return self.s.get(group, name, (x * ny + y) * ages, n * ages).reshape(n, ages)
+
+    def close(self):
+        self.s.close()
+
+
+def _write_transport(state, fname):
+    import torch
+    import torch.distributed as dist
+
+    vs, settings, sas = state.variables, state.settings, state.sas_context
+    vs.flush_to_device()
+    groups = _transport_small(state)
+    rank, world = rst.proc_rank, rst.proc_num
+    names = [k for k in AGE_STATE if k in state.var_meta]
+    out = None
+    if rank == 0:
+        logger.info(f"Writing restart file {fname}")
+        for k in names:
+            groups[MORE_GROUP][k] = h5lite.Deferred((settings.nx, settings.ny, sas.ages), np.float64)
+        out = _H5pyBlocks(fname, groups, "w") if _h5py() is not None else _LiteBlocks(h5lite.create(fname, groups))
+    step = _block_cells(sas)
+    dev = _p2p_device() if world > 1 else None
+    try:
+        for k in names:
+            for first in range(0, sas.n, step):   # (every rank holds the same number of cells: the blocks line up)
+                count = min(step, sas.n - first)
+                block = sas.download_cells(k, first, count)
+                if rank != 0:
+                    dist.send(torch.from_numpy(block).to(dev), dst=0)
+                    continue
+                for r in range(world):
+                    if r:
+                        t = torch.empty(block.shape, dtype=torch.float64, device=dev)
+                        dist.recv(t, src=r)
+                        block = t.cpu().numpy()
+                    for off, x, y, n in _row_runs(settings.nx, settings.ny, r, first, count):
+                        out.put_row(MORE_GROUP, k, x, y, block[off:off + n])
+    finally:
+        if out is not None:
+            out.close()
+
+
+def _read_transport(state, fname):
+    """The transport branch of `read_restart`: checks the file against the model, assigns the small variables, streams the age-resolved
+    storages of this rank's cells into the SAS context."""
+    from . import _native
+
+    vs, settings, sas = state.variables, state.settings, state.sas_context
+    if _h5py() is not None:
+        blocks = _H5pyBlocks(fname, None, "r")
+        small = {g: {k: np.asarray(v) for k, v in grp.items() if k not in AGE_STATE} for g, grp in blocks.f.items()}
+    else:
+        small, stream = h5lite.open_blocks(fname, streamed=AGE_STATE)
+        blocks = _LiteBlocks(stream)
+    try:
+        more = small.get(MORE_GROUP, {})
+        if "sas_tracer" not in more or not blocks.has(MORE_GROUP, "sa_rz"):
+            raise RuntimeError(f"{fname} is not a restart file of the offline transport model")
+        want = dict(sas_tracer=_TRACERS.index(sas.tracer), sas_solver=_native.SAS_SOLVERS[sas.solver])
+        for k, v in want.items():
+            if int(more[k]) != v:
+                raise RuntimeError(f"{fname} was written with {k} = {int(more[k])}, the model has {v} ({sas.tracer}, {sas.solver})")
+        shape = tuple(blocks.shape(MORE_GROUP, "sa_rz"))
+        if shape[:2] != (settings.nx, settings.ny):
+            raise RuntimeError(f"{fname} holds a {shape[0]} x {shape[1]} grid, the model has {settings.nx} x {settings.ny}")
+        if shape[2] != settings.ages or np.asarray(more.get("ages", ())).shape != (settings.ages,) or \
+                np.asarray(more.get("nages", ())).shape != (settings.nages,):
+            raise RuntimeError(f"{fname} holds {shape[2]} age classes, the model has settings.ages = {settings.ages}")
+        vs.flush_to_device()   # (what setup() assigned must not overwrite the streamed storages at the next native call)
+        nx, ny = settings.nx, settings.ny
+        (gx, gy), (lx, ly) = distributed.get_chunk_slices(nx, ny, rs.num_proc, rst.proc_rank, include_overlap=True)
+        with vs.unlock():
+            for gname in ("core", MORE_GROUP):
+                for key, val in small.get(gname, {}).items():
+                    if key not in state.var_meta or key in _NOT_STATE:
+                        continue
+                    var = state.var_meta[key]
+                    val = np.asarray(val)
+                    if var.dims is None:
+                        setattr(vs, key, val.item())
+                        continue
+                    if rst.proc_num > 1 and tuple(var.dims[:2]) == ("x", "y"):
+                        local = np.array(getattr(vs, key))
+                        local[lx, ly] = val[gx, gy]
+                        val = local
+                    elif rst.proc_num > 1 and tuple(var.dims) in (("x",), ("y",)):
+                        g, l = (gx, lx) if var.dims[0] == "x" else (gy, ly)
+                        local = np.array(getattr(vs, key))
+                        local[l] = val[g]
+                        val = local
+                    setattr(vs, key, val.astype(np.asarray(getattr(vs, key)).dtype))
+        with settings.unlock():
+            settings.warmup_done = bool(int(more["warmup_done"]))
+        vs.flush_to_device()
+        step = _block_cells(sas)
+        buf = np.empty((min(step, sas.n), sas.ages))
+        for k in (k for k in AGE_STATE if k in state.var_meta):
+            for first in range(0, sas.n, step):
+                count = min(step, sas.n - first)
+                for off, x, y, n in _row_runs(nx, ny, rst.proc_rank, first, count):
+                    buf[off:off + n] = blocks.get_row(MORE_GROUP, k, x, y, n)
+                sas.upload_cells(k, first, buf[:count])
+        vs.mark_device_newer([k for k in AGE_STATE if k in state.var_meta])
+    finally:
+        blocks.close()
+
+
 def write_restart(state, force=False, filename=None):
     """roger/restart.py:129-174.  Returns the file name (None if nothing was due)."""
     vs, settings = state.variables, state.settings
@@ -188,6 +456,9 @@ def write_restart(state, force=False, filename=None):
     if not write_now:
         return None
     fname = _restart_filename(state, str(template))
+    if state.settings.enable_offline_transport:
+        _write_transport(state, fname)
+        return fname
     groups = collect(state)
     if rst.proc_rank == 0:
         logger.info(f"Writing restart file {fname}")
@@ -208,6 +479,9 @@ def read_restart(state, filename=None):
     if not os.path.isfile(fname):
         raise IOError(f"restart file {fname} not found")
     logger.info(f"Reading restart data from {fname}")
+    if settings.enable_offline_transport:
+        _read_transport(state, fname)
+        return fname
     groups = _read_file(fname)
     if "core" not in groups:
         raise RuntimeError(f"{fname} has no group 'core': not a RoGeR restart file")

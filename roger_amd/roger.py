@@ -159,15 +159,22 @@ class RogerSetup(metaclass=abc.ABCMeta):
 
         if self.state.settings.enable_offline_transport:
             with self.state.timers["warmup"]:
-                for _ in range(repeat):
-                    self.run()
-                    soil.rescale_SA(self.state)
+                self._in_warmup = True   # (the warm-up runs write no restart file, neither restart_frequency's nor run()'s: the one
+                # below holds the rescaled state)
+                try:
+                    for _ in range(repeat):
+                        self.run()
+                        soil.rescale_SA(self.state)
+                finally:
+                    self._in_warmup = False
                 with self.state.variables.unlock():
                     self.state.variables.itt = 0
                     self.state.variables.time = 0
         with self.state.settings.unlock():
             self.state.settings.warmup_done = True
         diagnostics.output_transport(self.state)   # initial values after the warm-up, roger/roger.py:515-521
+        if self.state.settings.enable_offline_transport and self.state.settings.write_restart:
+            restart.write_restart(self.state, force=True)   # a warm-up that later runs can start from
 
     def _upload_luts(self):
         vs = self.state.variables
@@ -235,6 +242,9 @@ class RogerSetup(metaclass=abc.ABCMeta):
         from .core import transport
 
         vs = state.variables
+        if state.settings.restart_frequency > 0 and not getattr(self, "_in_warmup", False):
+            with state.timers["diagnostics"]:
+                restart.write_restart(state)   # at the start of a day step, as in step(); not during the warm-up runs
         with state.timers["main"]:
             with vs.unlock():
                 vs.itt = vs.itt + 1   # skip first iteration which contains initial values
@@ -398,7 +408,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
         else:
             failed = False
         finally:
-            if settings.write_restart and not settings.enable_offline_transport and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
+            in_warmup = settings.enable_offline_transport and getattr(self, "_in_warmup", False)
+            if settings.write_restart and not in_warmup and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
         diagnostics.close(self.state)

@@ -58,7 +58,9 @@ def allocate(dimensions, grid, dtype=None, include_ghosts=True, local=True, fill
     """roger/variables.py:6423-6435: host array of the reference's shape (read-only, like there)."""
     if dtype is None:
         dtype = np.float64
-    out = np.full(get_shape(dimensions, grid, include_ghosts=include_ghosts, local=local), fill, dtype=dtype)
+    shape = get_shape(dimensions, grid, include_ghosts=include_ghosts, local=local)
+    # (zeros: pages the host never writes stay unmapped -- the age-resolved mirrors of the transport model are gigabytes each)
+    out = np.zeros(shape, dtype=dtype) if fill == 0 else np.full(shape, fill, dtype=dtype)
     out.flags.writeable = False
     return out
 
