@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "rh_host.h"
 #include "roger_hip.h"
 #include "roger_hip_sas.h"
 #include "rh_sas_dev.h"
@@ -69,15 +70,13 @@ __global__ void k_selftest_pow(const double *x, const double *k, double *out, in
 // host side: context and C ABI
 // ---------------------------------------------------------------------------------------------
 struct rh_sas_ctx {
-    rh_sas_config cfg;
-    hipStream_t stream;
-    bool own_stream;
-    void *arr[SA_COUNT];
-    int64_t elems[SA_COUNT];
-    int *unsupported;
-    bool timing;
-    std::vector<hipEvent_t> events;
-    size_t ev_used;
+    Stream stream;                   // first member: destroyed last, after everything that was enqueued on it has been released
+    rh_sas_config cfg = {};
+    DevBuf<void> arr[SA_COUNT];      // the arrays of rh_sas_arrays.def this configuration holds
+    int64_t elems[SA_COUNT] = {};
+    DevBuf<int> unsupported;
+    bool timing = false;
+    EventPool events;                // pairs (start, stop) around the day's launch
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -155,32 +154,22 @@ int rh_sas_create(const rh_sas_config *cfg, rh_sas_ctx **out) {
     rh_sas_ctx *ctx = new (std::nothrow) rh_sas_ctx();
     if (!ctx) return sfail(nullptr, RH_ERR_ARG, "rh_sas_create: out of host memory");
     ctx->cfg = *cfg;
-    ctx->stream = nullptr;
-    ctx->own_stream = false;
-    ctx->unsupported = nullptr;
-    ctx->timing = false;
-    ctx->ev_used = 0;
-    for (int a = 0; a < SA_COUNT; ++a) {
-        ctx->arr[a] = nullptr;
-        ctx->elems[a] = 0;
-    }
     auto bail = [&](hipError_t e, const char *what) {
         std::string msg = std::string(what) + ": " + hipGetErrorString(e);
         rh_sas_destroy(ctx);
         return sfail(nullptr, RH_ERR_HIP, msg);
     };
     hipError_t e;
-    if ((e = hipStreamCreate(&ctx->stream)) != hipSuccess) return bail(e, "hipStreamCreate");
-    ctx->own_stream = true;
+    if ((e = ctx->stream.create()) != hipSuccess) return bail(e, "hipStreamCreate");
     for (int a = 0; a < SA_COUNT; ++a) {
         const int64_t ne = sas_elems(*cfg, a);
         if (!ne) continue;
         const size_t bytes = (size_t)ne * (SAS_KIND[a] == K_MASK ? sizeof(int32_t) : sizeof(double));
-        if ((e = hipMalloc(&ctx->arr[a], bytes)) != hipSuccess) return bail(e, "hipMalloc(SAS array)");
+        if ((e = ctx->arr[a].alloc(bytes)) != hipSuccess) return bail(e, "hipMalloc(SAS array)");
         if ((e = hipMemsetAsync(ctx->arr[a], 0, bytes, ctx->stream)) != hipSuccess) return bail(e, "hipMemset");
         ctx->elems[a] = ne;
     }
-    if ((e = hipMalloc((void **)&ctx->unsupported, sizeof(int))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = ctx->unsupported.alloc(sizeof(int))) != hipSuccess) return bail(e, "hipMalloc");
     if ((e = hipMemsetAsync(ctx->unsupported, 0, sizeof(int), ctx->stream)) != hipSuccess) return bail(e, "hipMemset");
     {   // maskCatch defaults to 1 (roger/variables.py)
         std::vector<int32_t> ones((size_t)cfg->n_cells, 1);
@@ -201,20 +190,12 @@ int rh_sas_create(const rh_sas_config *cfg, rh_sas_ctx **out) {
 void rh_sas_destroy(rh_sas_ctx *ctx) {
     if (!ctx) return;
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (auto &ev : ctx->events) (void)hipEventDestroy(ev);
-    for (int a = 0; a < SA_COUNT; ++a)
-        if (ctx->arr[a]) (void)hipFree(ctx->arr[a]);
-    if (ctx->unsupported) (void)hipFree(ctx->unsupported);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
 int rh_sas_set_stream(rh_sas_ctx *ctx, void *hip_stream) {
     if (!ctx) return RH_ERR_ARG;
-    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->own_stream) SHIPCHK(ctx, hipStreamDestroy(ctx->stream));
-    ctx->stream = (hipStream_t)hip_stream;
-    ctx->own_stream = false;
+    SHIPCHK(ctx, ctx->stream.adopt((hipStream_t)hip_stream));
     return RH_OK;
 }
 
@@ -274,7 +255,7 @@ int rh_sas_upload_cells(rh_sas_ctx *ctx, int a, int64_t first_cell, int64_t n_ce
     size_t off;
     const int rc = sas_check_cells(ctx, a, first_cell, n_cells, bytes, host, "rh_sas_upload_cells", &off);
     if (rc) return rc;
-    SHIPCHK(ctx, hipMemcpyAsync((char *)ctx->arr[a] + off, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync((char *)ctx->arr[a].get() + off, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
@@ -283,7 +264,7 @@ int rh_sas_download_cells(rh_sas_ctx *ctx, int a, int64_t first_cell, int64_t n_
     size_t off;
     const int rc = sas_check_cells(ctx, a, first_cell, n_cells, bytes, host, "rh_sas_download_cells", &off);
     if (rc) return rc;
-    SHIPCHK(ctx, hipMemcpyAsync(host, (const char *)ctx->arr[a] + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(host, (const char *)ctx->arr[a].get() + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return rh_sas_sync(ctx);
 }
 
@@ -291,12 +272,12 @@ int rh_sas_set_daily_from_device(rh_sas_ctx *ctx, int a, int64_t day_row, const 
     if (!ctx) return RH_ERR_ARG;
     if (a < 0 || a >= SA_COUNT || SAS_KIND[a] != K_DAILY) return sfail(ctx, RH_ERR_ARG, "rh_sas_set_daily_from_device: not a daily input array");
     if (day_row < 0 || day_row >= ctx->cfg.forcing_days || !dev_src) return sfail(ctx, RH_ERR_ARG, "rh_sas_set_daily_from_device: bad row or null source");
-    SHIPCHK(ctx, hipMemcpyAsync((double *)ctx->arr[a] + day_row * ctx->cfg.n_cells, dev_src, (size_t)ctx->cfg.n_cells * sizeof(double),
+    SHIPCHK(ctx, hipMemcpyAsync((double *)ctx->arr[a].get() + day_row * ctx->cfg.n_cells, dev_src, (size_t)ctx->cfg.n_cells * sizeof(double),
                                 hipMemcpyDeviceToDevice, ctx->stream));
     return RH_OK;
 }
 
-void *rh_sas_array_device_ptr(rh_sas_ctx *ctx, int a) { return (ctx && a >= 0 && a < SA_COUNT) ? ctx->arr[a] : nullptr; }
+void *rh_sas_array_device_ptr(rh_sas_ctx *ctx, int a) { return (ctx && a >= 0 && a < SA_COUNT) ? ctx->arr[a].get() : nullptr; }
 
 int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
     if (!ctx) return RH_ERR_ARG;
@@ -323,16 +304,8 @@ int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
     for (int a = 0; a < SA_COUNT; ++a) args.a[a] = ctx->arr[a];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ctx->timing) {
-        if (ctx->ev_used + 2 > ctx->events.size()) {
-            for (int k = 0; k < 2; ++k) {
-                hipEvent_t ev;
-                SHIPCHK(ctx, hipEventCreate(&ev));
-                ctx->events.push_back(ev);
-            }
-        }
-        ev0 = ctx->events[ctx->ev_used];
-        ev1 = ctx->events[ctx->ev_used + 1];
-        ctx->ev_used += 2;
+        SHIPCHK(ctx, ctx->events.next_pair(&ev0, &ev1));
+        ctx->events.taken();
         SHIPCHK(ctx, hipEventRecord(ev0, ctx->stream));
     }
     if (c.solver != RH_SAS_SOLVER_DETERMINISTIC && (stages & RH_SAS_ALL)) {
@@ -413,21 +386,15 @@ static int selftest2(const double *x, const double *k, double *out, int64_t n, i
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on) {
     if (!ctx) return RH_ERR_ARG;
     ctx->timing = on != 0;
-    ctx->ev_used = 0;
+    ctx->events.restart();
     return RH_OK;
 }
 
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches) {
     if (!ctx || !total_ms || !launches) return RH_ERR_ARG;
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    double tot = 0;
-    for (size_t k = 0; k + 1 < ctx->ev_used; k += 2) {
-        float ms = 0;
-        SHIPCHK(ctx, hipEventElapsedTime(&ms, ctx->events[k], ctx->events[k + 1]));
-        tot += ms;
-    }
-    *total_ms = tot;
-    *launches = (int64_t)(ctx->ev_used / 2);
+    SHIPCHK(ctx, ctx->events.total_ms(total_ms));
+    *launches = (int64_t)ctx->events.launches();
     return RH_OK;
 }
 

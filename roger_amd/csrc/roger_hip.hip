@@ -25,8 +25,10 @@
 #include <cstdlib>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
+#include "rh_host.h"
 #include "rh_physics.h"
 #include "rh_sets.inc"
 #include "roger_hip.h"
@@ -150,49 +152,80 @@ struct HostExport {
     unsigned long long seq;
 };
 
+// What the device currently holds that the next step may reuse.  A wrong flag is a silent wrong result, so they are written by the
+// named events next to planes_touched (host side, below) and by nobody else, two local exceptions apart: pmask_valid, which
+// rh_debug_swap_arenas also clears, and sparse_next, the request of the stepping loops (SparseRequestScope).
+struct DeviceHolds {
+    // --- the planes.  Cleared by planes_touched (somebody other than the fused kernel is about to change planes)
+    bool pmask_valid = false;      // DevState::pmask describes the planes as they are now.  Set by form_param_mask
+    // lazy tau -> taum1 rotation (k_step<.,.,LAZY>): rot_consistent = the last thing that touched the planes was a complete fused step,
+    // i.e. X_m1 == X logically for every rotation pair (set by fused_step_enqueued); m1_stale = the X_m1 PLANES do not hold that yet
+    // (set by fused_step_enqueued after a lazy step, cleared by materialise_m1)
+    bool rot_consistent = false, m1_stale = false;
+    // --- the summary path.  Cleared by planes_touched; the per-cell fronts, which do not read the summary word, clear the ones of
+    // this group they outdate (summary_path_left)
+    bool summary_valid = false;    // the summary word (words[3]) describes the columns as they are in the arena now.  Set by
+                                   // fused_step_enqueued (unless RH_TAIL_SKIP) and by summary_from_arena for the exchange paths
+    bool routed_summary = false;   // routing: sumw holds the summary bits of the arena's state (posted by k_routed_a2).  Set by
+                                   // routed_step_enqueued
+    bool exch_valid = false;       // exch_buf[0..63] holds the summary word of the columns as they are now (written by the last fused
+                                   // kernel's tail: fused_step_enqueued).  Also cleared when the buffer is reused (allreduce_word) and when
+                                   // the device's control inputs change behind it (control_inputs_changed(on_device): a hook launch)
+    // --- the control part of the next step.  Set by fused_step_enqueued from the launch's tail flags; cleared by planes_touched and by
+    // control_inputs_changed (scalars, forcing, weights, the time limit, the step log, a hook launch: whatever the control part reads)
+    bool pending_valid = false;    // S_next / X_next hold the control part of the next step (formed by the last fused kernel's tail)
+    bool pre_valid = false;        // ... or, multi-GPU step: pre_words hold its columns-independent half (pre_tail of the last fused
+                                   // launch), for k_ctrl behind the exchange
+    int pending_hooks = 0;         // ... formed with / without the device-side hooks
+    // --- sparse stores (k_step<.,.,LAZY,SPARSE>, k_routed_*<true>)
+    bool sparse_next = false;      // the step being enqueued is followed by another step of the same rh_run_steps call.  Set by the
+                                   // stepping loops, consumed by launch_fused_kernel, never survives a call (SparseRequestScope)
+    bool outputs_stale = false;    // the last step did not store the pure-output planes (only ever true INSIDE a call, or after a call
+                                   // that failed half-way).  Set by fused_step_enqueued / routed_step_enqueued, as is
+    bool last_sparse = false;      // ... what rh_step_mode reports of the last step
+    // --- per-cell forcing: the parts of the DAY that the front kernels cache on the device.  Set by cell_forcing_changed (new weights or
+    // stations; first use) and by front_takes_over (the other front formed them last); each is cleared by the launch that re-forms
+    // its part (launch_pred1, launch_cell_agg, launch_cell_front)
+    bool agg_daily_stale = true;   // per-cell daily forcing sums must be re-formed
+    bool pred_daily_stale = true;  // the same for the day's forcing bits kept by k_pred1
+    bool front_daily_stale = true; // ... and for the one-launch front (k_cell_front: daily sums + DevState::day_word)
+    int last_front = 0;            // which of the two formed the day's cached parts last (1: k_pred1 ... k_select, 2: k_cell_front)
+};
+
 struct rh_ctx {
-    unsigned long long *pmask_buf = nullptr;   // DevState::pmask
-    bool pmask_valid = false;                   // ... describes the planes as they are now
-    int pmask_flags = 7;                        // bit 0: uniform loads, bit 1: derived parameters, bit 2: the catchment mask as a constant (RH_NO_PARAM_UNIFORM / RH_NO_PARAM_DERIVE / RH_NO_MASK_CONSTANT clear them)
-    HostExport *hexp = nullptr;      // pinned + mapped
+    Stream stream;                   // first member: destroyed last, after everything that was enqueued on it has been released
+    rh_config cfg = {};
+    int64_t n = 0;
+    Arena arena = {};                // what the kernels are given; arena.base is arena_mem
+    DevBuf<char> arena_mem;
+    DevBuf<DevState> dev;
+    PinnedBlock<HostExport> hexp;    // pinned + mapped
     unsigned long long hexp_seq = 0;
-    rh_config cfg;
-    int64_t n;
-    Arena arena;
-    DevState *dev;
-    hipStream_t stream;
-    bool own_stream;
-    double *forc_cell_buf[3];
-    double *weight_buf[3];
-    int *station_buf;
-    double *forc_multi_buf;
-    double *transpose_buf;   // staging of one (n, 144) per-cell forcing array before its transposition
-    double *agg_cell_buf;
-    void *series_buf;
-    double *mlms_buf;
-    bool per_cell;
-    bool summary_valid;   // the summary word (words[3]) describes the columns as they are in the arena now
-    bool routed_summary = false;     // routing: sumw holds the summary bits of the arena's state (posted by k_routed_a2)
+    DevBuf<unsigned long long> pmask_buf;   // DevState::pmask
+    int pmask_flags = 7;             // bit 0: uniform loads, bit 1: derived parameters, bit 2: the catchment mask as a constant (RH_NO_PARAM_UNIFORM / RH_NO_PARAM_DERIVE / RH_NO_MASK_CONSTANT clear them)
+    DevBuf<double> forc_cell_buf[3];
+    DevBuf<double> weight_buf[3];
+    DevBuf<int> station_buf;
+    DevBuf<double> forc_multi_buf;
+    DevBuf<double> transpose_buf;    // staging of one (n, 144) per-cell forcing array before its transposition
+    DevBuf<double> agg_cell_buf;
+    DevBuf<char> series_buf;
+    DevBuf<double> mlms_buf;
+    DevBuf<void> stage_buf;          // one contiguous plane (n * 8 bytes): uploads and downloads pass through it
+    bool per_cell = false;
+    bool forcing_set = false;
+    DeviceHolds held;
     bool routed_device_ok = true;    // RH_ROUTED_BY_ROUTINE: rh_run_steps takes rh_step_routed per step (A/B, tests)
     bool defer_select_ok = true;     // RH_NO_DEFERRED_SELECT: k_select stores the per-cell prec / ta itself (A/B, tests)
     int64_t cell_agg_split_min = 65536;   // columns from which the per-cell aggregates run as two kernels (RH_CELL_AGG_SPLIT_MIN: tests)
-    bool pending_valid;   // S_next / X_next hold the control part of the next step (formed by the last fused kernel's tail)
-    bool pre_valid = false;   // ... or, multi-GPU step: pre_words hold its columns-independent half (pre_tail of the last fused launch), for k_ctrl behind the exchange
-    int pending_hooks;    // ... formed with / without the device-side hooks
-    bool tail_ok;         // RH_NO_TAIL_CTRL unset
-    int n_groups;         // fused kernel: completion groups (about 64 workgroups each, at most RH_DONE_GROUPS)
-    // lazy tau -> taum1 rotation (k_step<.,.,LAZY>): rot_consistent = the last thing that touched the planes was a complete
-    // fused step, i.e. X_m1 == X logically for every rotation pair; m1_stale = the X_m1 PLANES do not hold that yet
-    bool rot_consistent, m1_stale, lazy_ok, diag_reads_m1;
-    // sparse stores (k_step<.,.,LAZY,SPARSE>): sparse_next = the step being enqueued is followed by another step of the same
-    // rh_run_steps call; outputs_stale = the last fused step did not store the pure-output planes (only ever true INSIDE a call,
-    // or after a call that failed half-way); diag_reads_sparse = an accumulator was given one of those planes
-    bool sparse_ok = true, sparse_next = false, outputs_stale = false, diag_reads_sparse = false, last_sparse = false;
+    bool tail_ok = true;             // RH_NO_TAIL_CTRL unset
+    int n_groups = 1;                // fused kernel: completion groups (about 64 workgroups each, at most RH_DONE_GROUPS)
+    bool lazy_ok = true;             // RH_NO_LAZY_ROTATION unset
+    bool diag_reads_m1 = false;      // an accumulator was given an X_m1 plane: the fused kernel does not skip those stores
+    bool sparse_ok = true;           // RH_NO_SPARSE_STORES unset
+    bool diag_reads_sparse = false;  // an accumulator was given a pure-output plane (the KEEP variant of the sparse kernel stores those)
     int64_t t_end = -1;              // rh_set_time_limit (host copy of DevState::t_end)
     int64_t call_sparse_steps = 0;   // steps of the most recent rh_run_steps / rh_run_steps_dist call that ran with sparse stores
-    bool agg_daily_stale;   // per-cell daily forcing sums must be re-formed (new weights; first use)
-    bool pred_daily_stale;  // the same for the day's forcing bits kept by k_pred1
-    bool front_daily_stale = true;   // ... and for the one-launch front (k_cell_front: daily sums + DevState::day_word)
     bool cell_front_ok = true;       // RH_PER_CELL_OLD_FRONT unset: per-cell forcing takes k_cell_front instead of the five predicate-generation launches
     int64_t cell_front_max = 2097152; // ... on grids up to this many columns (RH_CELL_FRONT_MAX).  Measured, round 4 (profiles/r04_per_cell_front.txt), ms
                                      // per step with the predicate kernels / with the front: 80 x 53 columns 0.055 / 0.039 (launch-bound: one
@@ -200,37 +233,32 @@ struct rh_ctx {
                                      // 0.261 / 0.252, 10^7 columns 2.15 / 2.23 (one thread doing a column's aggregates, plane reads and bits in
                                      // sequence is latency-bound; two of the five predicate kernels are grid-stride).  Before the slots of the
                                      // device-wide words and the completion counters had a cache line each, the front took 0.320 ms at 10^6.
-    int last_front = 0;              // which of the two formed the day's cached parts last (1 old, 2 new): the other re-forms them when it takes over
-    double *diag_buf;
-    long long *diag_steps_buf;
-    long long diag_interval;
-    int diag_n, diag_slots;
-    int pred_blocks;
-    bool forcing_set;
-    bool timing;
-    std::vector<hipEvent_t> events;  // pairs (start, stop) around the fused kernel, one per timed step
-    size_t ev_used;
-    int *dt_log_buf;
-    std::vector<double> probe_ms;   // placement probing: streaming-kernel time per candidate arena, the chosen one first
-    void *stage_buf;      // one contiguous plane (n * 8 bytes): uploads and downloads pass through it
+    DevBuf<double> diag_buf;
+    DevBuf<long long> diag_steps_buf;
+    long long diag_interval = 86400;
+    int diag_n = 0, diag_slots = 0;
+    int pred_blocks = 0;
+    bool timing = false;
+    EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step
+    DevBuf<int> dt_log_buf;
+    std::vector<double> probe_ms;    // placement probing: streaming-kernel time per candidate arena, the chosen one first
     // multi-GPU: RCCL communicator and the exchange buffers of the summary word (64 int32 sent, 64 received)
-    ncclComm_t comm;
-    bool own_comm;
-    int *exch_buf;
-    bool exch_valid;      // exch_buf[0..63] holds the summary word of the columns as they are now (written by the last fused kernel's tail)
-    int comm_nranks, comm_rank;
-    int grid_px, grid_py; // process grid of the communicator, ranks x-fastest (rh_comm_set_grid; default (nranks, 1))
-    int planes_held;      // planes the arena has slots for: all of them for a routing context, otherwise all but the routing's (the last
+    ncclComm_t comm = nullptr;
+    bool own_comm = false;
+    DevBuf<int> exch_buf;
+    int comm_nranks = 1, comm_rank = 0;
+    int grid_px = 1, grid_py = 1;    // process grid of the communicator, ranks x-fastest (rh_comm_set_grid; default (nranks, 1))
+    int planes_held = 0;  // planes the arena has slots for: all of them for a routing context, otherwise all but the routing's (the last
                           // ones of rh_fields.def) -- the tile stride of the non-routing contexts stays what it was before the routing was
                           // added (at 10^6 columns the fused step ran 13 % slower with nine more slots per tile: 2.21 instead of 2.14 GB,
                           // A/B on one box)
     // routing (settings.enable_routing_1D): the rank's own border and the one-cell halo frame of its neighbours, both in the frame
     // layout of F = 2 ny + 2 nx + 4 values (route_frame_parts: west / east columns, south / north rows, four corners)
-    double *route_q;      // q_out: [0, F) own border, [F, 2 F) halo frame
-    int *route_i;         // [0, F) own flow direction, [F, 2 F) own mask, [2 F, 3 F) halo flow direction, [3 F, 4 F) halo mask
-    bool route_halo[2];   // a halo column is present on that side (rh_route_set_halo or the RCCL exchange)
-    bool route_frame;     // the halo frame holds a neighbour's data; the gathers read it (a part without a neighbour holds zeros)
-    bool route_static_done;   // the neighbours' flow direction and mask have been exchanged over RCCL
+    DevBuf<double> route_q;          // q_out: [0, F) own border, [F, 2 F) halo frame
+    DevBuf<int> route_i;             // [0, F) own flow direction, [F, 2 F) own mask, [2 F, 3 F) halo flow direction, [3 F, 4 F) halo mask
+    bool route_halo[2] = {false, false};   // a halo column is present on that side (rh_route_set_halo or the RCCL exchange)
+    bool route_frame = false;        // the halo frame holds a neighbour's data; the gathers read it (a part without a neighbour holds zeros)
+    bool route_static_done = false;  // the neighbours' flow direction and mask have been exchanged over RCCL
     std::string err;
 };
 #define RH_DT_LOG_CAP 65536
@@ -2528,32 +2556,123 @@ static int fail(rh_ctx *ctx, int code, const std::string &msg) {
     } while (0)
 
 static inline unsigned grid_for(int64_t n) { return (unsigned)((n + RH_BLOCK - 1) / RH_BLOCK); }
-// any per-column kernel other than the fused step may change what the summary words describe
+
+// A host value into a member of the device's control block, on the context's stream.  The copy is asynchronous: `v` must live until
+// the caller has synchronised the stream -- a stack local, before it goes out of scope.
+template <class M, class V>
+static hipError_t dev_put(rh_ctx *ctx, M DevState::*member, const V &v) {
+    static_assert(sizeof(M) == sizeof(V), "the host value must have the member's size");
+    return hipMemcpyAsync(&(ctx->dev.get()->*member), &v, sizeof(M), hipMemcpyHostToDevice, ctx->stream);
+}
+template <class M>
+static hipError_t dev_zero(rh_ctx *ctx, M DevState::*member) {
+    return hipMemsetAsync(&(ctx->dev.get()->*member), 0, sizeof(M), ctx->stream);
+}
+
+// ---- the events that change what the device holds (DeviceHolds) ---------------------------------------------------------------
 // The X_m1 planes from the X planes, if lazy steps left them behind (anything but the fused kernel that looks at the
 // planes calls this first).
 static void materialise_m1(rh_ctx *ctx) {
-    if (!ctx->m1_stale) return;
+    if (!ctx->held.m1_stale) return;
     hipLaunchKernelGGL(k_rotate_all, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena);
-    ctx->m1_stale = false;
+    ctx->held.m1_stale = false;
 }
-// somebody other than the fused kernel is about to change planes: X_m1 == X cannot be taken for granted afterwards
+// an input of the control part changed: what the last fused kernel's tail formed for the next step is not that step's.  on_device: the
+// change is made by a launch (the hooks), behind the summary word that the tail spread into the exchange buffer
+static void control_inputs_changed(rh_ctx *ctx, bool on_device = false) {
+    ctx->held.pending_valid = ctx->held.pre_valid = false;
+    if (on_device) ctx->held.exch_valid = false;
+}
+// somebody other than the fused kernel is about to change planes: X_m1 == X cannot be taken for granted afterwards, and any per-column
+// kernel other than the fused step may change what the summary words describe
 static void planes_touched(rh_ctx *ctx) {
     materialise_m1(ctx);
-    ctx->pmask_valid = false;   // (a parameter plane may be about to change: the wave words are formed again before the next lazy step)
-    ctx->rot_consistent = false;
-    ctx->summary_valid = false;
-    ctx->routed_summary = false;
-    ctx->pending_valid = ctx->pre_valid = false;
-    ctx->exch_valid = false;
+    ctx->held.pmask_valid = false;   // (a parameter plane may be about to change: the wave words are formed again before the next lazy step)
+    ctx->held.rot_consistent = false;
+    ctx->held.summary_valid = false;
+    ctx->held.routed_summary = false;
+    control_inputs_changed(ctx, true);
 }
+// per-cell forcing: the step's control part comes from a front that looks at the planes, not from the summary word -- nothing in front of
+// the fused kernel writes a plane (its lazy rotation stays), but what the summary path keeps does not describe the next step
+static void summary_path_left(rh_ctx *ctx) {
+    ctx->held.summary_valid = false;
+    control_inputs_changed(ctx, true);
+}
+// the per-cell forcing inputs changed (weights, stations): every cached part of the day is formed again
+static void cell_forcing_changed(rh_ctx *ctx) {
+    ctx->held.agg_daily_stale = true;
+    ctx->held.pred_daily_stale = true;
+    ctx->held.front_daily_stale = true;
+}
+// a front of kind 1 (k_pred1 ... k_select) or 2 (k_cell_front) forms this step's predicates: it re-forms the day's cached parts if the other
+// kind formed them last
+static void front_takes_over(rh_ctx *ctx, int kind) {
+    if (ctx->held.last_front != kind) {
+        if (kind == 1) ctx->held.agg_daily_stale = ctx->held.pred_daily_stale = true;
+        else ctx->held.front_daily_stale = true;
+    }
+    ctx->held.last_front = kind;
+}
+// a step was enqueued with / without sparse stores
+static void sparse_step_enqueued(rh_ctx *ctx, bool sparse) {
+    ctx->held.outputs_stale = ctx->held.last_sparse = sparse;
+    ctx->call_sparse_steps += sparse ? 1 : 0;
+}
+// a fused launch with these tail flags was enqueued (exch: its tail spreads the next step's summary word into the exchange buffer)
+static void fused_step_enqueued(rh_ctx *ctx, int flags, bool lazy, bool sparse, bool exch) {
+    ctx->held.rot_consistent = true;   // a complete step: after_timestep's X_m1 = X holds, physically (eager) or logically (lazy)
+    ctx->held.m1_stale = lazy;
+    sparse_step_enqueued(ctx, sparse);
+    ctx->held.summary_valid = !(flags & RH_TAIL_SKIP);  // the fused kernel's tail leaves the summary word of the state it wrote (words[3])
+    ctx->held.pending_valid = (flags & RH_TAIL_CTRL) != 0;
+    ctx->held.pre_valid = (flags & RH_TAIL_PRE) && !(flags & RH_TAIL_CTRL);
+    ctx->held.pending_hooks = (flags & RH_TAIL_HOOKS) != 0;
+    ctx->held.exch_valid = exch;
+}
+// a routed device step was enqueued: k_routed_a2 left the summary bits of the state the step ends in
+static void routed_step_enqueued(rh_ctx *ctx, bool sparse) {
+    ctx->held.routed_summary = true;
+    sparse_step_enqueued(ctx, sparse);
+}
+
 #define LAUNCH_CELLS(ctx, kern)                                                                                          \
     do {                                                                                                                 \
         planes_touched(ctx);                                                                                             \
         hipLaunchKernelGGL(kern, dim3(grid_for((ctx)->n)), dim3(RH_BLOCK), 0, (ctx)->stream, (ctx)->arena, (ctx)->dev); \
     } while (0)
+#define LAUNCH_PRED(ctx, kern)                                                                                           \
+    do {                                                                                                                 \
+        planes_touched(ctx);                                                                                             \
+        hipLaunchKernelGGL(kern, dim3((ctx)->pred_blocks), dim3(RH_BLOCK), 0, (ctx)->stream, (ctx)->arena, (ctx)->dev, 0); \
+    } while (0)
 #define LAUNCH_ONE(ctx, kern, ...) hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, (ctx)->stream, __VA_ARGS__)
 #define LAUNCH_WG(ctx, kern, ...) hipLaunchKernelGGL(kern, dim3(1), dim3(RH_BLOCK), 0, (ctx)->stream, __VA_ARGS__)
 #define CHECK_LAUNCH(ctx) HIPCHK(ctx, hipGetLastError())
+
+// a plane that the last step of a call that ended half-way did not store (sparse stores): rh_download and rh_plane_device_ptr refuse it
+static bool plane_is_stale(const rh_ctx *ctx, int plane) {
+    return ctx->held.outputs_stale && pure_output_planes()[ctx->cfg.enable_routing_1D ? 2 : (ctx->cfg.enable_lateral_flow ? 1 : 0)][plane];
+}
+// the parameter words of the lazy kernels' wavefronts, formed from the planes as they are (grid: the launch shape of the caller)
+static int form_param_mask(rh_ctx *ctx, dim3 grid) {
+    if (ctx->held.pmask_valid) return RH_OK;
+    hipLaunchKernelGGL(k_param_mask, grid, dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, ctx->pmask_buf, ctx->pmask_flags);
+    CHECK_LAUNCH(ctx);
+    ctx->held.pmask_valid = true;
+    return RH_OK;
+}
+// buffers allocated when the first caller needs them
+static int need_exch_buf(rh_ctx *ctx) {
+    HIPCHK(ctx, ctx->exch_buf.alloc_once(128 * sizeof(int)));
+    return RH_OK;
+}
+static int need_agg_cell_buf(rh_ctx *ctx) {
+    if (ctx->agg_cell_buf) return RH_OK;
+    HIPCHK(ctx, ctx->agg_cell_buf.alloc(sizeof(double) * 9 * (size_t)ctx->n));
+    HIPCHK(ctx, dev_put(ctx, &DevState::agg_cell, *ctx->agg_cell_buf.addr()));
+    return RH_OK;
+}
 
 // RCCL, resolved at run time: a single-GPU user needs no librccl, and a process that already holds one (PyTorch ships its own
 // copy under the same soname) keeps using that one.
@@ -2686,54 +2805,13 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     if (!ctx) return fail(nullptr, RH_ERR_ARG, "rh_create: out of host memory");
     ctx->cfg = *cfg;
     ctx->n = cfg->nx * cfg->ny;
-    ctx->stream = nullptr;
-    ctx->own_stream = false;
-    ctx->forcing_set = false;
-    ctx->timing = false;
-    ctx->ev_used = 0;
-    ctx->dt_log_buf = nullptr;
-    ctx->dev = nullptr;
-    ctx->arena.base = nullptr;
-    ctx->rot_consistent = false;
-    ctx->m1_stale = false;
-    ctx->agg_daily_stale = true;
-    ctx->pred_daily_stale = true;
-    ctx->front_daily_stale = true;
-    ctx->diag_reads_m1 = false;
     ctx->lazy_ok = std::getenv("RH_NO_LAZY_ROTATION") == nullptr;
     ctx->sparse_ok = std::getenv("RH_NO_SPARSE_STORES") == nullptr;
-    for (auto &b : ctx->forc_cell_buf) b = nullptr;
-    for (auto &b : ctx->weight_buf) b = nullptr;
-    ctx->station_buf = nullptr;
-    ctx->forc_multi_buf = nullptr;
-    ctx->transpose_buf = nullptr;
-    ctx->agg_cell_buf = nullptr;
-    ctx->series_buf = nullptr;
-    ctx->mlms_buf = nullptr;
-    ctx->diag_buf = nullptr;
-    ctx->diag_steps_buf = nullptr;
-    ctx->diag_interval = 86400;
-    ctx->diag_n = 0;
-    ctx->diag_slots = 0;
-    ctx->per_cell = false;
     const size_t n_tiles = ((size_t)ctx->n + RH_TILE_CELLS - 1) / RH_TILE_CELLS;
     ctx->planes_held = cfg->enable_routing_1D ? (int)RH_NPLANES : (int)RH_P_flow_dir_topo;
     const size_t stride = (size_t)(ctx->planes_held + RH_STRIDE_PAD) * RH_SLOT_BYTES, arena_bytes = n_tiles * stride;
     ctx->arena.stride = stride;
     ctx->arena.n = ctx->n;
-    ctx->stage_buf = nullptr;
-    ctx->comm = nullptr;
-    ctx->own_comm = false;
-    ctx->exch_buf = nullptr;
-    ctx->exch_valid = false;
-    ctx->comm_nranks = 1;
-    ctx->comm_rank = 0;
-    ctx->grid_px = ctx->grid_py = 1;
-    ctx->route_q = nullptr;
-    ctx->route_i = nullptr;
-    ctx->route_halo[0] = ctx->route_halo[1] = false;
-    ctx->route_frame = false;
-    ctx->route_static_done = false;
     if (cfg->enable_routing_1D && !cfg->enable_lateral_flow) {
         delete ctx;
         return fail(nullptr, RH_ERR_ARG, "rh_create: enable_routing_1D needs enable_lateral_flow (the routed subsurface runoff is the lateral flow)");
@@ -2744,8 +2822,7 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
         return fail(nullptr, RH_ERR_HIP, msg);
     };
     hipError_t e;
-    if ((e = hipStreamCreate(&ctx->stream)) != hipSuccess) return bail(e, "hipStreamCreate");
-    ctx->own_stream = true;
+    if ((e = ctx->stream.create()) != hipSuccess) return bail(e, "hipStreamCreate");
     {
         // Placement probing (rh_config.placement_probes): candidates are allocated one after the other and held until
         // the choice is made, so that each lands somewhere else; a copy of 96 planes with the fused kernel's access
@@ -2753,7 +2830,7 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
         int probes = cfg->placement_probes;
         if (const char *env = std::getenv("RH_PLACEMENT_PROBES")) probes = std::atoi(env);
         if (probes < 1 || ctx->n < 65536) probes = 1;   // small grids are latency-bound
-        std::vector<char *> cand;
+        std::vector<DevBuf<char>> cand;   // (the ones that are not chosen are released at the end of this block)
         std::vector<double> cand_ms;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         if (probes > 1 && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) probes = 1;
@@ -2763,21 +2840,21 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
                 if (hipMemGetInfo(&free_b, &total_b) != hipSuccess ||
                     (free_b + k * arena_bytes) / 4 < (k + 1) * arena_bytes) break;
             }
-            char *p = nullptr;
-            if ((e = hipMalloc((void **)&p, arena_bytes)) != hipSuccess) {
+            DevBuf<char> p;
+            if ((e = p.alloc(arena_bytes)) != hipSuccess) {
                 if (k == 0) return bail(e, "hipMalloc(arena)");
                 (void)hipGetLastError();
                 break;
             }
-            cand.push_back(p);
-            if ((e = hipMemsetAsync(p, 0, arena_bytes, ctx->stream)) != hipSuccess) {
-                for (char *q : cand) (void)hipFree(q);
+            cand.push_back(std::move(p));
+            if ((e = hipMemsetAsync(cand.back(), 0, arena_bytes, ctx->stream)) != hipSuccess) {
+                cand.clear();
                 return bail(e, "hipMemset");
             }
             double ms = 0;
             if (probes > 1) {
                 Arena probe = ctx->arena;
-                probe.base = p;
+                probe.base = cand.back();
                 float best = 1e30f;
                 for (int rep = 0; rep < 4; ++rep) {   // the first repetition warms up
                     (void)hipEventRecord(ev0, ctx->stream);
@@ -2796,33 +2873,29 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
         size_t pick = 0;
         for (size_t k = 1; k < cand.size(); ++k)
             if (cand_ms[k] < cand_ms[pick]) pick = k;
-        ctx->arena.base = cand[pick];
+        ctx->arena_mem = std::move(cand[pick]);
+        ctx->arena.base = ctx->arena_mem;
         if (probes > 1) {
             ctx->probe_ms.push_back(cand_ms[pick]);
             for (size_t k = 0; k < cand.size(); ++k)
                 if (k != pick) ctx->probe_ms.push_back(cand_ms[k]);
         }
-        for (size_t k = 0; k < cand.size(); ++k)
-            if (k != pick) (void)hipFree(cand[k]);
     }
-    if ((e = hipMalloc((void **)&ctx->stage_buf, (size_t)ctx->n * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(staging plane)");
-    if ((e = hipMalloc((void **)&ctx->dev, sizeof(DevState))) != hipSuccess) return bail(e, "hipMalloc(DevState)");
-    if ((e = hipHostMalloc((void **)&ctx->hexp, sizeof(HostExport), hipHostMallocMapped)) != hipSuccess) return bail(e, "hipHostMalloc(scalar export block)");
-    std::memset(ctx->hexp, 0, sizeof(HostExport));
+    if ((e = ctx->stage_buf.alloc((size_t)ctx->n * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(staging plane)");
+    if ((e = ctx->dev.alloc(sizeof(DevState))) != hipSuccess) return bail(e, "hipMalloc(DevState)");
+    if ((e = ctx->hexp.alloc()) != hipSuccess) return bail(e, "hipHostMalloc(scalar export block)");
     if ((e = hipMemsetAsync(ctx->dev, 0, sizeof(DevState), ctx->stream)) != hipSuccess) return bail(e, "hipMemset");
     {   // the parameter words of the fused step's wavefronts (all zero: plain loads; AFTER the control block was cleared) and their address in the control block
         const size_t words = ((size_t)ctx->n + 63) / 64;
-        if ((e = hipMalloc((void **)&ctx->pmask_buf, words * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(parameter words)");
+        if ((e = ctx->pmask_buf.alloc(words * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(parameter words)");
         if ((e = hipMemsetAsync(ctx->pmask_buf, 0, words * sizeof(unsigned long long), ctx->stream)) != hipSuccess) return bail(e, "hipMemset");
-        if ((e = hipMemcpyAsync(&ctx->dev->pmask, &ctx->pmask_buf, sizeof(ctx->pmask_buf), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-            return bail(e, "hipMemcpy(pmask)");
+        if ((e = dev_put(ctx, &DevState::pmask, *ctx->pmask_buf.addr())) != hipSuccess) return bail(e, "hipMemcpy(pmask)");
         if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
         ctx->pmask_flags = (std::getenv("RH_NO_PARAM_UNIFORM") ? 0 : 1) | (std::getenv("RH_NO_PARAM_DERIVE") ? 0 : 2) | (std::getenv("RH_NO_MASK_CONSTANT") ? 0 : 4);
     }
     {
         static const long long no_limit = -1;
-        if ((e = hipMemcpyAsync(&ctx->dev->t_end, &no_limit, sizeof(no_limit), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-            return bail(e, "hipMemcpy(t_end)");
+        if ((e = dev_put(ctx, &DevState::t_end, no_limit)) != hipSuccess) return bail(e, "hipMemcpy(t_end)");
     }
     Consts K;
     K.pi = cfg->pi; K.r_mp = cfg->r_mp; K.l_sc = cfg->l_sc; K.sf = cfg->sf; K.ta_fm = cfg->ta_fm; K.rmax = cfg->rmax;
@@ -2833,8 +2906,7 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     K.end_event = cfg->end_event; K.hpi = cfg->hpi;
     K.dx = cfg->dx; K.lateral = cfg->enable_lateral_flow ? 1 : 0;
     K.dy = cfg->dy; K.routing = cfg->enable_routing_1D ? 1 : 0;
-    if ((e = hipMemcpyAsync(&ctx->dev->K, &K, sizeof(K), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        return bail(e, "hipMemcpy(Consts)");
+    if ((e = dev_put(ctx, &DevState::K, K)) != hipSuccess) return bail(e, "hipMemcpy(Consts)");
     // scalars: roger/variables.py initial values (dt=1, dt_secs=3600, event_id_counter=1, year=1900, month=doy=1)
     rh_scalars S;
     std::memset(&S, 0, sizeof(S));
@@ -2845,11 +2917,8 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     S.month[0] = S.month[1] = 1;
     S.doy[0] = S.doy[1] = 1;
     S.sanity_ok = 1;
-    if ((e = hipMemcpyAsync(&ctx->dev->S, &S, sizeof(S), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        return bail(e, "hipMemcpy(scalars)");
+    if ((e = dev_put(ctx, &DevState::S, S)) != hipSuccess) return bail(e, "hipMemcpy(scalars)");
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");  // K, S are stack locals
-    ctx->pending_valid = ctx->pre_valid = false;
-    ctx->pending_hooks = 0;
     ctx->tail_ok = std::getenv("RH_NO_TAIL_CTRL") == nullptr;
     ctx->routed_device_ok = std::getenv("RH_ROUTED_BY_ROUTINE") == nullptr;
     ctx->defer_select_ok = std::getenv("RH_NO_DEFERRED_SELECT") == nullptr;
@@ -2859,10 +2928,8 @@ int rh_create(const rh_config *cfg, rh_ctx **out) {
     ctx->n_groups = (int)((grid_for(ctx->n) + 63) / 64);
     if (ctx->n_groups > RH_DONE_GROUPS) ctx->n_groups = RH_DONE_GROUPS;
     if (ctx->n_groups < 1) ctx->n_groups = 1;
-    ctx->summary_valid = false;
     ctx->pred_blocks = (int)(grid_for(ctx->n) < RH_PRED_BLOCKS ? grid_for(ctx->n) : RH_PRED_BLOCKS);
-    if ((e = hipMemcpyAsync(&ctx->dev->pred_blocks, &ctx->pred_blocks, sizeof(int), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        return bail(e, "hipMemcpy(pred_blocks)");
+    if ((e = dev_put(ctx, &DevState::pred_blocks, ctx->pred_blocks)) != hipSuccess) return bail(e, "hipMemcpy(pred_blocks)");
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
     hipLaunchKernelGGL(k_init_registry, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena);
     hipLaunchKernelGGL(k_sync_ctx, dim3(1), dim3(1), 0, ctx->stream, ctx->dev);
@@ -2899,39 +2966,13 @@ void rh_destroy(rh_ctx *ctx) {
         }
     }
 #endif
-    for (auto &ev : ctx->events) (void)hipEventDestroy(ev);
-    if (ctx->dt_log_buf) (void)hipFree(ctx->dt_log_buf);
-    for (auto &b : ctx->forc_cell_buf)
-        if (b) (void)hipFree(b);
-    for (auto &b : ctx->weight_buf)
-        if (b) (void)hipFree(b);
-    if (ctx->agg_cell_buf) (void)hipFree(ctx->agg_cell_buf);
-    if (ctx->station_buf) (void)hipFree(ctx->station_buf);
-    if (ctx->forc_multi_buf) (void)hipFree(ctx->forc_multi_buf);
-    if (ctx->transpose_buf) (void)hipFree(ctx->transpose_buf);
-    if (ctx->series_buf) (void)hipFree(ctx->series_buf);
-    if (ctx->mlms_buf) (void)hipFree(ctx->mlms_buf);
-    if (ctx->diag_buf) (void)hipFree(ctx->diag_buf);
-    if (ctx->diag_steps_buf) (void)hipFree(ctx->diag_steps_buf);
-    if (ctx->arena.base) (void)hipFree(ctx->arena.base);
-    if (ctx->stage_buf) (void)hipFree(ctx->stage_buf);
-    if (ctx->exch_buf) (void)hipFree(ctx->exch_buf);
-    if (ctx->route_q) (void)hipFree(ctx->route_q);
-    if (ctx->route_i) (void)hipFree(ctx->route_i);
     release_comm(ctx);
-    if (ctx->dev) (void)hipFree(ctx->dev);
-    if (ctx->hexp) (void)hipHostFree(ctx->hexp);
-    if (ctx->pmask_buf) (void)hipFree(ctx->pmask_buf);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
 int rh_set_stream(rh_ctx *ctx, void *hip_stream) {
     if (!ctx) return RH_ERR_ARG;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->own_stream) HIPCHK(ctx, hipStreamDestroy(ctx->stream));
-    ctx->stream = (hipStream_t)hip_stream;
-    ctx->own_stream = false;
+    HIPCHK(ctx, ctx->stream.adopt((hipStream_t)hip_stream));
     return RH_OK;
 }
 
@@ -2969,12 +3010,11 @@ int rh_upload(rh_ctx *ctx, int plane, const void *host, size_t bytes) {
     planes_touched(ctx);
     HIPCHK(ctx, hipMemcpyAsync(ctx->stage_buf, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     if (elem == sizeof(double))
-        hipLaunchKernelGGL(k_plane_scatter<double>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (const double *)ctx->stage_buf);
+        hipLaunchKernelGGL(k_plane_scatter<double>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (const double *)ctx->stage_buf.get());
     else
-        hipLaunchKernelGGL(k_plane_scatter<int>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (const int *)ctx->stage_buf);
+        hipLaunchKernelGGL(k_plane_scatter<int>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (const int *)ctx->stage_buf.get());
     CHECK_LAUNCH(ctx);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the host buffer may be a temporary
-    ctx->summary_valid = false;
     return RH_OK;
 }
 
@@ -2983,14 +3023,14 @@ int rh_download(rh_ctx *ctx, int plane, void *host, size_t bytes) {
     int rc = plane_bytes(ctx, plane, bytes, &elem);
     if (rc) return rc;
     if (!host) return fail(ctx, RH_ERR_ARG, "rh_download: null host pointer");
-    if (ctx->outputs_stale && pure_output_planes()[ctx->cfg.enable_routing_1D ? 2 : (ctx->cfg.enable_lateral_flow ? 1 : 0)][plane])   // only after an rh_run_steps call that failed half-way
+    if (plane_is_stale(ctx, plane))   // only after an rh_run_steps call that failed half-way
         return fail(ctx, RH_ERR_STATE, "rh_download: the last rh_run_steps call ended before its final step; this flux / diagnostic plane holds an "
                                        "earlier step's values (run one more step)");
     materialise_m1(ctx);
     if (elem == sizeof(double))
-        hipLaunchKernelGGL(k_plane_gather<double>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (double *)ctx->stage_buf);
+        hipLaunchKernelGGL(k_plane_gather<double>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (double *)ctx->stage_buf.get());
     else
-        hipLaunchKernelGGL(k_plane_gather<int>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (int *)ctx->stage_buf);
+        hipLaunchKernelGGL(k_plane_gather<int>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, plane, (int *)ctx->stage_buf.get());
     CHECK_LAUNCH(ctx);
     HIPCHK(ctx, hipMemcpyAsync(host, ctx->stage_buf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2999,7 +3039,7 @@ int rh_download(rh_ctx *ctx, int plane, void *host, size_t bytes) {
 
 void *rh_plane_device_ptr(rh_ctx *ctx, int plane) {
     if (!ctx || plane < 0 || plane >= ctx->planes_held) return nullptr;
-    if (ctx->outputs_stale && pure_output_planes()[ctx->cfg.enable_routing_1D ? 2 : (ctx->cfg.enable_lateral_flow ? 1 : 0)][plane]) {
+    if (plane_is_stale(ctx, plane)) {
         // (as rh_download: only after a stepping call that ended before its final, full-store step -- ADVICE r3)
         fail(ctx, RH_ERR_STATE, "rh_plane_device_ptr: the last rh_run_steps call ended before its final step; this plane holds an earlier step's values");
         return nullptr;
@@ -3010,9 +3050,9 @@ void *rh_plane_device_ptr(rh_ctx *ctx, int plane) {
 
 int rh_set_scalars(rh_ctx *ctx, const rh_scalars *s) {
     if (!ctx || !s) return RH_ERR_ARG;
-    ctx->pending_valid = ctx->pre_valid = false;
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->err_flags, 0, sizeof(unsigned), ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->S, s, sizeof(*s), hipMemcpyHostToDevice, ctx->stream));
+    control_inputs_changed(ctx);
+    HIPCHK(ctx, dev_zero(ctx, &DevState::err_flags));
+    HIPCHK(ctx, dev_put(ctx, &DevState::S, *s));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     LAUNCH_ONE(ctx, k_sync_ctx, ctx->dev);
     CHECK_LAUNCH(ctx);
@@ -3024,7 +3064,7 @@ int rh_set_scalars(rh_ctx *ctx, const rh_scalars *s) {
 // stream from time to time, so that a launch that failed ends the wait with its error instead of hanging.
 static int export_scalars(rh_ctx *ctx, rh_scalars *s) {
     const unsigned long long seq = ++ctx->hexp_seq;
-    hipLaunchKernelGGL(k_export, dim3(1), dim3(1), 0, ctx->stream, (const DevState *)ctx->dev, ctx->hexp, seq);
+    hipLaunchKernelGGL(k_export, dim3(1), dim3(1), 0, ctx->stream, (const DevState *)ctx->dev, ctx->hexp.get(), seq);
     CHECK_LAUNCH(ctx);
     const unsigned long long *p = &ctx->hexp->seq;
     for (unsigned long spins = 1;; ++spins) {
@@ -3038,7 +3078,7 @@ static int export_scalars(rh_ctx *ctx, rh_scalars *s) {
             if (q != hipErrorNotReady) HIPCHK(ctx, q);
         }
     }
-    const HostExport &H = *ctx->hexp;
+    const HostExport &H = *ctx->hexp.get();
     *s = H.S;
     // word 2 collects the sanity violations of the last step; the fused kernel's tail moves it to sanity_last
     s->sanity_ok = (H.bad | H.bad_last) ? 0 : 1;
@@ -3062,13 +3102,11 @@ int rh_set_luts(rh_ctx *ctx, const double *ilu, const double *gc, const double *
 
 int rh_set_lut_mlms(rh_ctx *ctx, const double *mlms, int64_t nrows) {
     if (!ctx || !mlms || nrows <= 0) return RH_ERR_ARG;
-    if (ctx->mlms_buf) HIPCHK(ctx, hipFree(ctx->mlms_buf));
-    ctx->mlms_buf = nullptr;
     const size_t nb = sizeof(double) * 9 * (size_t)nrows;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->mlms_buf, nb));
+    HIPCHK(ctx, ctx->mlms_buf.alloc(nb));
     HIPCHK(ctx, hipMemcpyAsync(ctx->mlms_buf, mlms, nb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->mlms, &ctx->mlms_buf, sizeof(double *), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->mlms_rows, &nrows, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::mlms, *ctx->mlms_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::mlms_rows, nrows));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
@@ -3076,7 +3114,7 @@ int rh_set_lut_mlms(rh_ctx *ctx, const double *mlms, int64_t nrows) {
 int rh_params_lateral(rh_ctx *ctx) {
     if (!ctx) return RH_ERR_ARG;
     if (!ctx->mlms_buf) return fail(ctx, RH_ERR_STATE, "rh_set_lut_mlms must be called first");
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->max_slope_per, 0, sizeof(int), ctx->stream));
+    HIPCHK(ctx, dev_zero(ctx, &DevState::max_slope_per));
     LAUNCH_CELLS(ctx, k_max_slope);
     LAUNCH_CELLS(ctx, k_params_lateral);
     CHECK_LAUNCH(ctx);
@@ -3086,30 +3124,29 @@ int rh_params_lateral(rh_ctx *ctx) {
 int rh_set_forcing_day(rh_ctx *ctx, const double *prec_day, const double *ta_day, const double *pet_day, int per_cell) {
     if (!ctx || !prec_day || !ta_day || !pet_day) return RH_ERR_ARG;
     const double *src[3] = {prec_day, ta_day, pet_day};
-    int pc = per_cell ? 1 : 0;
+    const int pc = per_cell ? 1 : 0;
+    const double *cell[3];
     if (!pc) {
         for (int k = 0; k < 3; ++k)
             HIPCHK(ctx, hipMemcpyAsync(ctx->dev->forc[k], src[k], sizeof(double) * RH_SLOTS_PER_DAY, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(&ctx->dev->day_cache_ok, 0, sizeof(int), ctx->stream));   // (ctrl_wave's cache of the day)
+        HIPCHK(ctx, dev_zero(ctx, &DevState::day_cache_ok));   // (ctrl_wave's cache of the day)
     } else {
         const size_t bytes = sizeof(double) * RH_SLOTS_PER_DAY * (size_t)ctx->n;
-        if (!ctx->transpose_buf) HIPCHK(ctx, hipMalloc((void **)&ctx->transpose_buf, bytes));
+        HIPCHK(ctx, ctx->transpose_buf.alloc_once(bytes));
         for (int k = 0; k < 3; ++k) {   // (n, 144) from the host -> (144, n) on the device
-            if (!ctx->forc_cell_buf[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->forc_cell_buf[k], bytes));
+            HIPCHK(ctx, ctx->forc_cell_buf[k].alloc_once(bytes));
+            cell[k] = ctx->forc_cell_buf[k];
             HIPCHK(ctx, hipMemcpyAsync(ctx->transpose_buf, src[k], bytes, hipMemcpyHostToDevice, ctx->stream));
             hipLaunchKernelGGL(k_transpose_forcing, dim3((unsigned)((ctx->n + 63) / 64), (RH_SLOTS_PER_DAY + 63) / 64), dim3(RH_BLOCK), 0, ctx->stream,
-                               (const double *)ctx->transpose_buf, ctx->forc_cell_buf[k], ctx->n);
+                               (const double *)ctx->transpose_buf, ctx->forc_cell_buf[k].get(), ctx->n);
             CHECK_LAUNCH(ctx);
         }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dev->forc_cell, ctx->forc_cell_buf, sizeof(double *) * 3, hipMemcpyHostToDevice, ctx->stream));
-        if (!ctx->agg_cell_buf) {
-            HIPCHK(ctx, hipMalloc((void **)&ctx->agg_cell_buf, sizeof(double) * 9 * (size_t)ctx->n));
-            HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->agg_cell, &ctx->agg_cell_buf, sizeof(double *), hipMemcpyHostToDevice, ctx->stream));
-        }
+        HIPCHK(ctx, dev_put(ctx, &DevState::forc_cell, cell));
+        if (int rc = need_agg_cell_buf(ctx)) return rc;
     }
     ctx->per_cell = pc != 0;
-    ctx->pending_valid = ctx->pre_valid = false;
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->per_cell, &pc, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    control_inputs_changed(ctx);
+    HIPCHK(ctx, dev_put(ctx, &DevState::per_cell, pc));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->forcing_set = true;
     return RH_OK;
@@ -3156,7 +3193,7 @@ int rh_infiltration(rh_ctx *ctx) {
 int rh_num_error(rh_ctx *ctx) {
     if (!ctx) return RH_ERR_ARG;
     HIPCHK(ctx, hipMemsetAsync(&ctx->dev->words[2], 0, sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->sanity_last, 0, sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, dev_zero(ctx, &DevState::sanity_last));
     if (ctx->cfg.enable_routing_1D)
         LAUNCH_CELLS(ctx, k_num_error_routed);
     else if (ctx->cfg.enable_lateral_flow)
@@ -3223,8 +3260,8 @@ static unsigned route_neighbours(const rh_ctx *ctx, int peer[8]) {
 static int route_buffers(rh_ctx *ctx) {
     if (ctx->route_q) return RH_OK;
     const size_t F = route_frame_size(ctx);
-    HIPCHK(ctx, hipMalloc((void **)&ctx->route_q, 2 * F * sizeof(double)));
-    HIPCHK(ctx, hipMalloc((void **)&ctx->route_i, 4 * F * sizeof(int)));
+    HIPCHK(ctx, ctx->route_q.alloc(2 * F * sizeof(double)));
+    HIPCHK(ctx, ctx->route_i.alloc(4 * F * sizeof(int)));
     HIPCHK(ctx, hipMemsetAsync(ctx->route_q, 0, 2 * F * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->route_i, 0, 4 * F * sizeof(int), ctx->stream));
     return RH_OK;
@@ -3241,11 +3278,11 @@ static void route_pack(rh_ctx *ctx, int which, unsigned parts) {
     const size_t F = route_frame_size(ctx);
     const dim3 grid((unsigned)((F + 255) / 256)), block(256);
     if (which < 0)
-        hipLaunchKernelGGL(k_route_pack<int>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, parts, (int)RH_P_flow_dir_topo, ctx->route_i,
+        hipLaunchKernelGGL(k_route_pack<int>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, parts, (int)RH_P_flow_dir_topo, ctx->route_i.get(),
                            (int)RH_P_maskCatch, ctx->route_i + F);
     else
         hipLaunchKernelGGL(k_route_pack<double>, grid, block, 0, ctx->stream, ctx->arena, nx, ny, parts,
-                           which == 0 ? (int)RH_P_q_sur_out : (int)RH_P_q_sub_out, ctx->route_q, 0, (double *)nullptr);
+                           which == 0 ? (int)RH_P_q_sur_out : (int)RH_P_q_sub_out, ctx->route_q.get(), 0, (double *)nullptr);
 }
 int rh_route_out(rh_ctx *ctx, int which) {
     int rc = route_check(ctx, which, "rh_route_out");
@@ -3378,23 +3415,13 @@ static int route_all(rh_ctx *ctx, int which) {
 int rh_surface_routing(rh_ctx *ctx) { return route_all(ctx, 0); }
 int rh_subsurface_routing(rh_ctx *ctx) { return route_all(ctx, 1); }
 
-#define LAUNCH_PRED(ctx, kern)                                                                                           \
-    do {                                                                                                                 \
-        planes_touched(ctx);                                                                                             \
-        hipLaunchKernelGGL(kern, dim3((ctx)->pred_blocks), dim3(RH_BLOCK), 0, (ctx)->stream, (ctx)->arena, (ctx)->dev, 0); \
-    } while (0)
-
-// the next pair of timing events (rh_enable_timing): they ride on a kernel's own dispatch (hipExtLaunchKernelGGL)
+// the next pair of timing events, if timing is on (rh_enable_timing; null otherwise): they ride on a kernel's own dispatch
+// (hipExtLaunchKernelGGL).  The pool is reused by the next rh_enable_timing(1), never beyond the cap
 static int timing_pair(rh_ctx *ctx, hipEvent_t *ev0, hipEvent_t *ev1) {
-    if (ctx->ev_used + 2 > 2 * (size_t)RH_DT_LOG_CAP)
+    if (!ctx->timing) return RH_OK;
+    if (ctx->events.used + 2 > 2 * (size_t)RH_DT_LOG_CAP)
         return fail(ctx, RH_ERR_STATE, "timing: more than 65536 timed steps since rh_enable_timing(1); read the timings and enable again");
-    while (ctx->events.size() < ctx->ev_used + 2) {
-        hipEvent_t ev;
-        HIPCHK(ctx, hipEventCreate(&ev));
-        ctx->events.push_back(ev);
-    }
-    *ev0 = ctx->events[ctx->ev_used];
-    *ev1 = ctx->events[ctx->ev_used + 1];
+    HIPCHK(ctx, ctx->events.next_pair(ev0, ev1));
     return RH_OK;
 }
 
@@ -3403,34 +3430,21 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
     // dispatch's completion signal) instead of two hipEventRecord packets around it, which cost 5 us per step at 10^6
     // columns.
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (ctx->timing) {
-        if (ctx->ev_used + 2 > 2 * (size_t)RH_DT_LOG_CAP)
-            return fail(ctx, RH_ERR_STATE, "timing: more than 65536 timed steps since rh_enable_timing(1); read the timings and enable again");
-        while (ctx->events.size() < ctx->ev_used + 2) {   // the pool is reused by the next rh_enable_timing(1), never beyond the cap
-            hipEvent_t ev;
-            HIPCHK(ctx, hipEventCreate(&ev));
-            ctx->events.push_back(ev);
-        }
-        ev0 = ctx->events[ctx->ev_used];
-        ev1 = ctx->events[ctx->ev_used + 1];
-    }
+    if (int rc = timing_pair(ctx, &ev0, &ev1)) return rc;
     // a launch whose tail forms the next step's control part gets one workgroup more: pre_tail
     if (flags & RH_TAIL_CTRL) flags |= RH_TAIL_PRE;
     const dim3 grid(grid_for(ctx->n) + ((flags & RH_TAIL_PRE) ? 1u : 0u)), block(RH_BLOCK);
     const bool lat = ctx->cfg.enable_lateral_flow != 0;
-#define RH_LAUNCH_K(K) hipExtLaunchKernelGGL(K, grid, block, 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev, flags, ctx->n_groups, dst64)
+#define RH_LAUNCH_K(K) hipExtLaunchKernelGGL(K, grid, block, 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev.get(), flags, ctx->n_groups, dst64)
     // lazy rotation: the planes were last touched by a complete fused step (X_m1 == X) and nobody who reads X_m1 planes
     // follows inside this call (the accumulator kernel may, if it was given an X_m1 plane)
-    const bool lazy = ctx->lazy_ok && ctx->rot_consistent && !ctx->diag_reads_m1;
+    const bool lazy = ctx->lazy_ok && ctx->held.rot_consistent && !ctx->diag_reads_m1;
     // sparse stores: another step of the same rh_run_steps call follows and nothing in between reads what this one only produces
-    const bool sparse = lazy && ctx->sparse_next && monthly < 0;   // (planes an accumulator reads are kept: DevState::keep, the KEEP variant)
+    const bool sparse = lazy && ctx->held.sparse_next && monthly < 0;   // (planes an accumulator reads are kept: DevState::keep, the KEEP variant)
     const bool keep = sparse && ctx->diag_reads_sparse;
-    ctx->sparse_next = false;
-    if (lazy && !ctx->pmask_valid) {   // the lazy kernels read the parameter planes through the wave words: formed from the planes as they are
-        hipLaunchKernelGGL(k_param_mask, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, ctx->pmask_buf, ctx->pmask_flags);
-        CHECK_LAUNCH(ctx);
-        ctx->pmask_valid = true;
-    }
+    ctx->held.sparse_next = false;
+    if (lazy)   // the lazy kernels read the parameter planes through the wave words
+        if (int rc = form_param_mask(ctx, grid)) return rc;
 #define RH_LAUNCH_STEP(MODE)                                          \
     do {                                                              \
         if (MODE == 2 && lat && keep)                                 \
@@ -3453,19 +3467,11 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
     if (monthly < 0) RH_LAUNCH_STEP(2);  // decided on the device
     else if (monthly) RH_LAUNCH_STEP(1);
     else RH_LAUNCH_STEP(0);
-    ctx->rot_consistent = true;   // a complete step: after_timestep's X_m1 = X holds, physically (eager) or logically (lazy)
-    ctx->m1_stale = lazy;
-    ctx->outputs_stale = ctx->last_sparse = sparse;
-    ctx->call_sparse_steps += sparse ? 1 : 0;
 #undef RH_LAUNCH_STEP
 #undef RH_LAUNCH_K
     CHECK_LAUNCH(ctx);
-    if (ctx->timing) ctx->ev_used += 2;
-    ctx->summary_valid = !(flags & RH_TAIL_SKIP);  // the fused kernel's tail leaves the summary word of the state it wrote (words[3])
-    ctx->pending_valid = (flags & RH_TAIL_CTRL) != 0;
-    ctx->pre_valid = (flags & RH_TAIL_PRE) && !(flags & RH_TAIL_CTRL);
-    ctx->pending_hooks = (flags & RH_TAIL_HOOKS) != 0;
-    ctx->exch_valid = dst64 != nullptr;
+    if (ctx->timing) ctx->events.taken();
+    fused_step_enqueued(ctx, flags, lazy, sparse, dst64 != nullptr);
     if (ctx->diag_n) {
         hipLaunchKernelGGL(k_diag, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, 1);
         CHECK_LAUNCH(ctx);
@@ -3473,14 +3479,17 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
     return RH_OK;
 }
 
+// the start-of-step predicates of the predicate-kernel front, with the day's forcing bits if they must be formed again
+static void launch_pred1(rh_ctx *ctx) {
+    hipLaunchKernelGGL(k_pred1, dim3(ctx->pred_blocks), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, ctx->held.pred_daily_stale ? 1 : 0);
+    ctx->held.pred_daily_stale = false;
+}
 int rh_step_phase1(rh_ctx *ctx) {
     if (!ctx) return RH_ERR_ARG;
     if (!ctx->forcing_set) return fail(ctx, RH_ERR_STATE, "rh_set_forcing_day / rh_set_forcing_series must be called before the first step");
     planes_touched(ctx);
-    if (ctx->last_front != 1) ctx->agg_daily_stale = ctx->pred_daily_stale = true;   // (the one-launch front formed the day's parts last)
-    ctx->last_front = 1;
-    hipLaunchKernelGGL(k_pred1, dim3(ctx->pred_blocks), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, ctx->pred_daily_stale ? 1 : 0);
-    ctx->pred_daily_stale = false;
+    front_takes_over(ctx, 1);
+    launch_pred1(ctx);
     LAUNCH_WG(ctx, k_reduce, ctx->dev, 0);
     CHECK_LAUNCH(ctx);
     return RH_OK;
@@ -3488,24 +3497,21 @@ int rh_step_phase1(rh_ctx *ctx) {
 // per-cell forcing: the columns' aggregates of the step (k_cell_agg); does not touch the planes
 static void launch_cell_agg(rh_ctx *ctx) {
     const dim3 grid(grid_for(ctx->n)), block(RH_BLOCK);
-    const int force = ctx->agg_daily_stale ? 1 : 0;
+    const int force = ctx->held.agg_daily_stale ? 1 : 0;
     if (ctx->n >= ctx->cell_agg_split_min) {
         hipLaunchKernelGGL(k_cell_agg<2>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force);
         hipLaunchKernelGGL(k_cell_agg<1>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force);
     } else
         hipLaunchKernelGGL(k_cell_agg<0>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force);
+    ctx->held.agg_daily_stale = false;
 }
 int rh_step_phase2(rh_ctx *ctx) {
     if (!ctx) return RH_ERR_ARG;
     LAUNCH_WG(ctx, k_agg, ctx->dev, 0, 0);
-    if (ctx->per_cell) {   // (does not touch the planes: no LAUNCH_CELLS)
-        launch_cell_agg(ctx);
-        ctx->agg_daily_stale = false;
-    }
-    LAUNCH_PRED(ctx, k_select);
+    if (ctx->per_cell) launch_cell_agg(ctx);   // (does not touch the planes: no LAUNCH_CELLS)
+    LAUNCH_PRED(ctx, k_select);   // (k_select rewrites prec / ta: the summary word is not that of the planes any more)
     LAUNCH_WG(ctx, k_reduce, ctx->dev, 1);
     CHECK_LAUNCH(ctx);
-    ctx->summary_valid = false;  // k_select rewrote prec / ta
     return RH_OK;
 }
 int rh_step_phase3(rh_ctx *ctx, int monthly) {
@@ -3514,6 +3520,31 @@ int rh_step_phase3(rh_ctx *ctx, int monthly) {
     int rc = launch_fused_kernel(ctx, monthly);
     if (rc) return rc;
     CHECK_LAUNCH(ctx);
+    return RH_OK;
+}
+// Where the next control kernel finds the summary word of the columns as they are: RH_SRC_WORD3 if the last fused kernel left it in
+// words[3], otherwise RH_SRC_SUMW, rebuilt from the arena here (or a negative error code).  stays_valid: only control kernels follow
+// before the next look at it (the exchange paths); a fused launch that follows re-forms it anyway.
+static int summary_from_arena(rh_ctx *ctx, bool stays_valid) {
+    if (ctx->held.summary_valid) return RH_SRC_WORD3;
+    HIPCHK(ctx, dev_zero(ctx, &DevState::sumw));
+    LAUNCH_CELLS(ctx, k_summary);
+    ctx->held.summary_valid = stays_valid;
+    return RH_SRC_SUMW;
+}
+// per-cell forcing, ONE per-column launch in front of the fused kernel (k_cell_front; a second one, returning at once unless a new day
+// began, for the daily sums of large grids): the set_forcing hook rides along with it (fresh_day / front_ctrl)
+static int launch_cell_front(rh_ctx *ctx, int hooks) {
+    const dim3 grid(grid_for(ctx->n)), block(RH_BLOCK);
+    const int force = ctx->held.front_daily_stale ? 1 : 0, m1 = ctx->held.m1_stale ? 1 : 0;
+    if (ctx->n >= ctx->cell_agg_split_min) {
+        hipLaunchKernelGGL(k_cell_front<2>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force, m1, ctx->n_groups, hooks);
+        hipLaunchKernelGGL(k_cell_front<0>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force, m1, ctx->n_groups, hooks);
+    } else {
+        hipLaunchKernelGGL(k_cell_front<1>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force, m1, ctx->n_groups, hooks);
+    }
+    CHECK_LAUNCH(ctx);
+    ctx->held.front_daily_stale = false;
     return RH_OK;
 }
 static void launch_hooks(rh_ctx *ctx);
@@ -3527,14 +3558,10 @@ static int step_fused_launches(rh_ctx *ctx, int monthly, int hooks) {
     if (!ctx->per_cell) {
         // summary path: the previous fused kernel left what the predicates need; one control kernel, one fused kernel
         // ... unless the previous fused kernel's tail has formed this step's control part already (S_next / X_next)
-        const bool use_next = ctx->pending_valid && ctx->pending_hooks == (hooks != 0);
+        const bool use_next = ctx->held.pending_valid && ctx->held.pending_hooks == (hooks != 0);
         if (!use_next) {
-            int src = RH_SRC_WORD3;
-            if (!ctx->summary_valid) {
-                HIPCHK(ctx, hipMemsetAsync(ctx->dev->sumw, 0, sizeof(ctx->dev->sumw), ctx->stream));
-                LAUNCH_CELLS(ctx, k_summary);
-                src = RH_SRC_SUMW;
-            }
+            const int src = summary_from_arena(ctx, false);
+            if (src < 0) return src;
             LAUNCH_ONE(ctx, k_ctrl, ctx->dev, hooks, src, (const int *)nullptr);
             CHECK_LAUNCH(ctx);
         }
@@ -3546,50 +3573,28 @@ static int step_fused_launches(rh_ctx *ctx, int monthly, int hooks) {
         launch_hooks(ctx);
         hooks = 0;
     }
+    int rc;
     if (front) {
-        // (the set_forcing hook rides along with the front kernel: fresh_day / front_ctrl)
-        // ONE per-column launch in front of the fused kernel (k_cell_front; a second one, returning at once unless a new day began, for the
-        // daily sums of large grids).  Nothing in front of the fused kernel writes a plane: its lazy rotation stays.
-        ctx->summary_valid = false;
-        ctx->pending_valid = ctx->pre_valid = false;
-        ctx->exch_valid = false;
-        const dim3 grid(grid_for(ctx->n)), block(RH_BLOCK);
-        const int force = (ctx->front_daily_stale || ctx->last_front != 2) ? 1 : 0, m1 = ctx->m1_stale ? 1 : 0;
-        if (ctx->n >= ctx->cell_agg_split_min) {
-            hipLaunchKernelGGL(k_cell_front<2>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force, m1, ctx->n_groups, hooks);
-            hipLaunchKernelGGL(k_cell_front<0>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force, m1, ctx->n_groups, hooks);
-        } else {
-            hipLaunchKernelGGL(k_cell_front<1>, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, force, m1, ctx->n_groups, hooks);
-        }
-        CHECK_LAUNCH(ctx);
-        ctx->front_daily_stale = false;
-        ctx->last_front = 2;
-        int rc = launch_fused_kernel(ctx, monthly, RH_TAIL_SKIP);   // (the next front reads the planes, not the summary word)
-        if (rc) return rc;
-        CHECK_LAUNCH(ctx);
-        return RH_OK;
+        summary_path_left(ctx);
+        front_takes_over(ctx, 2);
+        if ((rc = launch_cell_front(ctx, hooks))) return rc;
+        rc = launch_fused_kernel(ctx, monthly, RH_TAIL_SKIP);   // (the next front reads the planes, not the summary word)
+    } else {
+        front_takes_over(ctx, 1);
+        // None of the kernels in front of the fused one writes a plane: the selected prec / ta are applied inside the fused kernel
+        // (apply_sel = 2, from the per-cell aggregates), the predicate kernels read tau planes only -- with the rotation pending,
+        // prec_m1 / swe_m1 are the tau planes themselves.  So the fused kernel keeps its lazy rotation in the per-cell path too.
+        summary_path_left(ctx);
+        launch_pred1(ctx);
+        LAUNCH_WG(ctx, k_agg, ctx->dev, hooks, 1);
+        if (ctx->per_cell) launch_cell_agg(ctx);
+        const bool defer = ctx->per_cell && ctx->defer_select_ok;   // (shared forcing on this path, e.g. before the series is resident: k_select stores)
+        if (!defer) planes_touched(ctx);
+        hipLaunchKernelGGL(k_select, dim3(ctx->pred_blocks), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev,
+                           (ctx->held.m1_stale ? RH_SELECT_M1_PENDING : 0) | (defer ? RH_SELECT_DEFER : 0));
+        LAUNCH_WG(ctx, k_scalars, ctx->dev, 1, 1, defer ? 2 : 0);
+        rc = launch_fused_kernel(ctx, monthly);
     }
-    if (ctx->last_front != 1) ctx->agg_daily_stale = ctx->pred_daily_stale = true;
-    ctx->last_front = 1;
-    // None of the kernels in front of the fused one writes a plane: the selected prec / ta are applied inside the fused kernel
-    // (apply_sel = 2, from the per-cell aggregates), the predicate kernels read tau planes only -- with the rotation pending, prec_m1 /
-    // swe_m1 are the tau planes themselves.  So the fused kernel keeps its lazy rotation in the per-cell path too.
-    ctx->summary_valid = false;
-    ctx->pending_valid = ctx->pre_valid = false;
-    ctx->exch_valid = false;
-    hipLaunchKernelGGL(k_pred1, dim3(ctx->pred_blocks), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, ctx->pred_daily_stale ? 1 : 0);
-    ctx->pred_daily_stale = false;
-    LAUNCH_WG(ctx, k_agg, ctx->dev, hooks, 1);
-    if (ctx->per_cell) {
-        launch_cell_agg(ctx);
-        ctx->agg_daily_stale = false;
-    }
-    const bool defer = ctx->per_cell && ctx->defer_select_ok;   // (shared forcing on this path, e.g. before the series is resident: k_select stores)
-    if (!defer) planes_touched(ctx);
-    hipLaunchKernelGGL(k_select, dim3(ctx->pred_blocks), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev,
-                       (ctx->m1_stale ? RH_SELECT_M1_PENDING : 0) | (defer ? RH_SELECT_DEFER : 0));
-    LAUNCH_WG(ctx, k_scalars, ctx->dev, 1, 1, defer ? 2 : 0);
-    int rc = launch_fused_kernel(ctx, monthly);
     if (rc) return rc;
     CHECK_LAUNCH(ctx);
     return RH_OK;
@@ -3598,14 +3603,9 @@ static int step_summary(rh_ctx *ctx, int32_t *dev_dst64) {
     if (!ctx) return RH_ERR_ARG;
     if (!ctx->forcing_set) return fail(ctx, RH_ERR_STATE, "rh_set_forcing_day / rh_set_forcing_series must be called before the first step");
     if (ctx->per_cell) return fail(ctx, RH_ERR_STATE, "rh_step_summary: the summary path needs forcing shared by all columns; use rh_step_phase1/2/3");
-    int src = RH_SRC_WORD3;
-    if (!ctx->summary_valid) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->dev->sumw, 0, sizeof(ctx->dev->sumw), ctx->stream));
-        LAUNCH_CELLS(ctx, k_summary);
-        ctx->summary_valid = true;
-        src = RH_SRC_SUMW;
-    }
-    ctx->pending_valid = ctx->pre_valid = false;   // the ranks decide together: the control kernel follows the exchange
+    const int src = summary_from_arena(ctx, true);
+    if (src < 0) return src;
+    control_inputs_changed(ctx);   // the ranks decide together: the control kernel follows the exchange
     LAUNCH_WG(ctx, k_summary_reduce, ctx->dev, ctx->series_buf ? 1 : 0, (int *)dev_dst64, src);
     CHECK_LAUNCH(ctx);
     return RH_OK;
@@ -3645,10 +3645,7 @@ int rh_adaptive_dt(rh_ctx *ctx) {
     if (rc) return rc;
     rc = rh_step_phase2(ctx);
     if (rc) return rc;
-    LAUNCH_WG(ctx, k_scalars, ctx->dev, 0, 0);
-    LAUNCH_CELLS(ctx, k_select_pet);
-    CHECK_LAUNCH(ctx);
-    return RH_OK;
+    return rh_adaptive_dt_finish(ctx);
 }
 
 // the last part of rh_adaptive_dt on its own: with several ranks the two predicate words are exchanged between rh_step_phase1 /
@@ -3661,26 +3658,33 @@ int rh_adaptive_dt_finish(rh_ctx *ctx) {
     return RH_OK;
 }
 
+// The resident series -- (stations, nitt_forc) per variable, then the three calendar vectors -- and their addresses in the control
+// block; n_stations = 0: one series for all columns.  Synchronises (the address tables are stack locals).
+static int upload_series(rh_ctx *ctx, const double *prec, const double *ta, const double *pet, const int64_t *year, const int64_t *month,
+                         const int64_t *doy, int64_t nitt_forc, int n_stations) {
+    const size_t nb1 = sizeof(double) * (size_t)nitt_forc, nbS = nb1 * (size_t)(n_stations ? n_stations : 1);
+    HIPCHK(ctx, ctx->series_buf.alloc(3 * nbS + 3 * nb1));
+    char *base = ctx->series_buf;
+    const void *fsrc[3] = {prec, ta, pet}, *csrc[3] = {year, month, doy};
+    for (int k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(base + k * nbS, fsrc[k], nbS, hipMemcpyHostToDevice, ctx->stream));
+    for (int k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(base + 3 * nbS + k * nb1, csrc[k], nb1, hipMemcpyHostToDevice, ctx->stream));
+    const double *sp[3] = {(double *)base, (double *)(base + nbS), (double *)(base + 2 * nbS)};
+    const int64_t *cp[3] = {(int64_t *)(base + 3 * nbS), (int64_t *)(base + 3 * nbS + nb1), (int64_t *)(base + 3 * nbS + 2 * nb1)};
+    HIPCHK(ctx, dev_put(ctx, &DevState::series, sp));
+    HIPCHK(ctx, dev_put(ctx, &DevState::calendar, cp));
+    HIPCHK(ctx, dev_put(ctx, &DevState::nitt_forc, nitt_forc));
+    HIPCHK(ctx, dev_put(ctx, &DevState::n_stations, n_stations));
+    HIPCHK(ctx, dev_zero(ctx, &DevState::err_flags));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+
 int rh_set_forcing_series(rh_ctx *ctx, const double *prec, const double *ta, const double *pet, const int64_t *year,
                           const int64_t *month, const int64_t *doy, int64_t nitt_forc) {
     if (!ctx || !prec || !ta || !pet || !year || !month || !doy || nitt_forc <= 0) return RH_ERR_ARG;
-    const size_t nb = sizeof(double) * (size_t)nitt_forc;
-    if (ctx->series_buf) HIPCHK(ctx, hipFree(ctx->series_buf));
-    ctx->series_buf = nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->series_buf, 6 * nb));
-    char *base = (char *)ctx->series_buf;
-    const void *src[6] = {prec, ta, pet, year, month, doy};
-    for (int k = 0; k < 6; ++k) HIPCHK(ctx, hipMemcpyAsync(base + k * nb, src[k], nb, hipMemcpyHostToDevice, ctx->stream));
-    const double *sp[3] = {(double *)base, (double *)(base + nb), (double *)(base + 2 * nb)};
-    const int64_t *cp[3] = {(int64_t *)(base + 3 * nb), (int64_t *)(base + 4 * nb), (int64_t *)(base + 5 * nb)};
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev->series, sp, sizeof(sp), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev->calendar, cp, sizeof(cp), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->nitt_forc, &nitt_forc, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->err_flags, 0, sizeof(unsigned), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->n_stations, 0, sizeof(int), ctx->stream));   // one series for all columns
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = upload_series(ctx, prec, ta, pet, year, month, doy, nitt_forc, 0)) return rc;
     ctx->forcing_set = true;
-    ctx->pending_valid = ctx->pre_valid = false;
+    control_inputs_changed(ctx);
     ctx->per_cell = false;
     return RH_OK;
 }
@@ -3690,33 +3694,16 @@ int rh_set_forcing_stations(rh_ctx *ctx, const double *prec, const double *ta, c
     if (!ctx || !prec || !ta || !pet || !year || !month || !doy || !station_index || nitt_forc <= 0 || n_stations < 1)
         return ctx ? fail(ctx, RH_ERR_ARG, "rh_set_forcing_stations: bad arguments") : RH_ERR_ARG;
     if (n_stations > 4096) return fail(ctx, RH_ERR_ARG, "rh_set_forcing_stations: at most 4096 stations");
-    // the series: (n_stations, nitt_forc) per variable, then the calendar
-    const size_t nb1 = sizeof(double) * (size_t)nitt_forc, nbS = nb1 * (size_t)n_stations;
-    if (ctx->series_buf) HIPCHK(ctx, hipFree(ctx->series_buf));
-    ctx->series_buf = nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->series_buf, 3 * nbS + 3 * nb1));
-    char *base = (char *)ctx->series_buf;
-    const void *fsrc[3] = {prec, ta, pet}, *csrc[3] = {year, month, doy};
-    for (int k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(base + k * nbS, fsrc[k], nbS, hipMemcpyHostToDevice, ctx->stream));
-    for (int k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(base + 3 * nbS + k * nb1, csrc[k], nb1, hipMemcpyHostToDevice, ctx->stream));
-    const double *sp[3] = {(double *)base, (double *)(base + nbS), (double *)(base + 2 * nbS)};
-    const int64_t *cp[3] = {(int64_t *)(base + 3 * nbS), (int64_t *)(base + 3 * nbS + nb1), (int64_t *)(base + 3 * nbS + 2 * nb1)};
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev->series, sp, sizeof(sp), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev->calendar, cp, sizeof(cp), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->nitt_forc, &nitt_forc, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = upload_series(ctx, prec, ta, pet, year, month, doy, nitt_forc, n_stations)) return rc;
     // the station of every column, the staging table of a day
-    if (!ctx->station_buf) HIPCHK(ctx, hipMalloc((void **)&ctx->station_buf, sizeof(int) * (size_t)ctx->n));
+    HIPCHK(ctx, ctx->station_buf.alloc_once(sizeof(int) * (size_t)ctx->n));
     HIPCHK(ctx, hipMemcpyAsync(ctx->station_buf, station_index, sizeof(int) * (size_t)ctx->n, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->forc_multi_buf) HIPCHK(ctx, hipFree(ctx->forc_multi_buf));
-    ctx->forc_multi_buf = nullptr;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->forc_multi_buf, sizeof(double) * 3 * (size_t)n_stations * RH_SLOTS_PER_DAY));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->station_idx, &ctx->station_buf, sizeof(int *), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->forc_multi, &ctx->forc_multi_buf, sizeof(double *), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->n_stations, &n_stations, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->err_flags, 0, sizeof(unsigned), ctx->stream));
+    HIPCHK(ctx, ctx->forc_multi_buf.alloc(sizeof(double) * 3 * (size_t)n_stations * RH_SLOTS_PER_DAY));
+    HIPCHK(ctx, dev_put(ctx, &DevState::station_idx, *ctx->station_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::forc_multi, *ctx->forc_multi_buf.addr()));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->forcing_set = true;
-    ctx->pending_valid = ctx->pre_valid = false;
+    control_inputs_changed(ctx);
     // the station series reach the columns through the per-cell (weighted) path: neutral weights unless the caller sets some
     if (!ctx->weight_buf[0]) {
         std::vector<double> one((size_t)ctx->n, 1.0), zero((size_t)ctx->n, 0.0);
@@ -3724,17 +3711,14 @@ int rh_set_forcing_stations(rh_ctx *ctx, const double *prec, const double *ta, c
         if (rc) return rc;
     }
     ctx->per_cell = true;
-    ctx->agg_daily_stale = true;
-    ctx->pred_daily_stale = true;
-    ctx->front_daily_stale = true;
+    cell_forcing_changed(ctx);
     return RH_OK;
 }
 
 static void launch_hooks(rh_ctx *ctx) {
     // the hook rewrites D->S (itt_forc, itt_day, the calendar), D->forc and D->monthly: a control part the previous fused kernel's
     // tail formed for the next step (S_next / X_next) was formed BEFORE this hook ran and must not be used
-    ctx->pending_valid = ctx->pre_valid = false;
-    ctx->exch_valid = false;
+    control_inputs_changed(ctx, true);
     hipLaunchKernelGGL(k_set_forcing, dim3(1), dim3(RH_BLOCK), 0, ctx->stream, ctx->dev);
 }
 int rh_hooks_phase(rh_ctx *ctx) {
@@ -3753,24 +3737,25 @@ int rh_hooks_phase(rh_ctx *ctx) {
 static int allreduce_word(rh_ctx *ctx, int word) {
     RcclApi *api = rccl_api();
     if (!api->ok) return fail(ctx, RH_ERR_STATE, "rh_step_routed: " + api->why);
-    if (!ctx->exch_buf) HIPCHK(ctx, hipMalloc((void **)&ctx->exch_buf, 128 * sizeof(int)));
-    int rc = rh_predicates_expand(ctx, word, ctx->exch_buf);
+    int rc = need_exch_buf(ctx);
+    if (rc) return rc;
+    rc = rh_predicates_expand(ctx, word, ctx->exch_buf);
     if (rc) return rc;
     NCCLCHK(ctx, api->AllReduce(ctx->exch_buf, ctx->exch_buf + 64, 64, ncclInt32, ncclMax, ctx->comm, ctx->stream));
-    ctx->exch_valid = false;
+    ctx->held.exch_valid = false;   // (the buffer holds a predicate word now)
     return rh_predicates_compress(ctx, word, ctx->exch_buf + 64);
 }
 // interception ... numerics, itt / time (what rh_step_core is for the uncoupled columns)
 static int routed_core(rh_ctx *ctx, bool with_after) {
     int rc;
     HIPCHK(ctx, hipMemsetAsync(&ctx->dev->words[2], 0, sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(&ctx->dev->sanity_last, 0, sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, dev_zero(ctx, &DevState::sanity_last));
     {   // interception ... infiltration, the surface outflow: the longest of the three passes, the one rh_enable_timing times
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (ctx->timing && (rc = timing_pair(ctx, &ev0, &ev1))) return rc;
+        if ((rc = timing_pair(ctx, &ev0, &ev1))) return rc;
         planes_touched(ctx);
-        hipExtLaunchKernelGGL(k_routed_a, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev);
-        if (ctx->timing) ctx->ev_used += 2;
+        hipExtLaunchKernelGGL(k_routed_a, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev.get());
+        if (ctx->timing) ctx->events.taken();
     }
     if (ctx->comm && ctx->comm_nranks > 1 && (rc = route_exchange(ctx, 0))) return rc;
     if ((rc = rh_route_gather_only(ctx, 0))) return rc;
@@ -3804,12 +3789,12 @@ static int routed_step_device(rh_ctx *ctx, bool sparse_wanted = false) {
         api = rccl_api();
         if (!api->ok) return fail(ctx, RH_ERR_STATE, "routed step: " + api->why);
     }
-    if (!ctx->routed_summary) {   // first step, or somebody else touched the planes: the summary bits from the arena
-        HIPCHK(ctx, hipMemsetAsync(ctx->dev->sumw, 0, sizeof(ctx->dev->sumw), ctx->stream));
+    if (!ctx->held.routed_summary) {   // first step, or somebody else touched the planes: the summary bits from the arena
+        HIPCHK(ctx, dev_zero(ctx, &DevState::sumw));
         LAUNCH_CELLS(ctx, k_summary);
     }
     if (ctx->comm) {   // (a one-rank communicator takes the same path: tests)
-        if (!ctx->exch_buf) HIPCHK(ctx, hipMalloc((void **)&ctx->exch_buf, 128 * sizeof(int)));
+        if ((rc = need_exch_buf(ctx))) return rc;
         int *send = ctx->exch_buf, *recv = ctx->exch_buf + 64;
         LAUNCH_WG(ctx, k_summary_reduce, ctx->dev, 0, send, RH_SRC_SUMW);
         NCCLCHK(ctx, api->AllReduce(send, recv, 64, ncclInt32, ncclMax, ctx->comm, ctx->stream));
@@ -3819,10 +3804,10 @@ static int routed_step_device(rh_ctx *ctx, bool sparse_wanted = false) {
     planes_touched(ctx);
     {
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (ctx->timing && (rc = timing_pair(ctx, &ev0, &ev1))) return rc;
-        if (sparse) hipExtLaunchKernelGGL(k_routed_a2<true>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev);
-        else hipExtLaunchKernelGGL(k_routed_a2<false>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev);
-        if (ctx->timing) ctx->ev_used += 2;
+        if ((rc = timing_pair(ctx, &ev0, &ev1))) return rc;
+        if (sparse) hipExtLaunchKernelGGL(k_routed_a2<true>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev.get());
+        else hipExtLaunchKernelGGL(k_routed_a2<false>, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev.get());
+        if (ctx->timing) ctx->events.taken();
     }
     const dim3 grid(grid_for(ctx->n)), block(RH_BLOCK);
     const int nx = (int)ctx->cfg.nx, ny = (int)ctx->cfg.ny;
@@ -3844,9 +3829,7 @@ static int routed_step_device(rh_ctx *ctx, bool sparse_wanted = false) {
     else
         hipLaunchKernelGGL((k_routed_cg<true, false>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
     CHECK_LAUNCH(ctx);
-    ctx->routed_summary = true;   // k_routed_a2 left the summary bits of the state the step ends in
-    ctx->outputs_stale = ctx->last_sparse = sparse;
-    ctx->call_sparse_steps += sparse ? 1 : 0;
+    routed_step_enqueued(ctx, sparse);
     return RH_OK;
 }
 int rh_step_routed(rh_ctx *ctx, int monthly) {
@@ -3874,38 +3857,30 @@ int rh_set_forcing_weights(rh_ctx *ctx, const double *prec_weight, const double 
     const size_t nb = sizeof(double) * (size_t)ctx->n;
     const double *dptr[3] = {nullptr, nullptr, nullptr};
     if (clear) {
-        for (auto &b : ctx->weight_buf) {
-            if (b) HIPCHK(ctx, hipFree(b));
-            b = nullptr;
-        }
+        for (auto &b : ctx->weight_buf) HIPCHK(ctx, b.release());
     } else {
         for (int k = 0; k < 3; ++k) {
-            if (!ctx->weight_buf[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->weight_buf[k], nb));
+            HIPCHK(ctx, ctx->weight_buf[k].alloc_once(nb));
             HIPCHK(ctx, hipMemcpyAsync(ctx->weight_buf[k], src[k], nb, hipMemcpyHostToDevice, ctx->stream));
             dptr[k] = ctx->weight_buf[k];
         }
-        if (!ctx->agg_cell_buf) {
-            HIPCHK(ctx, hipMalloc((void **)&ctx->agg_cell_buf, sizeof(double) * 9 * (size_t)ctx->n));
-            HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->agg_cell, &ctx->agg_cell_buf, sizeof(double *), hipMemcpyHostToDevice, ctx->stream));
-        }
+        if (int rc = need_agg_cell_buf(ctx)) return rc;
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev->weights, dptr, sizeof(dptr), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::weights, dptr));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pending_valid = ctx->pre_valid = false;
+    control_inputs_changed(ctx);
     ctx->per_cell = !clear;   // from the next midnight on; rh_set_forcing_weights is a setup-time call
-    ctx->agg_daily_stale = true;
-    ctx->pred_daily_stale = true;
-    ctx->front_daily_stale = true;
+    cell_forcing_changed(ctx);
     return RH_OK;
 }
 
 int rh_set_time_limit(rh_ctx *ctx, int64_t t_end) {
     if (!ctx) return RH_ERR_ARG;
     const long long v = t_end < 0 ? -1 : (long long)t_end;
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->t_end, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::t_end, v));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (v is a stack local)
     ctx->t_end = v;
-    ctx->pending_valid = ctx->pre_valid = false;   // a control part formed under the old limit (possibly "halt") is not the next step's
+    control_inputs_changed(ctx);   // a control part formed under the old limit (possibly "halt") is not the next step's
     return RH_OK;
 }
 // with a time limit: 1 if the limit is reached already (nothing to enqueue), 0 if the first launch of the call will run a step --
@@ -3928,34 +3903,63 @@ static int limit_reached(rh_ctx *ctx, bool *reached) {
 // never set), it must not survive the call: the next single-step entry point would run the sparse kernel as a call's last step
 struct SparseRequestScope {
     rh_ctx *ctx;
-    explicit SparseRequestScope(rh_ctx *c) : ctx(c) { ctx->sparse_next = false; }
-    ~SparseRequestScope() { ctx->sparse_next = false; }
+    explicit SparseRequestScope(rh_ctx *c) : ctx(c) { ctx->held.sparse_next = false; }
+    ~SparseRequestScope() { ctx->held.sparse_next = false; }
 };
 
-int rh_run_steps(rh_ctx *ctx, int64_t nsteps) {
-    if (!ctx || nsteps < 0) return RH_ERR_ARG;
-    if (!ctx->series_buf) return fail(ctx, RH_ERR_STATE, "rh_set_forcing_series must be called first");
+// step k of the nsteps of a single-GPU call, or of any call with the routing (the routed step exchanges its predicate words and
+// border cells itself)
+static int call_step(rh_ctx *ctx, int64_t k, int64_t nsteps) {
+    if (!ctx->cfg.enable_routing_1D) {
+        ctx->held.sparse_next = ctx->sparse_ok && k + 1 < nsteps;   // the call's last step stores every plane
+        return step_fused_launches(ctx, -1, 1);
+    }
+    if (!ctx->per_cell && ctx->routed_device_ok) return routed_step_device(ctx, k + 1 < nsteps);
+    launch_hooks(ctx);   // the hooks, then the step routine by routine (rh_step_routed)
+    return rh_step_routed(ctx, -1);
+}
+// the steps of rh_run_steps_dist without the routing: one exchange of the summary word per step
+static int dist_steps(rh_ctx *ctx, int64_t nsteps) {
+    if (ctx->per_cell) return fail(ctx, RH_ERR_STATE, "rh_run_steps_dist: the one-exchange step needs forcing shared by all columns (rh_step_phase1/2/3 otherwise)");
+    RcclApi *api = rccl_api();
+    if (!api->ok) return fail(ctx, RH_ERR_STATE, "rh_run_steps_dist: " + api->why);
+    if (int rc = need_exch_buf(ctx)) return rc;
+    int *send = ctx->exch_buf, *recv = ctx->exch_buf + 64;
+    for (int64_t k = 0; k < nsteps; ++k) {
+        if (!ctx->held.exch_valid) {   // first step, or the host touched the planes: the summary word from words[3] or from the arena
+            const int src = summary_from_arena(ctx, true);
+            if (src < 0) return src;
+            LAUNCH_WG(ctx, k_summary_reduce, ctx->dev, 0, send, src);
+            CHECK_LAUNCH(ctx);
+        }
+        NCCLCHK(ctx, api->AllReduce(send, recv, 64, ncclInt32, ncclMax, ctx->comm, ctx->stream));
+        // the fused launch in front of the exchange formed the columns-independent half of this control part (pre_tail): the kernel behind
+        // the exchange keeps the decisions
+        LAUNCH_ONE(ctx, k_ctrl, ctx->dev, 1, RH_SRC_WORD3, (const int *)recv, ctx->held.pre_valid ? 1 : 0);
+        CHECK_LAUNCH(ctx);
+        ctx->held.sparse_next = ctx->sparse_ok && k + 1 < nsteps;
+        int rc = launch_fused_kernel(ctx, -1, RH_TAIL_PRE | RH_TAIL_HOOKS, send);   // the tail spreads the next step's summary word into `send`
+        if (rc) return rc;
+    }
+    return RH_OK;
+}
+// rh_run_steps (dist = false) and rh_run_steps_dist
+static int run_steps(rh_ctx *ctx, int64_t nsteps, bool dist) {
     SparseRequestScope sparse_scope(ctx);
     ctx->call_sparse_steps = 0;
     bool over = false;
     if (int rc = limit_reached(ctx, &over)) return rc;
     if (over) return RH_OK;
-    for (int64_t k = 0; k < nsteps; ++k) {
-        int rc;
-        if (ctx->cfg.enable_routing_1D) {
-            if (!ctx->per_cell && ctx->routed_device_ok)
-                rc = routed_step_device(ctx, k + 1 < nsteps);
-            else {   // the hooks, then the step routine by routine (rh_step_routed)
-                launch_hooks(ctx);
-                rc = rh_step_routed(ctx, -1);
-            }
-        } else {
-            ctx->sparse_next = ctx->sparse_ok && k + 1 < nsteps;   // the call's last step stores every plane
-            rc = step_fused_launches(ctx, -1, 1);
-        }
-        if (rc) return rc;
-    }
+    if (dist && !ctx->cfg.enable_routing_1D) return dist_steps(ctx, nsteps);
+    for (int64_t k = 0; k < nsteps; ++k)
+        if (int rc = call_step(ctx, k, nsteps)) return rc;
     return RH_OK;
+}
+
+int rh_run_steps(rh_ctx *ctx, int64_t nsteps) {
+    if (!ctx || nsteps < 0) return RH_ERR_ARG;
+    if (!ctx->series_buf) return fail(ctx, RH_ERR_STATE, "rh_set_forcing_series must be called first");
+    return run_steps(ctx, nsteps, false);
 }
 
 int rh_comm_unique_id(void *id128) {
@@ -4022,51 +4026,7 @@ int rh_run_steps_dist(rh_ctx *ctx, int64_t nsteps) {
     if (!ctx || nsteps < 0) return RH_ERR_ARG;
     if (!ctx->series_buf) return fail(ctx, RH_ERR_STATE, "rh_set_forcing_series must be called first");
     if (!ctx->comm) return fail(ctx, RH_ERR_STATE, "rh_run_steps_dist: no communicator (rh_comm_init / rh_set_comm)");
-    SparseRequestScope sparse_scope(ctx);
-    ctx->call_sparse_steps = 0;
-    bool over = false;
-    if (int rc = limit_reached(ctx, &over)) return rc;
-    if (over) return RH_OK;
-    if (ctx->cfg.enable_routing_1D) {   // the routed step exchanges its predicate words and border cells itself
-        for (int64_t k = 0; k < nsteps; ++k) {
-            int rc;
-            if (!ctx->per_cell && ctx->routed_device_ok)
-                rc = routed_step_device(ctx, k + 1 < nsteps);
-            else {
-                launch_hooks(ctx);
-                rc = rh_step_routed(ctx, -1);
-            }
-            if (rc) return rc;
-        }
-        return RH_OK;
-    }
-    if (ctx->per_cell) return fail(ctx, RH_ERR_STATE, "rh_run_steps_dist: the one-exchange step needs forcing shared by all columns (rh_step_phase1/2/3 otherwise)");
-    RcclApi *api = rccl_api();
-    if (!api->ok) return fail(ctx, RH_ERR_STATE, "rh_run_steps_dist: " + api->why);
-    if (!ctx->exch_buf) HIPCHK(ctx, hipMalloc((void **)&ctx->exch_buf, 128 * sizeof(int)));
-    int *send = ctx->exch_buf, *recv = ctx->exch_buf + 64;
-    for (int64_t k = 0; k < nsteps; ++k) {
-        if (!ctx->exch_valid) {   // first step, or the host touched the planes: the summary word from words[3] or from the arena
-            int src = RH_SRC_WORD3;
-            if (!ctx->summary_valid) {
-                HIPCHK(ctx, hipMemsetAsync(ctx->dev->sumw, 0, sizeof(ctx->dev->sumw), ctx->stream));
-                LAUNCH_CELLS(ctx, k_summary);
-                ctx->summary_valid = true;
-                src = RH_SRC_SUMW;
-            }
-            LAUNCH_WG(ctx, k_summary_reduce, ctx->dev, 0, send, src);
-            CHECK_LAUNCH(ctx);
-        }
-        NCCLCHK(ctx, api->AllReduce(send, recv, 64, ncclInt32, ncclMax, ctx->comm, ctx->stream));
-        // the fused launch in front of the exchange formed the columns-independent half of this control part (pre_tail): the kernel behind
-        // the exchange keeps the decisions
-        LAUNCH_ONE(ctx, k_ctrl, ctx->dev, 1, RH_SRC_WORD3, (const int *)recv, ctx->pre_valid ? 1 : 0);
-        CHECK_LAUNCH(ctx);
-        ctx->sparse_next = ctx->sparse_ok && k + 1 < nsteps;
-        int rc = launch_fused_kernel(ctx, -1, RH_TAIL_PRE | RH_TAIL_HOOKS, send);   // the tail spreads the next step's summary word into `send`
-        if (rc) return rc;
-    }
-    return RH_OK;
+    return run_steps(ctx, nsteps, true);
 }
 
 int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int *collect_planes, int n_collect, int n_slots) {
@@ -4089,8 +4049,8 @@ int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int
                 keep[planes[j] >> 6] |= 1ull << (planes[j] & 63);
             }
         const int any = ctx->diag_reads_sparse ? 1 : 0;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dev->keep, keep, sizeof(keep), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->keep_any, &any, sizeof(any), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
+        HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->diag_reads_m1 = false;   // an accumulated X_m1 plane keeps the fused kernel from skipping its stores
@@ -4100,35 +4060,29 @@ int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int
     }
     materialise_m1(ctx);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->diag_buf) {
-        HIPCHK(ctx, hipFree(ctx->diag_buf));
-        ctx->diag_buf = nullptr;
-    }
-    if (ctx->diag_steps_buf) {
-        HIPCHK(ctx, hipFree(ctx->diag_steps_buf));
-        ctx->diag_steps_buf = nullptr;
-    }
+    HIPCHK(ctx, ctx->diag_buf.release());
+    HIPCHK(ctx, ctx->diag_steps_buf.release());
     const int nv = n_rate + n_collect;
     ctx->diag_n = nv;
     ctx->diag_slots = n_slots;
     if (nv) {
         const size_t bytes = (size_t)n_slots * nv * ctx->n * sizeof(double);
-        HIPCHK(ctx, hipMalloc((void **)&ctx->diag_buf, bytes));
+        HIPCHK(ctx, ctx->diag_buf.alloc(bytes));
         HIPCHK(ctx, hipMemsetAsync(ctx->diag_buf, 0, bytes, ctx->stream));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->diag_steps_buf, (size_t)n_slots * 3 * sizeof(long long)));
+        HIPCHK(ctx, ctx->diag_steps_buf.alloc((size_t)n_slots * 3 * sizeof(long long)));
         HIPCHK(ctx, hipMemsetAsync(ctx->diag_steps_buf, 0xff, (size_t)n_slots * 3 * sizeof(long long), ctx->stream));   // -1: never touched
     }
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag_steps, &ctx->diag_steps_buf, sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_steps, *ctx->diag_steps_buf.addr()));
     {
         const long long day = 86400;
         if (ctx->diag_interval <= 0) ctx->diag_interval = day;
-        HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag_interval, &ctx->diag_interval, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, dev_put(ctx, &DevState::diag_interval, ctx->diag_interval));
     }
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag, &ctx->diag_buf, sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag_rate, &n_rate, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag_collect, &n_collect, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag_slots, &n_slots, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev->diag_planes, planes, sizeof(int) * 32, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag, *ctx->diag_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_rate, n_rate));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_collect, n_collect));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_slots, n_slots));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_planes, planes));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the sources are stack locals
     return RH_OK;
 }
@@ -4178,7 +4132,7 @@ int rh_diag_set_interval(rh_ctx *ctx, int64_t seconds) {
         return fail(ctx, RH_ERR_ARG, "rh_diag_set_interval: the output interval is a day, an hour or ten minutes (the step classes)");
     ctx->diag_interval = seconds;
     if (ctx->diag_n) {
-        HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->diag_interval, &ctx->diag_interval, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, dev_put(ctx, &DevState::diag_interval, ctx->diag_interval));
         HIPCHK(ctx, hipMemsetAsync(ctx->diag_steps_buf, 0xff, (size_t)ctx->diag_slots * 3 * sizeof(long long), ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -4231,8 +4185,9 @@ int rh_debug_swap_arenas(rh_ctx *a, rh_ctx *b) {
     if (!a || !b || a->n != b->n || a->arena.stride != b->arena.stride || a->planes_held != b->planes_held) return RH_ERR_ARG;
     HIPCHK(a, hipStreamSynchronize(a->stream));
     HIPCHK(b, hipStreamSynchronize(b->stream));
+    std::swap(a->arena_mem, b->arena_mem);
     std::swap(a->arena.base, b->arena.base);
-    a->pmask_valid = b->pmask_valid = false;   // (the wave words describe the planes of the arena a context steps on)
+    a->held.pmask_valid = b->held.pmask_valid = false;   // (the wave words describe the planes of the arena a context steps on)
     return RH_OK;
 }
 
@@ -4311,11 +4266,7 @@ int rh_plane_is_pure_output(int model, int plane) {
 int64_t rh_sparse_steps(const rh_ctx *ctx) { return ctx ? ctx->call_sparse_steps : 0; }
 int rh_param_stats(rh_ctx *ctx, double *derived_fraction, double *uniform_bytes_per_cell) {
     if (!ctx || !derived_fraction || !uniform_bytes_per_cell) return ctx ? fail(ctx, RH_ERR_ARG, "rh_param_stats: null pointer") : RH_ERR_ARG;
-    if (!ctx->pmask_valid) {
-        hipLaunchKernelGGL(k_param_mask, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, ctx->pmask_buf, ctx->pmask_flags);
-        CHECK_LAUNCH(ctx);
-        ctx->pmask_valid = true;
-    }
+    if (int rc = form_param_mask(ctx, dim3(grid_for(ctx->n)))) return rc;
     const size_t words = ((size_t)ctx->n + 63) / 64;
     std::vector<unsigned long long> w(words);
     HIPCHK(ctx, hipMemcpyAsync(w.data(), ctx->pmask_buf, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -4344,7 +4295,7 @@ int rh_param_stats(rh_ctx *ctx, double *derived_fraction, double *uniform_bytes_
 }
 int rh_step_mode(const rh_ctx *ctx) {
     if (!ctx) return 0;
-    return (ctx->m1_stale ? RH_STEP_MODE_LAZY : 0) | (ctx->pending_valid ? RH_STEP_MODE_TAIL : 0) | (ctx->last_sparse ? RH_STEP_MODE_SPARSE : 0);
+    return (ctx->held.m1_stale ? RH_STEP_MODE_LAZY : 0) | (ctx->held.pending_valid ? RH_STEP_MODE_TAIL : 0) | (ctx->held.last_sparse ? RH_STEP_MODE_SPARSE : 0);
 }
 
 void *rh_predicate_words(rh_ctx *ctx) { return ctx ? (void *)ctx->dev->words : nullptr; }
@@ -4352,14 +4303,14 @@ void *rh_predicate_words(rh_ctx *ctx) { return ctx ? (void *)ctx->dev->words : n
 int rh_enable_timing(rh_ctx *ctx, int on) {
     if (!ctx) return RH_ERR_ARG;
     ctx->timing = on != 0;
-    ctx->ev_used = 0;
-    ctx->pending_valid = ctx->pre_valid = false;   // the step log restarts: the next step's entry must be written after this call
-    if (on && !ctx->dt_log_buf) HIPCHK(ctx, hipMalloc((void **)&ctx->dt_log_buf, sizeof(int) * RH_DT_LOG_CAP));
-    int *log = on ? ctx->dt_log_buf : nullptr;
+    ctx->events.restart();
+    control_inputs_changed(ctx);   // the step log restarts: the next step's entry must be written after this call
+    if (on) HIPCHK(ctx, ctx->dt_log_buf.alloc_once(sizeof(int) * RH_DT_LOG_CAP));
+    int *log = on ? ctx->dt_log_buf.get() : nullptr;
     const int cap = RH_DT_LOG_CAP, zero = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->dt_log, &log, sizeof(int *), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->dt_log_cap, &cap, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->dev->dt_log_n, &zero, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::dt_log, log));
+    HIPCHK(ctx, dev_put(ctx, &DevState::dt_log_cap, cap));
+    HIPCHK(ctx, dev_put(ctx, &DevState::dt_log_n, zero));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
@@ -4368,7 +4319,7 @@ int rh_timing_detail(rh_ctx *ctx, double *kernel_ms, int32_t *dt_secs, int64_t c
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     int logged = 0;
     if (ctx->dt_log_buf) HIPCHK(ctx, hipMemcpy(&logged, &ctx->dev->dt_log_n, sizeof(int), hipMemcpyDeviceToHost));
-    const int64_t n = (int64_t)(ctx->ev_used / 2);
+    const int64_t n = (int64_t)ctx->events.launches();
     // (the tail of the last timed kernel has logged the step after it already: one entry more than launches)
     if ((logged != n && logged != n + 1) || n > RH_DT_LOG_CAP)
         return fail(ctx, RH_ERR_STATE, "rh_timing_detail: the step log does not match the timed launches (timing enabled mid-step, "
@@ -4377,7 +4328,7 @@ int rh_timing_detail(rh_ctx *ctx, double *kernel_ms, int32_t *dt_secs, int64_t c
     const int64_t m = n < cap ? n : cap;
     for (int64_t k = 0; k < m; ++k) {
         float ms = 0;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->events[2 * k], ctx->events[2 * k + 1]));
+        HIPCHK(ctx, ctx->events.elapsed_ms((size_t)k, &ms));
         kernel_ms[k] = ms;
     }
     if (m) HIPCHK(ctx, hipMemcpy(dt_secs, ctx->dt_log_buf, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
@@ -4386,14 +4337,8 @@ int rh_timing_detail(rh_ctx *ctx, double *kernel_ms, int32_t *dt_secs, int64_t c
 int rh_timing_summary(rh_ctx *ctx, double *total_ms, int64_t *launches) {
     if (!ctx || !total_ms || !launches) return RH_ERR_ARG;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    double sum = 0;
-    for (size_t k = 0; k + 1 < ctx->ev_used; k += 2) {
-        float ms = 0;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->events[k], ctx->events[k + 1]));
-        sum += ms;
-    }
-    *total_ms = sum;
-    *launches = (int64_t)(ctx->ev_used / 2);
+    HIPCHK(ctx, ctx->events.total_ms(total_ms));
+    *launches = (int64_t)ctx->events.launches();
     return RH_OK;
 }
 
