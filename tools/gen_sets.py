@@ -150,7 +150,7 @@ SEQUENCES = {
         "rt_subsurface_runoff_lateral", "rt_capillary_rise", "rt_storage", "rt_num_error_lateral",
         "rt_after_timestep_oned"],
 }
-# The three passes of the routed step (settings.enable_routing_1D, roger_hip.hip k_routed_a / _b / _c): staged like the fused step -- a
+# The three passes of the routed step (settings.enable_routing_1D, rh_routing.h k_routed_a / _b / _c): staged like the fused step -- a
 # plane is loaded right before the first stage that mentions it and stored right after the last stage that assigns it -- without the
 # rotation and summary machinery of the fused kernel.
 PLAIN_SEQUENCES = {
@@ -321,7 +321,7 @@ def main():
             for kind, key in (("ROT", "rot"), ("LOAD", "ld"), ("STORE", "st"), ("LLOAD", "lld"), ("LSTORE", "lst"), ("SSTORE", "sst"), ("KSTORE", "kst")):
                 lines.append(f"#define RH_SEQ_{seq}_{kind}_{rt}(X) " + " ".join(f"X({n})" for n in sorted(rec[key], key=order.get)))
             lines.append(f"#define RH_SEQ_{seq}_ALIAS_{rt}(A) " + " ".join(f"A({xm1}, {x})" for xm1, x in rec["alias"]))
-        # the fused kernel samples the summary bits of the next step's predicates (roger_hip.hip, k_step): prec and ta
+        # the fused kernel samples the summary bits of the next step's predicates (rh_step.h, k_step): prec and ta
         # after rt_select_pet, swe and swe_top after rt_snow -- nothing later may assign them
         for fld, after in (("prec", "rt_select_pet"), ("ta", "rt_select_pet"), ("swe", "rt_snow"), ("swe_top", "rt_snow")):
             late = [rt for rt in stages[stages.index(after) + 1:] if fld in sets[rt][1]]

@@ -3,7 +3,7 @@
 
     python tools/isa_census.py            # prints the table and rewrites roger_amd/csrc/rh_step_bytes.json
 
-The kernel is compiled with -DRH_CENSUS (the tail, which one wavefront of the whole grid runs, is left out), so every
+The kernel (rh_step.h; the routed passes: rh_routing.h -- both part of the unit roger_hip.hip) is compiled with -DRH_CENSUS (the tail, which one wavefront of the whole grid runs, is left out), so every
 global_load / global_store of the kernel is per-column traffic: the kernel loads no plane twice and the sub-step loops of the
 infiltration stages touch registers only.  The compiler drops the loads of planes the step assigns before reading them, so these
 counts -- not the plane sets of tools/gen_sets.py, which list every plane a stage mentions -- are the bytes the kernel requests:
