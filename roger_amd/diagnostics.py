@@ -190,7 +190,7 @@ def _transport_record(state, name):
 
 def output_transport(state):
     """After the warm-up (record 0: initial values, roger/roger.py:515-521) and after every step of the run proper."""
-    if not getattr(state, "_diag_transport", False) or not state.settings.warmup_done:
+    if not state._diag_transport or not state.settings.warmup_done:
         return
     for d in state._diag_active:
         for v in d.output_variables:
@@ -204,8 +204,8 @@ def output_transport(state):
 def output(state, final=False):
     """roger/diagnostics/api.py:47-70 for daily output: every completed day that has not been written yet becomes a
     record.  Called after each step of run() (one completed day at most) and after run_device() (all of them)."""
-    active = getattr(state, "_diag_active", None)
-    if not active or getattr(state, "_diag_transport", False):
+    active = state._diag_active
+    if not active or state._diag_transport:
         return
     ctx = state.backend_context
     iv = state._diag_interval
@@ -275,5 +275,5 @@ def _write(state, d):
 
 def close(state):
     """Write what is still held in memory (end of run)."""
-    for d in getattr(state, "_diag_active", None) or ():
+    for d in state._diag_active or ():
         _write(state, d)

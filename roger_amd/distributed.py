@@ -145,6 +145,14 @@ def global_sum(value, group=None):
     return _reduce(value, dist.ReduceOp.SUM, group)
 
 
+# the protocol a PhasedStepper backend states as its `protocol`
+THREE_PHASE, SUMMARY, SUMMARY_FUSED = "three-phase", "summary", "summary, fused exchange"
+
+
+def protocol_of(one_exchange, fused_exchange=False):
+    return THREE_PHASE if not one_exchange else SUMMARY_FUSED if fused_exchange else SUMMARY
+
+
 class PhasedStepper:
     """Runs whole time steps of a backend that exposes the three-phase step, all-reducing the two
     predicate words over `group` between the phases.
@@ -156,6 +164,10 @@ class PhasedStepper:
 
     def __init__(self, backend, group=None, always_exchange=False):
         self.backend = backend
+        # THREE_PHASE, SUMMARY or SUMMARY_FUSED, stated once by the backend: as `protocol`, or, by a backend written before there was
+        # one, as `one_exchange` alone (summary protocol with separate expand / compress, or the three phases)
+        self.protocol = backend.protocol if hasattr(backend, "protocol") else protocol_of(backend.one_exchange)
+        assert self.protocol in (THREE_PHASE, SUMMARY, SUMMARY_FUSED), self.protocol
         self.group = group
         self.always_exchange = always_exchange   # tests: go through the exchange buffers also with one rank
 
@@ -172,28 +184,27 @@ class PhasedStepper:
 
     def step(self):
         b = self.backend
-        if getattr(b, "one_exchange", False):
-            # summary path (shared forcing): both predicate words follow from one summary word, include/roger_hip.h
-            if getattr(b, "fused_exchange", False):
-                # the exchange format written / read by the summary and control kernels themselves: per step one
-                # reduction kernel, one 256-byte all-reduce, the control kernel and the fused kernel
-                import torch.distributed as dist
+        # the two summary protocols (shared forcing): both predicate words follow from one summary word, include/roger_hip.h
+        if self.protocol == SUMMARY_FUSED:
+            # the exchange format written / read by the summary and control kernels themselves: per step one
+            # reduction kernel, one 256-byte all-reduce, the control kernel and the fused kernel
+            import torch.distributed as dist
 
-                buf = b.summary_to_buffer()
-                if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
-                    dist.all_reduce(buf, op=dist.ReduceOp.MAX, group=self.group)
-                b.finish_from_buffer(buf)
-                return
+            buf = b.summary_to_buffer()
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+                dist.all_reduce(buf, op=dist.ReduceOp.MAX, group=self.group)
+            b.finish_from_buffer(buf)
+        elif self.protocol == SUMMARY:
             b.summary_phase()
             self._exchange(3)
             b.finish_phase()
-            return
-        b.hooks_phase()
-        b.phase1()
-        self._exchange(0)
-        b.phase2()
-        self._exchange(1)
-        b.phase3()
+        else:
+            b.hooks_phase()
+            b.phase1()
+            self._exchange(0)
+            b.phase2()
+            self._exchange(1)
+            b.phase3()
 
     def run(self, nsteps):
         for _ in range(nsteps):
@@ -232,10 +243,10 @@ class HipPhases:
         import torch
 
         self.ctx = ctx
-        self.one_exchange = one_exchange   # False: the three-phase protocol (needed with per-cell forcing)
-        # the summary / control kernels write and read the 64-int32 exchange format themselves (False: separate
-        # rh_predicates_expand / rh_predicates_compress launches, the generic route also used by the three-phase protocol)
-        self.fused_exchange = fused_exchange
+        # one_exchange False: the three-phase protocol (needed with per-cell forcing).  fused_exchange: the summary / control kernels
+        # write and read the 64-int32 exchange format themselves (False: separate rh_predicates_expand / rh_predicates_compress
+        # launches, the generic route also used by the three-phase protocol)
+        self.protocol = protocol_of(one_exchange, fused_exchange)
         self.buf = {w: torch.zeros(64, dtype=torch.int32, device=device) for w in (0, 1, 3)}
         ctx.set_stream(torch.cuda.current_stream(device).cuda_stream)
 

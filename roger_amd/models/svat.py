@@ -134,7 +134,7 @@ class SVATSetup(RogerSetup):
 
 # The per-step hooks above are what the device-side control part performs itself (roger_hip.hip: hooks_set_forcing / ctrl_wave, the
 # monthly pipeline of k_step, the rotation inside the fused kernel): RogerSetup.run() advances on the device as long as a setup
-# script does not override them (roger_amd/roger.py: device_run_possible).
+# script does not override them (roger_amd/stepping.py: run_loop, over the facts of RogerSetup._facts).
 for _hook in (SVATSetup.read_data, SVATSetup.set_boundary_conditions, SVATSetup.set_forcing, SVATSetup.set_parameters, SVATSetup.after_timestep):
     _hook.device_equivalent = True
 

@@ -165,7 +165,7 @@ def collect(state):
     # The day's 3 x (x, y, 144) forcing arrays are left out at midnight ONLY where the script's set_forcing is known to re-derive them
     # there (the stock hook, or one recognised as doing the same: roger_amd/hooks.py); a set_forcing of the script's own that does
     # not must find the arrays it left.
-    midnight = int(np.asarray(vs.time)) % 86400 == 0 and bool(getattr(state, "_stock_set_forcing", False))
+    midnight = int(np.asarray(vs.time)) % 86400 == 0 and state._stock_set_forcing
     more = {}
     for key, var in state.var_meta.items():
         if key in _NOT_STATE or key in _FORCING_SERIES or (midnight and key in _FORCING_DAY):
@@ -188,8 +188,8 @@ def collect(state):
                    "tracer_monitor": {"C_s": np.float64(0.0), "M_S": np.float64(0.0)},
                    "water_monitor": {"S_s": np.float64(0.0), "S_sur": np.float64(0.0)}})
     ctx = state.backend_context
-    active = getattr(state, "_diag_active", None)
-    if active and not getattr(state, "_diag_transport", False) and not multi and hasattr(ctx, "diag_slot_times"):
+    active = state._diag_active
+    if active and not state._diag_transport and not multi:
         # the accumulators of the output interval the run is in (roger_amd/diagnostics.py; completed intervals were written out)
         iv = state._diag_interval
         slot = int(int(np.asarray(vs.time)) // iv) % state._diag_slots
@@ -510,8 +510,8 @@ def read_restart(state, filename=None):
             if np.asarray(getattr(vs, key)).dtype == np.bool_:
                 val = val.astype(np.bool_)
             setattr(vs, key, val)
-    active = getattr(state, "_diag_active", None)
-    if active and "hip_diag" in groups and rst.proc_num == 1 and not getattr(state, "_diag_transport", False):
+    active = state._diag_active
+    if active and "hip_diag" in groups and rst.proc_num == 1 and not state._diag_transport:
         ctx = state.backend_context
         slot, steps, t0, t1, written = (int(v) for v in groups["hip_diag"]["slot_state"])
         for nm in dict.fromkeys(v for d in active for v in d.output_variables):

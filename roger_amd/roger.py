@@ -11,14 +11,17 @@ Same abstract hooks, same call order in `setup()` (roger.py:258-336) and `step()
     after_timestep                                           user hook; its after_timestep_kernel
                                                              is native
 
-`run()` uses that hook-preserving sequence.  `run_device(nsteps)` is the fast path for setups
+`step()` is that hook-preserving sequence.  `run_device(nsteps)` is the fast path for setups
 whose hooks are the benchmark's (forcing series sliced at midnight, monthly surface parameters):
 it uploads vs.PREC/TA/PET/YEAR/MONTH/DOY once and advances with rh_run_steps, no host round trip.
+
+Which loop `run()` takes, which form `step()`'s physics has and what `run_device()` advances with is
+ONE decision: roger_amd/stepping.py holds it as a truth table over the facts that `_facts()` gathers.
 """
 import abc
 import os
 
-from . import diagnostics, distributed, logger, restart, runtime_settings as rs, runtime_state as rst
+from . import diagnostics, distributed, logger, restart, runtime_settings as rs, runtime_state as rst, stepping
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -34,6 +37,12 @@ class RogerSetup(metaclass=abc.ABCMeta):
 
         self.state = RogerState()
         self._setup_done = False
+        self._hook_classes = None       # {hook: True if the device performs it}, probed once (hook_classes)
+        self._device_hooks = False      # the forcing series are on the device (enable_device_hooks)
+        self._per_cell_forcing = False  # ... with station weights or several stations
+        self._comm_ready = False        # the context's communicator is set up (_comm_init)
+        self._in_warmup = False         # inside warmup()'s runs of the offline transport model
+        self._steppers = {}             # {one_exchange: distributed.PhasedStepper}, made on first use
 
     # -- the abstract hooks, roger/roger.py:47-252 -------------------------------------------
     @abc.abstractmethod
@@ -186,9 +195,10 @@ class RogerSetup(metaclass=abc.ABCMeta):
     @roger_routine
     def step(self, state):
         self._ensure_setup_done()
-        if state.settings.enable_offline_transport:
+        facts = self._facts()
+        if facts.offline_transport:
             return self._step_offline_transport(state)
-        if state.settings.restart_frequency > 0:
+        if facts.restart_every_step:
             with state.timers["diagnostics"]:
                 restart.write_restart(state)   # roger/roger.py:385-386
         with state.timers["main"]:
@@ -198,7 +208,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 self.set_boundary_conditions(state)
             with state.timers["forcing"]:
                 self.set_forcing(state)
-            if self._fused_host_step_possible():
+            if stepping.step_form(facts, self.hook_classes) == stepping.FUSED:
                 # The script brought hooks of its own for what comes BEFORE the physics (read_data, set_boundary_conditions, set_forcing)
                 # and left set_parameters and after_timestep to the model class: the rest of the step -- adaptive time step, the monthly
                 # surface parameters, the processes, the rotation -- is the fused kernel's, one native call instead of three and
@@ -207,14 +217,14 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     vs = state.variables
                     monthly = bool((vs.month[vs.tau] != vs.month[vs.taum1]) & (vs.itt > 1))
                     vs.flush_to_device()
-                    if hasattr(state.backend_context, "step_scalars"):
+                    if facts.has_step_scalars:
                         vs.mark_device_newer(None, scalars=state.backend_context.step_scalars(monthly))
                     else:   # (the oracle double of the CPU tests)
                         state.backend_context.step(monthly)
                         vs.mark_device_newer(None)
                 return self._end_of_step(state)
             with state.timers["adaptive time-stepping"]:
-                if rst.proc_num > 1:
+                if facts.multi_rank:
                     # dt is ONE scalar for the whole domain: the ranks agree on the predicates before it is derived
                     # (adaptive_time_stepping_dist_safe.py:6-26 does it through rank 0)
                     state.variables.flush_to_device()
@@ -231,7 +241,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
 
     @staticmethod
     def _end_of_step(state):
-        if getattr(state, "_diag_active", None):   # roger/roger.py:458-465: output at the end of the time step
+        if state._diag_active:   # roger/roger.py:458-465: output at the end of the time step
             diagnostics.output(state)
         if rs.profile_mode:
             state.backend_context.sync()
@@ -242,7 +252,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         from .core import transport
 
         vs = state.variables
-        if state.settings.restart_frequency > 0 and not getattr(self, "_in_warmup", False):
+        if state.settings.restart_frequency > 0 and not self._in_warmup:
             with state.timers["diagnostics"]:
                 restart.write_restart(state)   # at the start of a day step, as in step(); not during the warm-up runs
         with state.timers["main"]:
@@ -277,35 +287,33 @@ class RogerSetup(metaclass=abc.ABCMeta):
         """{hook: True if the device performs it} -- the hooks of the ready-made model classes by their mark, a script's own by
         probing them once against the recording state (after setup(): the probes look at the forcing series and weights)."""
         self._ensure_setup_done()
-        if getattr(self, "_hook_classes", None) is None:
+        if self._hook_classes is None:
             from . import hooks
 
             self._hook_classes = hooks.classify(self, self.STEP_HOOKS)
-            self.state._stock_set_forcing = bool(self._hook_classes["set_forcing"])   # (restart.collect: the day arrays at midnight)
+            self.state._stock_set_forcing = bool(self._hook_classes["set_forcing"])   # (restart.collect; set this late: stepping.py)
         return self._hook_classes
 
-    def _fused_host_step_possible(self):
-        """step(): the hooks BEHIND set_forcing (set_parameters, after_timestep) are the device's own -- the model class's, or a script's
-        that do the same --, one rank, no routing: the physics of the step is one native call (rh_svat_step)."""
-        settings = self.state.settings
-        if rst.proc_num > 1 or settings.enable_routing_1D or settings.enable_offline_transport:
-            return False
-        # (RH_STEP_BY_ROUTINE=1: the three-call step of rounds 1 - 3, for A/B and for the tests of that path)
-        if not hasattr(self.state.backend_context, "step") or os.environ.get("RH_STEP_BY_ROUTINE"):
-            return False
-        classes = self.hook_classes()
-        return classes["set_parameters"] and classes["after_timestep"]
+    def _facts(self):
+        """What stepping.py decides on, as of now.  The one place that asks what kind of context this is (the CPU tests' double differs)."""
+        settings, ctx = self.state.settings, self.state.backend_context
+        return stepping.Facts(
+            offline_transport=settings.enable_offline_transport, routing=settings.enable_routing_1D, profile_mode=rs.profile_mode,
+            restart_every_step=settings.restart_frequency > 0, multi_rank=rst.proc_num > 1, per_cell_forcing=self._per_cell_forcing,
+            step_by_routine=bool(os.environ.get("RH_STEP_BY_ROUTINE")), no_lean_loop=bool(os.environ.get("RH_NO_LEAN_LOOP")),
+            has_step_scalars=hasattr(ctx, "step_scalars"), has_run_steps_dist=hasattr(ctx, "run_steps_dist"))
 
     def device_run_possible(self):
         """True if `run()` may advance on the device without returning to the host between steps: the setup script left the
         per-step hooks to the model class (SVATSetup / ONEDSetup: forcing series sliced at midnight, monthly surface parameters,
         tau -> taum1 rotation), and nothing was asked for that needs the host after every step."""
-        settings = self.state.settings
-        if settings.enable_offline_transport or rs.profile_mode or settings.restart_frequency > 0:
-            return False
-        if not hasattr(self.state.backend_context, "run_steps") or os.environ.get("RH_STEP_BY_ROUTINE"):
-            return False
-        return all(self.hook_classes().values())
+        return stepping.device_rounds_possible(self._facts(), self.hook_classes)
+
+    def _fused_host_step_possible(self):   # (asked by tests)
+        return stepping.step_form(self._facts(), self.hook_classes) == stepping.FUSED
+
+    def _lean_host_loop_possible(self):   # (asked by tests)
+        return stepping.lean_loop_possible(self._facts(), self.hook_classes)
 
     def _run_on_device(self, start_time, runlen):
         """`while vs.time - start_time < runlen: step()` (roger/roger.py:548-556) without the host in the loop.  The step length is
@@ -319,15 +327,13 @@ class RogerSetup(metaclass=abc.ABCMeta):
         state = self.state
         vs = state.variables
         ctx = state.backend_context
-        if not getattr(self, "_device_hooks", False):
+        if not self._device_hooks:
             self.enable_device_hooks()
         t_stop = start_time + runlen
         slots = iv = None
-        if getattr(state, "_diag_active", None) and not getattr(state, "_diag_transport", False):
+        if state._diag_active and not state._diag_transport:
             slots, iv = state._diag_slots, state._diag_interval   # output intervals resident on the device; their length
-        limit = hasattr(ctx, "set_time_limit") and not getattr(self, "_per_cell_forcing", False) and not state.settings.enable_routing_1D
-        if rst.proc_num > 1 and not hasattr(ctx, "run_steps_dist"):
-            limit = False   # (the Python orchestration of the rehearsals, distributed.PhasedStepper, does not observe the device-side limit)
+        limit = stepping.time_limit(self._facts())   # (after enable_device_hooks: per-cell forcing is known)
         try:
             steps0, first = int(vs.itt), True
             while True:
@@ -351,11 +357,6 @@ class RogerSetup(metaclass=abc.ABCMeta):
             if limit:
                 ctx.set_time_limit(None)
 
-    def _lean_host_loop_possible(self):
-        settings = self.state.settings
-        return (self._fused_host_step_possible() and not rs.profile_mode and settings.restart_frequency <= 0
-                and hasattr(self.state.backend_context, "step_scalars") and not os.environ.get("RH_NO_LEAN_LOOP"))
-
     def _run_host_hooks(self, start_time, runlen):
         """`while vs.time - start_time < runlen: step()` (roger/roger.py:548-556) for a script whose hooks in FRONT of the physics are
         its own: those run on the host, step by step, as in the reference; the rest of the step is ONE native call that also brings back
@@ -369,7 +370,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(getattr(state, "_diag_active", None))
+        diag = bool(state._diag_active)
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -393,9 +394,10 @@ class RogerSetup(metaclass=abc.ABCMeta):
         runlen = settings.runlen if settings.warmup_done else settings.runlen_warmup   # roger/roger.py:541-546
         start_time = vs.time
         try:
-            if self.device_run_possible():
+            loop = stepping.run_loop(self._facts(), self.hook_classes)
+            if loop == stepping.DEVICE_ROUNDS:
                 self._run_on_device(int(start_time), int(runlen))
-            elif self._lean_host_loop_possible():
+            elif loop == stepping.LEAN_LOOP:
                 self._run_host_hooks(int(start_time), int(runlen))
             else:
                 while vs.time - start_time < runlen:
@@ -408,7 +410,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         else:
             failed = False
         finally:
-            in_warmup = settings.enable_offline_transport and getattr(self, "_in_warmup", False)
+            in_warmup = settings.enable_offline_transport and self._in_warmup
             if settings.write_restart and not in_warmup and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
@@ -451,33 +453,26 @@ class RogerSetup(metaclass=abc.ABCMeta):
         self._comm_ready = True
 
     def _stepper(self, one_exchange):
-        key = "_stepper_one" if one_exchange else "_stepper_three"
-        if getattr(self, key, None) is None:
-            setattr(self, key, distributed.PhasedStepper(distributed.phases_for(self.state.backend_context, one_exchange=one_exchange)))
-        return getattr(self, key)
+        if one_exchange not in self._steppers:
+            phases = distributed.phases_for(self.state.backend_context, one_exchange=one_exchange)
+            self._steppers[one_exchange] = distributed.PhasedStepper(phases)
+        return self._steppers[one_exchange]
 
     def run_device(self, nsteps, final=True):
-        if not getattr(self, "_device_hooks", False):
+        if not self._device_hooks:
             self.enable_device_hooks()
         vs = self.state.variables
         vs.flush_to_device()
         ctx = self.state.backend_context
-        if rst.proc_num > 1 and getattr(self, "_per_cell_forcing", False):
-            # per-cell forcing (station weights / several stations): every column forms its own prec / ta, so both predicate words are
-            # evaluated over the columns and exchanged -- the three-phase protocol (rh_run_steps_dist and the summary path need
-            # forcing shared by all columns and say so with RH_ERR_STATE)
-            self._stepper(one_exchange=False).run(nsteps)
-        elif rst.proc_num > 1:
-            # several ranks: one exchange of the summary word per step -- from C over RCCL where the context offers it
-            # (rh_comm_init + rh_run_steps_dist), through torch.distributed otherwise
-            if hasattr(ctx, "run_steps_dist"):
-                if not getattr(self, "_comm_ready", False):
-                    self._comm_init(ctx)
-                ctx.run_steps_dist(nsteps)
-            else:
-                self._stepper(one_exchange=True).run(nsteps)
-        else:
+        engine = stepping.engine(self._facts())
+        if engine == stepping.RUN_STEPS:
             ctx.run_steps(nsteps)
+        elif engine == stepping.RUN_STEPS_DIST:   # the summary word is exchanged from C over RCCL (rh_comm_init + rh_run_steps_dist)
+            if not self._comm_ready:
+                self._comm_init(ctx)
+            ctx.run_steps_dist(nsteps)
+        else:   # through torch.distributed: the summary word, or with per-cell forcing both predicate words (the three-phase protocol)
+            self._stepper(one_exchange=engine == stepping.PHASED_ONE).run(nsteps)
         vs.mark_device_newer()
-        if getattr(self.state, "_diag_active", None):
+        if self.state._diag_active:
             diagnostics.output(self.state, final=final)

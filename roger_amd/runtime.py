@@ -68,7 +68,7 @@ class RuntimeSettings:
     def __setattr__(self, attr, val):
         if attr == "__locked__":
             return object.__setattr__(self, attr, val)
-        if getattr(self, "__locked__", False):
+        if self.__locked__:   # (assigned first thing in __init__)
             raise RuntimeError("Runtime settings cannot be modified after importing core modules")
         if attr not in _AVAILABLE:
             raise AttributeError(f"Unknown runtime setting {attr}")

@@ -340,7 +340,14 @@ class RogerState:
         self._settings = RogerSettings(setting_meta)
         self._dimensions = dimensions
         self._ctx = None
+        self._sas_ctx = None             # the `_native.SasContext` of an offline-transport run
         self._diagnostics = {}
+        # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
+        # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
+        self._diag_active = None
+        self._diag_transport = False
+        self._diag_interval = self._diag_slots = self._diag_written_day = 0
+        self._stock_set_forcing = False  # set_forcing re-derives the day's arrays at midnight (RogerSetup.hook_classes, restart.collect)
         self.timers = defaultdict(Timer)
         self.profile_timers = defaultdict(Timer)
 
@@ -421,4 +428,4 @@ class RogerState:
     @property
     def sas_context(self):
         """The `_native.SasContext` of an offline-transport run (None otherwise)."""
-        return getattr(self, "_sas_ctx", None)
+        return self._sas_ctx

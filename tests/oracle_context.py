@@ -10,6 +10,7 @@ import numpy as np
 
 import oracle_binding as ob
 from roger_amd import _native as N
+from roger_amd.distributed import protocol_of
 
 _SC = ("itt", "time", "dt_secs", "itt_day", "itt_forc", "time_event0", "event_id_counter", "dt", "sanity_ok")
 _SC2 = ("event_id", "year", "month", "doy")
@@ -354,7 +355,7 @@ class OraclePhases:
 
     def __init__(self, ctx, one_exchange=False):
         self.ctx = ctx
-        self.one_exchange = one_exchange
+        self.protocol = protocol_of(one_exchange)
 
     def summary_phase(self):
         self.ctx._hooks()
