@@ -348,7 +348,10 @@ int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int
 int rh_diag_download(rh_ctx *ctx, int j, int slot, double *host, size_t bytes); /* synchronises */
 void *rh_diag_device_ptr(rh_ctx *ctx, int j, int slot);
 /* Number of steps accumulated in a day slot: the divisor of the "average" diagnostic (roger/diagnostics/average.py:
- * `avg += var; n += 1`, output avg / n) for a variable registered as a rate plane.  Synchronises. */
+ * `avg += var; n += 1`, output avg / n) for a variable registered as a rate plane; 0 for a slot no step has touched.  A slot that is
+ * first touched INSIDE its interval (rh_diag_configure or rh_diag_set_interval in the middle of a day) counts the steps that were
+ * actually accumulated -- 1 after the first one -- and keeps t_start = -1 (rh_diag_slot_times): it never saw its interval begin.
+ * Synchronises. */
 /* Restart (roger/restart.py:140-174 writes the diagnostics' accumulators next to the core state): put an accumulator slot back --
  * the values of variable j, and the slot's bookkeeping (steps accumulated, start time of the interval's first step, end time of its
  * last step: what rh_diag_steps / rh_diag_slot_times report). */
@@ -359,7 +362,9 @@ int rh_diag_steps(rh_ctx *ctx, int slot, int64_t *steps);
  * start on).  Slots are then indexed by the interval of the step's start; an interval that a longer step covers is never
  * started and its slot stays untouched.  rh_diag_slot_times tells which interval a slot holds: the start time of its first
  * step (-1: never touched) and the end time of its last one -- the reference writes a record whenever `time % frequency
- * == 0` (roger/diagnostics/api.py:47-70), i.e. at that end time.  Call rh_diag_set_interval before the first step. */
+ * == 0` (roger/diagnostics/api.py:47-70), i.e. at that end time.  Call rh_diag_set_interval before the first step: on a configured
+ * context it keeps the values and sets the bookkeeping of every slot back to "never touched", so the interval the run is in is
+ * accumulated as one that was first touched inside (t_start = -1 above). */
 int rh_diag_set_interval(rh_ctx *ctx, int64_t seconds);
 int rh_diag_slot_times(rh_ctx *ctx, int slot, int64_t *t_start, int64_t *t_end);
 

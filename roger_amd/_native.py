@@ -633,10 +633,10 @@ class Context:
     def diag_configure(self, rate=(), collect=(), n_slots=1):
         """Device-side daily accumulators: `rate` variables are summed per day, `collect` variables keep their
         end-of-day value (time level tau); n_slots days stay resident."""
-        self._diag_names = list(rate) + list(collect)
         ids = lambda names: (C.c_int * max(1, len(names)))(*[self.index[n] for n in names])  # noqa: E731
         r, c = ids(list(rate)), ids(list(collect))
         self._check(self._lib.rh_diag_configure(self._h, r, len(rate), c, len(collect), int(n_slots)), "rh_diag_configure")
+        self._diag_names = list(rate) + list(collect)   # (a refused configuration leaves the previous one, names included)
 
     def diag_download(self, name, slot):
         a = np.empty(self.n, dtype=np.float64)

@@ -1164,7 +1164,8 @@ __global__ __launch_bounds__(RH_BLOCK) void k_summary(Arena a, DevState *D) {
 // Output accumulators: after a step that covered (t0, t1], day = t0 / 86400, slot = day mod diag_slots; the first
 // step of a day (t0 on midnight) overwrites.  Rate planes add this step's value (Rate.diagnose, roger/diagnostics/
 // rate.py:66-84: `rate += var[..., tau]`), collect planes keep the current one.  S.time / S.dt_secs were advanced by
-// the control kernel before the fused kernel ran.
+// the control kernel before the fused kernel ran.  Per slot {steps, t0 of the interval's first step, t1 of its last step}, -1 each
+// until a step touches the slot; a slot first touched inside its interval counts from 1 and keeps t0 = -1 (include/roger_hip.h).
 // after_fused: the launch follows a fused k_step, whose prologue has just written D->skipped (the step found the run over,
 // rh_set_time_limit: nothing to add).  Behind the routine-by-routine step (rh_step_core) and the routed passes there is no such
 // launch in front and the flag may be left over from an earlier device run under a limit: they pass 0.
@@ -1178,7 +1179,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_diag(Arena a, DevState *D, int aft
     double *base = D->diag + (size_t)slot * nv * a.n;
     if (i == 0) {
         long long *m = D->diag_steps + 3 * slot;
-        m[0] = first ? 1 : m[0] + 1;
+        m[0] = (first || m[0] < 0) ? 1 : m[0] + 1;   // (-1: never touched -- a slot first touched inside its interval counts the steps accumulated)
         if (first) m[1] = t0;
         m[2] = D->S.time;
     }

@@ -156,13 +156,16 @@ class OracleContext:
 
     # the device-side output accumulators (rh_diag_*), restated: a slot per day of the step's start
     def diag_configure(self, rate=(), collect=(), n_slots=1):
-        self._diag = dict(rate=list(rate), collect=list(collect), n_slots=int(n_slots), interval=86400,
+        interval = getattr(self, "_diag", {}).get("interval", 86400)   # (the context keeps its interval over a new configuration)
+        self._diag = dict(rate=list(rate), collect=list(collect), n_slots=int(n_slots), interval=interval,
                           data={v: np.zeros((int(n_slots), self.n)) for v in list(rate) + list(collect)},
-                          steps=np.zeros(int(n_slots), dtype=np.int64), t0=np.full(int(n_slots), -1, dtype=np.int64),
+                          steps=np.full(int(n_slots), -1, dtype=np.int64), t0=np.full(int(n_slots), -1, dtype=np.int64),
                           t1=np.full(int(n_slots), -1, dtype=np.int64))
 
     def diag_set_interval(self, seconds):
         self._diag["interval"] = int(seconds)
+        for k in ("steps", "t0", "t1"):   # rh_diag_set_interval: the bookkeeping of every slot starts over
+            self._diag[k][:] = -1
 
     def diag_slot_times(self, slot):
         return int(self._diag["t0"][int(slot)]), int(self._diag["t1"][int(slot)])
@@ -174,7 +177,7 @@ class OracleContext:
         s = self.st.scal
         t0, iv = s.time - s.dt_secs, d["interval"]
         slot, first = (t0 // iv) % d["n_slots"], t0 % iv == 0
-        d["steps"][slot] = 1 if first else d["steps"][slot] + 1
+        d["steps"][slot] = 1 if first else max(int(d["steps"][slot]), 0) + 1   # (-1: never touched; a slot first touched inside its interval counts from 1)
         if first:
             d["t0"][slot] = t0
         d["t1"][slot] = s.time
@@ -187,7 +190,7 @@ class OracleContext:
         return self._diag["data"][name][int(slot)].copy()
 
     def diag_steps(self, slot):
-        return int(self._diag["steps"][int(slot)])
+        return max(int(self._diag["steps"][int(slot)]), 0)   # (rh_diag_steps: 0 for a slot nobody has touched)
 
     def diag_upload(self, name, slot, values):
         self._diag["data"][name][int(slot)] = np.asarray(values, dtype=np.float64).reshape(-1)
