@@ -6,12 +6,19 @@
 // re-read within a kernel.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef RH_HOST   // rh_physics.h as host functions (tools/substep_dry_check.cpp): no arena, and a "wavefront" is the one column
+#include <math.h>
+#define RH_DEV static inline
+#define RH_WAVE_ALL(p) (p)
+#else
+#include <hip/hip_runtime.h>
+#define RH_DEV __device__ __forceinline__
+// the predicate holds on every ACTIVE lane of the wavefront (the grid's last wavefront may run with its upper lanes switched off): uniform
+#define RH_WAVE_ALL(p) (__ballot(!(p)) == 0)
+#endif
 
 #include "roger_hip.h"
-
-#define RH_DEV __device__ __forceinline__
 
 struct Col {
 #define RH_DECL_F64_1(name) double name;
@@ -51,6 +58,7 @@ struct Arena {
     int64_t n;      // cells
 };
 
+#ifndef RH_HOST
 // Address of cell i of a plane.  The tile index is uniform over the wavefront (every kernel maps lane l of a
 // wave to cell 64 * k + l), so it is taken from the first active lane and the whole tile/plane part of the address is
 // scalar arithmetic; the per-lane part is lane * element size.
@@ -74,6 +82,7 @@ RH_DEV void rh_ld(const Arena &a, int plane, int64_t i, double &dst) { dst = __b
 RH_DEV void rh_ld(const Arena &a, int plane, int64_t i, int &dst) { dst = __builtin_nontemporal_load(rh_cell<const int>(a, plane, i)); }
 RH_DEV void rh_st(const Arena &a, int plane, int64_t i, double v) { __builtin_nontemporal_store(v, rh_cell<double>(a, plane, i)); }
 RH_DEV void rh_st(const Arena &a, int plane, int64_t i, int v) { __builtin_nontemporal_store(v, rh_cell<int>(a, plane, i)); }
+#endif   // RH_HOST
 
 // Settings that the kernels read (subset of rh_config, device copy).
 struct Consts {

@@ -17,9 +17,14 @@
 
 // The power function of the physics: rh_pow (rh_pow.h: ~80 instructions instead of the library's 230, within 1 ulp of a correctly rounded
 // pow, the same bits on host and device; rounds 1 - 2 ran the library's pow).
+#ifndef RH_HOST
 #define RH_POW_FN __device__ __forceinline__
 #define RH_POW_CONST static __constant__
+#endif
 #include "rh_pow.h"
+#ifndef RH_DRY_NOTE   // (tools/substep_dry_check.cpp counts the stage calls that end in a dry path)
+#define RH_DRY_NOTE(k)
+#endif
 
 RH_DEV double h_b(bool x) { return x ? 1.0 : 0.0; }
 
@@ -429,7 +434,7 @@ RH_DEV void h_inf_mat(Col &c, double dt, double mk) {
     c.theta_d = (c.theta_d_t1 <= 0 ? c.theta_d_t0 : c.theta_d) * mk;  // :411-416
 }
 
-RH_DEV bool h_same(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+RH_DEV bool h_same(double a, double b) { return rh_pow_double_to_bits(a) == rh_pow_double_to_bits(b); }
 
 // Length of the front that macropores / cracks still reach, :443-518 and :1092-1167.  The
 // reference builds z_wf(_m1) twice and the second assignment wins, so only the second front
@@ -453,7 +458,45 @@ RH_DEV double h_open_length(double len, double z_wf_tau, const Col &c, int subst
 // as soon as one iteration maps its loop state onto itself bit for bit: the body is a pure
 // function of that state, so every further iteration would reproduce it.  On dry days (z0 = 0)
 // that happens after the second iteration; the wavefront runs until its last lane is done.
-RH_DEV void h_inf_mp(Col &c, const Consts &K, double dt, int substeps, double mk) {
+//
+// DRY reaches the helpers as a tag argument, not as h_inf_mp<DRY>(..): tools/gen_sets.py and tools/liveness.py follow calls by name.
+template <bool DRY> struct DryPath {};
+// The second half of a sub-step: the front's radius from the event's infiltration sum.
+RH_DEV double h_mp_radius(double ecs, const Col &c, const Consts &K, double mk) {
+    const double r = K.r_mp;
+    const double y = r + sqrt((ecs / (c.dmpv * c.theta_d)) / K.pi) * mk;
+    return (y < r ? r : y) * mk;
+}
+// DRY (the LAZY pipelines of the fused step): a wavefront whose columns all infiltrate +0.0 in every sub-step skips the loop.  Of
+// the loop's state only `y` and `inf` are read behind it.  If every sub-step's `di` is +0.0 (and substeps >= 1, mk is 0 or 1), then
+//   inf:  0.0, `inf += di * mk` = +0 + +0 = +0, `(inf < 0 ? 0.0 : inf) * mk` = +0 -- it never leaves +0.0;
+//   ecs:  `ecs += di * mk` adds +0.0: after the first sub-step ecs = ecs0 + 0.0 (ecs0 itself but for -0.0, which becomes +0.0, and a
+//         signalling NaN), and adding +0.0 again changes no bit;
+//   y:    the last sub-step's `y` is h_mp_radius(ecs, ..), a function of ecs and loop constants alone: h_mp_radius(ecs0 + 0.0, ..)
+//         whatever the number of sub-steps run and whatever t and ym1 were, so the fixed-point exit does not matter either.
+// When is every `di` +0.0?  The statements of the body that lead to it, in order:
+//   (A) lmpv_non_sat == 0:  `di = (c.lmpv_non_sat == 0 ? 0.0 : di) * mk` = 0.0 * mk = +0.0 for mk in {0, 1}, whatever the first half
+//       of the body computed, NaNs included.  (mk = 0 gives lmpv_non_sat = x * 0: +-0 -> here, or NaN -> neither case: the loop.)
+//   (B) otherwise all of: z0_di has the bits of +0.0;  theta_d, dmpv, lmpv_non_sat, K.pi and a = theta_d * r * r * mk are positive
+//       and finite (then mk = 1: lmpv_non_sat = x * mk is not zero; and r is finite and not zero);  0 <= ym1 < 1e150 for both values
+//       ym1 takes at the head of a sub-step: y_mp_m1 * mk in the first, Y = h_mp_radius(ecs0 + 0.0, ..) in all later ones.  Then
+//       cc, b1, b2   each is laundered (`isnan(x) ? 0.0 : x`) and b2 is clamped at 0 besides: b2 lies in [+0, +inf] whatever t and
+//                    geo = ks * wfs are -- no condition on them, nor on the t of the later sub-steps;
+//       cb           rh_pow(b2, 1/3) of b2 in [+0, +inf]: +0 at +0, positive on the short path (rh_pow.h: |y log2 x| < 342), the
+//                    library's pow for denormal b2 (positive) and +inf (+inf).  In [+0, +inf], never NaN, never -0;
+//       y1           (cb / theta_d) * 0.5 * mk in [+0, +inf] (theta_d positive, finite);
+//       y2           (a / cb) * 0.5 * mk: a positive and finite over cb in [+0, +inf] is in [+0, +inf] (+inf at cb = 0) -- not NaN;
+//       y            y1 + y2 + ym1: three terms >= 0, so no inf - inf: in [+0, +inf].  The two clamps only raise it and r, ym1 are
+//                    not NaN: y >= ym1 >= 0 afterwards;
+//       pot          y * y >= ym1 * ym1 (rounding is monotonic) and ym1 * ym1 < 1e300 is finite: the difference is in [+0, +inf],
+//                    +0 when equal (x - x = +0 in round-to-nearest).  Times K.pi, lmpv_non_sat, theta_d, dmpv, 1e-06, mk = 1, all
+//                    positive and finite: +inf stays +inf, +0 stays +0, nothing meets 0 * inf.  pot is +0 or in (0, +inf];
+//       di           `pot > z0_di ? z0_di : pot`: z0_di = +0 when pot > 0, pot = +0 otherwise.  `* mk`, the lmpv_non_sat select
+//                    (not zero: di) and `* mk` again leave +0.0.
+// Any column outside (A) and (B) -- water on the surface, a NaN early in an event, theta_d = 0, ... -- sends its whole wavefront
+// through the loop, which stays the definition (tools/substep_dry_check.cpp runs both on 10^7 states, every byte of the column equal).
+template <bool DRY = false>
+RH_DEV void h_inf_mp(Col &c, const Consts &K, double dt, int substeps, double mk, DryPath<DRY> = {}) {
     c.lmpv_non_sat = h_open_length(c.lmpv, c.z_wf, c, substeps, mk);
     const double zw = (c.no_wf == 2 ? 0.0 : c.z_wf_t1) * mk;
     const double r = K.r_mp, r3 = r * r * r;
@@ -464,7 +507,23 @@ RH_DEV void h_inf_mp(Col &c, const Consts &K, double dt, int substeps, double mk
     const double z0_di = c.z0 * (c.mp_drain_area / substeps) * mk;
     const double h = dt / substeps;
     double y = c.y_mp_m1 * mk, ym1 = c.y_mp_m1 * mk, ecs = c.inf_mp_event_csum * mk, t = 0.0, inf = 0.0;
-    for (int it = 0; it < substeps; ++it) {
+    bool dry = false;   // (uniform over the wavefront)
+    if constexpr (DRY) {
+        const double lns = c.lmpv_non_sat;
+        const bool mk01 = (mk == 0.0 || mk == 1.0) && substeps >= 1;
+        // in two votes: a wavefront with water on its surface pays the first only
+        if (RH_WAVE_ALL(mk01 && (lns == 0 || h_same(z0_di, 0.0)))) {
+            const double yd = h_mp_radius(ecs + 0.0, c, K, mk);
+            const bool pos = c.theta_d > 0 && c.theta_d < INFINITY && c.dmpv > 0 && c.dmpv < INFINITY && lns > 0 && lns < INFINITY &&
+                             K.pi > 0 && K.pi < INFINITY && a > 0 && a < INFINITY;
+            if (RH_WAVE_ALL(lns == 0 || (pos && ym1 >= 0 && ym1 < 1e150 && yd >= 0 && yd < 1e150))) {
+                y = yd;
+                dry = true;
+                RH_DRY_NOTE(0);
+            }
+        }
+    }
+    for (int it = 0; it < (dry ? 0 : substeps); ++it) {
         const double t_in = t, ym1_in = ym1, ecs_in = ecs, inf_in = inf;
         t += h * mk;
         double cc = geo * t * mk;
@@ -485,8 +544,7 @@ RH_DEV void h_inf_mp(Col &c, const Consts &K, double dt, int substeps, double mk
         di = (c.lmpv_non_sat == 0 ? 0.0 : di) * mk;
         inf += di * mk;
         ecs += di * mk;
-        y = r + sqrt((ecs / (c.dmpv * c.theta_d)) / K.pi) * mk;
-        y = (y < r ? r : y) * mk;
+        y = h_mp_radius(ecs, c, K, mk);
         t = c.theta_d / (geo * r) * ((y * y * y) / 3.0 - (y * y) * r / 2.0 + r3 / 6.0) * mk;
         inf = (inf < 0 ? 0.0 : inf) * mk;
         ym1 = y * mk;
@@ -528,13 +586,46 @@ RH_DEV void h_inf_mp(Col &c, const Consts &K, double dt, int substeps, double mk
 // shrinkage-crack infiltration :1081-1318.  In the reference the loop carry slot of inf_sc is
 // never written (:1278-1283), so inf_sc stays 0 and only y_sc / z_sc_non_sat change.  Same
 // fixed-point exit as above.
-RH_DEV void h_inf_sc(Col &c, const Consts &K, double dt, int substeps, double mk) {
+//
+// The second half of a sub-step: the crack front from the event's infiltration sum.
+RH_DEV double h_sc_front(double ecs, const Consts &K, double mk) { return (ecs / K.l_sc / 2) * mk; }
+// DRY, as in h_inf_mp: only `y` is read behind the loop, and the last sub-step leaves y = h_sc_front(ecs, ..).  If every sub-step's
+// `di` is +0.0 (substeps >= 1, mk 0 or 1), `di += di * mk` is +0.0 and `ecs += di * mk` makes ecs = ecs0 + 0.0 once and for all:
+// y = h_sc_front(ecs0 + 0.0, ..) whatever the number of sub-steps run.  Every `di` is +0.0 in two cases:
+//   (A) z_sc_non_sat <= 0:  `di = (c.z_sc_non_sat <= 0 ? 0.0 : di) * mk` = 0.0 * mk = +0.0, whatever pot was.
+//   (B) z0_di has the bits of +0.0 and pot is not NaN in any sub-step: `pot = (pot <= 0 ? 0.0 : pot) * mk` leaves +0 or a value in
+//       (0, +inf] (mk = 1, below); `pot > z0_di ? z0_di : pot` is z0_di = +0 in the second case and pot = +0 in the first.  pot is not
+//       NaN where w = z_sc_non_sat * theta_d * K.l_sc, theta_d, g2 = geo * 2 and h = dt / substeps are positive and finite (then mk = 1,
+//       as z_sc_non_sat = x * mk is not zero, and geo is positive and finite) and both values ym1 takes at the head of a sub-step
+//       are finite -- y_sc_m1 * mk in the first, Y = h_sc_front(ecs0 + 0.0, ..) in all later ones:
+//       t            at the head of sub-step 1 it is 0; later `((ym1 * ym1 * c.theta_d) / (geo * 2)) * mk` with ym1 finite:
+//                    ym1 * ym1 in [+0, +inf], times theta_d (positive, finite) in [+0, +inf], over g2 (positive, finite) in
+//                    [+0, +inf]: never NaN, never negative.  `t += h * mk` puts it into (0, +inf];
+//       y            sqrt((geo * t * 2) / theta_d): geo positive and finite times t in (0, +inf] is in [+0, +inf] (it may underflow,
+//                    it cannot be 0 * inf), times 2 and over theta_d likewise: the root of a value in [+0, +inf] is in [+0, +inf];
+//       pot          y - ym1 with ym1 finite is in [-inf, +inf], not NaN; w is positive and finite, so w * (y - ym1) is no 0 * inf:
+//                    not NaN, nor after `* 1e-06` and `* mk`.
+// Any other column sends its wavefront through the loop.
+template <bool DRY = false>
+RH_DEV void h_inf_sc(Col &c, const Consts &K, double dt, int substeps, double mk, DryPath<DRY> = {}) {
     c.z_sc_non_sat = h_open_length(c.z_sc, c.z_wf, c, substeps, mk);
     const double geo = c.ks * c.wfs;
     const double z0_di = (c.z0 / substeps) * mk;
     const double h = dt / substeps;
     double y = c.y_sc_m1 * mk, ym1 = c.y_sc_m1 * mk, ecs = c.inf_sc_event_csum * mk, t = 0.0;
-    for (int it = 0; it < substeps; ++it) {
+    bool dry = false;   // (uniform over the wavefront)
+    if constexpr (DRY) {
+        const double zns = c.z_sc_non_sat, w = zns * c.theta_d * K.l_sc, g2 = geo * 2;
+        const double yd = h_sc_front(ecs + 0.0, K, mk);
+        const bool pos = w > 0 && w < INFINITY && c.theta_d > 0 && c.theta_d < INFINITY && g2 > 0 && g2 < INFINITY && h > 0 && h < INFINITY;
+        const bool fin = ym1 > -INFINITY && ym1 < INFINITY && yd > -INFINITY && yd < INFINITY;
+        if (RH_WAVE_ALL((mk == 0.0 || mk == 1.0) && substeps >= 1 && (zns <= 0 || (h_same(z0_di, 0.0) && pos && fin)))) {
+            y = yd;
+            dry = true;
+            RH_DRY_NOTE(1);
+        }
+    }
+    for (int it = 0; it < (dry ? 0 : substeps); ++it) {
         const double t_in = t, ym1_in = ym1, ecs_in = ecs;
         t += h * mk;
         y = sqrt((geo * t * 2) / c.theta_d) * mk;
@@ -544,7 +635,7 @@ RH_DEV void h_inf_sc(Col &c, const Consts &K, double dt, int substeps, double mk
         di = (c.z_sc_non_sat <= 0 ? 0.0 : di) * mk;
         di += di * mk;  // :1248-1252
         ecs += di * mk;
-        y = (ecs / K.l_sc / 2) * mk;
+        y = h_sc_front(ecs, K, mk);
         t = ((ym1 * ym1 * c.theta_d) / (geo * 2)) * mk;
         ym1 = y * mk;
         if (h_same(t, t_in) && h_same(ym1, ym1_in) && h_same(ecs, ecs_in)) break;
@@ -613,11 +704,15 @@ RH_DEV void rt_inf_matrix(Col &c, const Consts &K, const StepCtx &X) {
     h_green_ampt(c, X.dt, mk);
     h_inf_mat(c, X.dt, mk);
 }
-RH_DEV void rt_inf_macropores(Col &c, const Consts &K, const StepCtx &X) {
-    h_inf_mp(c, K, X.dt, h_inf_substeps(X.dt), (double)c.maskCatch);
+// DRY: the dry paths of the two sub-step loops -- the LAZY pipelines of the fused step only; the per-routine kernels, the eager pipeline
+// and the routed passes keep the loops alone
+template <bool DRY = false>
+RH_DEV void rt_inf_macropores(Col &c, const Consts &K, const StepCtx &X, DryPath<DRY> dry = {}) {
+    h_inf_mp(c, K, X.dt, h_inf_substeps(X.dt), (double)c.maskCatch, dry);
 }
-RH_DEV void rt_inf_cracks(Col &c, const Consts &K, const StepCtx &X) {
-    h_inf_sc(c, K, X.dt, h_inf_substeps(X.dt), (double)c.maskCatch);
+template <bool DRY = false>
+RH_DEV void rt_inf_cracks(Col &c, const Consts &K, const StepCtx &X, DryPath<DRY> dry = {}) {
+    h_inf_sc(c, K, X.dt, h_inf_substeps(X.dt), (double)c.maskCatch, dry);
 }
 RH_DEV void rt_inf_finish(Col &c, const Consts &K, const StepCtx &X) {
     const double mk = (double)c.maskCatch;

@@ -185,9 +185,9 @@ __device__ unsigned long long g_step_phases[256 * 64];   // 256 copies (one addr
     RH_LOADS(seq, rt_inf_macropores) RH_PIN                                                                     \
     RH_DERIVE(rt_inf_matrix) rt_inf_matrix(c, K, X); RH_STORES(seq, rt_inf_matrix) RH_PH(6)                       \
     RH_LOADS(seq, rt_inf_cracks) RH_PIN                                                                         \
-    RH_DERIVE(rt_inf_macropores) rt_inf_macropores(c, K, X); RH_STORES(seq, rt_inf_macropores) RH_PH(7)           \
+    RH_DERIVE(rt_inf_macropores) rt_inf_macropores(c, K, X, DryPath<LAZY>()); RH_STORES(seq, rt_inf_macropores) RH_PH(7) \
     RH_LOADS(seq, rt_inf_finish) RH_PIN                                                                         \
-    rt_inf_cracks(c, K, X); RH_STORES(seq, rt_inf_cracks) RH_PH(8)                                                \
+    rt_inf_cracks(c, K, X, DryPath<LAZY>()); RH_STORES(seq, rt_inf_cracks) RH_PH(8)                               \
     RH_LOADS(seq, sub_rt) RH_PIN                                                                                \
     rt_inf_finish(c, K, X); RH_STORES(seq, rt_inf_finish) RH_PH(9)                                                \
     RH_LOADS(seq, rt_capillary_rise) RH_PIN                                                                     \
