@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 5   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid */
+#define RH_ABI_VERSION 6   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -367,6 +367,35 @@ int rh_diag_steps(rh_ctx *ctx, int slot, int64_t *steps);
  * accumulated as one that was first touched inside (t_start = -1 above). */
 int rh_diag_set_interval(rh_ctx *ctx, int64_t seconds);
 int rh_diag_slot_times(rh_ctx *ctx, int slot, int64_t *t_start, int64_t *t_end);
+
+/* ---- time series at observation columns ("points"), recorded on the device every step ---------------
+ * The accumulators above give whole grids per output interval; a comparison with a lysimeter, a soil-moisture profile or a gauge
+ * needs a handful of columns at the model's own time resolution, and inside rh_run_steps the host cannot look at a column between
+ * two steps.  After rh_points_configure every step -- wherever the accumulator kernel is launched: rh_step_core, the fused step
+ * (rh_svat_step, rh_run_steps, rh_run_steps_dist, rh_step_phase3, rh_step_finish) and both routed steps -- is followed by ONE
+ * workgroup that gathers planes x cells into the next row of a ring on the device, with the row's header {itt, time at the END of
+ * the step, dt_secs}.  A pure gather: every value is the bits of the plane.  A launch behind the time limit (rh_set_time_limit)
+ * records nothing.
+ *   cells[n_cells]:   interior column indices of the rank's block in C order over (x, y) -- the indices rh_upload / rh_download
+ *                     use; n_cells <= 256, no cell twice
+ *   planes[n_planes]: float64 plane ids below rh_planes_held; n_planes <= 32.  ANY such plane may be observed: one that the sparse
+ *                     steps of rh_run_steps leave out (the pure outputs, and k_rz, k_ss, h_rz, h_ss, ks_ss, which the storage stage
+ *                     computes in every step although the next lazy step does not load them) is stored after all by the KEEP variant
+ *                     of the sparse kernel, an X_m1 plane switches the lazy rotation off -- no plane is refused, none is recorded
+ *                     stale.  The keep bits and the rotation follow from the UNION of the accumulators' and the points' planes:
+ *                     rh_diag_configure and rh_points_configure may be called in either order.
+ *   capacity >= 1:    rows resident on the device, row r at r mod capacity: (capacity, n_planes, n_cells) float64
+ * n_cells == 0 or n_planes == 0 releases the buffers and stops the launches.  Every other call starts a new series (row 0).
+ * RH_ERR_ARG (rh_last_error names the value): a cell outside [0, n), an int32 plane or one the context does not hold, counts above
+ * the limits, a cell given twice, capacity < 1.
+ *   rh_points_count  rows recorded since rh_points_configure
+ *   rh_points_read   rows [first_row, first_row + n_rows) that are still resident (first_row >= rows_total - capacity): hdr (n_rows, 3)
+ *                    int64, values (n_rows, n_planes, n_cells) float64.  RH_ERR_ARG for rows that have been overwritten or not
+ *                    recorded yet -- never other data.
+ * Both synchronise; RH_ERR_STATE before rh_points_configure (or after it released the buffers). */
+int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const int *planes, int n_planes, int64_t capacity);
+int rh_points_count(rh_ctx *ctx, int64_t *rows_total);
+int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 5   # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 6   # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -155,6 +155,9 @@ def load():
     lib.rh_diag_steps.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.rh_diag_device_ptr.argtypes = [vp, i32, i32]
     lib.rh_diag_device_ptr.restype = vp
+    lib.rh_points_configure.argtypes = [vp, vp, i32, vp, i32, i64]
+    lib.rh_points_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_points_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -405,6 +408,7 @@ DECLARED_SYMBOLS = (
     "rh_step_summary", "rh_step_finish", "rh_diag_set_interval", "rh_diag_slot_times", "rh_placement_report", "rh_step_summary_expand", "rh_step_finish_compress", "rh_diag_configure", "rh_diag_download", "rh_diag_device_ptr", "rh_diag_steps",
     "rh_set_forcing_weights", "rh_adaptive_dt_finish", "rh_diag_upload", "rh_diag_set_slot_state", "rh_set_forcing_stations", "rh_step_mode", "rh_comm_unique_id", "rh_comm_init", "rh_set_comm", "rh_comm_info", "rh_comm_set_grid", "rh_plane_is_pure_output", "rh_sparse_steps", "rh_set_time_limit", "rh_run_steps_dist",
     "rh_surface_routing", "rh_subsurface_routing", "rh_step_routed", "rh_planes_held", "rh_route_out", "rh_route_in", "rh_route_get_edges", "rh_route_get_static_edges", "rh_route_set_halo",
+    "rh_points_configure", "rh_points_count", "rh_points_read",
 )
 
 
@@ -669,6 +673,33 @@ class Context:
 
     def diag_device_ptr(self, name, slot):
         return self._lib.rh_diag_device_ptr(self._h, self._diag_names.index(name), int(slot))
+
+    # -- time series at observation columns (rh_points_*) ---------------------------------------
+    def points_configure(self, cells, names, capacity=4096):
+        """Record `names` (float64 planes) at `cells` (interior indices of this context's block, C order) after every step, in a ring of
+        `capacity` rows on the device.  No cells or no names: release the buffers and stop recording."""
+        c = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1)
+        names = list(names)
+        ids = (C.c_int * max(1, len(names)))(*[self.index[n] for n in names])
+        self._check(self._lib.rh_points_configure(self._h, c.ctypes.data_as(C.c_void_p), c.size, ids, len(names), int(capacity)),
+                    "rh_points_configure")
+        self._points_shape = (len(names), c.size)   # (a refused configuration leaves the previous one)
+
+    def points_count(self):
+        """Rows recorded since points_configure."""
+        n = C.c_int64()
+        self._check(self._lib.rh_points_count(self._h, C.byref(n)), "rh_points_count")
+        return n.value
+
+    def points_read(self, first, n):
+        """Rows [first, first + n) of the ring: (hdr int64 (n, 3): itt, time at the end of the step, dt_secs; values float64 (n, V, K))."""
+        n = int(n)
+        nv, nc = getattr(self, "_points_shape", (0, 0))
+        hdr = np.empty((n, 3), dtype=np.int64)
+        values = np.empty((n, nv, nc), dtype=np.float64)
+        self._check(self._lib.rh_points_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                             values.nbytes), "rh_points_read")
+        return hdr, values
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

@@ -1190,6 +1190,33 @@ __global__ __launch_bounds__(RH_BLOCK) void k_diag(Arena a, DevState *D, int aft
         *p = (j < nr && !first) ? *p + v : v;
     }
 }
+// Time series at observation columns (rh_points_configure): after a step, ONE workgroup gathers planes x cells into row
+// points_rows mod points_cap of the ring and writes the row's header {itt, time at the end of the step, dt_secs} from D->S, as the
+// control part left them for this step.  The cells lie anywhere in the arena, so the address is formed per lane (rh_cell_any: the
+// tiled addressing without the wave-uniform tile of rh_cell).  Every thread reads the row counter, the barrier follows, and thread 0
+// writes counter + 1 last: no thread of a launch sees the counter this launch advanced.  after_fused as for k_diag: a fused launch
+// that found the run over (rh_set_time_limit) records nothing.
+__global__ __launch_bounds__(RH_BLOCK) void k_points(Arena a, DevState *D, int after_fused) {
+    if (after_fused && D->skipped) return;
+    const long long row = D->points_rows;
+    const int nc = D->points_ncells, nv = nc * D->points_nplanes;
+    const long long slot = row % D->points_cap;
+    double *dst = D->points + (size_t)slot * nv;
+    for (int k = threadIdx.x; k < nv; k += RH_BLOCK) {
+        const int j = k / nc, c = k - j * nc;
+        dst[k] = __builtin_nontemporal_load(rh_cell_any<const double>(a, D->points_planes[j], D->points_cells[c]));
+    }
+    const rh_scalars &S = D->S;
+    const long long itt = S.itt, time = S.time, dt_secs = S.dt_secs;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long *h = D->points_hdr + 3 * slot;
+        h[0] = itt;
+        h[1] = time;
+        h[2] = dt_secs;
+        D->points_rows = row + 1;
+    }
+}
 // multi-GPU: OR of the summary words into words[3] for the exchange
 // dst64 != null: also spread over 64 int32 (0 / 1) for the MAX all-reduce (k_words_expand folded in)
 __global__ __launch_bounds__(RH_BLOCK) void k_summary_reduce(DevState *D, int do_hooks, int *dst64, int src) {

@@ -27,6 +27,8 @@
 #define RH_WSTRIDE 16       // words between two slots of the device-wide OR words (sumw, frontw, dayw): 128 bytes -- a slot per cache line
 #endif
 #define RH_SRC_SUMW 1        // ... in sumw[] (k_summary rebuilt it from the arena)
+#define RH_POINTS_MAX_CELLS 256   // rh_points_configure: observation columns and planes per row -- at most 8 192 values, gathered by
+#define RH_POINTS_MAX_PLANES 32   // ONE workgroup (k_points)
 #ifndef RH_STEP_WAVES
 #define RH_STEP_WAVES 2     // waves per SIMD the fused kernel is compiled for (register budget 512 / waves)
 #endif
@@ -111,6 +113,16 @@ struct DevState {
     int64_t mlms_rows;
     int max_slope_per;
     Luts L;
+
+    // time series at observation columns (rh_points_configure; k_points): a ring of points_cap rows on the device, row r at r mod
+    // points_cap -- points (row, plane, cell) float64 and points_hdr {itt, time at the end of the step, dt_secs} per row.  points_rows
+    // counts the rows recorded since the configuration.  (Behind everything else: no member a k_step variant addresses moves.)
+    double *points;
+    long long *points_hdr;
+    long long points_rows, points_cap;
+    int points_ncells, points_nplanes;
+    int points_planes[RH_POINTS_MAX_PLANES];
+    long long points_cells[RH_POINTS_MAX_CELLS];
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

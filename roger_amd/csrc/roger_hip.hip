@@ -18,6 +18,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types only: the entry points are resolved with dlsym on first use (rccl_api)
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -230,9 +231,10 @@ struct rh_ctx {
     bool tail_ok = true;             // RH_NO_TAIL_CTRL unset
     int n_groups = 1;                // fused kernel: completion groups (about 64 workgroups each, at most RH_DONE_GROUPS)
     bool lazy_ok = true;             // RH_NO_LAZY_ROTATION unset
-    bool diag_reads_m1 = false;      // an accumulator was given an X_m1 plane: the fused kernel does not skip those stores
+    bool obs_reads_m1 = false;       // an observer (accumulators, points) was given an X_m1 plane: the fused kernel does not skip those stores
     bool sparse_ok = true;           // RH_NO_SPARSE_STORES unset
-    bool diag_reads_sparse = false;  // an accumulator was given a pure-output plane (the KEEP variant of the sparse kernel stores those)
+    bool obs_reads_sparse = false;   // an observer was given a plane the sparse kernel leaves out (its KEEP variant stores those); both
+                                     // formed by observers_changed from the union of the observers' planes, and by nobody else
     int64_t t_end = -1;              // rh_set_time_limit (host copy of DevState::t_end)
     int64_t call_sparse_steps = 0;   // steps of the most recent rh_run_steps / rh_run_steps_dist call that ran with sparse stores
     bool cell_front_ok = true;       // RH_PER_CELL_OLD_FRONT unset: per-cell forcing takes k_cell_front instead of the five predicate-generation launches
@@ -246,6 +248,13 @@ struct rh_ctx {
     DevBuf<long long> diag_steps_buf;
     long long diag_interval = 86400;
     int diag_n = 0, diag_slots = 0;
+    int diag_planes[32] = {};        // host copy of DevState::diag_planes (diag_n of them)
+    // time series at observation columns (rh_points_configure): the ring of points_cap rows and its headers
+    DevBuf<double> points_buf;
+    DevBuf<long long> points_hdr_buf;
+    int points_ncells = 0, points_nplanes = 0;   // both 0: not configured, no k_points launch
+    int64_t points_cap = 0;
+    int points_planes[RH_POINTS_MAX_PLANES] = {};
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step
@@ -444,6 +453,41 @@ static int need_agg_cell_buf(rh_ctx *ctx) {
     if (ctx->agg_cell_buf) return RH_OK;
     HIPCHK(ctx, ctx->agg_cell_buf.alloc(sizeof(double) * 9 * (size_t)ctx->n));
     HIPCHK(ctx, dev_put(ctx, &DevState::agg_cell, *ctx->agg_cell_buf.addr()));
+    return RH_OK;
+}
+
+// the points' row of the step that was just enqueued: ONE workgroup (at most 8 192 values)
+static void launch_points(rh_ctx *ctx, int after_fused) {
+    hipLaunchKernelGGL(k_points, dim3(1), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+}
+// The observers' planes changed (rh_diag_configure, rh_points_configure): what the fused kernel must leave in memory after every step,
+// from the UNION of the accumulators' and the points' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
+// five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in DevState::keep: the KEEP
+// variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
+static int observers_changed(rh_ctx *ctx) {
+    unsigned long long keep[(RH_NPLANES + 63) / 64] = {};
+    bool reads_sparse = false, reads_m1 = false;
+    const std::vector<unsigned char> &left_out = pure_output_planes()[ctx->cfg.enable_lateral_flow ? 1 : 0];
+    auto add = [&](const int *planes, int n) {
+        for (int j = 0; j < n; ++j) {
+            const int p = planes[j];
+            if (left_out[p]) {
+                reads_sparse = true;
+                keep[p >> 6] |= 1ull << (p & 63);
+            }
+            const size_t len = std::strlen(PLANE_NAMES[p]);
+            if (len > 3 && !std::strcmp(PLANE_NAMES[p] + len - 3, "_m1")) reads_m1 = true;
+        }
+    };
+    add(ctx->diag_planes, ctx->diag_n);
+    if (ctx->points_ncells) add(ctx->points_planes, ctx->points_nplanes);
+    const int any = reads_sparse ? 1 : 0;
+    HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
+    HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
+    ctx->obs_reads_sparse = reads_sparse;
+    ctx->obs_reads_m1 = reads_m1;
+    materialise_m1(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are stack locals)
     return RH_OK;
 }
 
@@ -923,6 +967,7 @@ int rh_step_core(rh_ctx *ctx) {
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, ctx->stream, ctx->dev);
     // the output accumulators follow every step, also in the hook-preserving flow (itt / time were just advanced)
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, 0);
+    if (ctx->points_ncells) launch_points(ctx, 0);
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -962,11 +1007,11 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
     const bool lat = ctx->cfg.enable_lateral_flow != 0;
 #define RH_LAUNCH_K(K) hipExtLaunchKernelGGL(K, grid, block, 0, ctx->stream, ev0, ev1, 0, ctx->arena, ctx->dev.get(), flags, ctx->n_groups, dst64)
     // lazy rotation: the planes were last touched by a complete fused step (X_m1 == X) and nobody who reads X_m1 planes
-    // follows inside this call (the accumulator kernel may, if it was given an X_m1 plane)
-    const bool lazy = ctx->lazy_ok && ctx->held.rot_consistent && !ctx->diag_reads_m1;
+    // follows inside this call (an observer kernel may, if it was given an X_m1 plane)
+    const bool lazy = ctx->lazy_ok && ctx->held.rot_consistent && !ctx->obs_reads_m1;
     // sparse stores: another step of the same rh_run_steps call follows and nothing in between reads what this one only produces
-    const bool sparse = lazy && ctx->held.sparse_next && monthly < 0;   // (planes an accumulator reads are kept: DevState::keep, the KEEP variant)
-    const bool keep = sparse && ctx->diag_reads_sparse;
+    const bool sparse = lazy && ctx->held.sparse_next && monthly < 0;   // (planes an observer reads are kept: DevState::keep, the KEEP variant)
+    const bool keep = sparse && ctx->obs_reads_sparse;
     ctx->held.sparse_next = false;
     if (lazy)   // the lazy kernels read the parameter planes through the wave words
         if (int rc = form_param_mask(ctx, grid)) return rc;
@@ -999,6 +1044,10 @@ static int launch_fused_kernel(rh_ctx *ctx, int monthly, int flags = 0, int *dst
     fused_step_enqueued(ctx, flags, lazy, sparse, dst64 != nullptr);
     if (ctx->diag_n) {
         hipLaunchKernelGGL(k_diag, grid, block, 0, ctx->stream, ctx->arena, ctx->dev, 1);
+        CHECK_LAUNCH(ctx);
+    }
+    if (ctx->points_ncells) {
+        launch_points(ctx, 1);
         CHECK_LAUNCH(ctx);
     }
     return RH_OK;
@@ -1287,14 +1336,15 @@ static int routed_core(rh_ctx *ctx, bool with_after) {
     LAUNCH_CELLS(ctx, k_routed_b);                    // the surface inflow, the lateral subsurface runoff, its outflow
     if (ctx->comm && ctx->comm_nranks > 1 && (rc = route_exchange(ctx, 1))) return rc;
     if ((rc = rh_route_gather_only(ctx, 1))) return rc;
-    // the subsurface inflow, capillary rise, storages, numerics [, after_timestep: the output accumulators then read the taum1 planes
+    // the subsurface inflow, capillary rise, storages, numerics [, after_timestep: the observers (accumulators, points) then read the taum1 planes
     // only for variables the rotation has just made equal to tau -- they accumulate tau values, kept by a separate pass otherwise]
-    const bool fuse_after = with_after && !ctx->diag_n;
+    const bool fuse_after = with_after && !ctx->diag_n && !ctx->points_ncells;
     if (fuse_after) LAUNCH_CELLS(ctx, k_routed_c_after);
     else LAUNCH_CELLS(ctx, k_routed_c);
     LAUNCH_ONE(ctx, k_sanity_to_scalars, ctx->dev);
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, ctx->stream, ctx->dev);
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, 0);
+    if (ctx->points_ncells) launch_points(ctx, 0);
     if (with_after) {
         if (fuse_after) LAUNCH_ONE(ctx, k_rotate_scalars, ctx->dev);
         else if ((rc = rh_after_timestep(ctx))) return rc;
@@ -1303,7 +1353,7 @@ static int routed_core(rh_ctx *ctx, bool with_after) {
     return RH_OK;
 }
 extern "C++" {   // (a template: not inside the extern "C" block)
-// the three passes of the device-driven routed step with the two halo exchanges between them; SPARSE: sparse stores (never with accumulators)
+// the three passes of the device-driven routed step with the two halo exchanges between them; SPARSE: sparse stores (never with observers)
 template <bool SPARSE>
 static int routed_passes(rh_ctx *ctx, bool ranks) {
     int rc;
@@ -1321,9 +1371,10 @@ static int routed_passes(rh_ctx *ctx, bool ranks) {
     if (ranks && (rc = route_exchange(ctx, 1))) return rc;
     // (the control kernel has advanced itt / time and rotated the scalars, scalars_update; the sanity word stays in words[2], where
     // rh_get_scalars reads it)
-    if (ctx->diag_n) {   // the accumulators read the planes between the numerics and the rotation
+    if (ctx->diag_n || ctx->points_ncells) {   // the observers read the planes between the numerics and the rotation
         hipLaunchKernelGGL((k_routed_cg<false, false>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
-        hipLaunchKernelGGL(k_diag, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, 0);
+        if (ctx->diag_n) hipLaunchKernelGGL(k_diag, dim3(grid_for(ctx->n)), dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, 0);
+        if (ctx->points_ncells) launch_points(ctx, 0);
         LAUNCH_CELLS(ctx, k_after_timestep_oned);
     } else
         hipLaunchKernelGGL((k_routed_cg<true, SPARSE>), grid, block, 0, ctx->stream, ctx->arena, ctx->dev, nx, ny, route_halo_of(ctx));
@@ -1334,8 +1385,8 @@ static int routed_passes(rh_ctx *ctx, bool ranks) {
 // between the ranks), three passes around the two gathers -- 6 launches instead of 17.
 static int routed_step_device(rh_ctx *ctx, bool sparse_wanted = false) {
     int rc;
-    // sparse stores: another step of the same rh_run_steps call follows and no accumulator reads the planes in between
-    const bool sparse = sparse_wanted && ctx->sparse_ok && !ctx->diag_n;
+    // sparse stores: another step of the same rh_run_steps call follows and no observer reads the planes in between
+    const bool sparse = sparse_wanted && ctx->sparse_ok && !ctx->diag_n && !ctx->points_ncells;
     RcclApi *api = nullptr;
     const bool ranks = ctx->comm && ctx->comm_nranks > 1;
     if (ctx->comm) {
@@ -1507,31 +1558,13 @@ int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int
         if (planes[j] < 0 || planes[j] >= ctx->planes_held || PLANE_IS_INT[planes[j]])
             return fail(ctx, RH_ERR_ARG, "rh_diag_configure: plane ids must name float64 planes");
     }
-    // an accumulated pure-output plane must be in memory after every step: the sparse kernel keeps storing THOSE planes (DevState::keep)
-    ctx->diag_reads_sparse = false;
-    {
-        unsigned long long keep[(RH_NPLANES + 63) / 64] = {};
-        for (int j = 0; j < n_rate + n_collect; ++j)
-            if (pure_output_planes()[ctx->cfg.enable_lateral_flow ? 1 : 0][planes[j]]) {
-                ctx->diag_reads_sparse = true;
-                keep[planes[j] >> 6] |= 1ull << (planes[j] & 63);
-            }
-        const int any = ctx->diag_reads_sparse ? 1 : 0;
-        HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
-        HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    ctx->diag_reads_m1 = false;   // an accumulated X_m1 plane keeps the fused kernel from skipping its stores
-    for (int j = 0; j < n_rate + n_collect; ++j) {
-        const size_t len = std::strlen(PLANE_NAMES[planes[j]]);
-        if (len > 3 && !std::strcmp(PLANE_NAMES[planes[j]] + len - 3, "_m1")) ctx->diag_reads_m1 = true;
-    }
-    materialise_m1(ctx);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, ctx->diag_buf.release());
-    HIPCHK(ctx, ctx->diag_steps_buf.release());
+    // an accumulated plane must be in memory after every step: the keep bits and the rotation, together with the points' planes
     const int nv = n_rate + n_collect;
     ctx->diag_n = nv;
+    std::memcpy(ctx->diag_planes, planes, sizeof(int) * (size_t)nv);
+    if (int rc = observers_changed(ctx)) return rc;
+    HIPCHK(ctx, ctx->diag_buf.release());
+    HIPCHK(ctx, ctx->diag_steps_buf.release());
     ctx->diag_slots = n_slots;
     if (nv) {
         const size_t bytes = (size_t)n_slots * nv * ctx->n * sizeof(double);
@@ -1620,6 +1653,102 @@ int rh_diag_slot_times(rh_ctx *ctx, int slot, int64_t *t_start, int64_t *t_end) 
 void *rh_diag_device_ptr(rh_ctx *ctx, int j, int slot) {
     if (diag_check(ctx, j, slot)) return nullptr;
     return ctx->diag_buf + ((size_t)slot * ctx->diag_n + j) * ctx->n;
+}
+
+// ---- time series at observation columns (include/roger_hip.h) ----
+int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const int *planes, int n_planes, int64_t capacity) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_cells < 0 || n_cells > RH_POINTS_MAX_CELLS)
+        return fail(ctx, RH_ERR_ARG, "rh_points_configure: n_cells = " + std::to_string(n_cells) + " (0 ... " + std::to_string(RH_POINTS_MAX_CELLS) + ")");
+    if (n_planes < 0 || n_planes > RH_POINTS_MAX_PLANES)
+        return fail(ctx, RH_ERR_ARG, "rh_points_configure: n_planes = " + std::to_string(n_planes) + " (0 ... " + std::to_string(RH_POINTS_MAX_PLANES) + ")");
+    const bool off = n_cells == 0 || n_planes == 0;
+    long long cell_list[RH_POINTS_MAX_CELLS] = {};
+    int plane_list[RH_POINTS_MAX_PLANES] = {};
+    if (!off) {
+        if (!cells || !planes) return fail(ctx, RH_ERR_ARG, "rh_points_configure: null pointer");
+        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_points_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_points_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
+        for (int j = 0; j < n_planes; ++j) {
+            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+                return fail(ctx, RH_ERR_ARG, "rh_points_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
+            if (PLANE_IS_INT[planes[j]])
+                return fail(ctx, RH_ERR_ARG, std::string("rh_points_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
+            plane_list[j] = planes[j];
+        }
+        std::vector<int64_t> seen(cells, cells + n_cells);
+        std::sort(seen.begin(), seen.end());
+        for (int c = 0; c < n_cells; ++c) {
+            if (cells[c] < 0 || cells[c] >= ctx->n)
+                return fail(ctx, RH_ERR_ARG, "rh_points_configure: cell " + std::to_string(cells[c]) + " is outside [0, " + std::to_string(ctx->n) + ")");
+            if (c && seen[c] == seen[c - 1]) return fail(ctx, RH_ERR_ARG, "rh_points_configure: cell " + std::to_string(seen[c]) + " is given twice");
+            cell_list[c] = (long long)cells[c];
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    HIPCHK(ctx, ctx->points_buf.release());
+    HIPCHK(ctx, ctx->points_hdr_buf.release());
+    ctx->points_ncells = ctx->points_nplanes = 0;
+    ctx->points_cap = 0;
+    if (!off) {
+        const size_t nv = (size_t)n_cells * n_planes;
+        HIPCHK(ctx, ctx->points_buf.alloc((size_t)capacity * nv * sizeof(double)));
+        HIPCHK(ctx, ctx->points_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        ctx->points_ncells = n_cells;
+        ctx->points_nplanes = n_planes;
+        ctx->points_cap = capacity;
+        std::memcpy(ctx->points_planes, plane_list, sizeof(plane_list));
+    }
+    const long long zero = 0, cap = (long long)ctx->points_cap;
+    HIPCHK(ctx, dev_put(ctx, &DevState::points, *ctx->points_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_hdr, *ctx->points_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_rows, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_cap, cap));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_ncells, ctx->points_ncells));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_nplanes, ctx->points_nplanes));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_planes, plane_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_cells, cell_list));
+    return observers_changed(ctx);   // synchronises: the sources above are stack locals
+}
+static int points_rows(rh_ctx *ctx, const char *who, long long *rows) {
+    if (!ctx->points_ncells) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_points_configure has not been called");
+    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->points_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_points_count(rh_ctx *ctx, int64_t *rows_total) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!rows_total) return fail(ctx, RH_ERR_ARG, "rh_points_count: null pointer");
+    long long rows = 0;
+    if (int rc = points_rows(ctx, "rh_points_count", &rows)) return rc;
+    *rows_total = (int64_t)rows;
+    return RH_OK;
+}
+int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = points_rows(ctx, "rh_points_read", &total)) return rc;
+    const size_t nv = (size_t)ctx->points_ncells * ctx->points_nplanes;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return fail(ctx, RH_ERR_ARG, "rh_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - ctx->points_cap)
+        return fail(ctx, RH_ERR_ARG, "rh_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->points_cap - 1) +
+                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->points_cap) + " of " +
+                                     std::to_string(total) + " rows)");
+    if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_points_read: size mismatch (n_rows x n_planes x n_cells float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % ctx->points_cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, ctx->points_cap - slot);
+        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->points_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        done += m;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
 }
 
 int rh_predicates_expand(rh_ctx *ctx, int word, int32_t *dev_dst64) {

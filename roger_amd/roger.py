@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, restart, runtime_settings as rs, runtime_state as rst, stepping
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, stepping
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -152,6 +152,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             state.diagnostics.update(diagnostics.create_default_diagnostics(state))   # roger/roger.py:296
             self.set_diagnostics(state)
             diagnostics.initialize(state)
+            points.initialize(state)
             self.set_boundary_conditions_setup(state)
             self.set_boundary_conditions(state)
             self.set_forcing_setup(state)
@@ -200,6 +201,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             return self._step_offline_transport(state)
         if facts.restart_every_step:
             with state.timers["diagnostics"]:
+                points.drain(state)            # (rows not yet drained are drained before a restart file is written)
                 restart.write_restart(state)   # roger/roger.py:385-386
         with state.timers["main"]:
             with state.timers["read data"]:
@@ -243,6 +245,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
     def _end_of_step(state):
         if state._diag_active:   # roger/roger.py:458-465: output at the end of the time step
             diagnostics.output(state)
+        points.stepped(state)    # the points' ring is drained every `capacity` step calls
         if rs.profile_mode:
             state.backend_context.sync()
             logger.info(" Time step took {:.2f}s".format(state.timers["main"].last_time))
@@ -351,6 +354,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
                         n = max(n, int((t_round - now) / max(600.0, (now - start_time) / done) * 1.1) + 8)
                 elif slots is not None:
                     n = min(n, max(1, slots - 1))          # (a step starts at most one output interval)
+                if state.points.active:
+                    n = min(n, int(state.points.capacity))   # (a round never records more rows than the points' ring holds)
                 self.run_device(int(n), final=False)
                 first = False
         finally:
@@ -370,7 +375,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(state._diag_active)
+        diag = bool(state._diag_active) or state.points.active
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -412,9 +417,12 @@ class RogerSetup(metaclass=abc.ABCMeta):
         finally:
             in_warmup = settings.enable_offline_transport and self._in_warmup
             if settings.write_restart and not in_warmup and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
+                if not failed:
+                    points.drain(self.state)
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
         diagnostics.close(self.state)
+        points.close(self.state)
 
     # -- fast path --------------------------------------------------------------------------------
     def enable_device_hooks(self):
@@ -462,6 +470,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
         if not self._device_hooks:
             self.enable_device_hooks()
         vs = self.state.variables
+        points.check_call(self.state, nsteps)   # (before anything is enqueued)
+        points.drain(self.state)
         vs.flush_to_device()
         ctx = self.state.backend_context
         engine = stepping.engine(self._facts())
@@ -474,5 +484,6 @@ class RogerSetup(metaclass=abc.ABCMeta):
         else:   # through torch.distributed: the summary word, or with per-cell forcing both predicate words (the three-phase protocol)
             self._stepper(one_exchange=engine == stepping.PHASED_ONE).run(nsteps)
         vs.mark_device_newer()
+        points.drain(self.state, final=final)
         if self.state._diag_active:
             diagnostics.output(self.state, final=final)

@@ -342,6 +342,9 @@ class RogerState:
         self._ctx = None
         self._sas_ctx = None             # the `_native.SasContext` of an offline-transport run
         self._diagnostics = {}
+        from .points import PointSeries
+
+        self.points = PointSeries()      # time series at observation columns (roger_amd/points.py); filled in by set_diagnostics
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None
