@@ -342,7 +342,9 @@ int rh_run_steps_dist(rh_ctx *ctx, int64_t nsteps);
  * rh_step_finish) is followed by one small kernel that updates the slots.
  *   rate_planes[n_rate]:       plane ids summed per day          (24 B of traffic per plane, column and step)
  *   collect_planes[n_collect]: plane ids whose end-of-day value is kept
- * n_rate + n_collect <= 32; n_slots >= 1 days are resident: (n_slots, n_rate + n_collect, n_cells) float64. */
+ * n_rate + n_collect <= 32; n_slots >= 1 days are resident: (n_slots, n_rate + n_collect, n_cells) float64.  Bad arguments leave the
+ * previous configuration; a call that fails after them (the device refuses the memory) leaves the accumulators off, as
+ * rh_diag_configure(ctx, NULL, 0, NULL, 0, 1) does. */
 int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int *collect_planes, int n_collect, int n_slots);
 /* One (variable, day slot) array: n_cells float64.  j counts the rate planes first, then the collect planes. */
 int rh_diag_download(rh_ctx *ctx, int j, int slot, double *host, size_t bytes); /* synchronises */

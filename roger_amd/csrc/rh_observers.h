@@ -1,0 +1,253 @@
+// rh_observers.h -- what follows every step: the output accumulators (rh_diag_*) and the time series at observation columns
+// (rh_points_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
+#pragma once
+// The observers' planes changed (rh_diag_configure, rh_points_configure): what the fused kernel must leave in memory after every step,
+// from the UNION of the accumulators' and the points' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
+// five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in DevState::keep: the KEEP
+// variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
+static int observers_changed(rh_ctx *ctx) {
+    unsigned long long keep[(RH_NPLANES + 63) / 64] = {};
+    bool reads_sparse = false, reads_m1 = false;
+    const std::vector<unsigned char> &left_out = pure_output_planes()[ctx->cfg.enable_lateral_flow ? 1 : 0];
+    auto add = [&](const int *planes, int n) {
+        for (int j = 0; j < n; ++j) {
+            const int p = planes[j];
+            if (left_out[p]) {
+                reads_sparse = true;
+                keep[p >> 6] |= 1ull << (p & 63);
+            }
+            const size_t len = std::strlen(PLANE_NAMES[p]);
+            if (len > 3 && !std::strcmp(PLANE_NAMES[p] + len - 3, "_m1")) reads_m1 = true;
+        }
+    };
+    add(ctx->diag_planes, ctx->diag_n);
+    if (ctx->points_ncells) add(ctx->points_planes, ctx->points_nplanes);
+    const int any = reads_sparse ? 1 : 0;
+    HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
+    HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
+    ctx->obs_reads_sparse = reads_sparse;
+    ctx->obs_reads_m1 = reads_m1;
+    materialise_m1(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are stack locals)
+    return RH_OK;
+}
+
+// The observers behind the step that was just enqueued: the accumulators over all columns (grid: the fused launch's own, which has one
+// workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values).
+// after_fused: rh_control.h, k_diag.
+static bool has_observers(const rh_ctx *ctx) { return ctx->diag_n || ctx->points_ncells; }
+static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
+    const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
+    if (ctx->diag_n) hipLaunchKernelGGL(k_diag, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    if (ctx->points_ncells) hipLaunchKernelGGL(k_points, dim3(1), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    CHECK_LAUNCH(ctx);
+    return RH_OK;
+}
+
+// the accumulators' buffers, cleared (rh_diag_configure)
+static int diag_alloc(rh_ctx *ctx, int nv, int n_slots) {
+    const size_t bytes = (size_t)n_slots * nv * ctx->n * sizeof(double), hdr = (size_t)n_slots * 3 * sizeof(long long);
+    HIPCHK(ctx, ctx->diag_buf.alloc(bytes));
+    HIPCHK(ctx, hipMemsetAsync(ctx->diag_buf, 0, bytes, ctx->stream));
+    HIPCHK(ctx, ctx->diag_steps_buf.alloc(hdr));
+    HIPCHK(ctx, hipMemsetAsync(ctx->diag_steps_buf, 0xff, hdr, ctx->stream));   // -1: never touched
+    return RH_OK;
+}
+int rh_diag_configure(rh_ctx *ctx, const int *rate_planes, int n_rate, const int *collect_planes, int n_collect, int n_slots) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_rate < 0 || n_collect < 0 || n_rate + n_collect > 32 || n_slots < 1 || (n_rate && !rate_planes) || (n_collect && !collect_planes))
+        return fail(ctx, RH_ERR_ARG, "rh_diag_configure: bad counts (n_rate + n_collect <= 32, n_slots >= 1)");
+    int planes[32];
+    for (int j = 0; j < n_rate + n_collect; ++j) {
+        planes[j] = j < n_rate ? rate_planes[j] : collect_planes[j - n_rate];
+        if (planes[j] < 0 || planes[j] >= ctx->planes_held || PLANE_IS_INT[planes[j]])
+            return fail(ctx, RH_ERR_ARG, "rh_diag_configure: plane ids must name float64 planes");
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that accumulate into the old buffers)
+    HIPCHK(ctx, ctx->diag_buf.release());
+    HIPCHK(ctx, ctx->diag_steps_buf.release());
+    ctx->diag_n = 0;
+    const int nv = n_rate + n_collect;
+    if (int rc = nv ? diag_alloc(ctx, nv, n_slots) : RH_OK) {   // refused: the accumulators are off, no later step launches k_diag
+        const std::string why = ctx->err;
+        (void)rh_diag_configure(ctx, nullptr, 0, nullptr, 0, 1);
+        return fail(ctx, rc, why);
+    }
+    // only now the counts: an accumulated plane must be in memory after every step (the keep bits and the rotation, together with the
+    // points' planes: observers_changed)
+    ctx->diag_n = nv;
+    ctx->diag_slots = n_slots;
+    std::memcpy(ctx->diag_planes, planes, sizeof(int) * (size_t)nv);
+    if (ctx->diag_interval <= 0) ctx->diag_interval = 86400;
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_steps, *ctx->diag_steps_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_interval, ctx->diag_interval));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag, *ctx->diag_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_rate, n_rate));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_collect, n_collect));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_slots, n_slots));
+    HIPCHK(ctx, dev_put(ctx, &DevState::diag_planes, planes));
+    return observers_changed(ctx);   // synchronises: the sources above are stack locals
+}
+static int diag_check(rh_ctx *ctx, int j, int slot) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->diag_n) return fail(ctx, RH_ERR_STATE, "rh_diag_configure has not been called");
+    if (j < 0 || j >= ctx->diag_n || slot < 0 || slot >= ctx->diag_slots) return fail(ctx, RH_ERR_ARG, "rh_diag: variable or slot out of range");
+    return RH_OK;
+}
+int rh_diag_download(rh_ctx *ctx, int j, int slot, double *host, size_t bytes) {
+    const int rc = diag_check(ctx, j, slot);
+    if (rc) return rc;
+    if (!host || bytes != (size_t)ctx->n * sizeof(double)) return fail(ctx, RH_ERR_ARG, "rh_diag_download: size mismatch");
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->diag_buf + ((size_t)slot * ctx->diag_n + j) * ctx->n, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_diag_upload(rh_ctx *ctx, int j, int slot, const double *host, size_t bytes) {
+    const int rc = diag_check(ctx, j, slot);
+    if (rc) return rc;
+    if (!host || bytes != (size_t)ctx->n * sizeof(double)) return fail(ctx, RH_ERR_ARG, "rh_diag_upload: size mismatch");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->diag_buf + ((size_t)slot * ctx->diag_n + j) * ctx->n, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_diag_set_slot_state(rh_ctx *ctx, int slot, int64_t steps, int64_t t_start, int64_t t_end) {
+    const int rc = diag_check(ctx, 0, slot);
+    if (rc) return rc;
+    const long long v[3] = {(long long)steps, (long long)t_start, (long long)t_end};
+    HIPCHK(ctx, hipMemcpyAsync(ctx->diag_steps_buf + 3 * slot, v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_diag_steps(rh_ctx *ctx, int slot, int64_t *steps) {
+    const int rc = diag_check(ctx, 0, slot);
+    if (rc) return rc;
+    if (!steps) return fail(ctx, RH_ERR_ARG, "rh_diag_steps: null pointer");
+    long long v = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&v, ctx->diag_steps_buf + 3 * slot, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *steps = (int64_t)(v < 0 ? 0 : v);
+    return RH_OK;
+}
+int rh_diag_set_interval(rh_ctx *ctx, int64_t seconds) {
+    if (!ctx) return RH_ERR_ARG;
+    if (seconds != 86400 && seconds != 3600 && seconds != 600)
+        return fail(ctx, RH_ERR_ARG, "rh_diag_set_interval: the output interval is a day, an hour or ten minutes (the step classes)");
+    ctx->diag_interval = seconds;
+    if (ctx->diag_n) {
+        HIPCHK(ctx, dev_put(ctx, &DevState::diag_interval, ctx->diag_interval));
+        HIPCHK(ctx, hipMemsetAsync(ctx->diag_steps_buf, 0xff, (size_t)ctx->diag_slots * 3 * sizeof(long long), ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return RH_OK;
+}
+int rh_diag_slot_times(rh_ctx *ctx, int slot, int64_t *t_start, int64_t *t_end) {
+    const int rc = diag_check(ctx, 0, slot);
+    if (rc) return rc;
+    if (!t_start || !t_end) return fail(ctx, RH_ERR_ARG, "rh_diag_slot_times: null pointer");
+    long long v[3] = {0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(v, ctx->diag_steps_buf + 3 * slot, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *t_start = (int64_t)v[1];
+    *t_end = (int64_t)v[2];
+    return RH_OK;
+}
+void *rh_diag_device_ptr(rh_ctx *ctx, int j, int slot) {
+    if (diag_check(ctx, j, slot)) return nullptr;
+    return ctx->diag_buf + ((size_t)slot * ctx->diag_n + j) * ctx->n;
+}
+
+// ---- time series at observation columns (include/roger_hip.h) ----
+int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const int *planes, int n_planes, int64_t capacity) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_cells < 0 || n_cells > RH_POINTS_MAX_CELLS)
+        return fail(ctx, RH_ERR_ARG, "rh_points_configure: n_cells = " + std::to_string(n_cells) + " (0 ... " + std::to_string(RH_POINTS_MAX_CELLS) + ")");
+    if (n_planes < 0 || n_planes > RH_POINTS_MAX_PLANES)
+        return fail(ctx, RH_ERR_ARG, "rh_points_configure: n_planes = " + std::to_string(n_planes) + " (0 ... " + std::to_string(RH_POINTS_MAX_PLANES) + ")");
+    const bool off = n_cells == 0 || n_planes == 0;
+    long long cell_list[RH_POINTS_MAX_CELLS] = {};
+    int plane_list[RH_POINTS_MAX_PLANES] = {};
+    if (!off) {
+        if (!cells || !planes) return fail(ctx, RH_ERR_ARG, "rh_points_configure: null pointer");
+        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_points_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_points_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
+        for (int j = 0; j < n_planes; ++j) {
+            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+                return fail(ctx, RH_ERR_ARG, "rh_points_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
+            if (PLANE_IS_INT[planes[j]])
+                return fail(ctx, RH_ERR_ARG, std::string("rh_points_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
+            plane_list[j] = planes[j];
+        }
+        std::vector<int64_t> seen(cells, cells + n_cells);
+        std::sort(seen.begin(), seen.end());
+        for (int c = 0; c < n_cells; ++c) {
+            if (cells[c] < 0 || cells[c] >= ctx->n)
+                return fail(ctx, RH_ERR_ARG, "rh_points_configure: cell " + std::to_string(cells[c]) + " is outside [0, " + std::to_string(ctx->n) + ")");
+            if (c && seen[c] == seen[c - 1]) return fail(ctx, RH_ERR_ARG, "rh_points_configure: cell " + std::to_string(seen[c]) + " is given twice");
+            cell_list[c] = (long long)cells[c];
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    HIPCHK(ctx, ctx->points_buf.release());
+    HIPCHK(ctx, ctx->points_hdr_buf.release());
+    ctx->points_ncells = ctx->points_nplanes = 0;
+    ctx->points_cap = 0;
+    if (!off) {
+        const size_t nv = (size_t)n_cells * n_planes;
+        HIPCHK(ctx, ctx->points_buf.alloc((size_t)capacity * nv * sizeof(double)));
+        HIPCHK(ctx, ctx->points_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        ctx->points_ncells = n_cells;
+        ctx->points_nplanes = n_planes;
+        ctx->points_cap = capacity;
+        std::memcpy(ctx->points_planes, plane_list, sizeof(plane_list));
+    }
+    const long long zero = 0, cap = (long long)ctx->points_cap;
+    HIPCHK(ctx, dev_put(ctx, &DevState::points, *ctx->points_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_hdr, *ctx->points_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_rows, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_cap, cap));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_ncells, ctx->points_ncells));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_nplanes, ctx->points_nplanes));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_planes, plane_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_cells, cell_list));
+    return observers_changed(ctx);   // synchronises: the sources above are stack locals
+}
+static int points_rows(rh_ctx *ctx, const char *who, long long *rows) {
+    if (!ctx->points_ncells) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_points_configure has not been called");
+    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->points_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_points_count(rh_ctx *ctx, int64_t *rows_total) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!rows_total) return fail(ctx, RH_ERR_ARG, "rh_points_count: null pointer");
+    long long rows = 0;
+    if (int rc = points_rows(ctx, "rh_points_count", &rows)) return rc;
+    *rows_total = (int64_t)rows;
+    return RH_OK;
+}
+int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = points_rows(ctx, "rh_points_read", &total)) return rc;
+    const size_t nv = (size_t)ctx->points_ncells * ctx->points_nplanes;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return fail(ctx, RH_ERR_ARG, "rh_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - ctx->points_cap)
+        return fail(ctx, RH_ERR_ARG, "rh_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->points_cap - 1) +
+                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->points_cap) + " of " +
+                                     std::to_string(total) + " rows)");
+    if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_points_read: size mismatch (n_rows x n_planes x n_cells float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % ctx->points_cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, ctx->points_cap - slot);
+        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->points_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        done += m;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
