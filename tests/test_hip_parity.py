@@ -150,34 +150,10 @@ def _oracle_setup(ob, nx, ny, seed, luts):
     golden generator's hetero_params)."""
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+    from extended_columns import oracle_state
     from make_golden import hetero_params
 
-    p = hetero_params(nx, ny, seed=seed)
-    st = ob.OracleState(nx * ny)
-    st.set_luts(*luts)
-    P = st.planes
-    P["maskCatch"][:] = 1
-    for nm in ("ta", "ta_m1"):
-        P[nm][:] = 15.0
-    for nm in ("z_gw", "z_gw_m1"):
-        P[nm][:] = 1000.0
-    P["c_int"][:] = 1.0
-    P["c_root"][:] = 1.0
-    for k in ("lu_id", "z_soil", "dmpv", "lmpv", "theta_ac", "theta_ufc", "theta_pwp", "ks", "kf", "sealing", "S_dep_tot"):
-        P[k][:] = p[k].ravel().astype(P[k].dtype)
-    st.scal.dt = 1.0
-    st.scal.dt_secs = 3600
-    st.scal.event_id_counter = 1
-    for k in ("year", "month", "doy"):
-        getattr(st.scal, k)[0] = getattr(st.scal, k)[1] = 1 if k != "year" else 1900
-    st.topo()
-    st.params_surface()
-    st.params_soil()
-    for lvl in ("", "_m1"):
-        P["theta_rz" + lvl][:] = p["theta_rz0"].ravel()
-        P["theta_ss" + lvl][:] = p["theta_ss0"].ravel()
-    st.initial_conditions()
-    return st
+    return oracle_state(ob, hetero_params(nx, ny, seed=seed), luts, lateral=False)   # (no z_gw among the primaries: 1000 m)
 
 
 @pytest.mark.parametrize("per_cell", [False, True])
