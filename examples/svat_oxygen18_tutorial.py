@@ -2,14 +2,17 @@
 """SVAT -> oxygen-18 transport, the reference's two-step workflow (examples/plot_scale/svat_tutorial followed by
 svat_oxygen18_tutorial) on the hip backend:
 
-    python examples/svat_oxygen18_tutorial.py /path/to/svat_tutorial/input [--days 365] [--ages 400] [--out output]
+    python examples/svat_oxygen18_tutorial.py /path/to/svat_tutorial/input [--days 365] [--ages 400] [--out output] [--points "0,0;1,0"]
 
 1. the SVAT tutorial (examples/svat_tutorial.py) writes the daily flux sums and storages (SVAT.rate.nc, SVAT.collect.nc);
 2. `read_svat_output` turns them into the transport model's input; the isotope signal of the precipitation is synthetic
    here (a seasonal cycle around -8 permil: the tutorial ships no measured d18O);
 3. the transport model (roger_amd/models/svat_transport.py; power-law StorAge selection with the benchmark's exponents,
    deterministic solver) warms up over the whole period once, rescales, and runs; it writes the daily signal of
-   transpiration and percolation and their median travel times as SVATOXYGEN18.average.nc.
+   transpiration and percolation and their median travel times as SVATOXYGEN18.average.nc;
+4. with `--points ix,iy[;ix,iy...]` the columns named (interior indices, 0-based) are recorded on the device after every day
+   (`state.transport_points`): the signal of percolation and root zone, the median travel time and the whole travel time
+   distribution of the percolation, the soil's water by age -> SVATOXYGEN18.transport_points.nc.
 """
 import argparse
 import importlib.util
@@ -40,7 +43,9 @@ def main(argv=None):
     ap.add_argument("--ages", type=int, default=400)
     ap.add_argument("--substeps", type=int, default=6)
     ap.add_argument("--out", default="output")
+    ap.add_argument("--points", default="", help="observation columns ix,iy[;ix,iy...]: their daily series go to <out>/SVATOXYGEN18.transport_points.nc")
     args = ap.parse_args(argv)
+    points = [tuple(int(v) for v in c.split(",")) for c in args.points.split(";") if c.strip()]
     _svat_example().main([args.input_dir, "--days", str(args.days), "--out", args.out])
     svat = read_svat_output(os.path.join(args.out, "SVAT.rate.nc"), os.path.join(args.out, "SVAT.collect.nc"))
     doy = np.arange(args.days + 1)
@@ -63,6 +68,11 @@ def main(argv=None):
             d.output_frequency = 24 * 60 * 60
             d.sampling_frequency = 1
             d.base_output_path = args.out
+            if points:
+                p = state.transport_points
+                p.cells = points
+                p.output_variables = ["C_iso_q_ss", "C_iso_rz", "tt50_q_ss", "TT_q_ss", "sa_s"]
+                p.base_output_path = args.out
 
     model = WithOutput()
     model.setup()
@@ -70,7 +80,7 @@ def main(argv=None):
     model.run()
     vs = model.state.variables
     print(f"transport: {vs.itt} days; d18O of the percolation on the last day {np.asarray(vs.C_iso_q_ss)[2:-2, 2:-2].ravel()} permil; "
-          f"output in {args.out}/SVATOXYGEN18.average.nc")
+          f"output in {args.out}/SVATOXYGEN18.average.nc" + (f", {len(points)} observation columns in {args.out}/SVATOXYGEN18.transport_points.nc" if points else ""))
     return model
 
 

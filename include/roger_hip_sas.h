@@ -145,6 +145,45 @@ int rh_sas_step(rh_sas_ctx *ctx, int64_t day);
 /* `ndays` whole steps for days day0, day0 + 1, ... enqueued back to back. */
 int rh_sas_run_days(rh_sas_ctx *ctx, int64_t day0, int64_t ndays);
 
+/* ---- time series at observation columns ("points"), recorded on the device after every day -----------
+ * A comparison with a lysimeter -- delta-18O or bromide in its percolate, the concentration in the root zone, the travel time
+ * distribution of q_ss -- needs a handful of columns every day, and inside rh_sas_run_days the host cannot look at a column between
+ * two days.  After rh_sas_points_configure, rh_sas_step and every day of rh_sas_run_days are followed by ONE launch (k_sas_points,
+ * roger_amd/csrc/rh_sas_points.h) that gathers arrays x cells into the next row of a ring on the device.  A pure gather: every value
+ * is the bits rh_sas_download returns after that day -- for the prognostic state sa_rz, msa_rz, sa_ss, msa_ss that is the value AFTER
+ * the day's ageing.  rh_sas_stages does not record, whatever its mask (a partial one, RH_SAS_ALL, RH_SAS_RESCALE): a driver that
+ * steps by stage, or wants the initial values as a row, calls rh_sas_points_record.  A context without points enqueues exactly what
+ * it enqueued before these entry points existed.
+ *   cells    [n_cells]  local cell indices as in rh_sas_upload_cells, no cell twice; at most RH_SAS_POINTS_MAX_CELLS
+ *   arrays   [n_arrays] registry indices (rh_sas_array_index), none twice; at most RH_SAS_POINTS_MAX_ARRAYS.  Per-cell float64
+ *                       arrays this context holds: the state, C_*, C_iso_*, M_*, the age statistics, the per-cell parameters
+ *                       (S_rz_init, alpha_q, ...) with width 1; tt_*, mtt_*, sa_s, msa_s and the state with width `ages`; TT_* with
+ *                       width `ages + 1`
+ *   capacity >= 1       rows resident on the device, row r at r mod capacity
+ * Row layout (rh_sas_points_row_elems float64): arrays in configured order, within an array the cells in configured order, within a
+ * cell the age axis contiguous -- the block of array j is (n_cells, width_j).  Per row one int64 tag, kept on the host: the `day`
+ * argument of the step, or the caller's value for rh_sas_points_record.
+ * n_cells == 0 or n_arrays == 0 releases the ring and stops the launches.  Every other call starts a new series (row 0).
+ * RH_ERR_ARG (rh_sas_last_error names the offender): a cell outside [0, n_cells) or given twice, an unknown array id or an array given
+ * twice, an int32 array (maskCatch, lu_id), a daily input or sas_params_* (inputs of the step, not per-cell results), counts above
+ * the limits, capacity < 1, a ring above 2 GiB (capacity x row_elems x 8).  RH_ERR_STATE: an array this context does not hold
+ * (age_statistics / keep_distributions off, M_* of an isotope context).  A refused call leaves the previous configuration in place.
+ *   rh_sas_points_record     one row now, behind what the stream holds, with the caller's tag
+ *   rh_sas_points_count      rows recorded since rh_sas_points_configure (the host enqueues every row: no synchronisation)
+ *   rh_sas_points_row_elems  float64 per row
+ *   rh_sas_points_read       rows [first_row, first_row + n_rows) that are still resident (first_row >= rows_total - capacity): tags
+ *                            (n_rows) int64, values (n_rows, row_elems) float64; synchronises.  RH_ERR_ARG for rows that have been
+ *                            overwritten (the message says which) or not recorded yet -- never other data.  A range across the
+ *                            ring's wrap is two copies.
+ * All four: RH_ERR_STATE before rh_sas_points_configure (or after it released the ring). */
+#define RH_SAS_POINTS_MAX_CELLS 256
+#define RH_SAS_POINTS_MAX_ARRAYS 32
+int rh_sas_points_configure(rh_sas_ctx *ctx, const int64_t *cells, int n_cells, const int *arrays, int n_arrays, int64_t capacity);
+int rh_sas_points_record(rh_sas_ctx *ctx, int64_t tag);
+int rh_sas_points_count(rh_sas_ctx *ctx, int64_t *rows_total);
+int rh_sas_points_row_elems(const rh_sas_ctx *ctx, int64_t *elems);
+int rh_sas_points_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 6   # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 7   # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -230,6 +230,11 @@ def _declare_sas(lib):
     lib.rh_sas_selftest_div.argtypes = [vp, vp, vp, i64]
     lib.rh_sas_enable_timing.argtypes = [vp, i32]
     lib.rh_sas_timing_summary.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.rh_sas_points_configure.argtypes = [vp, vp, i32, vp, i32, i64]
+    lib.rh_sas_points_record.argtypes = [vp, i64]
+    lib.rh_sas_points_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_sas_points_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_sas_points_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
 
 
 SAS_DECLARED_SYMBOLS = (
@@ -237,6 +242,7 @@ SAS_DECLARED_SYMBOLS = (
     "rh_sas_sync", "rh_sas_num_arrays", "rh_sas_array_name", "rh_sas_array_index", "rh_sas_array_elems",
     "rh_sas_array_is_int", "rh_sas_upload", "rh_sas_download", "rh_sas_upload_cells", "rh_sas_download_cells", "rh_sas_set_daily_from_device", "rh_sas_array_device_ptr", "rh_sas_stages",
     "rh_sas_step", "rh_sas_run_days", "rh_sas_enable_timing", "rh_sas_timing_summary", "rh_sas_selftest_pow", "rh_sas_selftest_div",
+    "rh_sas_points_configure", "rh_sas_points_record", "rh_sas_points_count", "rh_sas_points_row_elems", "rh_sas_points_read",
 )
 
 # stage bits of rh_sas_stages (include/roger_hip_sas.h)
@@ -367,6 +373,46 @@ class SasContext:
         ms, cnt = C.c_double(), C.c_int64()
         self._check(self._lib.rh_sas_timing_summary(self._h, C.byref(ms), C.byref(cnt)), "rh_sas_timing_summary")
         return ms.value, cnt.value
+
+    # -- time series at observation columns (rh_sas_points_*) -----------------------------------
+    def points_configure(self, cells, names, capacity=4096):
+        """Record `names` (arrays of the registry) at the local cells `cells` after every day into a ring of `capacity` rows; empty
+        cells or names switch the recorder off."""
+        names = list(names)
+        c = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1)
+        ids = (C.c_int * max(len(names), 1))(*[self.index(v) for v in names])
+        self._check(self._lib.rh_sas_points_configure(self._h, c.ctypes.data_as(C.c_void_p), c.size, ids, len(names), int(capacity)),
+                    "rh_sas_points_configure")
+        # (a refused configuration leaves the previous one)
+        on = bool(c.size and names)
+        self._points_names = names if on else []
+        self._points_widths = [int(np.prod(self.shape(v)[1:], dtype=np.int64)) for v in self._points_names]
+        self._points_ncells = int(c.size) if on else 0
+
+    def points_record(self, tag=0):
+        """One row now (the initial values; a driver that steps by stage)."""
+        self._check(self._lib.rh_sas_points_record(self._h, int(tag)), "rh_sas_points_record")
+
+    def points_count(self):
+        """Rows recorded since points_configure."""
+        n = C.c_int64()
+        self._check(self._lib.rh_sas_points_count(self._h, C.byref(n)), "rh_sas_points_count")
+        return n.value
+
+    def points_read(self, first, n):
+        """(tags (n,) int64, {name: (n, K) or (n, K, width) float64}) of the rows [first, first + n) that are still resident."""
+        n = int(n)
+        elems = C.c_int64()
+        self._check(self._lib.rh_sas_points_row_elems(self._h, C.byref(elems)), "rh_sas_points_row_elems")
+        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
+        self._check(self._lib.rh_sas_points_read(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                                 values.nbytes), "rh_sas_points_read")
+        out, off, K = {}, 0, self._points_ncells
+        for v, w in zip(self._points_names, self._points_widths):
+            block = values[:, off:off + K * w]
+            out[v] = block.copy() if w == 1 else block.reshape(n, K, w).copy()
+            off += K * w
+        return tags, out
 
 
 def sas_selftest_div(a, d):

@@ -30,6 +30,10 @@
 #include "roger_hip.h"
 #include "roger_hip_sas.h"
 #include "rh_sas_dev.h"
+#include "rh_sas_points.h"
+
+#include <algorithm>
+#include <memory>
 
 static const char *const SAS_NAMES[] = {
 #define RH_SAS_ARRAY(name, kind, when) #name,
@@ -77,6 +81,14 @@ struct rh_sas_ctx {
     DevBuf<int> unsupported;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the day's launch
+    // time series at observation columns (rh_sas_points_configure): a ring of points_cap rows of points_row_elems float64 on the device,
+    // row r at r mod points_cap, and the rows' tags in a host ring of the same capacity.  The host enqueues every row, so it counts them.
+    DevBuf<double> points_ring;
+    DevBuf<SasPointsDev> points_cfg;
+    std::unique_ptr<int64_t[]> points_tags;
+    int points_ncells = 0;           // 0: not configured, no k_sas_points launch
+    int points_blocks = 0;           // workgroups of one row's launch
+    int64_t points_cap = 0, points_row_elems = 0, points_rows = 0;
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -347,16 +359,151 @@ int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
     return RH_OK;
 }
 
-int rh_sas_step(rh_sas_ctx *ctx, int64_t day) { return rh_sas_stages(ctx, day, RH_SAS_ALL); }
+// ---- time series at observation columns (include/roger_hip_sas.h) ----
+// one row behind what the stream holds so far: the gather into the ring's next slot, the tag beside it
+static int sas_points_enqueue(rh_sas_ctx *ctx, int64_t tag) {
+    const int64_t slot = ctx->points_rows % ctx->points_cap;
+    hipLaunchKernelGGL(k_sas_points, dim3((unsigned)ctx->points_blocks), dim3(SAS_POINTS_BLOCK), 0, ctx->stream, ctx->points_cfg.get(),
+                       ctx->points_ring + (size_t)slot * (size_t)ctx->points_row_elems);
+    SHIPCHK(ctx, hipGetLastError());
+    ctx->points_tags[(size_t)slot] = tag;
+    ++ctx->points_rows;
+    return RH_OK;
+}
+
+// a whole day and, with points configured, its row
+static int sas_day(rh_sas_ctx *ctx, int64_t day) {
+    const int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
+    if (rc || !ctx->points_ncells) return rc;
+    return sas_points_enqueue(ctx, day);
+}
+
+int rh_sas_step(rh_sas_ctx *ctx, int64_t day) {
+    if (!ctx) return RH_ERR_ARG;
+    return sas_day(ctx, day);
+}
 
 int rh_sas_run_days(rh_sas_ctx *ctx, int64_t day0, int64_t ndays) {
     if (!ctx) return RH_ERR_ARG;
     if (ndays < 0) return sfail(ctx, RH_ERR_ARG, "rh_sas_run_days: negative ndays");
     for (int64_t d = 0; d < ndays; ++d) {
-        const int rc = rh_sas_stages(ctx, day0 + d, RH_SAS_ALL);
+        const int rc = sas_day(ctx, day0 + d);
         if (rc) return rc;
     }
     return RH_OK;
+}
+
+int rh_sas_points_configure(rh_sas_ctx *ctx, const int64_t *cells, int n_cells, const int *arrays, int n_arrays, int64_t capacity) {
+    const std::string who = "rh_sas_points_configure: ";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_cells < 0 || n_cells > RH_SAS_POINTS_MAX_CELLS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_cells = " + std::to_string(n_cells) + " (0 ... " + std::to_string(RH_SAS_POINTS_MAX_CELLS) + ")");
+    if (n_arrays < 0 || n_arrays > RH_SAS_POINTS_MAX_ARRAYS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_arrays = " + std::to_string(n_arrays) + " (0 ... " + std::to_string(RH_SAS_POINTS_MAX_ARRAYS) + ")");
+    const bool off = n_cells == 0 || n_arrays == 0;
+    SasPointsDev P = {};
+    int64_t row_elems = 0;
+    if (!off) {
+        if (!cells || !arrays) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+        if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
+        for (int j = 0; j < n_arrays; ++j) {
+            const int a = arrays[j];
+            if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
+            const std::string name = std::string("array ") + SAS_NAMES[a];
+            if (std::find(arrays, arrays + j, a) != arrays + j) return sfail(ctx, RH_ERR_ARG, who + name + " is given twice");
+            if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
+            if (SAS_KIND[a] == K_DAILY || SAS_KIND[a] == K_PARAM)
+                return sfail(ctx, RH_ERR_ARG, who + name + " is an input of the step, not a per-cell result (daily inputs and sas_params_* are not recorded)");
+            if (!ctx->arr[a])
+                return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
+            P.src[j] = (const double *)ctx->arr[a].get();
+            P.width[j] = (int)(ctx->elems[a] / ctx->cfg.n_cells);
+            P.off[j] = row_elems;
+            P.first_block[j + 1] = P.first_block[j] + (n_cells * P.width[j] + SAS_POINTS_BLOCK - 1) / SAS_POINTS_BLOCK;
+            row_elems += (int64_t)n_cells * P.width[j];
+        }
+        std::vector<int64_t> seen(cells, cells + n_cells);
+        std::sort(seen.begin(), seen.end());
+        for (int c = 0; c < n_cells; ++c) {
+            if (cells[c] < 0 || cells[c] >= ctx->cfg.n_cells)
+                return sfail(ctx, RH_ERR_ARG, who + "cell " + std::to_string(cells[c]) + " is outside [0, " + std::to_string(ctx->cfg.n_cells) + ")");
+            if (c && seen[c] == seen[c - 1]) return sfail(ctx, RH_ERR_ARG, who + "cell " + std::to_string(seen[c]) + " is given twice");
+            P.cells[c] = cells[c];
+        }
+        P.n_arrays = n_arrays;
+        P.n_cells = n_cells;
+        if (capacity > ((int64_t)1 << 31) / (row_elems * (int64_t)sizeof(double)))
+            return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " rows of " + std::to_string(row_elems) +
+                                              " float64 are a ring above 2 GiB");
+    }
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    SHIPCHK(ctx, ctx->points_ring.release());
+    SHIPCHK(ctx, ctx->points_cfg.release());
+    ctx->points_tags.reset();
+    ctx->points_ncells = ctx->points_blocks = 0;
+    ctx->points_cap = ctx->points_row_elems = ctx->points_rows = 0;
+    if (off) return RH_OK;
+    std::unique_ptr<int64_t[]> tags(new (std::nothrow) int64_t[(size_t)capacity]);
+    if (!tags) return sfail(ctx, RH_ERR_ARG, who + "out of host memory for the tags of " + std::to_string(capacity) + " rows");
+    SHIPCHK(ctx, ctx->points_ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
+    SHIPCHK(ctx, ctx->points_cfg.alloc(sizeof(SasPointsDev)));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->points_cfg, &P, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the source is a local)
+    ctx->points_tags = std::move(tags);
+    ctx->points_blocks = P.first_block[n_arrays];
+    ctx->points_cap = capacity;
+    ctx->points_row_elems = row_elems;
+    ctx->points_ncells = n_cells;
+    return RH_OK;
+}
+
+static int sas_points_on(rh_sas_ctx *ctx, const char *who) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->points_ncells) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_points_configure has not been called");
+    return RH_OK;
+}
+
+int rh_sas_points_record(rh_sas_ctx *ctx, int64_t tag) {
+    if (int rc = sas_points_on(ctx, "rh_sas_points_record")) return rc;
+    return sas_points_enqueue(ctx, tag);
+}
+
+int rh_sas_points_count(rh_sas_ctx *ctx, int64_t *rows_total) {
+    if (int rc = sas_points_on(ctx, "rh_sas_points_count")) return rc;
+    if (!rows_total) return sfail(ctx, RH_ERR_ARG, "rh_sas_points_count: null pointer");
+    *rows_total = ctx->points_rows;
+    return RH_OK;
+}
+
+int rh_sas_points_row_elems(const rh_sas_ctx *ctx, int64_t *elems) {
+    if (int rc = sas_points_on(const_cast<rh_sas_ctx *>(ctx), "rh_sas_points_row_elems")) return rc;
+    if (!elems) return RH_ERR_ARG;
+    *elems = ctx->points_row_elems;
+    return RH_OK;
+}
+
+int rh_sas_points_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes) {
+    if (int rc = sas_points_on(ctx, "rh_sas_points_read")) return rc;
+    const int64_t total = ctx->points_rows, cap = ctx->points_cap;
+    const size_t nv = (size_t)ctx->points_row_elems;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                          " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - cap)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
+                                          " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " +
+                                          std::to_string(total) + " rows)");
+    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_points_read: size mismatch (n_rows x row_elems float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
+        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        std::copy(ctx->points_tags.get() + slot, ctx->points_tags.get() + slot + m, tags + done);
+        done += m;
+    }
+    return rh_sas_sync(ctx);
 }
 
 static int selftest2(const double *x, const double *k, double *out, int64_t n, int which);

@@ -41,6 +41,56 @@ def local_cells(cells, nx, ny, num_proc, rank):
     return out
 
 
+def check_request(what, cells, n_variables, capacity, settings):
+    """What `state.points` and `state.transport_points` (roger_amd/sas_points.py) check alike -- the cells lie in the grid, none is
+    given twice, the counts are within the recorder's limits, the ring holds a row: the cells as tuples of ints."""
+    cells = [(int(c[0]), int(c[1])) for c in cells]
+    for ix, iy in cells:
+        if not (0 <= ix < settings.nx and 0 <= iy < settings.ny):
+            raise ValueError(f"{what}: cell ({ix}, {iy}) is outside the grid of {settings.nx} x {settings.ny} columns")
+    if len(set(cells)) != len(cells):
+        twice = sorted({c for c in cells if cells.count(c) > 1})
+        raise ValueError(f"{what}: cell {twice[0]} is given twice")
+    if len(cells) > MAX_CELLS or n_variables > MAX_VARIABLES:
+        raise ValueError(f"{what}: {len(cells)} cells x {n_variables} variables (at most {MAX_CELLS} x {MAX_VARIABLES})")
+    if int(capacity) < 1:
+        raise ValueError(f"{what}: capacity = {capacity} (at least one row resident on the device)")
+    return cells
+
+
+def output_file_name(series, state):
+    """The file of a series (`output_path`, `base_output_path`): one per rank, named like the diagnostics', with several ranks."""
+    from . import runtime_state
+
+    name = series.output_path.format(identifier=state.settings.identifier)
+    if runtime_state.proc_num > 1:
+        name = name[:-3] + f".{runtime_state.proc_rank:04d}.nc"
+    return os.path.join(series.base_output_path, name) if series.base_output_path else name
+
+
+def claim_output_file(series, state, what):
+    """The path the series writes to (None in diskless mode); a file that is already there is not overwritten unasked."""
+    path = None if rs.diskless_mode else output_file_name(series, state)
+    if path and os.path.isfile(path) and not getattr(rs, "force_overwrite", False):
+        raise IOError(f"output file {path} for the {what} exists (change the output path, enable the force_overwrite runtime "
+                      "setting or delete it)")
+    return path
+
+
+def point_coordinates(state, cells, local):
+    """ix, iy (global), x, y of the points [(k, local cell)] of this rank, as the variables of the file."""
+    vs, settings = state.variables, state.settings
+    nyl = settings.ny // rs.num_proc[1]
+    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
+    pts = [cells[k] for k, _ in local]
+    return {
+        "ix": (("point",), np.array([c[0] for c in pts], dtype=np.int64), {"long_name": "global interior x index", "units": ""}),
+        "iy": (("point",), np.array([c[1] for c in pts], dtype=np.int64), {"long_name": "global interior y index", "units": ""}),
+        "x": (("point",), np.array([x[c // nyl] for _, c in local], dtype=np.float64), {"long_name": "x", "units": "m"}),
+        "y": (("point",), np.array([y[c % nyl] for _, c in local], dtype=np.float64), {"long_name": "y", "units": "m"}),
+    }
+
+
 class PointSeries:
     """`state.points`: what the script sets (cells, output_variables, base_output_path, capacity) and the rows drained so far."""
 
@@ -64,12 +114,7 @@ class PointSeries:
         return bool(self.cells) and bool(self.output_variables)
 
     def get_output_file_name(self, state):
-        from . import runtime_state
-
-        name = self.output_path.format(identifier=state.settings.identifier)
-        if runtime_state.proc_num > 1:
-            name = name[:-3] + f".{runtime_state.proc_rank:04d}.nc"
-        return os.path.join(self.base_output_path, name) if self.base_output_path else name
+        return output_file_name(self, state)
 
 
 def initialize(state):
@@ -83,17 +128,7 @@ def initialize(state):
     if settings.enable_offline_transport:
         raise NotImplementedError("points: the offline transport model steps by the day and its output is read after every step "
                                   "(state.diagnostics); the recorder belongs to the SVAT / oneD step")
-    cells = [(int(c[0]), int(c[1])) for c in p.cells]
-    for ix, iy in cells:
-        if not (0 <= ix < settings.nx and 0 <= iy < settings.ny):
-            raise ValueError(f"points: cell ({ix}, {iy}) is outside the grid of {settings.nx} x {settings.ny} columns")
-    if len(set(cells)) != len(cells):
-        twice = sorted({c for c in cells if cells.count(c) > 1})
-        raise ValueError(f"points: cell {twice[0]} is given twice")
-    if len(cells) > MAX_CELLS or len(p.output_variables) > MAX_VARIABLES:
-        raise ValueError(f"points: {len(cells)} cells x {len(p.output_variables)} variables (at most {MAX_CELLS} x {MAX_VARIABLES})")
-    if int(p.capacity) < 1:
-        raise ValueError(f"points: capacity = {p.capacity} (at least one row resident on the device)")
+    cells = check_request("points", p.cells, len(p.output_variables), p.capacity, settings)
     for v in p.output_variables:
         meta = state.var_meta.get(v)
         if meta is None or meta.plane is None or meta.dtype is not None:
@@ -116,10 +151,7 @@ def initialize(state):
         first[0, j] = [a[c // nyl, c % nyl] for _, c in p._local]
     p._hdr = [np.array([[int(vs.itt), int(vs.time), 0]], dtype=np.int64)]
     p._values = [first]
-    p._path = None if rs.diskless_mode else p.get_output_file_name(state)
-    if p._path and os.path.isfile(p._path) and not getattr(rs, "force_overwrite", False):
-        raise IOError(f"output file {p._path} for the points exists (change the output path, enable the force_overwrite runtime "
-                      "setting or delete it)")
+    p._path = claim_output_file(p, state, "points")
     _write(state)
 
 
@@ -178,19 +210,13 @@ def _write(state):
     vs, settings = state.variables, state.settings
     os.makedirs(os.path.dirname(os.path.abspath(p._path)), exist_ok=True)
     hdr, values = np.concatenate(p._hdr), np.concatenate(p._values)
-    nyl = settings.ny // rs.num_proc[1]
-    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
-    pts = [p.cells[k] for k, _ in p._local]
-    dims = {"Time": None, "point": len(pts)}
+    dims = {"Time": None, "point": len(p._local)}
     variables = {
         "Time": (("Time",), hdr[:, 1] / float(DAY), {"long_name": "Time", "units": "days", "time_origin": str(settings.time_origin)}),
         "dt": (("Time",), hdr[:, 2].astype(np.float64), {"long_name": "length of the time step", "units": "s"}),
         "itt": (("Time",), hdr[:, 0].astype(np.int64), {"long_name": "time step", "units": ""}),
-        "ix": (("point",), np.array([c[0] for c in pts], dtype=np.int64), {"long_name": "global interior x index", "units": ""}),
-        "iy": (("point",), np.array([c[1] for c in pts], dtype=np.int64), {"long_name": "global interior y index", "units": ""}),
-        "x": (("point",), np.array([x[c // nyl] for _, c in p._local], dtype=np.float64), {"long_name": "x", "units": "m"}),
-        "y": (("point",), np.array([y[c % nyl] for _, c in p._local], dtype=np.float64), {"long_name": "y", "units": "m"}),
     }
+    variables.update(point_coordinates(state, p.cells, p._local))
     from .diagnostics import _UNITS
 
     for j, name in enumerate(p.output_variables):

@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, stepping
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, stepping
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -153,10 +153,13 @@ class RogerSetup(metaclass=abc.ABCMeta):
             self.set_diagnostics(state)
             diagnostics.initialize(state)
             points.initialize(state)
+            sas_points.initialize(state)
             self.set_boundary_conditions_setup(state)
             self.set_boundary_conditions(state)
             self.set_forcing_setup(state)
             restart.read_restart(state)   # roger/roger.py:324-326
+            if offline and state.settings.warmup_done:
+                sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
         self._setup_done = True
         if not state.settings.enable_offline_transport:   # roger/roger.py:324-327
             with state.settings.unlock():
@@ -183,6 +186,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         with self.state.settings.unlock():
             self.state.settings.warmup_done = True
         diagnostics.output_transport(self.state)   # initial values after the warm-up, roger/roger.py:515-521
+        sas_points.start(self.state)               # ... and record 0 of the transport points
         if self.state.settings.enable_offline_transport and self.state.settings.write_restart:
             restart.write_restart(self.state, force=True)   # a warm-up that later runs can start from
 
@@ -257,6 +261,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         vs = state.variables
         if state.settings.restart_frequency > 0 and not self._in_warmup:
             with state.timers["diagnostics"]:
+                sas_points.drain(state)        # (rows not yet drained are drained before a restart file is written)
                 restart.write_restart(state)   # at the start of a day step, as in step(); not during the warm-up runs
         with state.timers["main"]:
             with vs.unlock():
@@ -275,6 +280,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 with state.timers["StorAge selection"]:
                     transport.calculate_storage_selection(state)
                 diagnostics.output_transport(state)    # write_output, roger/core/transport.py:3399-3418
+                sas_points.stepped(state)              # (rh_sas_step recorded the day's row; the ring is drained every `capacity` steps)
         self.after_timestep(state)
         if rs.profile_mode:
             state.sas_context.sync()
@@ -419,10 +425,12 @@ class RogerSetup(metaclass=abc.ABCMeta):
             if settings.write_restart and not in_warmup and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
                 if not failed:
                     points.drain(self.state)
+                    sas_points.drain(self.state)
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
         diagnostics.close(self.state)
         points.close(self.state)
+        sas_points.close(self.state)
 
     # -- fast path --------------------------------------------------------------------------------
     def enable_device_hooks(self):

@@ -345,6 +345,9 @@ class RogerState:
         from .points import PointSeries
 
         self.points = PointSeries()      # time series at observation columns (roger_amd/points.py); filled in by set_diagnostics
+        from .sas_points import TransportPointSeries
+
+        self.transport_points = TransportPointSeries()   # ... of the offline transport model (roger_amd/sas_points.py)
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None

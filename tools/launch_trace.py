@@ -140,6 +140,14 @@ def scenario():
     ctx.comm_init(native.comm_unique_id(), 1, 0)
     ctx.run_steps_dist(4)
     done(ctx)
+    from roger_amd import sas as rsas
+
+    section("transport 96 columns x 300 ages, no points: rh_sas_run_days(3), rh_sas_step x 2", native)
+    sas = rsas.create_sas(96, 300, 3, 90.0, 260.0, daily=rsas.synthetic_daily_inputs(96, 8, seed=42), age_statistics=True)
+    sas.run_days(0, 3)
+    sas.step(3)
+    sas.step(4)
+    done(sas)
     section("end", native)
 
 
