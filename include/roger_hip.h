@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 7   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h) */
+#define RH_ABI_VERSION 8   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -398,6 +398,37 @@ int rh_diag_slot_times(rh_ctx *ctx, int slot, int64_t *t_start, int64_t *t_end);
 int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const int *planes, int n_planes, int64_t capacity);
 int rh_points_count(rh_ctx *ctx, int64_t *rows_total);
 int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
+
+/* ---- catchment totals: per-step sum, minimum and maximum over a masked area, recorded on the device ---------------
+ * The areal precipitation, evapotranspiration, runoff and storage of a catchment per step -- what is compared with a gauge and what
+ * closes a water balance -- without a plane leaving the device between two steps.  After rh_totals_configure every step, wherever the
+ * points' kernel is launched, is followed by two launches: a workgroup per 256 columns reduces every configured plane over its
+ * columns inside the mask, one workgroup combines the workgroups' partials and writes the next row of a ring, with the row's header
+ * {itt, time at the END of the step, dt_secs}.  A launch behind the time limit (rh_set_time_limit) records nothing.
+ * The ORDER of the sum is fixed (no atomics), so a restatement on the host gives the same bits:
+ *   1. the 64 columns of a wavefront: a tree with strides 32, 16, 8, 4, 2, 1 -- x[l] += x[l + stride] for l < stride;
+ *   2. the four wavefronts of a workgroup: (w0 + w1) + (w2 + w3);
+ *   3. the workgroups' partials p[0 .. tiles): 256 accumulators, accumulator t adds p[t], p[t + 256], ... in this order to the
+ *      identity; the 256 accumulators then take 1. and 2.
+ * A column outside the mask or beyond n contributes +0.0 to the sum, +inf to the minimum, -inf to the maximum; minimum and maximum
+ * take the same path with fmin / fmax.  The result depends on where a column sits in this order: the totals of two decompositions
+ * of one domain differ in the last bits.
+ *   mask[n]:          a byte per interior column of the rank's block (C order over (x, y), as rh_upload), non-zero: inside the
+ *                     area; NULL: every column.  Copied.
+ *   planes[n_planes]: float64 plane ids below rh_planes_held, n_planes <= 32; treated as the points' planes are (the KEEP variant
+ *                     of the sparse kernel stores a pure output after all, an X_m1 plane switches the lazy rotation off).
+ *                     rh_diag_configure, rh_points_configure and rh_totals_configure may be called in any order.
+ *   capacity >= 1:    rows resident on the device, row r at r mod capacity: (capacity, n_planes, 3) float64 -- sum, min, max
+ * n_planes == 0 releases the buffers and stops the launches.  Every other call starts a new series (row 0).  RH_ERR_ARG
+ * (rh_last_error names the value): an int32 plane or one the context does not hold, more than 32 planes, capacity < 1, a mask
+ * without a set byte.
+ *   rh_totals_count  rows recorded since rh_totals_configure, and the number of columns inside the mask
+ *   rh_totals_read   rows [first_row, first_row + n_rows) that are still resident: hdr (n_rows, 3) int64, values (n_rows, n_planes,
+ *                    3) float64.  RH_ERR_ARG for rows that have been overwritten or not recorded yet.
+ * Both synchronise; RH_ERR_STATE before rh_totals_configure (or after it released the buffers). */
+int rh_totals_configure(rh_ctx *ctx, const unsigned char *mask, const int *planes, int n_planes, int64_t capacity);
+int rh_totals_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells);
+int rh_totals_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

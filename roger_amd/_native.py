@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 7   # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 8   # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -158,6 +158,9 @@ def load():
     lib.rh_points_configure.argtypes = [vp, vp, i32, vp, i32, i64]
     lib.rh_points_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.rh_points_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_totals_configure.argtypes = [vp, vp, vp, i32, i64]
+    lib.rh_totals_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.rh_totals_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -455,6 +458,7 @@ DECLARED_SYMBOLS = (
     "rh_set_forcing_weights", "rh_adaptive_dt_finish", "rh_diag_upload", "rh_diag_set_slot_state", "rh_set_forcing_stations", "rh_step_mode", "rh_comm_unique_id", "rh_comm_init", "rh_set_comm", "rh_comm_info", "rh_comm_set_grid", "rh_plane_is_pure_output", "rh_sparse_steps", "rh_set_time_limit", "rh_run_steps_dist",
     "rh_surface_routing", "rh_subsurface_routing", "rh_step_routed", "rh_planes_held", "rh_route_out", "rh_route_in", "rh_route_get_edges", "rh_route_get_static_edges", "rh_route_set_halo",
     "rh_points_configure", "rh_points_count", "rh_points_read",
+    "rh_totals_configure", "rh_totals_count", "rh_totals_read",
 )
 
 
@@ -745,6 +749,38 @@ class Context:
         values = np.empty((n, nv, nc), dtype=np.float64)
         self._check(self._lib.rh_points_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
                                              values.nbytes), "rh_points_read")
+        return hdr, values
+
+    # -- catchment totals (rh_totals_*) ----------------------------------------------------------
+    def totals_configure(self, names, mask=None, capacity=4096):
+        """Record the sum, minimum and maximum of `names` (float64 planes) over the columns of `mask` (a flag per interior column of
+        this context's block, C order; None: every column) after every step, in a ring of `capacity` rows on the device.  No names:
+        release the buffers and stop recording."""
+        names = list(names)
+        ids = (C.c_int * max(1, len(names)))(*[self.index[n] for n in names])
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if m.size != self.n:
+                raise ValueError(f"totals_configure: the mask has {m.size} values, the context {self.n} columns")
+        self._check(self._lib.rh_totals_configure(self._h, None if m is None else m.ctypes.data_as(C.c_void_p), ids, len(names), int(capacity)),
+                    "rh_totals_configure")
+        self._totals_nv = len(names)   # (a refused configuration leaves the previous one)
+
+    def totals_count(self):
+        """(rows recorded since totals_configure, columns inside the mask)."""
+        n, cells = C.c_int64(), C.c_int64()
+        self._check(self._lib.rh_totals_count(self._h, C.byref(n), C.byref(cells)), "rh_totals_count")
+        return n.value, cells.value
+
+    def totals_read(self, first, n):
+        """Rows [first, first + n) of the ring: (hdr int64 (n, 3): itt, time at the end of the step, dt_secs; values float64 (n, V, 3):
+        sum, min, max)."""
+        n = int(n)
+        hdr = np.empty((n, 3), dtype=np.int64)
+        values = np.empty((n, getattr(self, "_totals_nv", 0), 3), dtype=np.float64)
+        self._check(self._lib.rh_totals_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                             values.nbytes), "rh_totals_read")
         return hdr, values
 
     def pure_output_planes(self):

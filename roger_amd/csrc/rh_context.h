@@ -96,7 +96,7 @@ struct rh_ctx {
     DeviceHolds held;
     Switches sw;                     // the environment as rh_create found it
     int n_groups = 1;                // fused kernel: completion groups (about 64 workgroups each, at most RH_DONE_GROUPS)
-    bool obs_reads_m1 = false;       // an observer (accumulators, points) was given an X_m1 plane: the fused kernel does not skip those stores
+    bool obs_reads_m1 = false;       // an observer (accumulators, points, totals) was given an X_m1 plane: the fused kernel does not skip those stores
     bool obs_reads_sparse = false;   // an observer was given a plane the sparse kernel leaves out (its KEEP variant stores those); both
                                      // formed by observers_changed from the union of the observers' planes, and by nobody else
     int64_t t_end = -1;              // rh_set_time_limit (host copy of DevState::t_end)
@@ -112,6 +112,13 @@ struct rh_ctx {
     int points_ncells = 0, points_nplanes = 0;   // both 0: not configured, no k_points launch
     int64_t points_cap = 0;
     int points_planes[RH_POINTS_MAX_PLANES] = {};
+    // catchment totals (rh_totals_configure): the ring and its headers, the tiles' partials, the mask (not held: every column)
+    DevBuf<double> totals_buf, totals_part_buf;
+    DevBuf<long long> totals_hdr_buf;
+    DevBuf<unsigned char> totals_mask_buf;
+    int totals_nplanes = 0;          // 0: not configured, no k_totals_* launch
+    int64_t totals_cap = 0, totals_ncells = 0;   // rows resident; columns inside the mask
+    int totals_planes[RH_POINTS_MAX_PLANES] = {};
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

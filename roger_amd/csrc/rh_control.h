@@ -1217,6 +1217,123 @@ __global__ __launch_bounds__(RH_BLOCK) void k_points(Arena a, DevState *D, int a
         D->points_rows = row + 1;
     }
 }
+// Catchment totals (rh_totals_configure): after a step, the sum, minimum and maximum of up to 32 planes over the masked columns, one row
+// of a ring per step.  The ORDER of the sum is fixed, so a host restatement (tests/totals_reference.py) gives the same bits:
+//   a wavefront:  the tree over its 64 lanes with strides 32 ... 1, lane l < stride becomes x[l] + x[l + stride] (the xor butterfly
+//                 gives lane 0 exactly that: every lane of a pair forms the same commutative sum)
+//   a workgroup:  (w0 + w1) + (w2 + w3) of its four wavefronts, through LDS
+//   the grid:     k_totals_finish, one workgroup: thread t adds the tiles' partials t, t + 256, ... in increasing order to the identity,
+//                 then the 256 thread values take the same two levels
+// The minimum and the maximum take the same path with fmin / fmax.  A column outside the mask or beyond n contributes the identity
+// (+0.0, +inf, -inf).  No floating-point atomics: the tiles' partials are plain stores into totals_part [plane][stat][tile].
+RH_DEV double totals_identity(int stat) { return stat == 0 ? 0.0 : (stat == 1 ? __builtin_huge_val() : -__builtin_huge_val()); }   // sum, min, max
+RH_DEV double totals_op(int stat, double x, double y) { return stat == 0 ? x + y : (stat == 1 ? fmin(x, y) : fmax(x, y)); }
+template <int STAT>
+RH_DEV double totals_wave(double x) {
+    for (int off = 32; off; off >>= 1) x = totals_op(STAT, x, __shfl_xor(x, off));
+    return x;
+}
+#define RH_TOTALS_CHUNK 8   // planes loaded before the first of them is reduced (memory-level parallelism of the tile kernel)
+__global__ __launch_bounds__(RH_BLOCK) void k_totals_tiles(Arena a, DevState *D, int after_fused) {
+    if (after_fused && D->skipped) return;
+    __shared__ double part[RH_POINTS_MAX_PLANES * 3][RH_BLOCK / 64];
+    const int64_t i = (int64_t)blockIdx.x * RH_BLOCK + threadIdx.x;
+    const int nv = D->totals_nplanes, wave = threadIdx.x >> 6;
+    const unsigned char *mask = D->totals_mask;
+    const bool inside = i < a.n;
+    const bool counted = inside && (!mask || __builtin_nontemporal_load(mask + i) != 0);
+    for (int j0 = 0; j0 < nv; j0 += RH_TOTALS_CHUNK) {
+        double v[RH_TOTALS_CHUNK];
+#pragma unroll
+        for (int k = 0; k < RH_TOTALS_CHUNK; ++k) {
+            v[k] = 0.0;
+            if (inside && j0 + k < nv) rh_ld(a, D->totals_planes[j0 + k], i, v[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < RH_TOTALS_CHUNK; ++k) {
+            if (j0 + k >= nv) break;
+            const double s = totals_wave<0>(counted ? v[k] : totals_identity(0));
+            const double lo = totals_wave<1>(counted ? v[k] : totals_identity(1));
+            const double hi = totals_wave<2>(counted ? v[k] : totals_identity(2));
+            if ((threadIdx.x & 63) == 0) {
+                part[(j0 + k) * 3 + 0][wave] = s;
+                part[(j0 + k) * 3 + 1][wave] = lo;
+                part[(j0 + k) * 3 + 2][wave] = hi;
+            }
+        }
+    }
+    __syncthreads();
+    const int ntiles = D->totals_ntiles;
+    for (int q = threadIdx.x; q < nv * 3; q += RH_BLOCK) {
+        const int stat = q % 3;
+        D->totals_part[(size_t)q * ntiles + blockIdx.x] = totals_op(stat, totals_op(stat, part[q][0], part[q][1]), totals_op(stat, part[q][2], part[q][3]));
+    }
+}
+// ONE workgroup: the tiles' partials into row totals_rows mod totals_cap, values (plane, {sum, min, max}), and the row's header from D->S
+// as k_points writes it.  Every thread reads the row counter, the barrier follows, thread 0 writes counter + 1 last.
+__global__ __launch_bounds__(RH_BLOCK) void k_totals_finish(DevState *D, int after_fused) {
+    if (after_fused && D->skipped) return;
+    __shared__ double part[RH_POINTS_MAX_PLANES * 3][RH_BLOCK / 64];
+    const long long row = D->totals_rows;
+    const long long slot = row % D->totals_cap;
+    const int nq = D->totals_nplanes * 3, ntiles = D->totals_ntiles;
+    // Four planes x three statistics x four partials per thread are loaded before the first is used: the loads of a thread are
+    // independent, only its additions are ordered (one partial per round would cost a memory latency each: 15 x 24 of them in a row at
+    // 10^6 columns and eight planes).
+    constexpr int PJ = 4, PT = 4;
+    for (int j0 = 0; j0 < nq / 3; j0 += PJ) {
+        double x[PJ][3];
+#pragma unroll
+        for (int j = 0; j < PJ; ++j)
+#pragma unroll
+            for (int st = 0; st < 3; ++st) x[j][st] = totals_identity(st);
+        for (int t0 = threadIdx.x; t0 < ntiles; t0 += PT * RH_BLOCK) {
+            double v[PJ][3][PT];
+#pragma unroll
+            for (int j = 0; j < PJ; ++j)
+#pragma unroll
+                for (int st = 0; st < 3; ++st)
+#pragma unroll
+                    for (int k = 0; k < PT; ++k) {
+                        const int t = t0 + k * RH_BLOCK;
+                        v[j][st][k] = (j0 + j < nq / 3 && t < ntiles) ? D->totals_part[(size_t)((j0 + j) * 3 + st) * ntiles + t] : 0.0;
+                    }
+#pragma unroll
+            for (int k = 0; k < PT; ++k)   // in increasing tile order
+                if (t0 + k * RH_BLOCK < ntiles) {
+#pragma unroll
+                    for (int j = 0; j < PJ; ++j)
+#pragma unroll
+                        for (int st = 0; st < 3; ++st) x[j][st] = totals_op(st, x[j][st], v[j][st][k]);
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < PJ; ++j) {
+            if (j0 + j >= nq / 3) break;
+            const double s = totals_wave<0>(x[j][0]), lo = totals_wave<1>(x[j][1]), hi = totals_wave<2>(x[j][2]);
+            if ((threadIdx.x & 63) == 0) {
+                part[(j0 + j) * 3 + 0][threadIdx.x >> 6] = s;
+                part[(j0 + j) * 3 + 1][threadIdx.x >> 6] = lo;
+                part[(j0 + j) * 3 + 2][threadIdx.x >> 6] = hi;
+            }
+        }
+    }
+    const rh_scalars &S = D->S;
+    const long long itt = S.itt, time = S.time, dt_secs = S.dt_secs;
+    __syncthreads();
+    double *dst = D->totals + (size_t)slot * nq;
+    for (int q = threadIdx.x; q < nq; q += RH_BLOCK) {
+        const int stat = q % 3;
+        dst[q] = totals_op(stat, totals_op(stat, part[q][0], part[q][1]), totals_op(stat, part[q][2], part[q][3]));
+    }
+    if (threadIdx.x == 0) {
+        long long *h = D->totals_hdr + 3 * slot;
+        h[0] = itt;
+        h[1] = time;
+        h[2] = dt_secs;
+        D->totals_rows = row + 1;
+    }
+}
 // multi-GPU: OR of the summary words into words[3] for the exchange
 // dst64 != null: also spread over 64 int32 (0 / 1) for the MAX all-reduce (k_words_expand folded in)
 __global__ __launch_bounds__(RH_BLOCK) void k_summary_reduce(DevState *D, int do_hooks, int *dst64, int src) {

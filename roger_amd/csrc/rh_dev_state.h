@@ -123,6 +123,17 @@ struct DevState {
     int points_ncells, points_nplanes;
     int points_planes[RH_POINTS_MAX_PLANES];
     long long points_cells[RH_POINTS_MAX_CELLS];
+
+    // catchment totals (rh_totals_configure; k_totals_tiles, k_totals_finish): a ring of totals_cap rows, row r at r mod totals_cap --
+    // totals (row, plane, {sum, min, max}) float64 and totals_hdr as points_hdr.  totals_part [plane][stat][tile]: the partials of the
+    // totals_ntiles workgroups of k_totals_tiles.  totals_mask: a byte per column (0: outside the area), or null: every column.
+    double *totals;
+    long long *totals_hdr;
+    double *totals_part;
+    const unsigned char *totals_mask;
+    long long totals_rows, totals_cap;
+    int totals_nplanes, totals_ntiles;
+    int totals_planes[RH_POINTS_MAX_PLANES];
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

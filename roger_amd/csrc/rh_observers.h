@@ -1,8 +1,8 @@
-// rh_observers.h -- what follows every step: the output accumulators (rh_diag_*) and the time series at observation columns
-// (rh_points_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
+// rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
+// (rh_points_*) and the catchment totals (rh_totals_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
 #pragma once
-// The observers' planes changed (rh_diag_configure, rh_points_configure): what the fused kernel must leave in memory after every step,
-// from the UNION of the accumulators' and the points' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
+// The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure): what the fused kernel must leave in memory
+// after every step, from the UNION of the accumulators', the points' and the totals' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
 // five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in DevState::keep: the KEEP
 // variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
 static int observers_changed(rh_ctx *ctx) {
@@ -22,6 +22,7 @@ static int observers_changed(rh_ctx *ctx) {
     };
     add(ctx->diag_planes, ctx->diag_n);
     if (ctx->points_ncells) add(ctx->points_planes, ctx->points_nplanes);
+    add(ctx->totals_planes, ctx->totals_nplanes);
     const int any = reads_sparse ? 1 : 0;
     HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
     HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
@@ -33,13 +34,17 @@ static int observers_changed(rh_ctx *ctx) {
 }
 
 // The observers behind the step that was just enqueued: the accumulators over all columns (grid: the fused launch's own, which has one
-// workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values).
-// after_fused: rh_control.h, k_diag.
-static bool has_observers(const rh_ctx *ctx) { return ctx->diag_n || ctx->points_ncells; }
+// workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values),
+// then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them.  after_fused: rh_control.h, k_diag.
+static bool has_observers(const rh_ctx *ctx) { return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes; }
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->points_ncells) hipLaunchKernelGGL(k_points, dim3(1), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    if (ctx->totals_nplanes) {
+        hipLaunchKernelGGL(k_totals_tiles, dim3(grid_for(ctx->n)), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_totals_finish, dim3(1), block, 0, ctx->stream, ctx->dev, after_fused);
+    }
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -245,6 +250,107 @@ int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr,
         HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
                                    hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->points_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        done += m;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+
+// ---- catchment totals (include/roger_hip.h) ----
+int rh_totals_configure(rh_ctx *ctx, const unsigned char *mask, const int *planes, int n_planes, int64_t capacity) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_planes < 0 || n_planes > RH_POINTS_MAX_PLANES)
+        return fail(ctx, RH_ERR_ARG, "rh_totals_configure: n_planes = " + std::to_string(n_planes) + " (0 ... " + std::to_string(RH_POINTS_MAX_PLANES) + ")");
+    const bool off = n_planes == 0;
+    int plane_list[RH_POINTS_MAX_PLANES] = {};
+    int64_t ncells = ctx->n;
+    if (!off) {
+        if (!planes) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: null pointer");
+        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
+        for (int j = 0; j < n_planes; ++j) {
+            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+                return fail(ctx, RH_ERR_ARG, "rh_totals_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
+            if (PLANE_IS_INT[planes[j]])
+                return fail(ctx, RH_ERR_ARG, std::string("rh_totals_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
+            plane_list[j] = planes[j];
+        }
+        if (mask) {
+            ncells = 0;
+            for (int64_t i = 0; i < ctx->n; ++i) ncells += mask[i] != 0;
+            if (!ncells) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: the mask holds no column (0 of " + std::to_string(ctx->n) + " bytes set)");
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    HIPCHK(ctx, ctx->totals_buf.release());
+    HIPCHK(ctx, ctx->totals_hdr_buf.release());
+    HIPCHK(ctx, ctx->totals_part_buf.release());
+    HIPCHK(ctx, ctx->totals_mask_buf.release());
+    ctx->totals_nplanes = 0;
+    ctx->totals_cap = ctx->totals_ncells = 0;
+    const int ntiles = (int)grid_for(ctx->n);
+    if (!off) {
+        HIPCHK(ctx, ctx->totals_buf.alloc((size_t)capacity * n_planes * 3 * sizeof(double)));
+        HIPCHK(ctx, ctx->totals_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        HIPCHK(ctx, ctx->totals_part_buf.alloc((size_t)n_planes * 3 * ntiles * sizeof(double)));
+        if (mask) {
+            HIPCHK(ctx, ctx->totals_mask_buf.alloc((size_t)ctx->n));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->totals_mask_buf, mask, (size_t)ctx->n, hipMemcpyHostToDevice, ctx->stream));
+        }
+        ctx->totals_nplanes = n_planes;
+        ctx->totals_cap = capacity;
+        ctx->totals_ncells = ncells;
+    }
+    std::memcpy(ctx->totals_planes, plane_list, sizeof(plane_list));
+    const long long zero = 0, cap = (long long)ctx->totals_cap;
+    const unsigned char *const mask_dev = ctx->totals_mask_buf;
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals, *ctx->totals_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_hdr, *ctx->totals_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_part, *ctx->totals_part_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_mask, mask_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_rows, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_cap, cap));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_nplanes, ctx->totals_nplanes));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_ntiles, ntiles));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_planes, plane_list));
+    return observers_changed(ctx);   // synchronises: the sources above are stack locals (and the caller's mask)
+}
+static int totals_rows(rh_ctx *ctx, const char *who, long long *rows) {
+    if (!ctx->totals_nplanes) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_totals_configure has not been called");
+    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->totals_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_totals_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!rows_total || !ncells) return fail(ctx, RH_ERR_ARG, "rh_totals_count: null pointer");
+    long long rows = 0;
+    if (int rc = totals_rows(ctx, "rh_totals_count", &rows)) return rc;
+    *rows_total = (int64_t)rows;
+    *ncells = ctx->totals_ncells;
+    return RH_OK;
+}
+int rh_totals_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = totals_rows(ctx, "rh_totals_read", &total)) return rc;
+    const size_t nv = (size_t)ctx->totals_nplanes * 3;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return fail(ctx, RH_ERR_ARG, "rh_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - ctx->totals_cap)
+        return fail(ctx, RH_ERR_ARG, "rh_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->totals_cap - 1) +
+                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->totals_cap) + " of " +
+                                     std::to_string(total) + " rows)");
+    if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_totals_read: size mismatch (n_rows x n_planes x 3 float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % ctx->totals_cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, ctx->totals_cap - slot);
+        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->totals_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->totals_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
                                    ctx->stream));
         done += m;
     }

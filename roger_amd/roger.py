@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, stepping
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, stepping, totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -153,6 +153,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             self.set_diagnostics(state)
             diagnostics.initialize(state)
             points.initialize(state)
+            totals.initialize(state)
             sas_points.initialize(state)
             self.set_boundary_conditions_setup(state)
             self.set_boundary_conditions(state)
@@ -206,6 +207,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         if facts.restart_every_step:
             with state.timers["diagnostics"]:
                 points.drain(state)            # (rows not yet drained are drained before a restart file is written)
+                totals.drain(state)
                 restart.write_restart(state)   # roger/roger.py:385-386
         with state.timers["main"]:
             with state.timers["read data"]:
@@ -250,6 +252,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         if state._diag_active:   # roger/roger.py:458-465: output at the end of the time step
             diagnostics.output(state)
         points.stepped(state)    # the points' ring is drained every `capacity` step calls
+        totals.stepped(state)    # ... and the totals'
         if rs.profile_mode:
             state.backend_context.sync()
             logger.info(" Time step took {:.2f}s".format(state.timers["main"].last_time))
@@ -362,6 +365,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     n = min(n, max(1, slots - 1))          # (a step starts at most one output interval)
                 if state.points.active:
                     n = min(n, int(state.points.capacity))   # (a round never records more rows than the points' ring holds)
+                if state.totals.active:
+                    n = min(n, int(state.totals.capacity))   # (... nor than the totals')
                 self.run_device(int(n), final=False)
                 first = False
         finally:
@@ -381,7 +386,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(state._diag_active) or state.points.active
+        diag = bool(state._diag_active) or state.points.active or state.totals.active
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -425,11 +430,13 @@ class RogerSetup(metaclass=abc.ABCMeta):
             if settings.write_restart and not in_warmup and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
                 if not failed:
                     points.drain(self.state)
+                    totals.drain(self.state)
                     sas_points.drain(self.state)
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
         diagnostics.close(self.state)
         points.close(self.state)
+        totals.close(self.state)
         sas_points.close(self.state)
 
     # -- fast path --------------------------------------------------------------------------------
@@ -479,7 +486,9 @@ class RogerSetup(metaclass=abc.ABCMeta):
             self.enable_device_hooks()
         vs = self.state.variables
         points.check_call(self.state, nsteps)   # (before anything is enqueued)
+        totals.check_call(self.state, nsteps)
         points.drain(self.state)
+        totals.drain(self.state)
         vs.flush_to_device()
         ctx = self.state.backend_context
         engine = stepping.engine(self._facts())
@@ -493,5 +502,6 @@ class RogerSetup(metaclass=abc.ABCMeta):
             self._stepper(one_exchange=engine == stepping.PHASED_ONE).run(nsteps)
         vs.mark_device_newer()
         points.drain(self.state, final=final)
+        totals.drain(self.state, final=final)
         if self.state._diag_active:
             diagnostics.output(self.state, final=final)

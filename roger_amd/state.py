@@ -348,6 +348,9 @@ class RogerState:
         from .sas_points import TransportPointSeries
 
         self.transport_points = TransportPointSeries()   # ... of the offline transport model (roger_amd/sas_points.py)
+        from .totals import AreaTotals
+
+        self.totals = AreaTotals()       # per-step sum, min and max over a masked area (roger_amd/totals.py)
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None
