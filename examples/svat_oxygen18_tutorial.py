@@ -12,7 +12,9 @@ svat_oxygen18_tutorial) on the hip backend:
    transpiration and percolation and their median travel times as SVATOXYGEN18.average.nc;
 4. with `--points ix,iy[;ix,iy...]` the columns named (interior indices, 0-based) are recorded on the device after every day
    (`state.transport_points`): the signal of percolation and root zone, the median travel time and the whole travel time
-   distribution of the percolation, the soil's water by age -> SVATOXYGEN18.transport_points.nc.
+   distribution of the percolation, the soil's water by age -> SVATOXYGEN18.transport_points.nc.  With `--totals` the catchment series
+   (`state.transport_totals`): the flux-weighted d18O of the percolation, the catchment's travel time distribution of q_ss and its
+   storage by age, reduced on the device after every day -> SVATOXYGEN18.transport_totals.nc.
 """
 import argparse
 import importlib.util
@@ -44,6 +46,9 @@ def main(argv=None):
     ap.add_argument("--substeps", type=int, default=6)
     ap.add_argument("--out", default="output")
     ap.add_argument("--points", default="", help="observation columns ix,iy[;ix,iy...]: their daily series go to <out>/SVATOXYGEN18.transport_points.nc")
+    ap.add_argument("--totals", action="store_true",
+                    help="catchment series -> <out>/SVATOXYGEN18.transport_totals.nc: the flux-weighted d18O of the percolation, the "
+                         "catchment's travel time distribution of q_ss, its storage by age")
     args = ap.parse_args(argv)
     points = [tuple(int(v) for v in c.split(",")) for c in args.points.split(";") if c.strip()]
     _svat_example().main([args.input_dir, "--days", str(args.days), "--out", args.out])
@@ -73,6 +78,10 @@ def main(argv=None):
                 p.cells = points
                 p.output_variables = ["C_iso_q_ss", "C_iso_rz", "tt50_q_ss", "TT_q_ss", "sa_s"]
                 p.base_output_path = args.out
+            if args.totals:
+                t = state.transport_totals      # (mask None: every column is the catchment)
+                t.output_variables = [("C_iso_q_ss", "q_ss"), ("tt_q_ss", "q_ss"), "sa_s"]
+                t.base_output_path = args.out
 
     model = WithOutput()
     model.setup()
@@ -80,7 +89,8 @@ def main(argv=None):
     model.run()
     vs = model.state.variables
     print(f"transport: {vs.itt} days; d18O of the percolation on the last day {np.asarray(vs.C_iso_q_ss)[2:-2, 2:-2].ravel()} permil; "
-          f"output in {args.out}/SVATOXYGEN18.average.nc" + (f", {len(points)} observation columns in {args.out}/SVATOXYGEN18.transport_points.nc" if points else ""))
+          f"output in {args.out}/SVATOXYGEN18.average.nc" + (f", {len(points)} observation columns in {args.out}/SVATOXYGEN18.transport_points.nc" if points else "")
+          + (f", catchment series in {args.out}/SVATOXYGEN18.transport_totals.nc (C_iso_q_ss_by_q_ss_mean, tt_q_ss_by_q_ss_mean)" if args.totals else ""))
     return model
 
 

@@ -184,6 +184,64 @@ int rh_sas_points_count(rh_sas_ctx *ctx, int64_t *rows_total);
 int rh_sas_points_row_elems(const rh_sas_ctx *ctx, int64_t *elems);
 int rh_sas_points_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes);
 
+/* ---- catchment totals, recorded on the device after every day -------------------------------------------------------------------
+ * A comparison at the catchment outlet needs the flux-weighted concentration of the percolate, sum(q_ss C_q_ss) / sum(q_ss), the
+ * catchment's backward travel time distribution, sum(q_ss tt_q_ss(T)) / sum(q_ss) per age class, and its storage by age, sum(sa_s(T)).
+ * After rh_sas_totals_configure, rh_sas_step and every day of rh_sas_run_days are followed by the totals' launches on the context's
+ * stream (behind the points' launch if both are on; kernels: roger_amd/csrc/rh_sas_totals.h) that reduce the configured items over
+ * the masked cells into the next row of a ring on the device.  rh_sas_stages never records; a context without totals enqueues exactly
+ * what it enqueued before these entry points existed.  Stands where the reference has its `tracer_monitor` diagnostic.
+ *   mask     [n_cells] bytes, non-zero = inside; NULL: every cell.  A mask with no cell inside is RH_ERR_ARG.
+ *   items    [n_items], at most RH_SAS_TOTALS_MAX_ITEMS, each (array, weight):
+ *            array   what rh_sas_points_configure accepts -- per-cell float64 arrays this context holds, of width 1, ages or ages + 1 --
+ *                    and the nine DAILY inputs, which have width 1: the value is row (day mod forcing_days)
+ *            weight  -1 (none) or one of the eight DAILY flux inputs (not C_in): row (day mod forcing_days), the row the day's kernel read
+ *   capacity >= 1    rows resident on the device, row r at r mod capacity; capacity x row_elems x 8 at most 2 GiB
+ * n_items == 0 releases everything and stops the launches.  Every other call starts a new series (row 0).  RH_ERR_ARG (rh_sas_last_error
+ * names the offender): an unknown id, an int32 array, sas_params_*, an array given twice with the same weight, a weight that is not a
+ * daily flux input, counts above the limit, capacity < 1, a ring above 2 GiB.  RH_ERR_STATE: an array this context does not hold.  A
+ * refused call leaves the previous configuration in place.
+ *
+ * Which cells count.  Cell c is ELIGIBLE for item j if it is inside the mask and either j has no weight or w[c] > 0 (a NaN or zero
+ * weight is not eligible).  With day < 0 (rh_sas_totals_record: "no daily row") an item that has a weight or a DAILY value has no
+ * eligible cell.  A term is t = v (no weight) or t = fl(v w): the product is rounded before it is added, never fused.
+ *   width 1      a cell is COUNTED if it is eligible and v is not NaN.  Row block [wsum, count, sum, min, max]: wsum = sum of w over the
+ *                counted cells (without a weight: = count), count as a double, sum = sum of t, min / max of v itself.  Nothing counted:
+ *                [+0.0, 0, +0.0, +inf, -inf].
+ *   width W > 1  row block [wsum, count, sum[0 ... W)]: wsum and count over the ELIGIBLE cells; per age class a NaN element contributes
+ *                +0.0 (the reference's nansum convention for msa_*, mtt_*).
+ * Infinities propagate.  Row layout (rh_sas_totals_row_elems float64): the items' blocks in configured order.  Per row one int64 tag,
+ * kept on the host: the `day` argument of the step, or the caller's value for rh_sas_totals_record.
+ *
+ * The ORDER of the sums is fixed, so that a host restatement (tests/sas_totals_reference.py) gives the same bits.  The result follows
+ * the cells of a rank's block: totals of different decompositions differ in the last bits.  No floating-point atomics.
+ *   width 1 (sum, wsum, count, min, max; also wsum and count of an age item): the order of rh_totals_* (roger_hip.h).  Cells padded to a
+ *       multiple of 256 with the identity (+0.0, +inf, -inf; also where a cell is not counted); per 64 cells the tree with strides
+ *       32 ... 1, x[l] = x[l] op x[l + stride]; per 256 cells (w0 + w1) + (w2 + w3); the tiles' partials p: accumulator t of 256 starts
+ *       from the identity and takes p[t], p[t + 256], ... in this order; the 256 accumulators go through the same two levels.
+ *   width W > 1, per age class: cut the sequence of cells into runs of 256 consecutive cells; sum each run left to right, starting
+ *       from +0.0, a skipped cell contributing +0.0; repeat on the sequence of partials (plain sums) until one value is left.  Lanes run
+ *       along the age axis, which is contiguous: every global load is unit stride and no butterfly crosses cells.
+ * Scratch on the device, sized at configure: items x 5 x ceil(n_cells / 256) float64 for the width-1 partials; for the age rule two
+ * buffers of ceil(n_cells / 256) x Wmax and ceil(n_cells / 65536) x Wmax float64, shared by the age items, which are reduced one after
+ * another (10^6 cells x 1000 ages: 31 MB + 0.13 MB).
+ *   rh_sas_totals_record     one row now, behind what the stream holds, with the caller's tag; day < 0: no daily row
+ *   rh_sas_totals_count      rows recorded since rh_sas_totals_configure (no synchronisation) and the cells inside the mask
+ *   rh_sas_totals_row_elems  float64 per row
+ *   rh_sas_totals_read       as rh_sas_points_read: the resident rows [first_row, first_row + n_rows), RH_ERR_ARG for rows that have been
+ *                            overwritten or not recorded yet; synchronises
+ * All four: RH_ERR_STATE before rh_sas_totals_configure (or after it released everything). */
+#define RH_SAS_TOTALS_MAX_ITEMS 32
+typedef struct rh_sas_totals_item {
+    int32_t array;
+    int32_t weight; /* -1 = none */
+} rh_sas_totals_item;
+int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh_sas_totals_item *items, int n_items, int64_t capacity);
+int rh_sas_totals_record(rh_sas_ctx *ctx, int64_t tag, int64_t day);
+int rh_sas_totals_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells);
+int rh_sas_totals_row_elems(const rh_sas_ctx *ctx, int64_t *elems);
+int rh_sas_totals_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

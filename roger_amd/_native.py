@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 8   # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 9   # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -238,6 +238,11 @@ def _declare_sas(lib):
     lib.rh_sas_points_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.rh_sas_points_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.rh_sas_points_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_sas_totals_configure.argtypes = [vp, vp, vp, i32, i64]
+    lib.rh_sas_totals_record.argtypes = [vp, i64, i64]
+    lib.rh_sas_totals_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.rh_sas_totals_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_sas_totals_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
 
 
 SAS_DECLARED_SYMBOLS = (
@@ -246,6 +251,7 @@ SAS_DECLARED_SYMBOLS = (
     "rh_sas_array_is_int", "rh_sas_upload", "rh_sas_download", "rh_sas_upload_cells", "rh_sas_download_cells", "rh_sas_set_daily_from_device", "rh_sas_array_device_ptr", "rh_sas_stages",
     "rh_sas_step", "rh_sas_run_days", "rh_sas_enable_timing", "rh_sas_timing_summary", "rh_sas_selftest_pow", "rh_sas_selftest_div",
     "rh_sas_points_configure", "rh_sas_points_record", "rh_sas_points_count", "rh_sas_points_row_elems", "rh_sas_points_read",
+    "rh_sas_totals_configure", "rh_sas_totals_record", "rh_sas_totals_count", "rh_sas_totals_row_elems", "rh_sas_totals_read",
 )
 
 # stage bits of rh_sas_stages (include/roger_hip_sas.h)
@@ -416,6 +422,60 @@ class SasContext:
             out[v] = block.copy() if w == 1 else block.reshape(n, K, w).copy()
             off += K * w
         return tags, out
+
+    # -- catchment totals (rh_sas_totals_*) -------------------------------------------------------
+    def totals_configure(self, items, mask=None, capacity=4096):
+        """Reduce `items` over the cells where `mask` is set (None: all) after every day into a ring of `capacity` rows.  An item is
+        an array's name or (array, weight) with a daily flux input as weight; no items switch the recorder off."""
+        items = [(it, None) if isinstance(it, str) else (it[0], it[1]) for it in items]
+        flat = np.array([[self.index(v), -1 if w is None else self.index(w)] for v, w in items], dtype=np.int32).reshape(-1, 2)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if m.size != self.n:
+                raise ValueError(f"totals_configure: the mask has {m.size} cells, the context {self.n}")
+        self._check(self._lib.rh_sas_totals_configure(self._h, None if m is None else m.ctypes.data_as(C.c_void_p),
+                                                      flat.ctypes.data_as(C.c_void_p), len(items), int(capacity)), "rh_sas_totals_configure")
+        # (a refused configuration leaves the previous one)
+        self._totals_items = [(totals_item_name(v, w), 1 if v in DAILY_INPUTS else int(np.prod(self.shape(v)[1:], dtype=np.int64)))
+                              for v, w in items]
+
+    def totals_record(self, tag=0, day=-1):
+        """One row now (the initial values; a driver that steps by stage).  day < 0: no daily row, so an item with a weight or a daily
+        value has no eligible cell."""
+        self._check(self._lib.rh_sas_totals_record(self._h, int(tag), int(day)), "rh_sas_totals_record")
+
+    def totals_count(self):
+        """(rows recorded since totals_configure, cells inside the mask)."""
+        rows, ncells = C.c_int64(), C.c_int64()
+        self._check(self._lib.rh_sas_totals_count(self._h, C.byref(rows), C.byref(ncells)), "rh_sas_totals_count")
+        return rows.value, ncells.value
+
+    def totals_read(self, first, n):
+        """(tags (n,) int64, {item: {"wsum", "count", "sum"[, "min", "max"]}}) of the rows [first, first + n) that are still resident;
+        an item's key is `<array>` or `<array>_by_<weight>`, its statistics are (n,) float64, "sum" of an age item (n, width)."""
+        n = int(n)
+        elems = C.c_int64()
+        self._check(self._lib.rh_sas_totals_row_elems(self._h, C.byref(elems)), "rh_sas_totals_row_elems")
+        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
+        self._check(self._lib.rh_sas_totals_read(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                                 values.nbytes), "rh_sas_totals_read")
+        out, off = {}, 0
+        for key, w in self._totals_items:
+            d = {"wsum": values[:, off].copy(), "count": values[:, off + 1].copy()}
+            if w == 1:
+                d.update(sum=values[:, off + 2].copy(), min=values[:, off + 3].copy(), max=values[:, off + 4].copy())
+                off += 5
+            else:
+                d["sum"] = values[:, off + 2:off + 2 + w].copy()
+                off += 2 + w
+            out[key] = d
+        return tags, out
+
+
+def totals_item_name(value, weight=None):
+    """The name of a totals item in rows and files: `<value>` or `<value>_by_<weight>`."""
+    return value if weight is None else f"{value}_by_{weight}"
 
 
 def sas_selftest_div(a, d):

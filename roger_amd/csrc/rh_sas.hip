@@ -31,6 +31,7 @@
 #include "roger_hip_sas.h"
 #include "rh_sas_dev.h"
 #include "rh_sas_points.h"
+#include "rh_sas_totals.h"
 
 #include <algorithm>
 #include <memory>
@@ -89,6 +90,17 @@ struct rh_sas_ctx {
     int points_ncells = 0;           // 0: not configured, no k_sas_points launch
     int points_blocks = 0;           // workgroups of one row's launch
     int64_t points_cap = 0, points_row_elems = 0, points_rows = 0;
+    // catchment totals (rh_sas_totals_configure): the ring and its tags as for the points; the width-1 partials, the two level buffers
+    // of the age rule (rh_sas_totals.h), the mask on the device, and the host's copy of what the kernels are told
+    DevBuf<double> totals_ring, totals_part, totals_lvl[2];
+    DevBuf<SasTotalsDev> totals_cfg;
+    DevBuf<unsigned char> totals_mask;
+    std::unique_ptr<int64_t[]> totals_tags;
+    SasTotalsDev totals_host = {};
+    int totals_items = 0;            // 0: not configured, no launches
+    int totals_width[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    const double *totals_src[RH_SAS_TOTALS_MAX_ITEMS] = {};   // the age items' arrays
+    int64_t totals_cap = 0, totals_row_elems = 0, totals_rows = 0, totals_ncells = 0;
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -371,11 +383,14 @@ static int sas_points_enqueue(rh_sas_ctx *ctx, int64_t tag) {
     return RH_OK;
 }
 
-// a whole day and, with points configured, its row
+static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
+
+// a whole day and, with points or totals configured, their rows
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
-    const int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
-    if (rc || !ctx->points_ncells) return rc;
-    return sas_points_enqueue(ctx, day);
+    int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
+    if (!rc && ctx->points_ncells) rc = sas_points_enqueue(ctx, day);
+    if (!rc && ctx->totals_items) rc = sas_totals_enqueue(ctx, day, day);
+    return rc;
 }
 
 int rh_sas_step(rh_sas_ctx *ctx, int64_t day) {
@@ -501,6 +516,182 @@ int rh_sas_points_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64
         SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
                                     hipMemcpyDeviceToHost, ctx->stream));
         std::copy(ctx->points_tags.get() + slot, ctx->points_tags.get() + slot + m, tags + done);
+        done += m;
+    }
+    return rh_sas_sync(ctx);
+}
+
+// ---- catchment totals (include/roger_hip_sas.h; kernels and orders: rh_sas_totals.h) ----
+// one row behind what the stream holds so far: the width-1 statistics of every item, then the age items one after another
+static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
+    const int64_t slot = ctx->totals_rows % ctx->totals_cap, n = ctx->cfg.n_cells;
+    const int64_t day_off = day < 0 ? -1 : (day % ctx->cfg.forcing_days) * n;
+    const SasTotalsDev &P = ctx->totals_host;
+    double *row = ctx->totals_ring + (size_t)slot * (size_t)ctx->totals_row_elems;
+    hipLaunchKernelGGL(k_sas_totals_tiles, dim3((unsigned)P.ntiles), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->totals_cfg.get(), day_off);
+    hipLaunchKernelGGL(k_sas_totals_finish, dim3((unsigned)P.n_items), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->totals_cfg.get(), row);
+    for (int j = 0; j < P.n_items; ++j) {
+        const int W = ctx->totals_width[j];
+        if (W == 1) continue;
+        const unsigned bs = (unsigned)std::min(SAS_TOTALS_BLOCK, (W + 63) / 64 * 64);
+        const unsigned chunks = ((unsigned)W + bs - 1) / bs;
+        const double *src = ctx->totals_src[j];
+        int64_t m = n;
+        for (int lvl = 0;; ++lvl) {
+            const int64_t runs = (m + SAS_TOTALS_RUN - 1) / SAS_TOTALS_RUN;
+            double *dst = runs == 1 ? row + P.off[j] + 2 : ctx->totals_lvl[lvl & 1].get();
+            if (lvl == 0)
+                hipLaunchKernelGGL(k_sas_totals_ages<true>, dim3((unsigned)runs, chunks), dim3(bs), 0, ctx->stream, src, m, W, P.mask,
+                                   P.wgt[j] ? P.wgt[j] + std::max<int64_t>(day_off, 0) : nullptr, (P.wgt[j] && day_off < 0) ? 0 : 1, dst);
+            else
+                hipLaunchKernelGGL(k_sas_totals_ages<false>, dim3((unsigned)runs, chunks), dim3(bs), 0, ctx->stream, src, m, W,
+                                   (const unsigned char *)nullptr, (const double *)nullptr, 1, dst);
+            if (runs == 1) break;
+            src = dst;
+            m = runs;
+        }
+    }
+    SHIPCHK(ctx, hipGetLastError());
+    ctx->totals_tags[(size_t)slot] = tag;
+    ++ctx->totals_rows;
+    return RH_OK;
+}
+
+int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh_sas_totals_item *items, int n_items, int64_t capacity) {
+    const std::string who = "rh_sas_totals_configure: ";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_SAS_TOTALS_MAX_ITEMS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_TOTALS_MAX_ITEMS) + ")");
+    const int64_t n = ctx->cfg.n_cells;
+    SasTotalsDev P = {};
+    int width[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    const double *srcs[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    int64_t row_elems = 0, ncells = n;
+    int wmax = 0;
+    if (n_items) {
+        if (!items) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+        if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
+        for (int j = 0; j < n_items; ++j) {
+            const int a = items[j].array, w = items[j].weight;
+            if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
+            if (w < -1 || w >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown weight id " + std::to_string(w));
+            const std::string name = std::string("array ") + SAS_NAMES[a];
+            for (int k = 0; k < j; ++k)
+                if (items[k].array == a && items[k].weight == w) return sfail(ctx, RH_ERR_ARG, who + name + " is given twice with the same weight");
+            if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
+            if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* are not reduced)");
+            if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
+                return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
+            if (!ctx->arr[a])
+                return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
+            const double *base = (const double *)ctx->arr[a].get();
+            width[j] = SAS_KIND[a] == K_DAILY ? 1 : (int)(ctx->elems[a] / n);
+            P.val[j] = width[j] == 1 ? base : nullptr;
+            srcs[j] = width[j] == 1 ? nullptr : base;
+            P.val_daily[j] = SAS_KIND[a] == K_DAILY;
+            P.wgt[j] = w >= 0 ? (const double *)ctx->arr[w].get() : nullptr;
+            P.off[j] = row_elems;
+            row_elems += width[j] == 1 ? SAS_TOTALS_NSTAT : 2 + width[j];
+            if (width[j] > 1) wmax = std::max(wmax, width[j]);
+        }
+        if (mask) {
+            ncells = 0;
+            for (int64_t c = 0; c < n; ++c) ncells += mask[c] != 0;
+            if (!ncells) return sfail(ctx, RH_ERR_ARG, who + "the mask holds no cell");
+        }
+        if (capacity > ((int64_t)1 << 31) / (row_elems * (int64_t)sizeof(double)))
+            return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " rows of " + std::to_string(row_elems) +
+                                              " float64 are a ring above 2 GiB");
+    }
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    SHIPCHK(ctx, ctx->totals_ring.release());
+    SHIPCHK(ctx, ctx->totals_part.release());
+    SHIPCHK(ctx, ctx->totals_lvl[0].release());
+    SHIPCHK(ctx, ctx->totals_lvl[1].release());
+    SHIPCHK(ctx, ctx->totals_cfg.release());
+    SHIPCHK(ctx, ctx->totals_mask.release());
+    ctx->totals_tags.reset();
+    ctx->totals_items = 0;
+    ctx->totals_cap = ctx->totals_row_elems = ctx->totals_rows = ctx->totals_ncells = 0;
+    if (!n_items) return RH_OK;
+    std::unique_ptr<int64_t[]> tags(new (std::nothrow) int64_t[(size_t)capacity]);
+    if (!tags) return sfail(ctx, RH_ERR_ARG, who + "out of host memory for the tags of " + std::to_string(capacity) + " rows");
+    const int64_t ntiles = (n + SAS_TOTALS_BLOCK - 1) / SAS_TOTALS_BLOCK, runs1 = (n + SAS_TOTALS_RUN - 1) / SAS_TOTALS_RUN;
+    const int64_t runs2 = (runs1 + SAS_TOTALS_RUN - 1) / SAS_TOTALS_RUN;
+    SHIPCHK(ctx, ctx->totals_ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
+    SHIPCHK(ctx, ctx->totals_part.alloc((size_t)n_items * SAS_TOTALS_NSTAT * (size_t)ntiles * sizeof(double)));
+    if (wmax && runs1 > 1) {
+        SHIPCHK(ctx, ctx->totals_lvl[0].alloc((size_t)runs1 * (size_t)wmax * sizeof(double)));
+        SHIPCHK(ctx, ctx->totals_lvl[1].alloc((size_t)runs2 * (size_t)wmax * sizeof(double)));
+    }
+    if (mask) {
+        SHIPCHK(ctx, ctx->totals_mask.alloc((size_t)n));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->totals_mask, mask, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    P.n_items = n_items;
+    P.ntiles = (int)ntiles;
+    P.n = n;
+    P.mask = ctx->totals_mask.get();
+    P.part = ctx->totals_part.get();
+    SHIPCHK(ctx, ctx->totals_cfg.alloc(sizeof(SasTotalsDev)));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->totals_cfg, &P, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and a local)
+    ctx->totals_host = P;
+    std::copy(width, width + RH_SAS_TOTALS_MAX_ITEMS, ctx->totals_width);
+    std::copy(srcs, srcs + RH_SAS_TOTALS_MAX_ITEMS, ctx->totals_src);
+    ctx->totals_tags = std::move(tags);
+    ctx->totals_cap = capacity;
+    ctx->totals_row_elems = row_elems;
+    ctx->totals_ncells = ncells;
+    ctx->totals_items = n_items;
+    return RH_OK;
+}
+
+static int sas_totals_on(rh_sas_ctx *ctx, const char *who) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->totals_items) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_totals_configure has not been called");
+    return RH_OK;
+}
+
+int rh_sas_totals_record(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
+    if (int rc = sas_totals_on(ctx, "rh_sas_totals_record")) return rc;
+    return sas_totals_enqueue(ctx, tag, day);
+}
+
+int rh_sas_totals_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
+    if (int rc = sas_totals_on(ctx, "rh_sas_totals_count")) return rc;
+    if (!rows_total || !ncells) return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_count: null pointer");
+    *rows_total = ctx->totals_rows;
+    *ncells = ctx->totals_ncells;
+    return RH_OK;
+}
+
+int rh_sas_totals_row_elems(const rh_sas_ctx *ctx, int64_t *elems) {
+    if (int rc = sas_totals_on(const_cast<rh_sas_ctx *>(ctx), "rh_sas_totals_row_elems")) return rc;
+    if (!elems) return RH_ERR_ARG;
+    *elems = ctx->totals_row_elems;
+    return RH_OK;
+}
+
+int rh_sas_totals_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes) {
+    if (int rc = sas_totals_on(ctx, "rh_sas_totals_read")) return rc;
+    const int64_t total = ctx->totals_rows, cap = ctx->totals_cap;
+    const size_t nv = (size_t)ctx->totals_row_elems;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                          " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - cap)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
+                                          " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " +
+                                          std::to_string(total) + " rows)");
+    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_read: size mismatch (n_rows x row_elems float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
+        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->totals_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        std::copy(ctx->totals_tags.get() + slot, ctx->totals_tags.get() + slot + m, tags + done);
         done += m;
     }
     return rh_sas_sync(ctx);

@@ -351,6 +351,9 @@ class RogerState:
         from .totals import AreaTotals
 
         self.totals = AreaTotals()       # per-step sum, min and max over a masked area (roger_amd/totals.py)
+        from .sas_totals import TransportTotals
+
+        self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None

@@ -108,7 +108,8 @@ def initialize(state):
     settings = state.settings
     if settings.enable_offline_transport:
         raise NotImplementedError("totals: the offline transport model steps by the day and its output is read after every step "
-                                  "(state.diagnostics); the recorder belongs to the SVAT / oneD step")
+                                  "(state.diagnostics); the recorder belongs to the SVAT / oneD step -- the transport model's own totals are "
+                                  "state.transport_totals (roger_amd/sas_totals.py)")
     if len(t.output_variables) > MAX_VARIABLES:
         raise ValueError(f"totals: {len(t.output_variables)} variables (at most {MAX_VARIABLES})")
     check_request("totals", (), len(t.output_variables), t.capacity, settings)   # (no cells to check: the capacity)
