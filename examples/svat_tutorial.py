@@ -13,6 +13,8 @@ import argparse
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from roger_amd import roger_routine  # noqa: E402
@@ -27,7 +29,7 @@ CONFIG = dict(LU_ID=8, SEALING=0, Z_SOIL=900, DMPV=0, LMPV=500, THETA_AC=0.1, TH
               OUTPUT_COLLECT=["S_rz", "S_ss", "S_pwp_rz", "S_pwp_ss", "S_sat_rz", "S_sat_ss", "theta", "S_snow", "S"])
 
 
-def make_model(input_dir, ndays, out_dir):
+def make_model(input_dir, ndays, out_dir, zones=0):
     forcing = forcing_from_txt(input_dir, ndays=ndays)
 
     class Tutorial(SVATSetup):
@@ -68,6 +70,12 @@ def make_model(input_dir, ndays, out_dir):
                 d[kind].output_frequency = CONFIG["OUTPUT_FREQUENCY"]
                 d[kind].sampling_frequency = 1
                 d[kind].base_output_path = out_dir
+            if zones:   # zonal totals of N stripes along x after every step -> SVAT.zonal_totals.nc
+                nx, ny = state.settings.nx, state.settings.ny
+                state.zonal_totals.zones = np.repeat(1 + np.arange(nx) * zones // nx, ny).reshape(nx, ny)
+                state.zonal_totals.output_variables = ["prec", "aet", "q_ss", "S_rz", "S_ss"]
+                state.zonal_totals.base_output_path = out_dir
+                state.zonal_totals.capacity = 64
 
     return Tutorial(forcing=forcing, nx=1, ny=1, ndays=ndays)
 
@@ -77,9 +85,10 @@ def main(argv=None):
     ap.add_argument("input_dir", help="directory with PREC.txt, TA.txt, PET.txt")
     ap.add_argument("--days", type=int, default=365)
     ap.add_argument("--out", default="output")
+    ap.add_argument("--zones", type=int, default=0, help="also write zonal totals of N stripes along x (SVAT.zonal_totals.nc)")
     args = ap.parse_args(argv)
     os.makedirs(args.out, exist_ok=True)
-    model = make_model(args.input_dir, args.days, args.out)
+    model = make_model(args.input_dir, args.days, args.out, args.zones)
     model.setup()
     vs = model.state.variables
     end = args.days * 86400

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 9   /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h) */
+#define RH_ABI_VERSION 10  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -429,6 +429,34 @@ int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr,
 int rh_totals_configure(rh_ctx *ctx, const unsigned char *mask, const int *planes, int n_planes, int64_t capacity);
 int rh_totals_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells);
 int rh_totals_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
+
+/* ---- zonal totals: per-step sum, minimum and maximum for every zone of a zone map, recorded on the device -----------
+ * What rh_totals_* records over one masked area, for every zone of a map -- sub-catchments, land uses, soil classes -- in ONE pass over
+ * the planes.  After rh_zonal_configure every step, wherever the totals' kernels are launched, is followed by two more launches: a
+ * workgroup per 256 columns reduces every configured plane over its columns of every zone it holds, a workgroup per zone combines
+ * the partials and writes the zone's part of the next row of a ring; the row's header is {itt, time at the END of the step, dt_secs}.
+ * A launch behind the time limit (rh_set_time_limit) records nothing.
+ * The ORDER is that of rh_totals_* applied to the mask zone == z (1. - 3. above), except that accumulator t takes only the partials of
+ * the tiles that hold a column of z -- which changes no bit: the partial of a tile without one is the identity, the accumulator of
+ * the sum starts at +0.0 and is never -0.0, those of the minimum and maximum are never NaN (roger_amd/csrc/rh_zonal.h).  The sums of
+ * row z are bit for bit the sums rh_totals_* records with the mask zone == z.
+ *   zone[n]:          int32 per interior column of the rank's block (C order over (x, y), as rh_upload): -1 outside every zone, else
+ *                     0 ... n_zones - 1.  Copied.  A zone without a column on this rank is allowed: its part of a row holds the
+ *                     identities (+0.0, +inf, -inf) and its ncells is 0.
+ *   n_zones:          1 ... RH_ZONAL_MAX_ZONES
+ *   planes[n_planes]: as for rh_totals_configure; the four configure calls may come in any order.
+ *   capacity >= 1:    rows resident on the device, row r at r mod capacity: (capacity, n_zones, n_planes, 3) float64 -- sum, min, max
+ * n_planes == 0 releases the buffers and stops the launches.  Every other call starts a new series (row 0).  RH_ERR_ARG
+ * (rh_last_error names the value): an int32 plane or one the context does not hold, more than 32 planes, n_zones out of range, a
+ * zone id out of range, a map with no column in any zone, capacity < 1.
+ *   rh_zonal_count   rows recorded since rh_zonal_configure, and ncells[n_zones]: the columns of every zone
+ *   rh_zonal_read    rows [first_row, first_row + n_rows) that are still resident: hdr (n_rows, 3) int64, values (n_rows, n_zones,
+ *                    n_planes, 3) float64.  RH_ERR_ARG for rows that have been overwritten or not recorded yet.
+ * Both synchronise; RH_ERR_STATE before rh_zonal_configure (or after it released the buffers). */
+#define RH_ZONAL_MAX_ZONES 1024
+int rh_zonal_configure(rh_ctx *ctx, const int32_t *zone, int n_zones, const int *planes, int n_planes, int64_t capacity);
+int rh_zonal_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells);
+int rh_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

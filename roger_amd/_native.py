@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 9   # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 10  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -161,6 +161,9 @@ def load():
     lib.rh_totals_configure.argtypes = [vp, vp, vp, i32, i64]
     lib.rh_totals_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.rh_totals_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_zonal_configure.argtypes = [vp, vp, i32, vp, i32, i64]
+    lib.rh_zonal_count.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    lib.rh_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -519,6 +522,7 @@ DECLARED_SYMBOLS = (
     "rh_surface_routing", "rh_subsurface_routing", "rh_step_routed", "rh_planes_held", "rh_route_out", "rh_route_in", "rh_route_get_edges", "rh_route_get_static_edges", "rh_route_set_halo",
     "rh_points_configure", "rh_points_count", "rh_points_read",
     "rh_totals_configure", "rh_totals_count", "rh_totals_read",
+    "rh_zonal_configure", "rh_zonal_count", "rh_zonal_read",
 )
 
 
@@ -841,6 +845,40 @@ class Context:
         values = np.empty((n, getattr(self, "_totals_nv", 0), 3), dtype=np.float64)
         self._check(self._lib.rh_totals_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
                                              values.nbytes), "rh_totals_read")
+        return hdr, values
+
+    # -- zonal totals (rh_zonal_*) ---------------------------------------------------------------
+    def zonal_configure(self, names, zones=None, n_zones=0, capacity=4096):
+        """Record the sum, minimum and maximum of `names` (float64 planes) for every zone of `zones` (an int per interior column of this
+        context's block, C order: -1 outside, else 0 ... n_zones - 1) after every step, in a ring of `capacity` rows on the device.  No
+        names: release the buffers and stop recording."""
+        names = list(names)
+        ids = (C.c_int * max(1, len(names)))(*[self.index[n] for n in names])
+        z = None
+        if names:
+            z = np.ascontiguousarray(np.asarray(zones).reshape(-1), dtype=np.int32)
+            if z.size != self.n:
+                raise ValueError(f"zonal_configure: the zone map has {z.size} values, the context {self.n} columns")
+        self._check(self._lib.rh_zonal_configure(self._h, None if z is None else z.ctypes.data_as(C.c_void_p), int(n_zones), ids, len(names),
+                                                 int(capacity)), "rh_zonal_configure")
+        self._zonal_shape = (int(n_zones) if names else 0, len(names))   # (a refused configuration leaves the previous one)
+
+    def zonal_count(self):
+        """(rows recorded since zonal_configure, columns of every zone: int64 (n_zones,))."""
+        n = C.c_int64()
+        cells = np.zeros(max(1, getattr(self, "_zonal_shape", (0, 0))[0]), dtype=np.int64)
+        self._check(self._lib.rh_zonal_count(self._h, C.byref(n), cells.ctypes.data_as(C.c_void_p)), "rh_zonal_count")
+        return n.value, cells[: self._zonal_shape[0]]
+
+    def zonal_read(self, first, n):
+        """Rows [first, first + n) of the ring: (hdr int64 (n, 3): itt, time at the end of the step, dt_secs; values float64
+        (n, Z, V, 3): sum, min, max)."""
+        n = int(n)
+        nz, nv = getattr(self, "_zonal_shape", (0, 0))
+        hdr = np.empty((n, 3), dtype=np.int64)
+        values = np.empty((n, nz, nv, 3), dtype=np.float64)
+        self._check(self._lib.rh_zonal_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                            values.nbytes), "rh_zonal_read")
         return hdr, values
 
     def pure_output_planes(self):

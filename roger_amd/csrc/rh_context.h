@@ -119,6 +119,14 @@ struct rh_ctx {
     int totals_nplanes = 0;          // 0: not configured, no k_totals_* launch
     int64_t totals_cap = 0, totals_ncells = 0;   // rows resident; columns inside the mask
     int totals_planes[RH_POINTS_MAX_PLANES] = {};
+    // zonal totals (rh_zonal_configure): the ring and its headers, the (tile, zone) partials, the zone map and the index over it
+    DevBuf<double> zonal_buf, zonal_part_buf;
+    DevBuf<long long> zonal_hdr_buf;
+    DevBuf<int> zonal_index_buf;     // zone[n], tile_ptr[ntiles + 1], tile_zone[S], acc_ptr[Z * 256 + 1], acc_slot[S] in one allocation
+    int zonal_nplanes = 0, zonal_nzones = 0;   // 0: not configured, no k_zonal_* launch
+    int64_t zonal_cap = 0;
+    int zonal_planes[RH_POINTS_MAX_PLANES] = {};
+    std::vector<int64_t> zonal_ncells;         // columns of every zone on this rank
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

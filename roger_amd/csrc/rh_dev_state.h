@@ -134,6 +134,19 @@ struct DevState {
     long long totals_rows, totals_cap;
     int totals_nplanes, totals_ntiles;
     int totals_planes[RH_POINTS_MAX_PLANES];
+
+    // zonal totals (rh_zonal_configure; k_zonal_tiles, k_zonal_finish in rh_zonal.h): a ring of zonal_cap rows, row r at r mod zonal_cap --
+    // zonal (row, zone, plane, {sum, min, max}) float64 and zonal_hdr as points_hdr.  zonal_zone: the zone of every column (-1: outside).
+    // The index rh_zonal_configure builds once: tile b holds the zones zonal_tile_zone[zonal_tile_ptr[b] ... zonal_tile_ptr[b + 1]),
+    // ascending; that position s is the (tile, zone) pair's SLOT, its partials are zonal_part [slot][plane][stat].  Accumulator t of zone
+    // z takes the slots zonal_acc_slot[zonal_acc_ptr[z * 256 + t] ... zonal_acc_ptr[z * 256 + t + 1]), in increasing tile order.
+    double *zonal;
+    long long *zonal_hdr;
+    double *zonal_part;
+    const int *zonal_zone, *zonal_tile_ptr, *zonal_tile_zone, *zonal_acc_ptr, *zonal_acc_slot;
+    long long zonal_rows, zonal_cap;
+    int zonal_nplanes, zonal_nzones;
+    int zonal_planes[RH_POINTS_MAX_PLANES];
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

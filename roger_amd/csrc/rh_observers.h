@@ -1,8 +1,9 @@
 // rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
-// (rh_points_*) and the catchment totals (rh_totals_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
+// (rh_points_*), the catchment totals (rh_totals_*) and the zonal totals (rh_zonal_*).  Part of the one translation unit roger_hip.hip,
+// behind rh_context.h.
 #pragma once
-// The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure): what the fused kernel must leave in memory
-// after every step, from the UNION of the accumulators', the points' and the totals' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
+// The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure): what the fused kernel must
+// leave in memory after every step, from the UNION of the accumulators', the points', the totals' and the zonal totals' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
 // five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in DevState::keep: the KEEP
 // variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
 static int observers_changed(rh_ctx *ctx) {
@@ -23,6 +24,7 @@ static int observers_changed(rh_ctx *ctx) {
     add(ctx->diag_planes, ctx->diag_n);
     if (ctx->points_ncells) add(ctx->points_planes, ctx->points_nplanes);
     add(ctx->totals_planes, ctx->totals_nplanes);
+    add(ctx->zonal_planes, ctx->zonal_nplanes);
     const int any = reads_sparse ? 1 : 0;
     HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
     HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
@@ -35,8 +37,9 @@ static int observers_changed(rh_ctx *ctx) {
 
 // The observers behind the step that was just enqueued: the accumulators over all columns (grid: the fused launch's own, which has one
 // workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values),
-// then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them.  after_fused: rh_control.h, k_diag.
-static bool has_observers(const rh_ctx *ctx) { return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes; }
+// then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them -- then the zonal totals' row: a
+// workgroup per RH_BLOCK columns and one per zone (rh_zonal.h).  after_fused: rh_control.h, k_diag.
+static bool has_observers(const rh_ctx *ctx) { return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes; }
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
@@ -44,6 +47,10 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     if (ctx->totals_nplanes) {
         hipLaunchKernelGGL(k_totals_tiles, dim3(grid_for(ctx->n)), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
         hipLaunchKernelGGL(k_totals_finish, dim3(1), block, 0, ctx->stream, ctx->dev, after_fused);
+    }
+    if (ctx->zonal_nplanes) {
+        hipLaunchKernelGGL(k_zonal_tiles, dim3(grid_for(ctx->n)), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_zonal_finish, dim3(ctx->zonal_nzones), block, 0, ctx->stream, ctx->dev, after_fused);
     }
     CHECK_LAUNCH(ctx);
     return RH_OK;
@@ -351,6 +358,162 @@ int rh_totals_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr,
         HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->totals_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
                                    hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->totals_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        done += m;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+
+// ---- zonal totals (include/roger_hip.h; the kernels and the order: rh_zonal.h) ----
+// The index over a zone map: per tile of RH_BLOCK columns the ascending zones present -- the position of a (tile, zone) pair in that list
+// is its slot -- and per (zone, accumulator) the slots in increasing tile order.  buf: zone[n], tile_ptr[ntiles + 1], tile_zone[S],
+// acc_ptr[Z * RH_BLOCK + 1], acc_slot[S]; returns S.
+static int64_t zonal_index(const int32_t *zone, int64_t n, int n_zones, std::vector<int> &buf, int64_t off[5]) {
+    const int64_t ntiles = (int64_t)grid_for(n);
+    std::vector<int> tile_ptr(ntiles + 1, 0), tile_zone;
+    std::vector<int> present;
+    for (int64_t b = 0; b < ntiles; ++b) {
+        present.clear();
+        for (int64_t i = b * RH_BLOCK; i < std::min<int64_t>(n, (b + 1) * RH_BLOCK); ++i)
+            if (zone[i] >= 0) present.push_back(zone[i]);
+        std::sort(present.begin(), present.end());
+        present.erase(std::unique(present.begin(), present.end()), present.end());
+        tile_zone.insert(tile_zone.end(), present.begin(), present.end());
+        tile_ptr[b + 1] = (int)tile_zone.size();
+    }
+    const int64_t S = (int64_t)tile_zone.size();
+    std::vector<int> acc_ptr((size_t)n_zones * RH_BLOCK + 1, 0), acc_slot(S);
+    for (int64_t b = 0; b < ntiles; ++b)
+        for (int s = tile_ptr[b]; s < tile_ptr[b + 1]; ++s) ++acc_ptr[(size_t)tile_zone[s] * RH_BLOCK + b % RH_BLOCK + 1];
+    for (size_t k = 1; k < acc_ptr.size(); ++k) acc_ptr[k] += acc_ptr[k - 1];
+    std::vector<int> fill(acc_ptr.begin(), acc_ptr.end() - 1);
+    for (int64_t b = 0; b < ntiles; ++b)   // increasing tile order within every (zone, accumulator) list
+        for (int s = tile_ptr[b]; s < tile_ptr[b + 1]; ++s) acc_slot[fill[(size_t)tile_zone[s] * RH_BLOCK + b % RH_BLOCK]++] = s;
+    buf.clear();
+    off[0] = 0;
+    buf.insert(buf.end(), zone, zone + n);
+    off[1] = (int64_t)buf.size();
+    buf.insert(buf.end(), tile_ptr.begin(), tile_ptr.end());
+    off[2] = (int64_t)buf.size();
+    buf.insert(buf.end(), tile_zone.begin(), tile_zone.end());
+    off[3] = (int64_t)buf.size();
+    buf.insert(buf.end(), acc_ptr.begin(), acc_ptr.end());
+    off[4] = (int64_t)buf.size();
+    buf.insert(buf.end(), acc_slot.begin(), acc_slot.end());
+    return S;
+}
+int rh_zonal_configure(rh_ctx *ctx, const int32_t *zone, int n_zones, const int *planes, int n_planes, int64_t capacity) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_planes < 0 || n_planes > RH_POINTS_MAX_PLANES)
+        return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: n_planes = " + std::to_string(n_planes) + " (0 ... " + std::to_string(RH_POINTS_MAX_PLANES) + ")");
+    const bool off = n_planes == 0;
+    int plane_list[RH_POINTS_MAX_PLANES] = {};
+    std::vector<int64_t> ncells;
+    std::vector<int> index;
+    int64_t at[5] = {}, S = 0;
+    if (!off) {
+        if (!planes || !zone) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: null pointer");
+        if (n_zones < 1 || n_zones > RH_ZONAL_MAX_ZONES)
+            return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_ZONAL_MAX_ZONES) + ")");
+        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
+        if (ctx->n >= (int64_t)1 << 31) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: " + std::to_string(ctx->n) + " columns (the index holds int32 slots)");
+        for (int j = 0; j < n_planes; ++j) {
+            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+                return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
+            if (PLANE_IS_INT[planes[j]])
+                return fail(ctx, RH_ERR_ARG, std::string("rh_zonal_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
+            plane_list[j] = planes[j];
+        }
+        ncells.assign((size_t)n_zones, 0);
+        int64_t inside = 0;
+        for (int64_t i = 0; i < ctx->n; ++i) {
+            if (zone[i] < -1 || zone[i] >= n_zones)
+                return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: zone id " + std::to_string(zone[i]) + " of column " + std::to_string(i) +
+                                             " (-1: outside, else 0 ... " + std::to_string(n_zones - 1) + ")");
+            if (zone[i] >= 0) {
+                ++ncells[(size_t)zone[i]];
+                ++inside;
+            }
+        }
+        if (!inside) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: the map holds no column in any zone (0 of " + std::to_string(ctx->n) + " columns)");
+        S = zonal_index(zone, ctx->n, n_zones, index, at);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    HIPCHK(ctx, ctx->zonal_buf.release());
+    HIPCHK(ctx, ctx->zonal_hdr_buf.release());
+    HIPCHK(ctx, ctx->zonal_part_buf.release());
+    HIPCHK(ctx, ctx->zonal_index_buf.release());
+    ctx->zonal_nplanes = ctx->zonal_nzones = 0;
+    ctx->zonal_cap = 0;
+    ctx->zonal_ncells.clear();
+    if (!off) {
+        HIPCHK(ctx, ctx->zonal_buf.alloc((size_t)capacity * n_zones * n_planes * 3 * sizeof(double)));
+        HIPCHK(ctx, ctx->zonal_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        HIPCHK(ctx, ctx->zonal_part_buf.alloc((size_t)S * n_planes * 3 * sizeof(double)));
+        HIPCHK(ctx, ctx->zonal_index_buf.alloc(index.size() * sizeof(int)));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->zonal_index_buf, index.data(), index.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        ctx->zonal_nplanes = n_planes;
+        ctx->zonal_nzones = n_zones;
+        ctx->zonal_cap = capacity;
+        ctx->zonal_ncells = ncells;
+    }
+    std::memcpy(ctx->zonal_planes, plane_list, sizeof(plane_list));
+    const long long zero = 0, cap = (long long)ctx->zonal_cap;
+    const int *const base = ctx->zonal_index_buf;
+    const int *const part[5] = {base, base ? base + at[1] : nullptr, base ? base + at[2] : nullptr, base ? base + at[3] : nullptr,
+                                base ? base + at[4] : nullptr};
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal, *ctx->zonal_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_hdr, *ctx->zonal_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_part, *ctx->zonal_part_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_zone, part[0]));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_tile_ptr, part[1]));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_tile_zone, part[2]));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_acc_ptr, part[3]));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_acc_slot, part[4]));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_rows, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_cap, cap));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_nplanes, ctx->zonal_nplanes));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_nzones, ctx->zonal_nzones));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_planes, plane_list));
+    return observers_changed(ctx);   // synchronises: the sources above are locals
+}
+static int zonal_rows(rh_ctx *ctx, const char *who, long long *rows) {
+    if (!ctx->zonal_nplanes) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_zonal_configure has not been called");
+    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->zonal_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_zonal_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!rows_total || !ncells) return fail(ctx, RH_ERR_ARG, "rh_zonal_count: null pointer");
+    long long rows = 0;
+    if (int rc = zonal_rows(ctx, "rh_zonal_count", &rows)) return rc;
+    *rows_total = (int64_t)rows;
+    std::copy(ctx->zonal_ncells.begin(), ctx->zonal_ncells.end(), ncells);
+    return RH_OK;
+}
+int rh_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = zonal_rows(ctx, "rh_zonal_read", &total)) return rc;
+    const size_t nv = (size_t)ctx->zonal_nzones * ctx->zonal_nplanes * 3;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return fail(ctx, RH_ERR_ARG, "rh_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - ctx->zonal_cap)
+        return fail(ctx, RH_ERR_ARG, "rh_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->zonal_cap - 1) +
+                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->zonal_cap) + " of " +
+                                     std::to_string(total) + " rows)");
+    if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_zonal_read: size mismatch (n_rows x n_zones x n_planes x 3 float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % ctx->zonal_cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, ctx->zonal_cap - slot);
+        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->zonal_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->zonal_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
                                    ctx->stream));
         done += m;
     }

@@ -36,6 +36,7 @@
 
 #include "rh_dev_state.h"
 #include "rh_control.h"
+#include "rh_zonal.h"
 #include "rh_step.h"
 #include "rh_routing.h"
 

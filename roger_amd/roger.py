@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, stepping, totals
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -154,6 +154,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             diagnostics.initialize(state)
             points.initialize(state)
             totals.initialize(state)
+            zonal_totals.initialize(state)
             sas_points.initialize(state)
             sas_totals.initialize(state)
             self.set_boundary_conditions_setup(state)
@@ -211,6 +212,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             with state.timers["diagnostics"]:
                 points.drain(state)            # (rows not yet drained are drained before a restart file is written)
                 totals.drain(state)
+                zonal_totals.drain(state)
                 restart.write_restart(state)   # roger/roger.py:385-386
         with state.timers["main"]:
             with state.timers["read data"]:
@@ -256,6 +258,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             diagnostics.output(state)
         points.stepped(state)    # the points' ring is drained every `capacity` step calls
         totals.stepped(state)    # ... and the totals'
+        zonal_totals.stepped(state)
         if rs.profile_mode:
             state.backend_context.sync()
             logger.info(" Time step took {:.2f}s".format(state.timers["main"].last_time))
@@ -372,6 +375,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     n = min(n, int(state.points.capacity))   # (a round never records more rows than the points' ring holds)
                 if state.totals.active:
                     n = min(n, int(state.totals.capacity))   # (... nor than the totals')
+                if state.zonal_totals._on:
+                    n = min(n, int(state.zonal_totals.capacity))
                 self.run_device(int(n), final=False)
                 first = False
         finally:
@@ -391,7 +396,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(state._diag_active) or state.points.active or state.totals.active
+        diag = bool(state._diag_active) or state.points.active or state.totals.active or state.zonal_totals.active
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -436,6 +441,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 if not failed:
                     points.drain(self.state)
                     totals.drain(self.state)
+                    zonal_totals.drain(self.state)
                     sas_points.drain(self.state)
                     sas_totals.drain(self.state)
                 restart.write_restart(self.state, force=True)
@@ -443,6 +449,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         diagnostics.close(self.state)
         points.close(self.state)
         totals.close(self.state)
+        zonal_totals.close(self.state)
         sas_points.close(self.state)
         sas_totals.close(self.state)
 
@@ -494,8 +501,10 @@ class RogerSetup(metaclass=abc.ABCMeta):
         vs = self.state.variables
         points.check_call(self.state, nsteps)   # (before anything is enqueued)
         totals.check_call(self.state, nsteps)
+        zonal_totals.check_call(self.state, nsteps)
         points.drain(self.state)
         totals.drain(self.state)
+        zonal_totals.drain(self.state)
         vs.flush_to_device()
         ctx = self.state.backend_context
         engine = stepping.engine(self._facts())
@@ -510,5 +519,6 @@ class RogerSetup(metaclass=abc.ABCMeta):
         vs.mark_device_newer()
         points.drain(self.state, final=final)
         totals.drain(self.state, final=final)
+        zonal_totals.drain(self.state, final=final)
         if self.state._diag_active:
             diagnostics.output(self.state, final=final)

@@ -351,6 +351,9 @@ class RogerState:
         from .totals import AreaTotals
 
         self.totals = AreaTotals()       # per-step sum, min and max over a masked area (roger_amd/totals.py)
+        from .zonal_totals import ZonalTotals
+
+        self.zonal_totals = ZonalTotals()   # ... for every zone of a zone map (roger_amd/zonal_totals.py)
         from .sas_totals import TransportTotals
 
         self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
