@@ -1,7 +1,7 @@
 """Columns beyond the golden recipe (golden/make_golden.py: hetero_params), for the tests that pin rh_physics.h to the oracle where no
 golden file reaches: the water land uses (lu_id 14 / 20 / 999, whose columns the setup kernels take out of the catchment), every land use
 the look-up tables and the root-depth code know, groundwater within reach of the soil, and a depression storage.  Crops (lu_id 500-599)
-are not drawn: the tables hold no rows for them (scope).
+are not drawn here: tests/crop_columns.py builds on this module and holds them (their branches of the step need no table row).
 
 hetero_params itself stays as it is -- the goldens depend on its random sequence; what is added here is drawn from a generator of its own."""
 import os

@@ -1,7 +1,8 @@
 """The device's column code (roger_amd/csrc/rh_physics.h, compiled for the host: tests/host_physics.cpp) against the oracle, routine
 by routine, on columns the golden recipe never draws (tests/extended_columns.py): the water land uses 14 / 20 / 999 and with them columns
 outside the catchment, every land use of the look-up tables and of the root-depth code, groundwater within reach of the soil, a
-depression storage.  Crops (lu_id 500-599) are not covered.
+depression storage.  Crops (lu_id 500-599) go the same walk in tests/test_physics_host_vs_oracle_crops.py, on the columns of
+tests/crop_columns.py; crop phenology itself (enable_crop_phenology) is out of scope.
 
 Every comparison starts from the ORACLE's state: a copy of it before a routine goes through the host-compiled device routine and must
 equal the oracle's state after its own routine on every plane, at the tolerance the project states for "HIP path against the oracle"
@@ -107,10 +108,15 @@ def walk(lateral, groundwater, forcing_kind):
 
     ob.build()
     st = _start(ob, lateral, groundwater, month=4 if forcing_kind == "month_change" else None)
+    return walk_from(ob, st, _forcing(forcing_kind), lateral)
+
+
+def walk_from(ob, st, F, lateral, observer=None):
+    """walk() from the start state `st` through the forcing `F`.  observer: before(name, P) sees the oracle's planes P ahead of every
+    routine of the step, after(name, P, H, step) the oracle's planes behind it and those the host-compiled routine left (H)."""
     O = Blocks(st)
     T, host = _twin(ob, st)      # one routine at a time
     W, whole = _twin(ob, st)     # the whole core in one call
-    F = _forcing(forcing_kind)
     drv = ob.ForcingDriver(F)
     sub, err, core = (("rt_subsurface_runoff_lateral", "rt_num_error_lateral", "rt_step_core_lateral") if lateral
                       else ("rt_subsurface_runoff", "rt_num_error", "rt_step_core"))
@@ -142,8 +148,12 @@ def walk(lateral, groundwater, forcing_kind):
         ok_whole = whole.call(core, X)
         for name, oracle_routine in routines:
             T.take(O)
+            if observer is not None:
+                observer.before(name, P)
             ok_o = oracle_routine()
             ok_h = host.call(name, X)
+            if observer is not None:
+                observer.after(name, P, T.st.planes, step)
             msg = T.equals(O, f"{name}, step {step} (dt {st.scal.dt_secs} s)")
             if msg is None and name == err and bool(ok_h) != bool(ok_o):
                 msg = f"{name}, step {step}: sanity bit {ok_h}, the oracle's {int(ok_o)}"

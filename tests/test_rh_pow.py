@@ -55,6 +55,23 @@ def _arguments(n, seed=5):
     return x, y
 
 
+# the anoxia ratio S_lp_rz / S_ac_rz of rt_evapotranspiration at its edges (an empty and a full pore space, the largest double below 1,
+# the smallest positive double), raised to 1.5
+ANOXIA_EDGES = np.array([0.0, 1.0, np.nextafter(1.0, 0.0), 2.0 ** -1074])
+
+
+def test_anoxia_ratio_edges_with_exponent_one_and_a_half(host):
+    import math
+
+    got, short = host(ANOXIA_EDGES, np.full(ANOXIA_EDGES.size, 1.5))
+    ref = np.array([math.pow(a, 1.5) for a in ANOXIA_EDGES])
+    assert got[0] == 0.0 and not np.signbit(got[0]) and got[1] == 1.0 and got[3] == 0.0
+    assert (_ulps(got[:3], ref[:3]) <= 1.0)[[1, 2]].all() and 0.0 < got[2] < 1.0
+    np.testing.assert_array_equal(got[[0, 1, 3]], ref[[0, 1, 3]])
+    assert short[1] and short[2]
+    assert ((1 - got >= 0) & (1 - got <= 1)).all()       # transp_coeff = 1 - ratio ** 1.5 stays a coefficient
+
+
 def _ulps(got, ref):
     with np.errstate(all="ignore"):
         return np.abs(got - ref) / np.spacing(np.abs(ref))
@@ -107,12 +124,14 @@ def test_device_has_the_hosts_bits(host):
     from roger_amd import _native as N
 
     x, y = _arguments(2_000_000, seed=11)
-    x = np.concatenate([x, [-8.0, 0.0, -0.0, np.inf, np.nan, 1e-320, 2.0, 4.0, 0.25]])
-    y = np.concatenate([y, [1 / 3, 1 / 3, 3.0, 0.5, 1.0, 0.5, np.nan, 0.5, -0.5]])
+    x = np.concatenate([x, [-8.0, 0.0, -0.0, np.inf, np.nan, 1e-320, 2.0, 4.0, 0.25], ANOXIA_EDGES])
+    y = np.concatenate([y, [1 / 3, 1 / 3, 3.0, 0.5, 1.0, 0.5, np.nan, 0.5, -0.5], np.full(ANOXIA_EDGES.size, 1.5)])
     dev = N.selftest_pow(x, y)
     ref, short = host(x, y)
     same = (dev == ref) | (np.isnan(dev) & np.isnan(ref))
     assert same[short].all(), "the short path differs between host and device"
+    edges = slice(x.size - ANOXIA_EDGES.size, x.size)
+    assert same[edges].all(), (dev[edges], ref[edges])      # an exact 0 and 1 among them: transp_coeff 1 and 0
     # outside the short path both call their library's pow: equal up to the libraries' last bit
     with np.errstate(all="ignore"):
         assert (same | (_ulps(dev, ref) <= 1))[~short].all()
