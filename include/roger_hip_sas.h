@@ -242,6 +242,52 @@ int rh_sas_totals_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells);
 int rh_sas_totals_row_elems(const rh_sas_ctx *ctx, int64_t *elems);
 int rh_sas_totals_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes);
 
+/* ---- zonal totals: the catchment totals for EVERY zone of a zone map, in one pass ------------------------------------------------------
+ * Sub-catchments (one gauge and one isotope series each), land uses, soil classes: after rh_sas_zonal_configure, rh_sas_step and every
+ * day of rh_sas_run_days are followed by the zonal launches on the context's stream (behind the points' and the totals' launches where
+ * those are on; kernels: roger_amd/csrc/rh_sas_zonal.h) that reduce the configured items over the cells of every zone into the next row
+ * of a ring on the device, loading each row of an age-resolved array once whatever the number of zones.  rh_sas_stages never records; a
+ * context without the recorder enqueues exactly what it enqueued before these entry points existed.  Points, totals and zonal totals
+ * work side by side, configured in any order.
+ *   zone     [n_cells] int32: -1 = outside every zone, else 0 ... n_zones - 1; 1 <= n_zones <= RH_SAS_ZONAL_MAX_ZONES
+ *   items, capacity   as rh_sas_totals_configure; capacity x row_elems x 8 at most 2 GiB
+ * n_items == 0 releases everything and stops the launches.  Every other call starts a new series (row 0).  The refusals of
+ * rh_sas_totals_configure, and RH_ERR_ARG for n_zones outside its range, a zone id outside -1 ... n_zones - 1, a map with no cell in any
+ * zone, a level-1 buffer (below) above 2 GiB -- the message names the slot count.  A refused call leaves the previous configuration in
+ * place.
+ *
+ * Row layout (rh_sas_zonal_row_elems float64): zone-major; a zone's part holds the items' blocks as a row of rh_sas_totals_* does.  Block
+ * (z, j) is, bit for bit, the block that rh_sas_totals_* records for item j with mask = (zone == z): the counting rules, the NaN rules,
+ * fl(v w) rounded before it is added, day < 0, and [+0.0, 0, +0.0, +inf, -inf] (sums +0.0) for a zone without a counted cell are the ones
+ * stated above.  Per row one int64 tag, kept on the host.
+ *
+ * The ORDER.  A (tile of 256 cells, zone) pair that exists is a SLOT; the pairs that do not exist are left out, which changes no bit.
+ *   width 1: each slot gets the wavefront trees and (w0 op w1) op (w2 op w3) over its tile, the cells of other zones holding the identity;
+ *       a zone has 256 accumulators, accumulator t takes the slots of the tiles with tile mod 256 == t in increasing tile order; the 256
+ *       accumulators go through the same two levels.  The dense rule would also take the partials of the pairs that do not exist: trees of
+ *       identities, and x op identity == x in every bit for an accumulator that starts at the identity (a sum that starts at +0.0 is never
+ *       -0.0, a minimum or maximum that starts at an infinity is never NaN).
+ *   width W > 1, per age class: a run of the age rule is a tile, so the slots are the same.  Level 1: the cells of z in the run, left to
+ *       right from +0.0.  The dense rule then sums 256 consecutive partials left to right, then 256 of those, ...; a run or a group of
+ *       runs without a cell of z has the partial +0.0, and adding +0.0 to a running sum that started at +0.0 (never -0.0), or passing a
+ *       value through an extra level +0.0 + x, changes no bit.  So the zone's slots are walked once in increasing run order with nested
+ *       accumulators: a2 takes the slot partials, is added into a3 and cleared where run / 256 changes, a3 into a4 where run / 65536
+ *       changes; both are flushed at the end.
+ * Scratch on the device, sized at configure (S slots): S x items x 5 float64 for the width-1 partials; ONE level-1 buffer of S x Wmax
+ * float64, shared by the age items, which are reduced one after another; the index over the map (about 2 n_cells + 5 S + 257 n_zones
+ * int32).  No floating-point atomics, no counter on the device.
+ *   rh_sas_zonal_record     one row now, behind what the stream holds, with the caller's tag; day < 0: no daily row
+ *   rh_sas_zonal_count      rows recorded since rh_sas_zonal_configure (no synchronisation) and the cells of every zone, ncells[n_zones]
+ *   rh_sas_zonal_row_elems  float64 per row
+ *   rh_sas_zonal_read       as rh_sas_totals_read
+ * All four: RH_ERR_STATE before rh_sas_zonal_configure (or after it released everything). */
+#define RH_SAS_ZONAL_MAX_ZONES 1024
+int rh_sas_zonal_configure(rh_sas_ctx *ctx, const int32_t *zone, int n_zones, const rh_sas_totals_item *items, int n_items, int64_t capacity);
+int rh_sas_zonal_record(rh_sas_ctx *ctx, int64_t tag, int64_t day);
+int rh_sas_zonal_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells);
+int rh_sas_zonal_row_elems(const rh_sas_ctx *ctx, int64_t *elems);
+int rh_sas_zonal_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

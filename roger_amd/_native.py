@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 10  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 11  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -246,6 +246,11 @@ def _declare_sas(lib):
     lib.rh_sas_totals_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.rh_sas_totals_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.rh_sas_totals_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_sas_zonal_configure.argtypes = [vp, vp, i32, vp, i32, i64]
+    lib.rh_sas_zonal_record.argtypes = [vp, i64, i64]
+    lib.rh_sas_zonal_count.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    lib.rh_sas_zonal_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_sas_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
 
 
 SAS_DECLARED_SYMBOLS = (
@@ -255,6 +260,7 @@ SAS_DECLARED_SYMBOLS = (
     "rh_sas_step", "rh_sas_run_days", "rh_sas_enable_timing", "rh_sas_timing_summary", "rh_sas_selftest_pow", "rh_sas_selftest_div",
     "rh_sas_points_configure", "rh_sas_points_record", "rh_sas_points_count", "rh_sas_points_row_elems", "rh_sas_points_read",
     "rh_sas_totals_configure", "rh_sas_totals_record", "rh_sas_totals_count", "rh_sas_totals_row_elems", "rh_sas_totals_read",
+    "rh_sas_zonal_configure", "rh_sas_zonal_record", "rh_sas_zonal_count", "rh_sas_zonal_row_elems", "rh_sas_zonal_read",
 )
 
 # stage bits of rh_sas_stages (include/roger_hip_sas.h)
@@ -471,6 +477,58 @@ class SasContext:
                 off += 5
             else:
                 d["sum"] = values[:, off + 2:off + 2 + w].copy()
+                off += 2 + w
+            out[key] = d
+        return tags, out
+
+    # -- zonal totals (rh_sas_zonal_*) ------------------------------------------------------------
+    def zonal_configure(self, items, zones=None, n_zones=0, capacity=4096):
+        """Reduce `items` (as totals_configure) over the cells of every zone of `zones` -- an index per cell, -1: outside, else
+        0 ... n_zones - 1 -- after every day into a ring of `capacity` rows; no items switch the recorder off."""
+        items = [(it, None) if isinstance(it, str) else (it[0], it[1]) for it in items]
+        flat = np.array([[self.index(v), -1 if w is None else self.index(w)] for v, w in items], dtype=np.int32).reshape(-1, 2)
+        z = None
+        if zones is not None:
+            z = np.ascontiguousarray(np.asarray(zones).reshape(-1), dtype=np.int32)
+            if z.size != self.n:
+                raise ValueError(f"zonal_configure: the zone map has {z.size} cells, the context {self.n}")
+        self._check(self._lib.rh_sas_zonal_configure(self._h, None if z is None else z.ctypes.data_as(C.c_void_p), int(n_zones),
+                                                     flat.ctypes.data_as(C.c_void_p), len(items), int(capacity)), "rh_sas_zonal_configure")
+        # (a refused configuration leaves the previous one)
+        self._zonal_items = [(totals_item_name(v, w), 1 if v in DAILY_INPUTS else int(np.prod(self.shape(v)[1:], dtype=np.int64)))
+                             for v, w in items]
+        self._zonal_nzones = int(n_zones) if items else 0
+
+    def zonal_record(self, tag=0, day=-1):
+        """One row now; day < 0: no daily row (as totals_record)."""
+        self._check(self._lib.rh_sas_zonal_record(self._h, int(tag), int(day)), "rh_sas_zonal_record")
+
+    def zonal_count(self):
+        """(rows recorded since zonal_configure, cells of every zone: int64 (n_zones,))."""
+        rows = C.c_int64()
+        nz = getattr(self, "_zonal_nzones", 0)
+        cells = np.zeros(max(1, nz), dtype=np.int64)
+        self._check(self._lib.rh_sas_zonal_count(self._h, C.byref(rows), cells.ctypes.data_as(C.c_void_p)), "rh_sas_zonal_count")
+        return rows.value, cells[:nz]
+
+    def zonal_read(self, first, n):
+        """(tags (n,) int64, {item: {"wsum", "count", "sum"[, "min", "max"]}}) of the rows [first, first + n) that are still resident;
+        the statistics are (n, Z) float64, "sum" of an age item (n, Z, width)."""
+        n = int(n)
+        elems = C.c_int64()
+        self._check(self._lib.rh_sas_zonal_row_elems(self._h, C.byref(elems)), "rh_sas_zonal_row_elems")
+        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
+        self._check(self._lib.rh_sas_zonal_read(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                                values.nbytes), "rh_sas_zonal_read")
+        values = values.reshape(n, self._zonal_nzones, elems.value // self._zonal_nzones)
+        out, off = {}, 0
+        for key, w in self._zonal_items:
+            d = {"wsum": values[:, :, off].copy(), "count": values[:, :, off + 1].copy()}
+            if w == 1:
+                d.update(sum=values[:, :, off + 2].copy(), min=values[:, :, off + 3].copy(), max=values[:, :, off + 4].copy())
+                off += 5
+            else:
+                d["sum"] = values[:, :, off + 2:off + 2 + w].copy()
                 off += 2 + w
             out[key] = d
         return tags, out

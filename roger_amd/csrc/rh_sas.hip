@@ -32,6 +32,7 @@
 #include "rh_sas_dev.h"
 #include "rh_sas_points.h"
 #include "rh_sas_totals.h"
+#include "rh_sas_zonal.h"
 
 #include <algorithm>
 #include <memory>
@@ -101,6 +102,20 @@ struct rh_sas_ctx {
     int totals_width[RH_SAS_TOTALS_MAX_ITEMS] = {};
     const double *totals_src[RH_SAS_TOTALS_MAX_ITEMS] = {};   // the age items' arrays
     int64_t totals_cap = 0, totals_row_elems = 0, totals_rows = 0, totals_ncells = 0;
+    // zonal totals (rh_sas_zonal_configure): the ring and its tags as for the totals; the slots' width-1 partials, the ONE level-1 buffer
+    // of the age rule, the index over the zone map (rh_sas_zonal.h) and where its parts start
+    DevBuf<double> zonal_ring, zonal_part, zonal_lvl;
+    DevBuf<SasZonalDev> zonal_cfg;
+    DevBuf<int> zonal_index;
+    std::unique_ptr<int64_t[]> zonal_tags;
+    SasZonalDev zonal_host = {};
+    int zonal_items = 0;             // 0: not configured, no launches
+    int zonal_nzones = 0;
+    int zonal_width[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    const double *zonal_src[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    int64_t zonal_at[SZ_PARTS] = {};
+    int64_t zonal_cap = 0, zonal_row_elems = 0, zonal_rows = 0, zonal_ntiles = 0;
+    std::vector<int64_t> zonal_ncells;   // cells of every zone
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -384,12 +399,14 @@ static int sas_points_enqueue(rh_sas_ctx *ctx, int64_t tag) {
 }
 
 static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
+static int sas_zonal_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
 
-// a whole day and, with points or totals configured, their rows
+// a whole day and, with points, totals or zonal totals configured, their rows
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
     if (!rc && ctx->points_ncells) rc = sas_points_enqueue(ctx, day);
     if (!rc && ctx->totals_items) rc = sas_totals_enqueue(ctx, day, day);
+    if (!rc && ctx->zonal_items) rc = sas_zonal_enqueue(ctx, day, day);
     return rc;
 }
 
@@ -557,6 +574,38 @@ static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
     return RH_OK;
 }
 
+// What the items of rh_sas_totals_configure and rh_sas_zonal_configure are: ids checked, the arrays and weights on the device, the widths
+// and the blocks' places in a row (a zone's part of it).  `who` opens the message of a refusal.
+static int sas_totals_items(rh_sas_ctx *ctx, const std::string &who, const rh_sas_totals_item *items, int n_items, const double **val,
+                            const double **wgt, int64_t *off, unsigned char *val_daily, int *width, const double **srcs, int64_t *row_elems,
+                            int *wmax) {
+    const int64_t n = ctx->cfg.n_cells;
+    for (int j = 0; j < n_items; ++j) {
+        const int a = items[j].array, w = items[j].weight;
+        if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
+        if (w < -1 || w >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown weight id " + std::to_string(w));
+        const std::string name = std::string("array ") + SAS_NAMES[a];
+        for (int k = 0; k < j; ++k)
+            if (items[k].array == a && items[k].weight == w) return sfail(ctx, RH_ERR_ARG, who + name + " is given twice with the same weight");
+        if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
+        if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* are not reduced)");
+        if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
+            return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
+        if (!ctx->arr[a])
+            return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
+        const double *base = (const double *)ctx->arr[a].get();
+        width[j] = SAS_KIND[a] == K_DAILY ? 1 : (int)(ctx->elems[a] / n);
+        val[j] = width[j] == 1 ? base : nullptr;
+        srcs[j] = width[j] == 1 ? nullptr : base;
+        val_daily[j] = SAS_KIND[a] == K_DAILY;
+        wgt[j] = w >= 0 ? (const double *)ctx->arr[w].get() : nullptr;
+        off[j] = *row_elems;
+        *row_elems += width[j] == 1 ? SAS_TOTALS_NSTAT : 2 + width[j];
+        if (width[j] > 1) *wmax = std::max(*wmax, width[j]);
+    }
+    return RH_OK;
+}
+
 int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh_sas_totals_item *items, int n_items, int64_t capacity) {
     const std::string who = "rh_sas_totals_configure: ";
     if (!ctx) return RH_ERR_ARG;
@@ -571,29 +620,7 @@ int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh
     if (n_items) {
         if (!items) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
         if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
-        for (int j = 0; j < n_items; ++j) {
-            const int a = items[j].array, w = items[j].weight;
-            if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
-            if (w < -1 || w >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown weight id " + std::to_string(w));
-            const std::string name = std::string("array ") + SAS_NAMES[a];
-            for (int k = 0; k < j; ++k)
-                if (items[k].array == a && items[k].weight == w) return sfail(ctx, RH_ERR_ARG, who + name + " is given twice with the same weight");
-            if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
-            if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* are not reduced)");
-            if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
-                return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
-            if (!ctx->arr[a])
-                return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
-            const double *base = (const double *)ctx->arr[a].get();
-            width[j] = SAS_KIND[a] == K_DAILY ? 1 : (int)(ctx->elems[a] / n);
-            P.val[j] = width[j] == 1 ? base : nullptr;
-            srcs[j] = width[j] == 1 ? nullptr : base;
-            P.val_daily[j] = SAS_KIND[a] == K_DAILY;
-            P.wgt[j] = w >= 0 ? (const double *)ctx->arr[w].get() : nullptr;
-            P.off[j] = row_elems;
-            row_elems += width[j] == 1 ? SAS_TOTALS_NSTAT : 2 + width[j];
-            if (width[j] > 1) wmax = std::max(wmax, width[j]);
-        }
+        if (int rc = sas_totals_items(ctx, who, items, n_items, P.val, P.wgt, P.off, P.val_daily, width, srcs, &row_elems, &wmax)) return rc;
         if (mask) {
             ncells = 0;
             for (int64_t c = 0; c < n; ++c) ncells += mask[c] != 0;
@@ -692,6 +719,170 @@ int rh_sas_totals_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64
         SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->totals_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
                                     hipMemcpyDeviceToHost, ctx->stream));
         std::copy(ctx->totals_tags.get() + slot, ctx->totals_tags.get() + slot + m, tags + done);
+        done += m;
+    }
+    return rh_sas_sync(ctx);
+}
+
+// ---- zonal totals (include/roger_hip_sas.h; kernels, index and orders: rh_sas_zonal.h) ----
+// one row behind what the stream holds so far: every item's width-1 statistics for every zone, then the age items one after another
+static int sas_zonal_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
+    const int64_t slot = ctx->zonal_rows % ctx->zonal_cap, n = ctx->cfg.n_cells;
+    const int64_t day_off = day < 0 ? -1 : (day % ctx->cfg.forcing_days) * n;
+    const SasZonalDev &P = ctx->zonal_host;
+    const int *ix = ctx->zonal_index.get();
+    const int64_t *at = ctx->zonal_at;
+    double *row = ctx->zonal_ring + (size_t)slot * (size_t)ctx->zonal_row_elems;
+    const unsigned ntiles = (unsigned)ctx->zonal_ntiles, nz = (unsigned)ctx->zonal_nzones;
+    hipLaunchKernelGGL(k_sas_zonal_tiles, dim3(ntiles), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->zonal_cfg.get(), day_off);
+    hipLaunchKernelGGL(k_sas_zonal_finish, dim3(nz), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->zonal_cfg.get(), row);
+    for (int j = 0; j < P.n_items; ++j) {
+        const int W = ctx->zonal_width[j];
+        if (W == 1) continue;
+        const unsigned bs = (unsigned)std::min(SAS_TOTALS_BLOCK, (W + 63) / 64 * 64);
+        const unsigned chunks = ((unsigned)W + bs - 1) / bs;
+        hipLaunchKernelGGL(k_sas_zonal_ages, dim3(ntiles, chunks), dim3(bs), 0, ctx->stream, ctx->zonal_src[j], W, ix + at[SZ_TILE_PTR],
+                           ix + at[SZ_CELL_PTR], ix + at[SZ_CELL], P.wgt[j] ? P.wgt[j] + std::max<int64_t>(day_off, 0) : nullptr,
+                           (P.wgt[j] && day_off < 0) ? 0 : 1, ctx->zonal_lvl.get());
+        hipLaunchKernelGGL(k_sas_zonal_ages_finish, dim3(nz, chunks), dim3(bs), 0, ctx->stream, (const double *)ctx->zonal_lvl.get(), W,
+                           ix + at[SZ_RUN_PTR], ix + at[SZ_RUN_SLOT], ix + at[SZ_SLOT_TILE], row + P.off[j] + 2, P.zone_elems);
+    }
+    SHIPCHK(ctx, hipGetLastError());
+    ctx->zonal_tags[(size_t)slot] = tag;
+    ++ctx->zonal_rows;
+    return RH_OK;
+}
+
+int rh_sas_zonal_configure(rh_sas_ctx *ctx, const int32_t *zone, int n_zones, const rh_sas_totals_item *items, int n_items, int64_t capacity) {
+    const std::string who = "rh_sas_zonal_configure: ";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_SAS_TOTALS_MAX_ITEMS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_TOTALS_MAX_ITEMS) + ")");
+    const int64_t n = ctx->cfg.n_cells;
+    SasZonalDev P = {};
+    int width[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    const double *srcs[RH_SAS_TOTALS_MAX_ITEMS] = {};
+    int64_t zone_elems = 0, at[SZ_PARTS] = {}, S = 0;
+    int wmax = 0;
+    std::vector<int64_t> ncells;
+    std::vector<int> index;
+    if (n_items) {
+        if (!items || !zone) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+        if (n_zones < 1 || n_zones > RH_SAS_ZONAL_MAX_ZONES)
+            return sfail(ctx, RH_ERR_ARG, who + "n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_SAS_ZONAL_MAX_ZONES) + ")");
+        if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (int rc = sas_totals_items(ctx, who, items, n_items, P.val, P.wgt, P.off, P.val_daily, width, srcs, &zone_elems, &wmax)) return rc;
+        ncells.assign((size_t)n_zones, 0);
+        int64_t inside = 0;
+        for (int64_t c = 0; c < n; ++c) {
+            if (zone[c] < -1 || zone[c] >= n_zones)
+                return sfail(ctx, RH_ERR_ARG, who + "zone id " + std::to_string(zone[c]) + " of cell " + std::to_string(c) +
+                                                  " (-1: outside, else 0 ... " + std::to_string(n_zones - 1) + ")");
+            if (zone[c] >= 0) {
+                ++ncells[(size_t)zone[c]];
+                ++inside;
+            }
+        }
+        if (!inside) return sfail(ctx, RH_ERR_ARG, who + "the map holds no cell in any zone (0 of " + std::to_string(n) + " cells)");
+        if (capacity > ((int64_t)1 << 31) / (zone_elems * n_zones * (int64_t)sizeof(double)))
+            return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " rows of " + std::to_string(n_zones) + " zones x " +
+                                              std::to_string(zone_elems) + " float64 are a ring above 2 GiB");
+        S = sas_zonal_index(zone, n, n_zones, index, at);
+        if (wmax && S > ((int64_t)1 << 31) / ((int64_t)wmax * (int64_t)sizeof(double)))
+            return sfail(ctx, RH_ERR_ARG, who + std::to_string(S) + " (tile, zone) slots x " + std::to_string(wmax) +
+                                              " float64 are a level-1 buffer above 2 GiB");
+    }
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    SHIPCHK(ctx, ctx->zonal_ring.release());
+    SHIPCHK(ctx, ctx->zonal_part.release());
+    SHIPCHK(ctx, ctx->zonal_lvl.release());
+    SHIPCHK(ctx, ctx->zonal_cfg.release());
+    SHIPCHK(ctx, ctx->zonal_index.release());
+    ctx->zonal_tags.reset();
+    ctx->zonal_items = ctx->zonal_nzones = 0;
+    ctx->zonal_cap = ctx->zonal_row_elems = ctx->zonal_rows = ctx->zonal_ntiles = 0;
+    ctx->zonal_ncells.clear();
+    if (!n_items) return RH_OK;
+    std::unique_ptr<int64_t[]> tags(new (std::nothrow) int64_t[(size_t)capacity]);
+    if (!tags) return sfail(ctx, RH_ERR_ARG, who + "out of host memory for the tags of " + std::to_string(capacity) + " rows");
+    const int64_t row_elems = zone_elems * n_zones;
+    SHIPCHK(ctx, ctx->zonal_ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
+    SHIPCHK(ctx, ctx->zonal_part.alloc((size_t)S * (size_t)n_items * SAS_TOTALS_NSTAT * sizeof(double)));
+    if (wmax) SHIPCHK(ctx, ctx->zonal_lvl.alloc((size_t)S * (size_t)wmax * sizeof(double)));
+    SHIPCHK(ctx, ctx->zonal_index.alloc(index.size() * sizeof(int)));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->zonal_index, index.data(), index.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const int *ix = ctx->zonal_index.get();
+    P.n_items = n_items;
+    P.n = n;
+    P.zone_elems = zone_elems;
+    P.zone = ix + at[SZ_ZONE];
+    P.tile_ptr = ix + at[SZ_TILE_PTR];
+    P.tile_zone = ix + at[SZ_TILE_ZONE];
+    P.acc_ptr = ix + at[SZ_ACC_PTR];
+    P.acc_slot = ix + at[SZ_ACC_SLOT];
+    P.part = ctx->zonal_part.get();
+    SHIPCHK(ctx, ctx->zonal_cfg.alloc(sizeof(SasZonalDev)));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->zonal_cfg, &P, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are locals)
+    ctx->zonal_host = P;
+    std::copy(width, width + RH_SAS_TOTALS_MAX_ITEMS, ctx->zonal_width);
+    std::copy(srcs, srcs + RH_SAS_TOTALS_MAX_ITEMS, ctx->zonal_src);
+    std::copy(at, at + SZ_PARTS, ctx->zonal_at);
+    ctx->zonal_tags = std::move(tags);
+    ctx->zonal_cap = capacity;
+    ctx->zonal_row_elems = row_elems;
+    ctx->zonal_ntiles = (n + SAS_TOTALS_BLOCK - 1) / SAS_TOTALS_BLOCK;
+    ctx->zonal_ncells = std::move(ncells);
+    ctx->zonal_nzones = n_zones;
+    ctx->zonal_items = n_items;
+    return RH_OK;
+}
+
+static int sas_zonal_on(rh_sas_ctx *ctx, const char *who) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->zonal_items) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_zonal_configure has not been called");
+    return RH_OK;
+}
+
+int rh_sas_zonal_record(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
+    if (int rc = sas_zonal_on(ctx, "rh_sas_zonal_record")) return rc;
+    return sas_zonal_enqueue(ctx, tag, day);
+}
+
+int rh_sas_zonal_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
+    if (int rc = sas_zonal_on(ctx, "rh_sas_zonal_count")) return rc;
+    if (!rows_total || !ncells) return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_count: null pointer");
+    *rows_total = ctx->zonal_rows;
+    std::copy(ctx->zonal_ncells.begin(), ctx->zonal_ncells.end(), ncells);
+    return RH_OK;
+}
+
+int rh_sas_zonal_row_elems(const rh_sas_ctx *ctx, int64_t *elems) {
+    if (int rc = sas_zonal_on(const_cast<rh_sas_ctx *>(ctx), "rh_sas_zonal_row_elems")) return rc;
+    if (!elems) return RH_ERR_ARG;
+    *elems = ctx->zonal_row_elems;
+    return RH_OK;
+}
+
+int rh_sas_zonal_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes) {
+    if (int rc = sas_zonal_on(ctx, "rh_sas_zonal_read")) return rc;
+    const int64_t total = ctx->zonal_rows, cap = ctx->zonal_cap;
+    const size_t nv = (size_t)ctx->zonal_row_elems;
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+                                          " have not been recorded (" + std::to_string(total) + " rows so far)");
+    if (n_rows && first_row < total - cap)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
+                                          " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " +
+                                          std::to_string(total) + " rows)");
+    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_read: size mismatch (n_rows x row_elems float64)");
+    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
+        const int64_t slot = (first_row + done) % cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
+        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->zonal_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        std::copy(ctx->zonal_tags.get() + slot, ctx->zonal_tags.get() + slot + m, tags + done);
         done += m;
     }
     return rh_sas_sync(ctx);

@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, stepping, totals, zonal_totals
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, sas_zonal_totals, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -157,6 +157,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             zonal_totals.initialize(state)
             sas_points.initialize(state)
             sas_totals.initialize(state)
+            sas_zonal_totals.initialize(state)
             self.set_boundary_conditions_setup(state)
             self.set_boundary_conditions(state)
             self.set_forcing_setup(state)
@@ -164,6 +165,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             if offline and state.settings.warmup_done:
                 sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
                 sas_totals.start(state)
+                sas_zonal_totals.start(state)
         self._setup_done = True
         if not state.settings.enable_offline_transport:   # roger/roger.py:324-327
             with state.settings.unlock():
@@ -192,6 +194,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         diagnostics.output_transport(self.state)   # initial values after the warm-up, roger/roger.py:515-521
         sas_points.start(self.state)               # ... and record 0 of the transport points
         sas_totals.start(self.state)
+        sas_zonal_totals.start(self.state)
         if self.state.settings.enable_offline_transport and self.state.settings.write_restart:
             restart.write_restart(self.state, force=True)   # a warm-up that later runs can start from
 
@@ -272,6 +275,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             with state.timers["diagnostics"]:
                 sas_points.drain(state)        # (rows not yet drained are drained before a restart file is written)
                 sas_totals.drain(state)
+                sas_zonal_totals.drain(state)
                 restart.write_restart(state)   # at the start of a day step, as in step(); not during the warm-up runs
         with state.timers["main"]:
             with vs.unlock():
@@ -292,6 +296,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 diagnostics.output_transport(state)    # write_output, roger/core/transport.py:3399-3418
                 sas_points.stepped(state)              # (rh_sas_step recorded the day's row; the ring is drained every `capacity` steps)
                 sas_totals.stepped(state)
+                sas_zonal_totals.stepped(state)
         self.after_timestep(state)
         if rs.profile_mode:
             state.sas_context.sync()
@@ -444,6 +449,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     zonal_totals.drain(self.state)
                     sas_points.drain(self.state)
                     sas_totals.drain(self.state)
+                    sas_zonal_totals.drain(self.state)
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
         diagnostics.close(self.state)
@@ -452,6 +458,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         zonal_totals.close(self.state)
         sas_points.close(self.state)
         sas_totals.close(self.state)
+        sas_zonal_totals.close(self.state)
 
     # -- fast path --------------------------------------------------------------------------------
     def enable_device_hooks(self):

@@ -65,7 +65,7 @@ class TransportTotals:
         return output_file_name(self, state)
 
 
-def _items(output_variables):
+def _items(output_variables, who="transport_totals"):
     out = []
     for it in output_variables:
         if isinstance(it, str):
@@ -73,41 +73,49 @@ def _items(output_variables):
         elif isinstance(it, (tuple, list)) and len(it) == 2 and all(isinstance(s, str) for s in it):
             out.append((it[0], it[1]))
         else:
-            raise ValueError(f"transport_totals: {it!r} is neither a variable's name nor a pair (value, weight)")
+            raise ValueError(f"{who}: {it!r} is neither a variable's name nor a pair (value, weight)")
     return out
+
+
+def check_items(state, output_variables, capacity, who="transport_totals"):
+    """[(value, weight or None)] of what a script asked for, or the refusal; `who` opens the messages (roger_amd/sas_zonal_totals.py
+    asks with its own name)."""
+    from .diagnostics import _AGED
+
+    settings = state.settings
+    items = _items(output_variables, who)
+    if len(items) > MAX_VARIABLES:
+        raise ValueError(f"{who}: {len(items)} items (at most {MAX_VARIABLES})")
+    check_request(who, (), len(items), capacity, settings)   # (no cells to check: the capacity)
+    if len(set(items)) != len(items):
+        raise ValueError(f"{who}: an item is given twice")
+    for v, w in items:
+        meta = state.var_meta.get(v)
+        if v in _AGED:
+            raise NotImplementedError(f"{who}: {v!r} would be reduced after the ageing, the reference writes it before "
+                                      "(use sa_s / msa_s)")
+        if meta is not None and meta.dims is not None and tuple(meta.dims[:2]) == ("x", "y") and meta.sas is None:
+            raise NotImplementedError(f"{who}: {v!r} exists on the host only (the setup script's hooks form it): "
+                                      "not an array of the SAS context")
+        if meta is None or meta.dims is None or tuple(meta.dims) not in _GRIDS or meta.dtype is not None:
+            raise NotImplementedError(f"{who}: {v!r} is not a float64 per-cell variable of the transport step")
+        if w is not None:
+            wmeta = state.var_meta.get(w)
+            if wmeta is None or wmeta.sas not in DAILY_INPUTS or wmeta.sas == "C_in":
+                raise NotImplementedError(f"{who}: the weight {w!r} of {v!r} is not a daily flux input "
+                                          f"({', '.join(d for d in DAILY_INPUTS if d != 'C_in')})")
+    return items
 
 
 def initialize(state):
     """setup(): validate what the script asked for.  The recorder itself starts with the run proper (start)."""
-    from .diagnostics import _AGED
-
     t = state.transport_totals
     if not t.active:
         return
     settings = state.settings
     if not settings.enable_offline_transport:
         raise NotImplementedError("transport_totals: the totals of the offline transport model; the SVAT / oneD step records through state.totals")
-    items = _items(t.output_variables)
-    if len(items) > MAX_VARIABLES:
-        raise ValueError(f"transport_totals: {len(items)} items (at most {MAX_VARIABLES})")
-    check_request("transport_totals", (), len(items), t.capacity, settings)   # (no cells to check: the capacity)
-    if len(set(items)) != len(items):
-        raise ValueError("transport_totals: an item is given twice")
-    for v, w in items:
-        meta = state.var_meta.get(v)
-        if v in _AGED:
-            raise NotImplementedError(f"transport_totals: {v!r} would be reduced after the ageing, the reference writes it before "
-                                      "(use sa_s / msa_s)")
-        if meta is not None and meta.dims is not None and tuple(meta.dims[:2]) == ("x", "y") and meta.sas is None:
-            raise NotImplementedError(f"transport_totals: {v!r} exists on the host only (the setup script's hooks form it): "
-                                      "not an array of the SAS context")
-        if meta is None or meta.dims is None or tuple(meta.dims) not in _GRIDS or meta.dtype is not None:
-            raise NotImplementedError(f"transport_totals: {v!r} is not a float64 per-cell variable of the transport step")
-        if w is not None:
-            wmeta = state.var_meta.get(w)
-            if wmeta is None or wmeta.sas not in DAILY_INPUTS or wmeta.sas == "C_in":
-                raise NotImplementedError(f"transport_totals: the weight {w!r} of {v!r} is not a daily flux input "
-                                          f"({', '.join(d for d in DAILY_INPUTS if d != 'C_in')})")
+    items = check_items(state, t.output_variables, t.capacity)
     if t.mask is not None:
         mask = np.asarray(t.mask)
         if mask.shape != (settings.nx, settings.ny):

@@ -357,6 +357,9 @@ class RogerState:
         from .sas_totals import TransportTotals
 
         self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
+        from .sas_zonal_totals import TransportZonalTotals
+
+        self.transport_zonal_totals = TransportZonalTotals()   # ... for every zone of a zone map (roger_amd/sas_zonal_totals.py)
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None

@@ -122,7 +122,8 @@ def initialize(state):
     if settings.enable_offline_transport:
         raise NotImplementedError("zonal totals: the offline transport model steps by the day and its output is read after every step "
                                   "(state.diagnostics); the recorder belongs to the SVAT / oneD step -- the transport model's own totals are "
-                                  "state.transport_totals (roger_amd/sas_totals.py)")
+                                  "state.transport_totals (roger_amd/sas_totals.py), per zone state.transport_zonal_totals "
+                                  "(roger_amd/sas_zonal_totals.py)")
     if len(t.output_variables) > MAX_VARIABLES:
         raise ValueError(f"zonal totals: {len(t.output_variables)} variables (at most {MAX_VARIABLES})")
     zones = np.asarray(t.zones)
