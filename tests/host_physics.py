@@ -52,13 +52,18 @@ _lib = None
 _tmp = None
 
 
-def lib():
-    """Builds (once per session) and loads the library."""
+def lib(prebuilt=None):
+    """Builds (once per session) and loads the library.  prebuilt, or the environment variable HOST_PHYSICS_SO: the path of a library
+    built elsewhere with compile_command, loaded as it is (tools/physics_branches.py: a coverage build)."""
     global _lib, _tmp
     if _lib is None:
-        _tmp = tempfile.TemporaryDirectory(prefix="host_physics_")
-        so = os.path.join(_tmp.name, "libhost_physics.so")
-        subprocess.run(compile_command(so, ("-shared", "-fPIC")), check=True)
+        prebuilt = prebuilt or os.environ.get("HOST_PHYSICS_SO")
+        if prebuilt:
+            so = os.path.abspath(prebuilt)
+        else:
+            _tmp = tempfile.TemporaryDirectory(prefix="host_physics_")
+            so = os.path.join(_tmp.name, "libhost_physics.so")
+            subprocess.run(compile_command(so, ("-shared", "-fPIC")), check=True)
         L = C.CDLL(so)
         L.host_plane_name.restype = C.c_char_p
         L.host_plane_name.argtypes = [C.c_int]

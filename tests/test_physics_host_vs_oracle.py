@@ -111,13 +111,14 @@ def walk(lateral, groundwater, forcing_kind):
     return walk_from(ob, st, _forcing(forcing_kind), lateral)
 
 
-def walk_from(ob, st, F, lateral, observer=None):
+def walk_from(ob, st, F, lateral, observer=None, driver=None):
     """walk() from the start state `st` through the forcing `F`.  observer: before(name, P) sees the oracle's planes P ahead of every
-    routine of the step, after(name, P, H, step) the oracle's planes behind it and those the host-compiled routine left (H)."""
+    routine of the step, after(name, P, H, step) the oracle's planes behind it and those the host-compiled routine left (H).
+    driver: an oracle_binding.ForcingDriver over F in place of the plain one (per-cell weights, stations)."""
     O = Blocks(st)
     T, host = _twin(ob, st)      # one routine at a time
     W, whole = _twin(ob, st)     # the whole core in one call
-    drv = ob.ForcingDriver(F)
+    drv = driver if driver is not None else ob.ForcingDriver(F)
     sub, err, core = (("rt_subsurface_runoff_lateral", "rt_num_error_lateral", "rt_step_core_lateral") if lateral
                       else ("rt_subsurface_runoff", "rt_num_error", "rt_step_core"))
     routines = (("rt_interception", st.interception), ("rt_evapotranspiration", st.evapotranspiration), ("rt_snow", st.snow),
