@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 11  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h) */
+#define RH_ABI_VERSION 12  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -457,6 +457,35 @@ int rh_totals_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr,
 int rh_zonal_configure(rh_ctx *ctx, const int32_t *zone, int n_zones, const int *planes, int n_planes, int64_t capacity);
 int rh_zonal_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells);
 int rh_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
+
+/* ---- scores against observed series: per-column moments of simulated against observed interval values, kept on the device ----
+ * A parameter study fills the grid with parameter sets of one plot and needs one goodness-of-fit number per column.  After
+ * rh_scores_configure every step, wherever the accumulators' kernel is launched, is followed by one more launch over all columns
+ * (k_scores, roger_amd/csrc/rh_scores.h).  With (t0, t1] the step, iv = interval_seconds:
+ *   first  = t0 % iv == 0;   closes = t1 % iv == 0 && t1 - t0 <= iv  (a step longer than the interval never closes one)
+ *   k      = t1 / iv - 1 - t_first / iv, scored only when 0 <= k < n_intervals
+ * Column i belongs to series s = series[i] (NULL: every column to series 0); s < 0 is not scored and costs nothing.  Per item j:
+ *   kind 0 (SUM):   acc = first ? v : acc + v on every step (the accumulators' rate rule, the same order of additions)
+ *   kind 1 (LAST):  acc = v on a closing step, nothing otherwise
+ *   on a scored closing step, o = obs[(j * n_series + s) * n_intervals + k]; unless o is NaN (a missing observation), in this order
+ *   and without fused multiply-adds:  m1 += acc;  m2 += acc * acc;  m3 += acc * o;  d = acc - o, m4 += d * d.
+ * The first scored closing step of interval k sets closed[k] = 1.  A launch behind the time limit (rh_set_time_limit) changes nothing.
+ *   planes, kinds:    n_items (at most 16) float64 planes and their kinds.  An X_m1 plane switches the lazy rotation off.
+ *   obs:              (n_items, n_series, n_intervals) float64, copied; n_series 1 ... 1024
+ *   series[n]:        int32 per interior column of the rank's block (C order over (x, y), as rh_upload), copied, or NULL
+ *   interval_seconds: 86400, 3600 or 600
+ *   t_first:          the start of interval 0: a multiple of the interval, not behind the context's clock
+ * n_items == 0 releases the buffers and stops the launches.  Every other call clears the moments.  RH_ERR_ARG (rh_last_error names the
+ * value): more than 16 items, an int32 plane or one the context does not hold, a kind other than 0 / 1, n_series or n_intervals out
+ * of range, another interval, a t_first off the interval's grid or behind the clock, a series value >= n_series.
+ *   rh_scores_read   moments (n_items, 5, n) float64: {acc, m1, m2, m3, m4} per column (the acc plane of a LAST item stays +0.0), and
+ *                    closed[n_intervals].  Synchronises; RH_ERR_STATE before rh_scores_configure (or after it released the buffers). */
+#define RH_SCORES_MAX_SERIES 1024
+int rh_scores_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 LAST */, int n_items,
+                        const double *obs /* (n_items, n_series, n_intervals) */, int n_series, int64_t n_intervals,
+                        const int32_t *series /* [n], < 0: not scored; NULL: all 0 */, int64_t interval_seconds, int64_t t_first);
+int rh_scores_read(rh_ctx *ctx, double *moments /* (n_items, 5, n) */, size_t moment_bytes, unsigned char *closed /* [n_intervals] */,
+                   size_t closed_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

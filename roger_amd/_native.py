@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 11  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 12  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -164,6 +164,8 @@ def load():
     lib.rh_zonal_configure.argtypes = [vp, vp, i32, vp, i32, i64]
     lib.rh_zonal_count.argtypes = [vp, C.POINTER(C.c_int64), vp]
     lib.rh_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_scores_configure.argtypes = [vp, vp, vp, i32, vp, i32, i64, vp, i64, i64]
+    lib.rh_scores_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -581,6 +583,7 @@ DECLARED_SYMBOLS = (
     "rh_points_configure", "rh_points_count", "rh_points_read",
     "rh_totals_configure", "rh_totals_count", "rh_totals_read",
     "rh_zonal_configure", "rh_zonal_count", "rh_zonal_read",
+    "rh_scores_configure", "rh_scores_read",
 )
 
 
@@ -938,6 +941,42 @@ class Context:
         self._check(self._lib.rh_zonal_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
                                             values.nbytes), "rh_zonal_read")
         return hdr, values
+
+    # -- scores against observed series (rh_scores_*) ------------------------------------------------
+    def scores_configure(self, names, kinds=(), obs=None, series=None, interval=86400, t_first=0):
+        """After every step aggregate `names` (float64 planes; kinds: 0 sum over the interval, 1 value at its end) to the observation
+        interval and, at every interval's end, add the comparison with `obs` (n_items, n_series, n_intervals; NaN: missing) into four
+        moments per column that stay on the device.  `series`: the series of every interior column of this context's block (C order,
+        < 0: not scored), None: every column series 0.  Interval k is (t_first + k interval, t_first + (k + 1) interval].  No names:
+        release the buffers and stop."""
+        names = list(names)
+        ids = (C.c_int * max(1, len(names)))(*[self.index[n] for n in names])
+        kd = (C.c_int * max(1, len(names)))(*[int(k) for k in kinds])
+        o, sr, shape = None, None, (0, 0, 0)
+        if names:
+            o = np.ascontiguousarray(obs, dtype=np.float64)
+            if o.ndim != 3 or o.shape[0] != len(names) or len(kinds) != len(names):
+                raise ValueError(f"scores_configure: observations of shape {o.shape} and {len(kinds)} kinds for {len(names)} items "
+                                 "((n_items, n_series, n_intervals))")
+            shape = o.shape
+            if series is not None:
+                sr = np.ascontiguousarray(np.asarray(series).reshape(-1), dtype=np.int32)
+                if sr.size != self.n:
+                    raise ValueError(f"scores_configure: the series map has {sr.size} values, the context {self.n} columns")
+        self._check(self._lib.rh_scores_configure(self._h, ids, kd, len(names), None if o is None else o.ctypes.data_as(C.c_void_p),
+                                                  int(shape[1]), int(shape[2]), None if sr is None else sr.ctypes.data_as(C.c_void_p),
+                                                  int(interval), int(t_first)), "rh_scores_configure")
+        self._scores_shape = (len(names), int(shape[2]) if names else 0)   # (a refused configuration leaves the previous one)
+
+    def scores_read(self):
+        """(moments float64 (n_items, 5, n): acc, m1 = sum sim, m2 = sum sim^2, m3 = sum sim obs, m4 = sum (sim - obs)^2;
+        closed uint8 (n_intervals,)).  Synchronises."""
+        ni, nk = getattr(self, "_scores_shape", (0, 0))
+        moments = np.empty((ni, 5, self.n), dtype=np.float64)
+        closed = np.empty(nk, dtype=np.uint8)
+        self._check(self._lib.rh_scores_read(self._h, moments.ctypes.data_as(C.c_void_p), moments.nbytes, closed.ctypes.data_as(C.c_void_p),
+                                             closed.nbytes), "rh_scores_read")
+        return moments, closed
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

@@ -127,6 +127,14 @@ struct rh_ctx {
     int64_t zonal_cap = 0;
     int zonal_planes[RH_POINTS_MAX_PLANES] = {};
     std::vector<int64_t> zonal_ncells;         // columns of every zone on this rank
+    // scores against observed series (rh_scores_configure): the moments, the observations, the series map (not held: every column
+    // series 0) and the closed flags
+    DevBuf<double> scores_buf, scores_obs_buf;
+    DevBuf<int> scores_series_buf;
+    DevBuf<unsigned char> scores_closed_buf;
+    int scores_nitems = 0;           // 0: not configured, no k_scores launch
+    int64_t scores_nintervals = 0;
+    int scores_planes[16] = {};      // RH_SCORES_MAX_ITEMS
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

@@ -147,6 +147,18 @@ struct DevState {
     long long zonal_rows, zonal_cap;
     int zonal_nplanes, zonal_nzones;
     int zonal_planes[RH_POINTS_MAX_PLANES];
+
+    // scores against observed series (rh_scores_configure; k_scores in rh_scores.h): scores (item, {acc, m1, m2, m3, m4}, n) float64,
+    // scores_obs (item, series, interval) float64 with NaN for a missing observation, scores_series: the series of every column (< 0: not
+    // scored) or null (every column series 0), scores_closed: a byte per interval, set when a scored step closed it.  Interval k covers
+    // (scores_t_first + k * scores_interval, scores_t_first + (k + 1) * scores_interval].
+    double *scores;
+    const double *scores_obs;
+    const int *scores_series;
+    unsigned char *scores_closed;
+    long long scores_interval, scores_t_first, scores_nintervals;
+    int scores_nitems, scores_nseries;
+    int scores_planes[16], scores_kinds[16];   // RH_SCORES_MAX_ITEMS; kinds: 0 SUM, 1 LAST
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

@@ -1,6 +1,6 @@
 // rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
-// (rh_points_*), the catchment totals (rh_totals_*) and the zonal totals (rh_zonal_*).  Part of the one translation unit roger_hip.hip,
-// behind rh_context.h.
+// (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*) and the scores against observed series
+// (rh_scores_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure): what the fused kernel must
 // leave in memory after every step, from the UNION of the accumulators', the points', the totals' and the zonal totals' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
@@ -25,6 +25,7 @@ static int observers_changed(rh_ctx *ctx) {
     if (ctx->points_ncells) add(ctx->points_planes, ctx->points_nplanes);
     add(ctx->totals_planes, ctx->totals_nplanes);
     add(ctx->zonal_planes, ctx->zonal_nplanes);
+    add(ctx->scores_planes, ctx->scores_nitems);
     const int any = reads_sparse ? 1 : 0;
     HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
     HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
@@ -38,8 +39,11 @@ static int observers_changed(rh_ctx *ctx) {
 // The observers behind the step that was just enqueued: the accumulators over all columns (grid: the fused launch's own, which has one
 // workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values),
 // then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them -- then the zonal totals' row: a
-// workgroup per RH_BLOCK columns and one per zone (rh_zonal.h).  after_fused: rh_control.h, k_diag.
-static bool has_observers(const rh_ctx *ctx) { return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes; }
+// workgroup per RH_BLOCK columns and one per zone (rh_zonal.h) -- then the scores' moments over all columns, on the accumulators' grid
+// (rh_scores.h).  after_fused: rh_control.h, k_diag.
+static bool has_observers(const rh_ctx *ctx) {
+    return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems;
+}
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
@@ -52,6 +56,7 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
         hipLaunchKernelGGL(k_zonal_tiles, dim3(grid_for(ctx->n)), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
         hipLaunchKernelGGL(k_zonal_finish, dim3(ctx->zonal_nzones), block, 0, ctx->stream, ctx->dev, after_fused);
     }
+    if (ctx->scores_nitems) hipLaunchKernelGGL(k_scores, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -517,6 +522,109 @@ int rh_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, 
                                    ctx->stream));
         done += m;
     }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+
+// ---- scores against observed series (include/roger_hip.h; the kernel and the rule: rh_scores.h) ----
+static int scores_alloc(rh_ctx *ctx, int n_items, const double *obs, int n_series, int64_t n_intervals, const int32_t *series) {
+    const size_t mb = (size_t)n_items * 5 * ctx->n * sizeof(double), ob = (size_t)n_items * n_series * n_intervals * sizeof(double);
+    HIPCHK(ctx, ctx->scores_buf.alloc(mb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->scores_buf, 0, mb, ctx->stream));
+    HIPCHK(ctx, ctx->scores_obs_buf.alloc(ob));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scores_obs_buf, obs, ob, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, ctx->scores_closed_buf.alloc((size_t)n_intervals));
+    HIPCHK(ctx, hipMemsetAsync(ctx->scores_closed_buf, 0, (size_t)n_intervals, ctx->stream));
+    if (series) {
+        HIPCHK(ctx, ctx->scores_series_buf.alloc((size_t)ctx->n * sizeof(int)));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scores_series_buf, series, (size_t)ctx->n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return RH_OK;
+}
+int rh_scores_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, const double *obs, int n_series, int64_t n_intervals,
+                        const int32_t *series, int64_t interval_seconds, int64_t t_first) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_SCORES_MAX_ITEMS)
+        return fail(ctx, RH_ERR_ARG, "rh_scores_configure: n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SCORES_MAX_ITEMS) + ")");
+    const bool off = n_items == 0;
+    int plane_list[RH_SCORES_MAX_ITEMS] = {}, kind_list[RH_SCORES_MAX_ITEMS] = {};
+    if (!off) {
+        if (!planes || !kinds || !obs) return fail(ctx, RH_ERR_ARG, "rh_scores_configure: null pointer");
+        if (n_series < 1 || n_series > RH_SCORES_MAX_SERIES)
+            return fail(ctx, RH_ERR_ARG, "rh_scores_configure: n_series = " + std::to_string(n_series) + " (1 ... " + std::to_string(RH_SCORES_MAX_SERIES) + ")");
+        if (n_intervals < 1 || n_intervals > (int64_t)1 << 31)
+            return fail(ctx, RH_ERR_ARG, "rh_scores_configure: n_intervals = " + std::to_string(n_intervals) + " (at least one, at most 2^31)");
+        if (interval_seconds != 86400 && interval_seconds != 3600 && interval_seconds != 600)
+            return fail(ctx, RH_ERR_ARG, "rh_scores_configure: interval_seconds = " + std::to_string(interval_seconds) +
+                                         " (the observation interval is a day, an hour or ten minutes: the step classes)");
+        if (t_first < 0 || t_first % interval_seconds)
+            return fail(ctx, RH_ERR_ARG, "rh_scores_configure: t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
+                                         std::to_string(interval_seconds) + " s)");
+        for (int j = 0; j < n_items; ++j) {
+            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+                return fail(ctx, RH_ERR_ARG, "rh_scores_configure: plane id " + std::to_string(planes[j]) + " is not held by this context (plane ids must name float64 planes)");
+            if (PLANE_IS_INT[planes[j]])
+                return fail(ctx, RH_ERR_ARG, std::string("rh_scores_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (plane ids must name float64 planes)");
+            if (kinds[j] != RH_SCORES_SUM && kinds[j] != RH_SCORES_LAST)
+                return fail(ctx, RH_ERR_ARG, "rh_scores_configure: kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: LAST)");
+            plane_list[j] = planes[j];
+            kind_list[j] = kinds[j];
+        }
+        if (series)
+            for (int64_t i = 0; i < ctx->n; ++i)
+                if (series[i] >= n_series)
+                    return fail(ctx, RH_ERR_ARG, "rh_scores_configure: series " + std::to_string(series[i]) + " of column " + std::to_string(i) +
+                                                 " (< 0: not scored, else 0 ... " + std::to_string(n_series - 1) + ")");
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that add into the old moments; the clock below)
+    if (!off) {
+        long long now = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&now, &ctx->dev->S.time, sizeof(now), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (t_first < now)
+            return fail(ctx, RH_ERR_ARG, "rh_scores_configure: t_first = " + std::to_string(t_first) + " lies behind the context's clock (" +
+                                         std::to_string(now) + " s): pass the next interval boundary");
+    }
+    HIPCHK(ctx, ctx->scores_buf.release());
+    HIPCHK(ctx, ctx->scores_obs_buf.release());
+    HIPCHK(ctx, ctx->scores_series_buf.release());
+    HIPCHK(ctx, ctx->scores_closed_buf.release());
+    ctx->scores_nitems = 0;
+    ctx->scores_nintervals = 0;
+    if (int rc = off ? RH_OK : scores_alloc(ctx, n_items, obs, n_series, n_intervals, series)) {   // refused: the scores are off
+        const std::string why = ctx->err;
+        (void)rh_scores_configure(ctx, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0);
+        return fail(ctx, rc, why);
+    }
+    if (!off) {
+        ctx->scores_nitems = n_items;
+        ctx->scores_nintervals = n_intervals;
+    }
+    std::memcpy(ctx->scores_planes, plane_list, sizeof(plane_list));
+    const long long iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first, nk = (long long)ctx->scores_nintervals;
+    const int ns = off ? 0 : n_series;
+    const double *const obs_dev = ctx->scores_obs_buf;
+    const int *const series_dev = ctx->scores_series_buf;
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores, *ctx->scores_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_obs, obs_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_series, series_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_closed, *ctx->scores_closed_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_interval, iv));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_t_first, tf));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_nintervals, nk));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_nitems, ctx->scores_nitems));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_nseries, ns));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_planes, plane_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_kinds, kind_list));
+    return observers_changed(ctx);   // synchronises: the sources above are locals (and the caller's observations and series map)
+}
+int rh_scores_read(rh_ctx *ctx, double *moments, size_t moment_bytes, unsigned char *closed, size_t closed_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->scores_nitems) return fail(ctx, RH_ERR_STATE, "rh_scores_read: rh_scores_configure has not been called");
+    if (!moments || !closed || moment_bytes != (size_t)ctx->scores_nitems * 5 * ctx->n * sizeof(double) || closed_bytes != (size_t)ctx->scores_nintervals)
+        return fail(ctx, RH_ERR_ARG, "rh_scores_read: size mismatch (n_items x 5 x n float64, n_intervals bytes)");
+    HIPCHK(ctx, hipMemcpyAsync(moments, ctx->scores_buf, moment_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(closed, ctx->scores_closed_buf, closed_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }

@@ -39,6 +39,7 @@
 #include "rh_zonal.h"
 #include "rh_step.h"
 #include "rh_routing.h"
+#include "rh_scores.h"   // (last: the kernels in front of it keep their places in the code object)
 
 // The host side, one file per concern.  The entry points get their C linkage from their declarations in roger_hip.h.
 #include "rh_host_kernels.h"

@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, sas_zonal_totals, stepping, totals, zonal_totals
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -155,6 +155,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             points.initialize(state)
             totals.initialize(state)
             zonal_totals.initialize(state)
+            scores.initialize(state)
             sas_points.initialize(state)
             sas_totals.initialize(state)
             sas_zonal_totals.initialize(state)
@@ -162,6 +163,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             self.set_boundary_conditions(state)
             self.set_forcing_setup(state)
             restart.read_restart(state)   # roger/roger.py:324-326
+            scores.start(state)           # (the clock is known: a continued run scores from the next interval boundary)
             if offline and state.settings.warmup_done:
                 sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
                 sas_totals.start(state)
@@ -456,6 +458,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         points.close(self.state)
         totals.close(self.state)
         zonal_totals.close(self.state)
+        scores.close(self.state)
         sas_points.close(self.state)
         sas_totals.close(self.state)
         sas_zonal_totals.close(self.state)

@@ -354,6 +354,9 @@ class RogerState:
         from .zonal_totals import ZonalTotals
 
         self.zonal_totals = ZonalTotals()   # ... for every zone of a zone map (roger_amd/zonal_totals.py)
+        from .scores import Scores
+
+        self.scores = Scores()              # per-column scores against observed series, moments on the device (roger_amd/scores.py)
         from .sas_totals import TransportTotals
 
         self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
