@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 12  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read */
+#define RH_ABI_VERSION 13  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h) */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {

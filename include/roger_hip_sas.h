@@ -288,6 +288,66 @@ int rh_sas_zonal_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells);
 int rh_sas_zonal_row_elems(const rh_sas_ctx *ctx, int64_t *elems);
 int rh_sas_zonal_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes);
 
+/* ---- scores against observed tracer samples: per-column moments that stay on the device ---------------------------------------------
+ * A SAS parameter study draws its parameters by the thousand -- every column one draw of the same plot -- and judges each draw against
+ * delta-18O, delta-2H, bromide or chloride measured in a lysimeter's percolate.  Such samples are BULK samples over irregular windows (a
+ * weekly or fortnightly bottle, a gap of a month): what is compared with sample k is the flux-weighted mean over its window,
+ * sum(q C) / sum(q).  After rh_sas_scores_configure, rh_sas_step and every day of rh_sas_run_days that lies inside a window are followed
+ * by ONE launch (k_sas_scores, roger_amd/csrc/rh_sas_scores.h; behind the points', the totals' and the zonal launches where those are on);
+ * a day outside every window launches nothing, rh_sas_stages never scores, and a context without scores enqueues exactly what it enqueued
+ * before these entry points existed.  Points, totals, zonal totals and scores work side by side, configured in any order.
+ *   items    [n_items], at most RH_SAS_SCORES_MAX_ITEMS, each (value, weight, kind):
+ *            value   a per-cell float64 array of width 1 this context holds: C_*, C_iso_*, M_*, the age statistics, the per-cell parameters
+ *            weight  -1 (none) or one of the eight DAILY flux inputs (not C_in): row (day mod forcing_days), the row the day's kernel read
+ *            kind    RH_SAS_SCORES_BULK (needs a weight), _MEAN or _LAST (take none)
+ *   series   [n_cells] int32, the series of every cell, < 0: not scored; NULL: every cell series 0.  1 <= n_series <= RH_SAS_SCORES_MAX_SERIES
+ *   obs      [n_items][n_series][n_samples] float64, NaN: missing
+ *   first_day, last_day  [n_samples] int64: window k is the days [first_day[k], last_day[k]], inclusive, of the context's DAY COUNT
+ * The day count.  The context counts scored days from 0 at configure: day t is the t-th day stepped (rh_sas_step, a day of
+ * rh_sas_run_days) or recorded by hand (rh_sas_scores_record) since configure.  The `day` argument of those calls is the row of the daily
+ * inputs and nothing else -- a host that keeps one row steps with day 0 throughout.  Windows are strictly increasing and do not overlap:
+ * first_day[k] <= last_day[k] < first_day[k + 1].  Window k is OPEN from the day its first day was scored until its last;
+ * closed[k] = 1 exactly when the closing day of an open window was scored.  A window whose first day was never scored -- first_day[k] < 0:
+ * the series was configured mid-window -- is never open and never compared.
+ *
+ * The rule (each +, -, *, / one IEEE operation in the order written; the library is built with -ffp-contract=off).  Cell i has
+ * s = series[i] (no map: s = 0); s < 0 loads and stores nothing.  Per item, v the value after the day:
+ *   BULK: wd = weight[row][i];  MEAN: wd = 1.0.  On the window's first day num and den restart from +0.0.  The day is ELIGIBLE if wd > 0 and
+ *         v == v (a NaN weight is not > 0): num = num + fl(v * wd), den = den + wd.  A day that is not eligible leaves both as they are.
+ *   LAST: nothing before the closing day.
+ *   On the closing day of an open window, o = obs[(j * n_series + s) * n_samples + k]:
+ *         BULK / MEAN: the sample is COUNTED if o == o and den > 0; sim = num / den.   LAST: COUNTED if o == o and v == v; sim = v.
+ *         A counted sample: n += 1.0; m1 += sim; m2 += sim * sim; m3 += sim * o; d = sim - o; m4 += d * d; so += o; soo += o * o.
+ * The simulated concentration is NaN on a day without flux, so a window may hold water for one column and none for its neighbour: the
+ * count n and the observation moments so, soo are per-column planes.  Nothing assumes positive sums (delta values are negative).
+ * moments [n_items][9][n_cells] float64 = {num, den, n, m1, m2, m3, m4, so, soo}, cleared to +0.0 at configure.  No atomics.
+ *
+ * n_items == 0 releases everything and stops the launches.  Every other call clears the moments and restarts the day count.  RH_ERR_ARG
+ * (rh_sas_last_error names the offender): an unknown id, an int32 array, a DAILY input, sas_params_* or an age-resolved array as value; a
+ * weight that is not a daily flux input (or is C_in); BULK without a weight, MEAN / LAST with one; an unknown kind; the same (value,
+ * weight, kind) twice; more than 16 items, n_series outside 1 ... 1024; a series id >= n_series; no cell scored; n_samples < 1; windows out
+ * of order or overlapping; null pointers.  RH_ERR_STATE: an array this context does not hold.  A refused call leaves the previous
+ * configuration in place.
+ *   rh_sas_scores_record   scores "now", behind what the stream holds, as the next day of the count, with `day` (>= 0) the daily row:
+ *                          for a driver that steps with rh_sas_stages
+ *   rh_sas_scores_read     moments (n_items x 9 x n_cells float64), closed (n_samples bytes), days_scored (may be NULL); synchronises
+ * Both: RH_ERR_STATE before rh_sas_scores_configure (or after it released everything). */
+#define RH_SAS_SCORES_MAX_ITEMS 16
+#define RH_SAS_SCORES_MAX_SERIES 1024
+#define RH_SAS_SCORES_BULK 0
+#define RH_SAS_SCORES_MEAN 1
+#define RH_SAS_SCORES_LAST 2
+typedef struct rh_sas_scores_item {
+    int32_t value;
+    int32_t weight; /* -1 = none */
+    int32_t kind;
+} rh_sas_scores_item;
+int rh_sas_scores_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const int32_t *series, int n_series,
+                            const double *obs, const int64_t *first_day, const int64_t *last_day, int64_t n_samples);
+int rh_sas_scores_record(rh_sas_ctx *ctx, int64_t day);
+int rh_sas_scores_read(rh_sas_ctx *ctx, double *moments, size_t moment_bytes, unsigned char *closed, size_t closed_bytes,
+                       int64_t *days_scored);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

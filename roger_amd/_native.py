@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 12  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 13  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -253,6 +253,9 @@ def _declare_sas(lib):
     lib.rh_sas_zonal_count.argtypes = [vp, C.POINTER(C.c_int64), vp]
     lib.rh_sas_zonal_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.rh_sas_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_sas_scores_configure.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i64]
+    lib.rh_sas_scores_record.argtypes = [vp, i64]
+    lib.rh_sas_scores_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
 
 
 SAS_DECLARED_SYMBOLS = (
@@ -263,7 +266,11 @@ SAS_DECLARED_SYMBOLS = (
     "rh_sas_points_configure", "rh_sas_points_record", "rh_sas_points_count", "rh_sas_points_row_elems", "rh_sas_points_read",
     "rh_sas_totals_configure", "rh_sas_totals_record", "rh_sas_totals_count", "rh_sas_totals_row_elems", "rh_sas_totals_read",
     "rh_sas_zonal_configure", "rh_sas_zonal_record", "rh_sas_zonal_count", "rh_sas_zonal_row_elems", "rh_sas_zonal_read",
+    "rh_sas_scores_configure", "rh_sas_scores_record", "rh_sas_scores_read",
 )
+
+# RH_SAS_SCORES_*: how a sample's window is aggregated (include/roger_hip_sas.h)
+SAS_SCORES_KINDS = {"bulk": 0, "mean": 1, "last": 2}
 
 # stage bits of rh_sas_stages (include/roger_hip_sas.h)
 SAS_STAGES = dict(INF_RZ=1, EVAP=2, TRANSP=4, Q_RZ=8, INF_SS=16, Q_SS=32, CPR=64, STORAGE=128, AGEING=256, ALL=511,
@@ -534,6 +541,47 @@ class SasContext:
                 off += 2 + w
             out[key] = d
         return tags, out
+
+    # -- scores against observed samples (rh_sas_scores_*) ----------------------------------------
+    def scores_configure(self, items, obs=None, windows=None, series=None):
+        """Score `items` against `obs` (n_items, n_series, n_samples; NaN: missing) over the windows (first_day, last_day), int (K,)
+        each, inclusive, in the context's count of scored days, which restarts at 0 here.  An item is (value, weight or None, kind)
+        with kind "bulk" (flux-weighted mean over the window, needs a weight), "mean" or "last".  `series`: the series of every cell
+        (< 0: not scored), None: every cell series 0.  No items: release everything and stop."""
+        items = [(v, w, SAS_SCORES_KINDS[k] if isinstance(k, str) else int(k)) for v, w, k in items]
+        flat = np.array([[self.index(v), -1 if w is None else self.index(w), k] for v, w, k in items], dtype=np.int32).reshape(-1, 3)
+        o = first = last = sr = None
+        shape = (0, 0, 0)
+        if items:
+            o = np.ascontiguousarray(obs, dtype=np.float64)
+            first, last = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in windows)
+            if o.ndim != 3 or o.shape[0] != len(items) or o.shape[2] != first.size or last.size != first.size:
+                raise ValueError(f"scores_configure: observations of shape {o.shape} and windows of {first.size} and {last.size} days "
+                                 f"for {len(items)} items ((n_items, n_series, n_samples))")
+            shape = o.shape
+            if series is not None:
+                sr = np.ascontiguousarray(np.asarray(series).reshape(-1), dtype=np.int32)
+                if sr.size != self.n:
+                    raise ValueError(f"scores_configure: the series map has {sr.size} cells, the context {self.n}")
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self._lib.rh_sas_scores_configure(self._h, ptr(flat), len(items), ptr(sr), int(shape[1]), ptr(o), ptr(first), ptr(last),
+                                                      int(shape[2])), "rh_sas_scores_configure")
+        self._scores_shape = (len(items), int(shape[2]))   # (a refused configuration leaves the previous one)
+
+    def scores_record(self, day=0):
+        """Score now as the next day of the count, `day` the row of the daily inputs (a driver that steps by stage)."""
+        self._check(self._lib.rh_sas_scores_record(self._h, int(day)), "rh_sas_scores_record")
+
+    def scores_read(self):
+        """(moments float64 (n_items, 9, n): num, den, n, m1 = sum sim, m2 = sum sim^2, m3 = sum sim obs, m4 = sum (sim - obs)^2,
+        so = sum obs, soo = sum obs^2; closed uint8 (n_samples,); days scored since scores_configure).  Synchronises."""
+        ni, nk = getattr(self, "_scores_shape", (0, 0))
+        moments = np.empty((ni, 9, self.n), dtype=np.float64)
+        closed = np.empty(nk, dtype=np.uint8)
+        days = C.c_int64()
+        self._check(self._lib.rh_sas_scores_read(self._h, moments.ctypes.data_as(C.c_void_p), moments.nbytes, closed.ctypes.data_as(C.c_void_p),
+                                                 closed.nbytes, C.byref(days)), "rh_sas_scores_read")
+        return moments, closed, days.value
 
 
 def totals_item_name(value, weight=None):

@@ -33,6 +33,7 @@
 #include "rh_sas_points.h"
 #include "rh_sas_totals.h"
 #include "rh_sas_zonal.h"
+#include "rh_sas_scores.h"
 
 #include <algorithm>
 #include <memory>
@@ -116,6 +117,16 @@ struct rh_sas_ctx {
     int64_t zonal_at[SZ_PARTS] = {};
     int64_t zonal_cap = 0, zonal_row_elems = 0, zonal_rows = 0, zonal_ntiles = 0;
     std::vector<int64_t> zonal_ncells;   // cells of every zone
+    // scores against observed samples (rh_sas_scores_configure): the moments, the observations and the series map on the device; the
+    // windows, the day count, the window the count stands in or before, and the closed flags are the host's (rh_sas_scores.h)
+    DevBuf<double> scores_buf, scores_obs;
+    DevBuf<int32_t> scores_series;
+    DevBuf<SasScoresDev> scores_cfg;
+    std::vector<int64_t> scores_first, scores_last;
+    std::vector<unsigned char> scores_closed;
+    int scores_items = 0;            // 0: not configured, no launches
+    bool scores_accumulate = false;  // an item is BULK or MEAN: the days before a window's last are launched too
+    int64_t scores_days = 0, scores_k = 0, scores_open = -1;
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -400,13 +411,15 @@ static int sas_points_enqueue(rh_sas_ctx *ctx, int64_t tag) {
 
 static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
 static int sas_zonal_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
+static int sas_scores_enqueue(rh_sas_ctx *ctx, int64_t day);
 
-// a whole day and, with points, totals or zonal totals configured, their rows
+// a whole day and, with points, totals, zonal totals or scores configured, their rows and the day's scoring
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
     if (!rc && ctx->points_ncells) rc = sas_points_enqueue(ctx, day);
     if (!rc && ctx->totals_items) rc = sas_totals_enqueue(ctx, day, day);
     if (!rc && ctx->zonal_items) rc = sas_zonal_enqueue(ctx, day, day);
+    if (!rc && ctx->scores_items) rc = sas_scores_enqueue(ctx, day);
     return rc;
 }
 
@@ -885,6 +898,156 @@ int rh_sas_zonal_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_
         std::copy(ctx->zonal_tags.get() + slot, ctx->zonal_tags.get() + slot + m, tags + done);
         done += m;
     }
+    return rh_sas_sync(ctx);
+}
+
+// ---- scores against observed samples (include/roger_hip_sas.h; the kernel and the rule: rh_sas_scores.h) ----
+// the next day of the count, behind what the stream holds so far: which window it lies in is decided here, the kernel is told
+static int sas_scores_enqueue(rh_sas_ctx *ctx, int64_t day) {
+    const int64_t t = ctx->scores_days++, K = (int64_t)ctx->scores_first.size(), n = ctx->cfg.n_cells;
+    int64_t &k = ctx->scores_k;
+    while (k < K && ctx->scores_last[(size_t)k] < t) ++k;   // (windows that passed without being open)
+    if (k >= K || t < ctx->scores_first[(size_t)k]) return RH_OK;
+    const bool first = t == ctx->scores_first[(size_t)k], closes = t == ctx->scores_last[(size_t)k];
+    if (first) ctx->scores_open = k;
+    if (ctx->scores_open != k) return RH_OK;                // (its first day was never scored)
+    if (closes || ctx->scores_accumulate) {
+        hipLaunchKernelGGL(k_sas_scores, dim3((unsigned)((n + SAS_SCORES_BLOCK - 1) / SAS_SCORES_BLOCK)), dim3(SAS_SCORES_BLOCK), 0, ctx->stream,
+                           ctx->scores_cfg.get(), k, first ? 1 : 0, closes ? 1 : 0, (day % ctx->cfg.forcing_days) * n);
+        SHIPCHK(ctx, hipGetLastError());
+    }
+    if (closes) {
+        ctx->scores_closed[(size_t)k] = 1;
+        ctx->scores_open = -1;
+        ++k;
+    }
+    return RH_OK;
+}
+
+int rh_sas_scores_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const int32_t *series, int n_series,
+                            const double *obs, const int64_t *first_day, const int64_t *last_day, int64_t n_samples) {
+    const std::string who = "rh_sas_scores_configure: ";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_SAS_SCORES_MAX_ITEMS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_SCORES_MAX_ITEMS) + ")");
+    const int64_t n = ctx->cfg.n_cells;
+    SasScoresDev P = {};
+    bool accumulate = false;
+    if (n_items) {
+        if (!items || !obs || !first_day || !last_day) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+        if (n_series < 1 || n_series > RH_SAS_SCORES_MAX_SERIES)
+            return sfail(ctx, RH_ERR_ARG, who + "n_series = " + std::to_string(n_series) + " (1 ... " + std::to_string(RH_SAS_SCORES_MAX_SERIES) + ")");
+        if (n_samples < 1 || n_samples > (int64_t)1 << 31)
+            return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one, at most 2^31)");
+        static const char *const KIND[] = {"BULK", "MEAN", "LAST"};
+        for (int j = 0; j < n_items; ++j) {
+            const int a = items[j].value, w = items[j].weight, kind = items[j].kind;
+            if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
+            if (w < -1 || w >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown weight id " + std::to_string(w));
+            const std::string name = std::string("array ") + SAS_NAMES[a];
+            if (kind < RH_SAS_SCORES_BULK || kind > RH_SAS_SCORES_LAST)
+                return sfail(ctx, RH_ERR_ARG, who + "kind " + std::to_string(kind) + " of " + name + " (0: BULK, 1: MEAN, 2: LAST)");
+            for (int q = 0; q < j; ++q)
+                if (items[q].value == a && items[q].weight == w && items[q].kind == kind)
+                    return sfail(ctx, RH_ERR_ARG, who + name + " is given twice with the same weight and kind");
+            if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
+            if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* are not scored)");
+            if (SAS_KIND[a] == K_DAILY) return sfail(ctx, RH_ERR_ARG, who + name + " is a daily input of the step, not a result (daily inputs are weights here)");
+            if (SAS_KIND[a] != K_CELL) return sfail(ctx, RH_ERR_ARG, who + name + " is age-resolved (a sample is compared with one value per cell)");
+            if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
+                return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
+            if (kind == RH_SAS_SCORES_BULK && w < 0) return sfail(ctx, RH_ERR_ARG, who + name + " is BULK and has no weight");
+            if (kind != RH_SAS_SCORES_BULK && w >= 0)
+                return sfail(ctx, RH_ERR_ARG, who + name + " is " + KIND[kind] + " and has the weight " + SAS_NAMES[w] + " (only BULK takes one)");
+            if (!ctx->arr[a])
+                return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
+            P.val[j] = (const double *)ctx->arr[a].get();
+            P.wgt[j] = w >= 0 ? (const double *)ctx->arr[w].get() : nullptr;
+            P.kind[j] = kind;
+            accumulate = accumulate || kind != RH_SAS_SCORES_LAST;
+        }
+        if (series) {
+            int64_t scored = 0;
+            for (int64_t c = 0; c < n; ++c) {
+                if (series[c] >= n_series)
+                    return sfail(ctx, RH_ERR_ARG, who + "series " + std::to_string(series[c]) + " of cell " + std::to_string(c) +
+                                                      " (< 0: not scored, else 0 ... " + std::to_string(n_series - 1) + ")");
+                scored += series[c] >= 0;
+            }
+            if (!scored) return sfail(ctx, RH_ERR_ARG, who + "the series map scores no cell (0 of " + std::to_string(n) + " cells)");
+        }
+        for (int64_t k = 0; k < n_samples; ++k) {
+            if (first_day[k] > last_day[k])
+                return sfail(ctx, RH_ERR_ARG, who + "window " + std::to_string(k) + " is [" + std::to_string(first_day[k]) + ", " +
+                                                  std::to_string(last_day[k]) + "]: its last day lies before its first");
+            if (k && first_day[k] <= last_day[k - 1])
+                return sfail(ctx, RH_ERR_ARG, who + "window " + std::to_string(k) + " starts on day " + std::to_string(first_day[k]) + ", window " +
+                                                  std::to_string(k - 1) + " ends on day " + std::to_string(last_day[k - 1]) +
+                                                  " (windows are in increasing order and do not overlap)");
+        }
+    }
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that add into the old moments)
+    SHIPCHK(ctx, ctx->scores_buf.release());
+    SHIPCHK(ctx, ctx->scores_obs.release());
+    SHIPCHK(ctx, ctx->scores_series.release());
+    SHIPCHK(ctx, ctx->scores_cfg.release());
+    ctx->scores_first.clear();
+    ctx->scores_last.clear();
+    ctx->scores_closed.clear();
+    ctx->scores_items = 0;
+    ctx->scores_accumulate = false;
+    ctx->scores_days = ctx->scores_k = 0;
+    ctx->scores_open = -1;
+    if (!n_items) return RH_OK;
+    const size_t mb = (size_t)n_items * SAS_SCORES_NMOM * (size_t)n * sizeof(double);
+    const size_t ob = (size_t)n_items * (size_t)n_series * (size_t)n_samples * sizeof(double);
+    SHIPCHK(ctx, ctx->scores_buf.alloc(mb));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->scores_buf, 0, mb, ctx->stream));
+    SHIPCHK(ctx, ctx->scores_obs.alloc(ob));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->scores_obs, obs, ob, hipMemcpyHostToDevice, ctx->stream));
+    if (series) {
+        SHIPCHK(ctx, ctx->scores_series.alloc((size_t)n * sizeof(int32_t)));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->scores_series, series, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    P.n_items = n_items;
+    P.n_series = n_series;
+    P.n = n;
+    P.n_samples = n_samples;
+    P.series = ctx->scores_series.get();
+    P.obs = ctx->scores_obs.get();
+    P.scores = ctx->scores_buf.get();
+    SHIPCHK(ctx, ctx->scores_cfg.alloc(sizeof(SasScoresDev)));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->scores_cfg, &P, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and a local)
+    ctx->scores_first.assign(first_day, first_day + n_samples);
+    ctx->scores_last.assign(last_day, last_day + n_samples);
+    ctx->scores_closed.assign((size_t)n_samples, 0);
+    ctx->scores_accumulate = accumulate;
+    ctx->scores_items = n_items;
+    return RH_OK;
+}
+
+static int sas_scores_on(rh_sas_ctx *ctx, const char *who) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->scores_items) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_scores_configure has not been called");
+    return RH_OK;
+}
+
+int rh_sas_scores_record(rh_sas_ctx *ctx, int64_t day) {
+    if (int rc = sas_scores_on(ctx, "rh_sas_scores_record")) return rc;
+    if (day < 0) return sfail(ctx, RH_ERR_ARG, "rh_sas_scores_record: day = " + std::to_string(day) + " (the row of the daily inputs, >= 0)");
+    return sas_scores_enqueue(ctx, day);
+}
+
+int rh_sas_scores_read(rh_sas_ctx *ctx, double *moments, size_t moment_bytes, unsigned char *closed, size_t closed_bytes,
+                       int64_t *days_scored) {
+    if (int rc = sas_scores_on(ctx, "rh_sas_scores_read")) return rc;
+    if (!moments || !closed || moment_bytes != (size_t)ctx->scores_items * SAS_SCORES_NMOM * (size_t)ctx->cfg.n_cells * sizeof(double) ||
+        closed_bytes != ctx->scores_closed.size())
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_scores_read: size mismatch (n_items x 9 x n_cells float64, n_samples bytes)");
+    SHIPCHK(ctx, hipMemcpyAsync(moments, ctx->scores_buf, moment_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    std::copy(ctx->scores_closed.begin(), ctx->scores_closed.end(), closed);
+    if (days_scored) *days_scored = ctx->scores_days;
     return rh_sas_sync(ctx);
 }
 

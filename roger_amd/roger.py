@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
+from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -159,6 +159,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             sas_points.initialize(state)
             sas_totals.initialize(state)
             sas_zonal_totals.initialize(state)
+            sas_scores.initialize(state)
             self.set_boundary_conditions_setup(state)
             self.set_boundary_conditions(state)
             self.set_forcing_setup(state)
@@ -168,6 +169,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
                 sas_totals.start(state)
                 sas_zonal_totals.start(state)
+                sas_scores.start(state)   # (the moments are not in the file: a continued run scores the windows that begin from here on)
         self._setup_done = True
         if not state.settings.enable_offline_transport:   # roger/roger.py:324-327
             with state.settings.unlock():
@@ -197,6 +199,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         sas_points.start(self.state)               # ... and record 0 of the transport points
         sas_totals.start(self.state)
         sas_zonal_totals.start(self.state)
+        sas_scores.start(self.state)               # ... and the day count of the transport scores starts with the next step
         if self.state.settings.enable_offline_transport and self.state.settings.write_restart:
             restart.write_restart(self.state, force=True)   # a warm-up that later runs can start from
 
@@ -462,6 +465,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         sas_points.close(self.state)
         sas_totals.close(self.state)
         sas_zonal_totals.close(self.state)
+        sas_scores.close(self.state)
 
     # -- fast path --------------------------------------------------------------------------------
     def enable_device_hooks(self):

@@ -76,7 +76,12 @@ def derive(moments, closed, obs, series=None):
     pick = np.where(scored, s, 0)
     n = np.where(scored, n_s[pick], 0).astype(np.int64)
     so, soo = so_s[pick], soo_s[pick]
-    m1, m2, m3, m4 = moments[1], moments[2], moments[3], moments[4]
+    return metrics(moments[1], moments[2], moments[3], moments[4], n, so, soo, scored)
+
+
+def metrics(m1, m2, m3, m4, n, so, soo, scored):
+    """The raw moments, n and the metrics of the docstring above from per-column m1 ... m4, n (int64), So, Soo and the scored flags,
+    (ncol,) each: what `derive` returns.  roger_amd/sas_scores.py derives its maps through it with per-column n, So and Soo."""
     ok = scored & (n >= 2)
     out = {key: np.where(scored, m, FILL) for key, m in zip(MOMENTS, (m1, m2, m3, m4))}
     out["n"] = n
@@ -152,8 +157,9 @@ def initialize(state):
         return
     settings = state.settings
     if settings.enable_offline_transport:
-        raise NotImplementedError("scores: the offline transport model steps by the day and its output is read after every step "
-                                  "(state.diagnostics); the moments belong to the SVAT / oneD step")
+        raise NotImplementedError("scores: the offline transport model steps by the day and scores its tracers against bulk samples "
+                                  "over windows of days through state.transport_scores (roger_amd/sas_scores.py); the moments of "
+                                  "state.scores belong to the SVAT / oneD step")
     names = list(s.observations)
     if len(names) > MAX_VARIABLES:
         raise ValueError(f"scores: {len(names)} variables (at most {MAX_VARIABLES})")

@@ -363,6 +363,9 @@ class RogerState:
         from .sas_zonal_totals import TransportZonalTotals
 
         self.transport_zonal_totals = TransportZonalTotals()   # ... for every zone of a zone map (roger_amd/sas_zonal_totals.py)
+        from .sas_scores import TransportScores
+
+        self.transport_scores = TransportScores()   # per-column scores of the transport model against observed samples (roger_amd/sas_scores.py)
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None
