@@ -67,6 +67,144 @@ def test_distributed_input_setups_on_device(case, device_hooks):
     compare(S.snapshot_from_vs(vs, names), g[f"s{nsteps:05d}"], names, what=f"{case} step {nsteps}")
 
 
+@pytest.mark.parametrize("case", ["svat_stations", "svat_eberbaechle_weights"])
+def test_distributed_input_setups_with_every_output_on_device(case, tmp_path):
+    """The same two setups with everything a script can ask for in set_diagnostics -- daily rate / collect output, state.points,
+    state.totals, state.zonal_totals, state.scores -- once with the hooks on the host (device_hooks False: step, the per-cell day handed
+    over every midnight) and once with the hooks on the device (device_hooks True: run_device, the observers behind k_cell_front and the
+    fused kernel): every variable of every written file is the same bits in the two runs.  And the files hold what the restatements of
+    tests/per_cell_observers.py make of a context without observers that starts from the model's own state after setup() and steps with
+    rh_run_steps(1): the daily sums, the points' rows, the totals and the moments, at tolerance zero."""
+    import per_cell_observers as P
+    import svat_scripts as S
+    from diag_reference import HostAccumulator
+    from golden_util import load_stations, load_weights
+    from nc_util import netcdf_file
+    from roger_amd import _native as native, diagnostics, points, roger_routine, runtime_settings as rs, scores, totals, zonal_totals
+    from scores_reference import HostScores, SUM
+    from totals_reference import tree_totals
+
+    g, names, forcing = load_case(case)
+    nx, ny = (int(v) for v in g["nx_ny"])
+    w = load_weights(g)
+    weights = {k: v.reshape(nx, ny) for k, v in w.items()}
+    stations = None
+    if load_stations(g) is not None:
+        stations = dict(station_ids=g["station_station_ids"], station_id=g["station_station_id"], PREC=g["station_PREC"],
+                        TA=g["station_TA"], PET=g["station_PET"])
+    ndays = int(g["scal"][P.prefix_steps(case) - 1, 1]) // 86400          # whole days inside the prefix of tests/per_cell_observers.py
+    nsteps = int(np.sum(g["scal"][:, 1] <= ndays * 86400))
+    assert ndays >= 4 and set(g["scal"][:nsteps, 2]) >= {3600, 86400}
+    variables = list(P.VARS)
+    rate, collect = P.split(variables)
+    cells = [(0, 0), (2, 1), (3, 2), (1, 2)]
+    rng = np.random.default_rng(4)
+    mask = rng.random((nx, ny)) < 0.6
+    zones = np.array([[10, 20, 0], [20, 10, 10], [-10, 20, 20], [10, 0, 20]])
+    series = np.array([[0, 1, 2], [-1, 0, 1], [2, 2, 0], [1, -1, 0]])
+    obs = rng.uniform(0.0, 3.0, size=(len(variables), 3, ndays + 1))      # tests/test_hip_scores.py's script test: uniform values, a missing one
+    obs[0, 0, 2] = np.nan
+    files = ("rate", "collect", "points", "totals", "zonal_totals", "scores")
+    out, start = {}, None
+    prev = rs.diskless_mode
+    object.__setattr__(rs, "diskless_mode", False)
+    try:
+        for device_hooks in (False, True):
+            path = tmp_path / ("device" if device_hooks else "host")
+            path.mkdir()
+            model = S.make_model(S.params_from_golden(g, names), forcing, len(forcing["PREC"]) // 144, weights=weights, stations=stations)
+
+            def set_diagnostics(self, state, path=path):
+                for kind, vs_ in (("rate", rate), ("collect", collect)):
+                    d = state.diagnostics[kind]
+                    d.output_variables, d.output_frequency, d.sampling_frequency, d.base_output_path = list(vs_), 86400, 1, str(path)
+                state.points.cells, state.points.output_variables, state.points.base_output_path = list(cells), list(variables), str(path)
+                state.totals.mask, state.totals.output_variables, state.totals.base_output_path = mask, list(variables), str(path)
+                state.zonal_totals.zones, state.zonal_totals.output_variables, state.zonal_totals.base_output_path = zones, list(variables), str(path)
+                state.scores.observations = {v: obs[j] for j, v in enumerate(variables)}
+                state.scores.aggregation = {v: "sum" if P.KIND_OF[v] == SUM else "last" for v in variables}
+                state.scores.series, state.scores.base_output_path = series, str(path)
+
+            type(model).set_diagnostics = roger_routine(set_diagnostics)
+            model.setup()
+            ctx, vs = model.state.backend_context, model.state.variables
+            if start is None:       # the model's own state after setup(), for the reference below
+                vs.flush_to_device()
+                start = ({nm: ctx.download(nm) for nm, _ in ctx.planes[: ctx.planes_held]}, ctx.get_scalars(),
+                         [np.array(getattr(vs, k)) for k in ("lut_ilu", "lut_gc", "lut_gcm", "lut_rdlu")])
+            if device_hooks:
+                model.run_device(nsteps)
+            else:
+                for _ in range(nsteps):
+                    model.step(model.state)
+            assert int(vs.itt) == nsteps and int(vs.time) == ndays * 86400
+            ctx.sync()
+            for mod in (diagnostics, points, totals, zonal_totals, scores):
+                mod.close(model.state)
+            ident = model.state.settings.identifier
+            out[device_hooks] = {}
+            for kind in files:
+                with netcdf_file(str(path / f"{ident}.{kind}.nc"), "r", mmap=False) as f:
+                    out[device_hooks][kind] = {k: np.array(f.variables[k][:]) for k in f.variables}
+            ctx.close()
+    finally:
+        object.__setattr__(rs, "diskless_mode", prev)
+    host, dev = out[False], out[True]
+    for kind in files:
+        assert set(host[kind]) == set(dev[kind]), kind
+        for k, a in dev[kind].items():
+            b = host[kind][k]
+            exact = a.dtype.kind != "f" or k.endswith(("_min", "_max"))
+            assert a.shape == b.shape and (np.array_equal(a, b) if exact else P.same_bits(a, b)), (kind, k)
+    # the reference of tests/per_cell_observers.py from the model's own start: no observer, rh_run_steps(1), downloads after every call
+    planes, scal, luts = start
+    ref_ctx = native.Context(nx, ny)
+    for nm, a in planes.items():
+        ref_ctx.upload(nm, a)
+    ref_ctx.set_scalars(scal)
+    ref_ctx.set_luts(*luts)
+    st = load_stations(g)
+    if st is not None:
+        ref_ctx.set_forcing_stations(dict(PREC=st["PREC"], TA=st["TA"], PET=st["PET"], YEAR=forcing["YEAR"], MONTH=forcing["MONTH"],
+                                          DOY=forcing["DOY"]), st["station_index"])
+    else:
+        ref_ctx.set_forcing_series(forcing)
+    ref_ctx.set_forcing_weights(w["prec_weight"], w["ta_offset"], w["pet_weight"])
+    rec = P.Record(variables)
+    for _ in range(nsteps):
+        ref_ctx.run_steps(1)
+        rec.take(ref_ctx)
+    rec.freeze()
+    ref_ctx.close()
+    np.testing.assert_array_equal(rec.hdr, g["scal"][:nsteps, :3].astype(np.int64))
+    flat = lambda a: np.ascontiguousarray(a.T).reshape(-1)   # noqa: E731  a (y, x) map of a file as the columns of the context (C order of (x, y))
+    acc = HostAccumulator(rate, collect, ndays, nx * ny)
+    for k in range(nsteps):
+        acc.add(rec.hdr[k, 1], rec.hdr[k, 2], {v: rec.planes[v][k] for v in variables})
+    for kind, vs_ in (("rate", rate), ("collect", collect)):
+        for v in vs_:
+            assert dev[kind][v].shape == (ndays + 1, ny, nx)
+            for d in range(ndays):
+                assert P.same_bits(flat(dev[kind][v][d + 1]), acc.data[v][d]), (kind, v, "day", d)
+    for j, v in enumerate(variables):
+        want = np.stack([rec.planes[v][:, x * ny + y] for x, y in cells], axis=1)
+        assert P.same_bits(dev["points"][v][1:], want), ("points", v)
+        for name, m, col in [("totals", mask.reshape(-1), None)] + [("zonal_totals", (zones == z).reshape(-1), i) for i, z in enumerate((10, 20))]:
+            want = np.array([tree_totals(rec.planes[v][k], m) for k in range(nsteps)])
+            got = [dev[name][f"{v}_{s}"][1:] if col is None else dev[name][f"{v}_{s}"][1:, col] for s in ("sum", "min", "max")]
+            assert P.same_bits(got[0], want[:, 0]) and (got[1] == want[:, 1]).all() and (got[2] == want[:, 2]).all(), (name, v, col)
+    h = HostScores([P.KIND_OF[v] for v in variables], obs, nx * ny, series.reshape(-1), 86400, 0)
+    for k in range(nsteps):
+        h.add(int(rec.hdr[k, 1] - rec.hdr[k, 2]), int(rec.hdr[k, 1]), [rec.planes[v][k] for v in variables])
+    assert list(dev["scores"]["closed"]) == list(h.closed) == [1] * ndays + [0]
+    scored = series.reshape(-1) >= 0
+    for j, v in enumerate(variables):
+        for m, key in ((1, "sum_sim"), (2, "sum_sim2"), (3, "sum_simobs"), (4, "sse")):
+            assert P.same_bits(flat(dev["scores"][f"{v}_{key}"])[scored], h.moments[j, m][scored]), ("scores", v, key)   # (a fill value elsewhere)
+        assert np.any(h.moments[j, 1] != 0), v
+    assert list(dev["zonal_totals"]["zone"]) == [10, 20]
+
+
 def test_tutorial_year_on_device():
     """BASELINE configs[0]: examples/plot_scale/svat_tutorial (one cell, config.yml parameters, a year of measured forcing
     read by forcing_from_txt in the golden generator): setup() and the whole year through RogerSetup.step with the hooks on
