@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 13  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h) */
+#define RH_ABI_VERSION 14  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -486,6 +486,34 @@ int rh_scores_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SU
                         const int32_t *series /* [n], < 0: not scored; NULL: all 0 */, int64_t interval_seconds, int64_t t_first);
 int rh_scores_read(rh_ctx *ctx, double *moments /* (n_items, 5, n) */, size_t moment_bytes, unsigned char *closed /* [n_intervals] */,
                    size_t closed_bytes);
+
+/* ---- event outputs: per rainfall event and per column the sum, the peak intensity, the first and the last value of planes ----
+ * The adaptive time stepping numbers the rainfall events (rh_scalars.event_id[1] of a step: 0 between events).  After
+ * rh_events_configure every step, wherever the accumulators' kernel is launched, is followed by one more launch over all columns
+ * (k_events, roger_amd/csrc/rh_events.h, which states the rule in full); a step of no event ends that launch after one scalar load.
+ * Event e accumulates in slot e % n_slots.  Per item, v the plane's value after the step, dt the step in hours:
+ *   kind 0 (SUM):    p = first ? v : p + v           kind 2 (FIRST):  p = v on the event's first step in the slot
+ *   kind 1 (PEAK):   r = v / dt; p = first ? r : (r > p || (p is NaN and r is not) ? r : p)           kind 3 (LAST):  p = v on every step
+ * Header per slot: int64 {event id, steps, t0 of the first step, t1 of the last step, steps of 600 s, steps of 3600 s}, -1 until a step
+ * touches the slot.  The event running at the configuration (event_id[1] of the last finished step) keeps t0 = -1.
+ * The slots are not overwritten unread: a step of event e with e - drained > n_slots stores nothing and raises the lost flag, where
+ * `drained` is the highest event id the caller has read out (rh_events_set_drained; the configuration sets it to the id before the
+ * running or the next event).  More slots, or shorter rh_run_steps calls with a read-out between them, are the remedy.
+ *   planes, kinds:  n_items (at most 16) float64 planes and their kinds.  An X_m1 plane switches the lazy rotation off.
+ *   n_slots:        1 ... 65536 events resident
+ * n_items == 0 releases the buffers and stops the launches.  Every other call clears the slots.  RH_ERR_ARG (rh_last_error names the
+ * value): more than 16 items, an int32 plane or one the context does not hold, a kind other than 0 ... 3, n_slots out of range.  A
+ * refused allocation leaves the observer off.
+ *   rh_events_headers      hdr (n_slots, 6) int64
+ *   rh_events_download     the map of one item in one slot, n float64
+ *   rh_events_lost         *lost = 1 once a step found its slot unread
+ * All synchronise; RH_ERR_STATE before rh_events_configure (or after it released the buffers). */
+#define RH_EVENTS_MAX_SLOTS 65536
+int rh_events_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 PEAK, 2 FIRST, 3 LAST */, int n_items, int n_slots);
+int rh_events_headers(rh_ctx *ctx, int64_t *hdr /* (n_slots, 6) */, size_t bytes);
+int rh_events_download(rh_ctx *ctx, int item, int slot, double *host, size_t bytes);
+int rh_events_set_drained(rh_ctx *ctx, int64_t event_id);
+int rh_events_lost(rh_ctx *ctx, int *lost);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

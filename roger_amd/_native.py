@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 13  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 14  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -166,6 +166,11 @@ def load():
     lib.rh_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_scores_configure.argtypes = [vp, vp, vp, i32, vp, i32, i64, vp, i64, i64]
     lib.rh_scores_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
+    lib.rh_events_configure.argtypes = [vp, vp, vp, i32, i32]
+    lib.rh_events_headers.argtypes = [vp, vp, C.c_size_t]
+    lib.rh_events_download.argtypes = [vp, i32, i32, vp, C.c_size_t]
+    lib.rh_events_set_drained.argtypes = [vp, i64]
+    lib.rh_events_lost.argtypes = [vp, C.POINTER(C.c_int)]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -632,6 +637,7 @@ DECLARED_SYMBOLS = (
     "rh_totals_configure", "rh_totals_count", "rh_totals_read",
     "rh_zonal_configure", "rh_zonal_count", "rh_zonal_read",
     "rh_scores_configure", "rh_scores_read",
+    "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
 )
 
 
@@ -1025,6 +1031,41 @@ class Context:
         self._check(self._lib.rh_scores_read(self._h, moments.ctypes.data_as(C.c_void_p), moments.nbytes, closed.ctypes.data_as(C.c_void_p),
                                              closed.nbytes), "rh_scores_read")
         return moments, closed
+
+    # -- event outputs (rh_events_*) -----------------------------------------------------------------
+    def events_configure(self, names, kinds=(), n_slots=1):
+        """After every step of a rainfall event accumulate `names` (float64 planes; kinds: 0 sum, 1 peak of value / dt, 2 first, 3 last)
+        into the event's slot (event id mod n_slots) on the device.  No names: release the buffers and stop."""
+        names = list(names)
+        if len(kinds) != len(names):
+            raise ValueError(f"events_configure: {len(kinds)} kinds for {len(names)} items")
+        ids = (C.c_int * max(1, len(names)))(*[self.index[n] for n in names])
+        kd = (C.c_int * max(1, len(names)))(*[int(k) for k in kinds])
+        self._check(self._lib.rh_events_configure(self._h, ids, kd, len(names), int(n_slots) if names else 0), "rh_events_configure")
+        self._events_shape = (len(names), int(n_slots) if names else 0)   # (a refused configuration leaves the previous one)
+
+    def events_read(self, slots=None):
+        """(headers int64 (n_slots, 6): event id, steps, t0 of the first step, t1 of the last, steps of 600 s, steps of 3600 s -- -1 each
+        while untouched; values {slot: float64 (n_items, n)} of the `slots` asked for (None: every touched one); lost: a step found
+        its slot unread).  Synchronises."""
+        ni, ns = getattr(self, "_events_shape", (0, 0))
+        hdr = np.empty((ns, 6), dtype=np.int64)
+        self._check(self._lib.rh_events_headers(self._h, hdr.ctypes.data_as(C.c_void_p), hdr.nbytes), "rh_events_headers")
+        if slots is None:
+            slots = [s for s in range(ns) if hdr[s, 0] >= 0]
+        values = {}
+        for s in slots:
+            a = np.empty((ni, self.n), dtype=np.float64)
+            for j in range(ni):
+                self._check(self._lib.rh_events_download(self._h, j, int(s), a[j].ctypes.data_as(C.c_void_p), a[j].nbytes), "rh_events_download")
+            values[int(s)] = a
+        lost = C.c_int()
+        self._check(self._lib.rh_events_lost(self._h, C.byref(lost)), "rh_events_lost")
+        return hdr, values, bool(lost.value)
+
+    def events_set_drained(self, event_id):
+        """Publish the highest event id that has been read out: the slots of the events up to it may be taken again."""
+        self._check(self._lib.rh_events_set_drained(self._h, int(event_id)), "rh_events_set_drained")
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

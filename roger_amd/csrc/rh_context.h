@@ -135,6 +135,11 @@ struct rh_ctx {
     int scores_nitems = 0;           // 0: not configured, no k_scores launch
     int64_t scores_nintervals = 0;
     int scores_planes[16] = {};      // RH_SCORES_MAX_ITEMS
+    // event outputs (rh_events_configure): the slots' maps, their headers and the per-workgroup copies of the slots' ids
+    DevBuf<double> events_buf;
+    DevBuf<long long> events_hdr_buf, events_ids_buf;
+    int events_nitems = 0, events_nslots = 0;   // 0: not configured, no k_events launch
+    int events_planes[16] = {};      // RH_EVENTS_MAX_ITEMS
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

@@ -159,6 +159,17 @@ struct DevState {
     long long scores_interval, scores_t_first, scores_nintervals;
     int scores_nitems, scores_nseries;
     int scores_planes[16], scores_kinds[16];   // RH_SCORES_MAX_ITEMS; kinds: 0 SUM, 1 LAST
+
+    // event outputs (rh_events_configure; k_events in rh_events.h): events (slot, item, n) float64, event e in slot e mod events_nslots;
+    // events_hdr (slot, 6) {event id, steps, t0 of its first step, t1 of its last step, steps of 600 s, steps of 3600 s}, -1 each until a
+    // step touches the slot; events_ids (slot, events_nblk): the slot's event id once per workgroup of the launch (each workgroup reads
+    // and writes its own copy only).  events_drained: the highest event id the host has read out; events_running: the id of the event
+    // that was running when the observer was configured (0: none) -- it keeps t0 = -1; events_lost: a step found no free slot.
+    double *events;
+    long long *events_hdr, *events_ids;
+    long long events_drained, events_running;
+    int events_lost, events_nitems, events_nslots, events_nblk;
+    int events_planes[16], events_kinds[16];   // RH_EVENTS_MAX_ITEMS; kinds: 0 SUM, 1 PEAK, 2 FIRST, 3 LAST
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

@@ -1,6 +1,6 @@
 // rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
-// (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*) and the scores against observed series
-// (rh_scores_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
+// (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*), the scores against observed series
+// (rh_scores_*) and the event outputs (rh_events_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure): what the fused kernel must
 // leave in memory after every step, from the UNION of the accumulators', the points', the totals' and the zonal totals' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
@@ -26,6 +26,7 @@ static int observers_changed(rh_ctx *ctx) {
     add(ctx->totals_planes, ctx->totals_nplanes);
     add(ctx->zonal_planes, ctx->zonal_nplanes);
     add(ctx->scores_planes, ctx->scores_nitems);
+    add(ctx->events_planes, ctx->events_nitems);
     const int any = reads_sparse ? 1 : 0;
     HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
     HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
@@ -40,9 +41,9 @@ static int observers_changed(rh_ctx *ctx) {
 // workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values),
 // then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them -- then the zonal totals' row: a
 // workgroup per RH_BLOCK columns and one per zone (rh_zonal.h) -- then the scores' moments over all columns, on the accumulators' grid
-// (rh_scores.h).  after_fused: rh_control.h, k_diag.
+// (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h).  after_fused: rh_control.h, k_diag.
 static bool has_observers(const rh_ctx *ctx) {
-    return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems;
+    return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems;
 }
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
@@ -57,6 +58,7 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
         hipLaunchKernelGGL(k_zonal_finish, dim3(ctx->zonal_nzones), block, 0, ctx->stream, ctx->dev, after_fused);
     }
     if (ctx->scores_nitems) hipLaunchKernelGGL(k_scores, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    if (ctx->events_nitems) hipLaunchKernelGGL(k_events, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -625,6 +627,114 @@ int rh_scores_read(rh_ctx *ctx, double *moments, size_t moment_bytes, unsigned c
         return fail(ctx, RH_ERR_ARG, "rh_scores_read: size mismatch (n_items x 5 x n float64, n_intervals bytes)");
     HIPCHK(ctx, hipMemcpyAsync(moments, ctx->scores_buf, moment_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(closed, ctx->scores_closed_buf, closed_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+
+// ---- event outputs (include/roger_hip.h; the kernel and the rule: rh_events.h) ----
+static int events_alloc(rh_ctx *ctx, int n_items, int n_slots, int nblk) {
+    const size_t vb = (size_t)n_slots * n_items * ctx->n * sizeof(double), hb = (size_t)n_slots * 6 * sizeof(long long),
+                 ib = (size_t)n_slots * nblk * sizeof(long long);
+    HIPCHK(ctx, ctx->events_buf.alloc(vb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->events_buf, 0, vb, ctx->stream));
+    HIPCHK(ctx, ctx->events_hdr_buf.alloc(hb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->events_hdr_buf, 0xff, hb, ctx->stream));   // -1: never touched
+    HIPCHK(ctx, ctx->events_ids_buf.alloc(ib));
+    HIPCHK(ctx, hipMemsetAsync(ctx->events_ids_buf, 0xff, ib, ctx->stream));   // -1: no event's id
+    return RH_OK;
+}
+int rh_events_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, int n_slots) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_EVENTS_MAX_ITEMS)
+        return fail(ctx, RH_ERR_ARG, "rh_events_configure: n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_EVENTS_MAX_ITEMS) + ")");
+    const bool off = n_items == 0;
+    int plane_list[RH_EVENTS_MAX_ITEMS] = {}, kind_list[RH_EVENTS_MAX_ITEMS] = {};
+    if (!off) {
+        if (!planes || !kinds) return fail(ctx, RH_ERR_ARG, "rh_events_configure: null pointer");
+        if (n_slots < 1 || n_slots > RH_EVENTS_MAX_SLOTS)
+            return fail(ctx, RH_ERR_ARG, "rh_events_configure: n_slots = " + std::to_string(n_slots) + " (1 ... " + std::to_string(RH_EVENTS_MAX_SLOTS) + ")");
+        for (int j = 0; j < n_items; ++j) {
+            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+                return fail(ctx, RH_ERR_ARG, "rh_events_configure: plane id " + std::to_string(planes[j]) + " is not held by this context (plane ids must name float64 planes)");
+            if (PLANE_IS_INT[planes[j]])
+                return fail(ctx, RH_ERR_ARG, std::string("rh_events_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (plane ids must name float64 planes)");
+            if (kinds[j] < RH_EVENTS_SUM || kinds[j] > RH_EVENTS_LAST)
+                return fail(ctx, RH_ERR_ARG, "rh_events_configure: kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: PEAK, 2: FIRST, 3: LAST)");
+            plane_list[j] = planes[j];
+            kind_list[j] = kinds[j];
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that add into the old slots; the scalars below)
+    HIPCHK(ctx, ctx->events_buf.release());
+    HIPCHK(ctx, ctx->events_hdr_buf.release());
+    HIPCHK(ctx, ctx->events_ids_buf.release());
+    ctx->events_nitems = ctx->events_nslots = 0;
+    const int nblk = (int)grid_for(ctx->n) + 1;   // (the fused launch's grid with RH_TAIL_PRE)
+    if (int rc = off ? RH_OK : events_alloc(ctx, n_items, n_slots, nblk)) {   // refused: the event outputs are off
+        const std::string why = ctx->err;
+        (void)rh_events_configure(ctx, nullptr, nullptr, 0, 0);
+        return fail(ctx, rc, why);
+    }
+    // the event that is running now (the id of the last finished step) keeps t0 = -1; every later event has an id of at least the
+    // counter's, so everything below it counts as read out
+    long long running = 0, drained = 0;
+    if (!off) {
+        rh_scalars S;
+        HIPCHK(ctx, hipMemcpyAsync(&S, &ctx->dev->S, sizeof(S), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        running = (long long)S.event_id[1];
+        drained = (long long)(running > 0 ? running : S.event_id_counter) - 1;
+        ctx->events_nitems = n_items;
+        ctx->events_nslots = n_slots;
+    }
+    std::memcpy(ctx->events_planes, plane_list, sizeof(plane_list));
+    const int zero = 0;
+    HIPCHK(ctx, dev_put(ctx, &DevState::events, *ctx->events_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_hdr, *ctx->events_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_ids, *ctx->events_ids_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_drained, drained));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_running, running));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_lost, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_nitems, ctx->events_nitems));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_nslots, ctx->events_nslots));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_nblk, nblk));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_planes, plane_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_kinds, kind_list));
+    return observers_changed(ctx);   // synchronises: the sources above are locals
+}
+static int events_check(rh_ctx *ctx, const char *who) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->events_nitems) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_events_configure has not been called");
+    return RH_OK;
+}
+int rh_events_headers(rh_ctx *ctx, int64_t *hdr, size_t bytes) {
+    if (int rc = events_check(ctx, "rh_events_headers")) return rc;
+    if (!hdr || bytes != (size_t)ctx->events_nslots * 6 * sizeof(int64_t)) return fail(ctx, RH_ERR_ARG, "rh_events_headers: size mismatch (n_slots x 6 int64)");
+    HIPCHK(ctx, hipMemcpyAsync(hdr, ctx->events_hdr_buf, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_events_download(rh_ctx *ctx, int item, int slot, double *host, size_t bytes) {
+    if (int rc = events_check(ctx, "rh_events_download")) return rc;
+    if (item < 0 || item >= ctx->events_nitems || slot < 0 || slot >= ctx->events_nslots)
+        return fail(ctx, RH_ERR_ARG, "rh_events_download: item " + std::to_string(item) + " or slot " + std::to_string(slot) + " out of range (" +
+                                     std::to_string(ctx->events_nitems) + " items, " + std::to_string(ctx->events_nslots) + " slots)");
+    if (!host || bytes != (size_t)ctx->n * sizeof(double)) return fail(ctx, RH_ERR_ARG, "rh_events_download: size mismatch (n float64)");
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->events_buf + ((size_t)slot * ctx->events_nitems + item) * ctx->n, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_events_set_drained(rh_ctx *ctx, int64_t event_id) {
+    if (int rc = events_check(ctx, "rh_events_set_drained")) return rc;
+    const long long v = (long long)event_id;
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_drained, v));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (v is a stack local)
+    return RH_OK;
+}
+int rh_events_lost(rh_ctx *ctx, int *lost) {
+    if (int rc = events_check(ctx, "rh_events_lost")) return rc;
+    if (!lost) return fail(ctx, RH_ERR_ARG, "rh_events_lost: null pointer");
+    HIPCHK(ctx, hipMemcpyAsync(lost, &ctx->dev->events_lost, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }

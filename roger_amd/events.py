@@ -1,0 +1,189 @@
+"""Event outputs: one map per rainfall event and item -- the event's sum, its peak intensity, the value it started from, the value it
+ended with -- accumulated on the device after every step (include/roger_hip.h, rh_events_*; k_events in roger_amd/csrc/rh_events.h).
+The adaptive time stepping numbers the events (`event_id`); here the accumulators' slot is the event, not the day.  The event runoff
+coefficient of every column is `(q_hof + q_sof) / prec` of two or three "sum" items, without ten-minute output of the whole run.
+
+A setup script fills `state.events` in `set_diagnostics`:
+
+    state.events.items = [("prec", "sum"), ("q_hof", "sum"), ("q_sof", "sum"), ("q_sur", "peak"), ("theta_rz", "first")]
+    state.events.n_slots = 16                     # events resident on the device between two read-outs
+    state.events.base_output_path = ...           # as for the diagnostics
+
+and gets `<identifier>.events.nc`: dimensions event (unlimited), y and x; per event `event_id`, `event_start` and `event_end` (days, with
+`time_origin`; the start of its first and the end of its last step), `event_steps`, `event_steps_10min`, `event_steps_hourly`; per
+item a variable `<name>_<kind>` (event, y, x) float64.  The kinds: "sum" adds the value of every step of the event, "peak" keeps the
+largest value / dt in mm/h (a NaN is never taken over a number), "first" keeps the value after the event's first step, "last" the value
+after its last.
+
+An event is complete once a later step ran under another event id (0, between events, included), or at the end of run().  Completed
+events are read out after every round of device steps and after each step of the host loops, and their slots are handed back to the
+device.  The device overwrites no slot that has not been read: if more than `n_slots` events pass between two read-outs, the run stops
+with an error that names the remedy.  With several ranks a rank writes one file of its own for its block, named as the diagnostics
+name theirs.
+
+Start and restart.  An event that is already running when the observer is configured -- a run continued from a restart file written
+in mid-event -- is written with `event_start = -1`: its maps cover the steps from the configuration on.  The maps are NOT part of
+restart files."""
+import datetime
+import os
+
+import numpy as np
+
+from . import runtime_settings as rs
+from .points import DAY, claim_output_file, output_file_name
+
+MAX_ITEMS = 16                    # roger_amd/csrc/rh_events.h: RH_EVENTS_MAX_ITEMS
+MAX_SLOTS = 65536                 # include/roger_hip.h: RH_EVENTS_MAX_SLOTS
+KINDS = {"sum": 0, "peak": 1, "first": 2, "last": 3}
+WRITE_BYTES = 32 << 20            # maps drained since the last write beyond which the file is written (as points.py)
+
+
+class Events:
+    """`state.events`: what the script sets (items, n_slots, base_output_path) and the events drained so far."""
+
+    def __init__(self):
+        self.items = []
+        self.n_slots = 16
+        self.base_output_path = None
+        self.output_path = "{identifier}.events.nc"
+        self._on = False         # start() configured the device
+        self._items = []         # [(name, kind string)] as validated
+        self._hdr = []           # drained headers, (6,) int64 each
+        self._values = []        # drained maps, (n_items, n) float64 each
+        self._drained = None     # the highest event id read out (None: as the configuration left it)
+        self._last_id = 0        # the event id of the last step a host loop looked at
+        self._unwritten = 0
+        self._path = None
+
+    @property
+    def active(self):
+        return bool(self.items)
+
+    def get_output_file_name(self, state):
+        return output_file_name(self, state)
+
+
+def initialize(state):
+    """Validate what the script asked for (after set_diagnostics); the device is configured by `start`, once the event ids are known."""
+    ev = state.events
+    if not ev.active:
+        return
+    if state.settings.enable_offline_transport:
+        raise NotImplementedError("events: the offline transport model steps by the day and knows no rainfall events; the event "
+                                  "outputs belong to the SVAT / oneD step")
+    items = []
+    for item in ev.items:
+        if not isinstance(item, (tuple, list)) or len(item) != 2:
+            raise ValueError(f"events: item {item!r} (a pair (variable, kind), kind one of " + ", ".join(f'"{k}"' for k in KINDS) + ")")
+        v, kind = item
+        if kind not in KINDS:
+            raise ValueError(f"events: kind of {v!r} is {kind!r} (" + ", ".join(f'"{k}"' for k in KINDS) + ")")
+        meta = state.var_meta.get(v)
+        if meta is None or meta.plane is None or meta.dtype is not None:
+            raise NotImplementedError(f"events: {v!r} is not a float64 (x, y) variable of the device arena")
+        if (v, kind) in items:
+            raise ValueError(f"events: item ({v!r}, {kind!r}) is given twice")
+        items.append((v, kind))
+    if len(items) > MAX_ITEMS:
+        raise ValueError(f"events: {len(items)} items (at most {MAX_ITEMS})")
+    if not 1 <= int(ev.n_slots) <= MAX_SLOTS:
+        raise ValueError(f"events: n_slots = {ev.n_slots} (1 ... {MAX_SLOTS} events resident on the device)")
+    ev._items = items
+
+
+def start(state):
+    """Configure the device (after the restart file was read: an event that is running now keeps event_start = -1)."""
+    ev = state.events
+    if not ev.active or not ev._items:
+        return
+    state.variables.flush_to_device()
+    state.backend_context.events_configure([v for v, _ in ev._items], [KINDS[k] for _, k in ev._items], int(ev.n_slots))
+    ev._on, ev._hdr, ev._values, ev._drained, ev._unwritten = True, [], [], None, 0
+    ev._last_id = int(state.backend_context.get_scalars().event_id[1])
+    ev._path = claim_output_file(ev, state, "events")
+
+
+def drain(state, final=False, write=False):
+    """Read out the completed events: every resident event but the one the last step belonged to (final, the end of run(): that one
+    too).  write: the file is written now (otherwise when enough has been read out)."""
+    ev = state.events
+    if not ev._on:
+        return
+    ctx = state.backend_context
+    hdr, _, lost = ctx.events_read(slots=())
+    if lost:
+        raise RuntimeError(f"events: more than {int(ev.n_slots)} rainfall events passed between two read-outs and the device kept no "
+                           "slot for the last ones: raise state.events.n_slots (more slots), or call run_device() in shorter pieces")
+    current = 0 if final else int(ctx.get_scalars().event_id[1])
+    ev._last_id = current
+    done = sorted((int(hdr[s, 0]), s) for s in range(hdr.shape[0])
+                  if hdr[s, 0] > 0 and int(hdr[s, 0]) != current and (ev._drained is None or int(hdr[s, 0]) > ev._drained))
+    if done:
+        _, values, _ = ctx.events_read(slots=[s for _, s in done])
+        for e, s in done:
+            ev._hdr.append(hdr[s].copy())
+            ev._values.append(values[s])
+            ev._unwritten += values[s].nbytes
+        ev._drained = done[-1][0]
+        ctx.events_set_drained(ev._drained)
+    if final or write or ev._unwritten > WRITE_BYTES:
+        _write(state)
+
+
+def stepped(state):
+    """A host loop made one step: read out when the step ran under another event id than the one before it (an event ended)."""
+    ev = state.events
+    if not ev._on:
+        return
+    e = int(state.variables._get_scalars().event_id[1])
+    if e != ev._last_id:
+        if ev._last_id > 0:
+            drain(state)
+        ev._last_id = e
+
+
+def close(state):
+    """End of run(): the event that is still running counts as complete, and the file."""
+    drain(state, final=True)
+
+
+def _write(state):
+    """The whole file from the events held in memory, through roger_amd.nc4lite."""
+    ev = state.events
+    ev._unwritten = 0
+    if not ev._path:
+        return
+    from . import nc4lite
+    from .diagnostics import _UNITS
+
+    vs, settings = state.variables, state.settings
+    nxl, nyl = settings.nx // rs.num_proc[0], settings.ny // rs.num_proc[1]
+    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
+    hdr = np.stack(ev._hdr) if ev._hdr else np.zeros((0, 6), dtype=np.int64)
+    days = lambda t: np.where(t < 0, -1.0, t / float(DAY))   # noqa: E731  (-1: the event was running when the observer was configured)
+    time_attrs = {"units": "days", "time_origin": str(settings.time_origin)}
+    variables = {
+        "x": (("x",), x, {"long_name": "x", "units": "m"}),
+        "y": (("y",), y, {"long_name": "y", "units": "m"}),
+        "event_id": (("event",), hdr[:, 0].astype(np.int64), {"long_name": "event id of the adaptive time stepping", "units": ""}),
+        "event_start": (("event",), days(hdr[:, 2].astype(np.float64)), dict(time_attrs, long_name="start of the event's first step (-1: before the run was (re)started)")),
+        "event_end": (("event",), days(hdr[:, 3].astype(np.float64)), dict(time_attrs, long_name="end of the event's last step")),
+        "event_steps": (("event",), hdr[:, 1].astype(np.int64), {"long_name": "time steps of the event", "units": ""}),
+        "event_steps_10min": (("event",), hdr[:, 4].astype(np.int64), {"long_name": "ten-minute steps of the event", "units": ""}),
+        "event_steps_hourly": (("event",), hdr[:, 5].astype(np.int64), {"long_name": "hourly steps of the event", "units": ""}),
+    }
+    long_names = {"sum": "sum over the event", "peak": "peak intensity of the event", "first": "value after the event's first step",
+                  "last": "value after the event's last step"}
+    for j, (v, kind) in enumerate(ev._items):
+        a = np.stack([m[j].reshape(nxl, nyl).T for m in ev._values]) if ev._values else np.zeros((0, nyl, nxl))
+        unit = _UNITS.get(v, "")
+        if kind == "peak":
+            unit = "mm/h" if unit == "mm/dt" else (unit + "/h" if unit else "1/h")
+        elif kind == "sum" and unit == "mm/dt":
+            unit = "mm"
+        variables[f"{v}_{kind}"] = (("event", "y", "x"), np.ascontiguousarray(a), {"long_name": f"{v}: {long_names[kind]}", "units": unit})
+    os.makedirs(os.path.dirname(os.path.abspath(ev._path)), exist_ok=True)
+    nc4lite.write(ev._path, {"event": None, "y": len(y), "x": len(x)}, variables, {
+        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
+        "comment": "One record per rainfall event of the adaptive time stepping, accumulated on the device after every step.",
+        "setup_identifier": str(settings.identifier)})

@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
+from . import diagnostics, distributed, events, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -156,6 +156,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             totals.initialize(state)
             zonal_totals.initialize(state)
             scores.initialize(state)
+            events.initialize(state)
             sas_points.initialize(state)
             sas_totals.initialize(state)
             sas_zonal_totals.initialize(state)
@@ -165,6 +166,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             self.set_forcing_setup(state)
             restart.read_restart(state)   # roger/roger.py:324-326
             scores.start(state)           # (the clock is known: a continued run scores from the next interval boundary)
+            events.start(state)           # (the event ids are known: an event that is running now keeps event_start = -1)
             if offline and state.settings.warmup_done:
                 sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
                 sas_totals.start(state)
@@ -267,6 +269,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         points.stepped(state)    # the points' ring is drained every `capacity` step calls
         totals.stepped(state)    # ... and the totals'
         zonal_totals.stepped(state)
+        events.stepped(state)    # completed events are read out when the event id changes
         if rs.profile_mode:
             state.backend_context.sync()
             logger.info(" Time step took {:.2f}s".format(state.timers["main"].last_time))
@@ -406,7 +409,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(state._diag_active) or state.points.active or state.totals.active or state.zonal_totals.active
+        diag = bool(state._diag_active) or state.points.active or state.totals.active or state.zonal_totals.active or state.events.active
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -462,6 +465,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         totals.close(self.state)
         zonal_totals.close(self.state)
         scores.close(self.state)
+        events.close(self.state)
         sas_points.close(self.state)
         sas_totals.close(self.state)
         sas_zonal_totals.close(self.state)
@@ -534,5 +538,6 @@ class RogerSetup(metaclass=abc.ABCMeta):
         points.drain(self.state, final=final)
         totals.drain(self.state, final=final)
         zonal_totals.drain(self.state, final=final)
+        events.drain(self.state, write=final)   # (completed events; the running one stays on the device until it ends or run() does)
         if self.state._diag_active:
             diagnostics.output(self.state, final=final)

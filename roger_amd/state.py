@@ -357,6 +357,9 @@ class RogerState:
         from .scores import Scores
 
         self.scores = Scores()              # per-column scores against observed series, moments on the device (roger_amd/scores.py)
+        from .events import Events
+
+        self.events = Events()              # per-column sums, peaks, first and last values of every rainfall event (roger_amd/events.py)
         from .sas_totals import TransportTotals
 
         self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
