@@ -221,22 +221,23 @@ def split(names):
     return tuple(v for v in names if KIND_OF[v] == SUM), tuple(v for v in names if KIND_OF[v] == LAST)
 
 
-def configure(ctx, rec, which, names=VARS, t_first=0, seed=0):
-    """Configure the observers named in `which` on `names`; returns the scores' observations (None without scores)."""
+def configure(ctx, rec, which, names=VARS, t_first=0, seed=0, cells=None, mask=None, zones=None, series=None):
+    """Configure the observers named in `which` on `names`; returns the scores' observations (None without scores).  cells, mask,
+    zones = (map, number of zones), series: the context's own instead of the grid's (a rank's block of a global domain)."""
     n = ctx.n
     obs = None
     if "diag" in which:
         rate, collect = split(names)
         ctx.diag_configure(rate=rate, collect=collect, n_slots=n_days(rec))
     if "points" in which:
-        ctx.points_configure(POINTS[(ctx.nx, ctx.ny)], names)
+        ctx.points_configure(POINTS[(ctx.nx, ctx.ny)] if cells is None else cells, names)
     if "totals" in which:
-        ctx.totals_configure(names, mask_of(n))
+        ctx.totals_configure(names, mask_of(n) if mask is None else mask)
     if "zonal" in which:
-        ctx.zonal_configure(names, *zones_of(n))
+        ctx.zonal_configure(names, *(zones_of(n) if zones is None else zones))
     if "scores" in which:
         obs = obs_of(rec, names, t_first, seed)
-        ctx.scores_configure(names, [KIND_OF[v] for v in names], obs, series_of(n)[0], DAY, t_first)
+        ctx.scores_configure(names, [KIND_OF[v] for v in names], obs, series_of(n)[0] if series is None else series, DAY, t_first)
     return obs
 
 
@@ -281,9 +282,9 @@ def assert_diag(ctx, rec, names, first=0, stop=None, what="", n_slots=None):
     return acc
 
 
-def assert_points(ctx, rec, names, first=0, stop=None, what=""):
+def assert_points(ctx, rec, names, first=0, stop=None, what="", cells=None):
     stop = len(rec.hdr) if stop is None else stop
-    cells = list(POINTS[(ctx.nx, ctx.ny)])
+    cells = list(POINTS[(ctx.nx, ctx.ny)] if cells is None else cells)
     assert ctx.points_count() == stop - first, (what, ctx.points_count(), stop - first)
     hdr, vals = ctx.points_read(0, stop - first)
     np.testing.assert_array_equal(hdr, rec.hdr[first:stop], err_msg=f"{what}: headers of the points' rows")
@@ -306,17 +307,17 @@ def _assert_sum_min_max(got, want, names, axis_v, what):
             assert ok.all(), (what, v, stat, "at", np.argwhere(~ok)[:5], g[..., k][~ok][:3], w[..., k][~ok][:3])
 
 
-def assert_totals(ctx, rec, names, want, first=0, stop=None, what=""):
+def assert_totals(ctx, rec, names, want, first=0, stop=None, what="", mask=None):
     stop = len(rec.hdr) if stop is None else stop
-    assert ctx.totals_count() == (stop - first, int(mask_of(ctx.n).sum())), (what, ctx.totals_count())
+    assert ctx.totals_count() == (stop - first, int((mask_of(ctx.n) if mask is None else np.asarray(mask)).sum())), (what, ctx.totals_count())
     hdr, vals = ctx.totals_read(0, stop - first)
     np.testing.assert_array_equal(hdr, rec.hdr[first:stop], err_msg=f"{what}: headers of the totals' rows")
     _assert_sum_min_max(vals, want, names, 1, f"{what}: totals")
 
 
-def assert_zonal(ctx, rec, names, want, first=0, stop=None, what=""):
+def assert_zonal(ctx, rec, names, want, first=0, stop=None, what="", zones=None):
     stop = len(rec.hdr) if stop is None else stop
-    zone, nz = zones_of(ctx.n)
+    zone, nz = zones_of(ctx.n) if zones is None else zones
     rows, cells = ctx.zonal_count()
     assert rows == stop - first and list(cells) == list(np.bincount(zone[zone >= 0], minlength=nz)), (what, rows, cells)
     hdr, vals = ctx.zonal_read(0, stop - first)
@@ -324,8 +325,8 @@ def assert_zonal(ctx, rec, names, want, first=0, stop=None, what=""):
     _assert_sum_min_max(vals, want, names, 2, f"{what}: zonal totals")
 
 
-def want_scores(rec, names, obs, n, t_first=0, first=0, stop=None):
-    h = HostScores([KIND_OF[v] for v in names], obs, n, series_of(n)[0], DAY, t_first)
+def want_scores(rec, names, obs, n, t_first=0, first=0, stop=None, series=None):
+    h = HostScores([KIND_OF[v] for v in names], obs, n, series_of(n)[0] if series is None else series, DAY, t_first)
     for k in range(first, len(rec.hdr) if stop is None else stop):
         t1, dt = int(rec.hdr[k, 1]), int(rec.hdr[k, 2])
         h.add(t1 - dt, t1, [rec.planes[v][k] for v in names])
@@ -340,20 +341,23 @@ def assert_scores(ctx, want, what=""):
     assert ok.all(), (what, "scores (item, moment, column)", np.argwhere(~ok)[:5], moments[~ok][:3], want.moments[~ok][:3])
 
 
-def assert_observers(ctx, rec, which, names, obs, totals=None, zonal=None, first=0, stop=None, t_first=0, what=""):
+def assert_observers(ctx, rec, which, names, obs, totals=None, zonal=None, first=0, stop=None, t_first=0, what="", cells=None, mask=None,
+                     zones=None, series=None):
     """Every observer of `which` against its restatement over rows first ... stop - 1 of the record.  totals / zonal: the expected rows
-    if they are at hand (reference_totals / reference_zonal), formed here otherwise."""
+    if they are at hand (reference_totals / reference_zonal), formed here otherwise.  cells, mask, zones, series: as `configure`."""
     n = ctx.n
     if "diag" in which:
         assert_diag(ctx, rec, names, first, stop, what)
     if "points" in which:
-        assert_points(ctx, rec, names, first, stop, what)
+        assert_points(ctx, rec, names, first, stop, what, cells)
     if "totals" in which:
-        assert_totals(ctx, rec, names, want_totals(rec, names, mask_of(n), first, stop) if totals is None else totals, first, stop, what)
+        m = mask_of(n) if mask is None else mask
+        assert_totals(ctx, rec, names, want_totals(rec, names, m, first, stop) if totals is None else totals, first, stop, what, mask)
     if "zonal" in which:
-        assert_zonal(ctx, rec, names, want_zonal(rec, names, *zones_of(n), first, stop) if zonal is None else zonal, first, stop, what)
+        z = zones_of(n) if zones is None else zones
+        assert_zonal(ctx, rec, names, want_zonal(rec, names, *z, first, stop) if zonal is None else zonal, first, stop, what, zones)
     if "scores" in which:
-        assert_scores(ctx, want_scores(rec, names, obs, n, t_first, first, stop), what)
+        assert_scores(ctx, want_scores(rec, names, obs, n, t_first, first, stop, series), what)
 
 
 def read_observers(ctx, rec, names=VARS):

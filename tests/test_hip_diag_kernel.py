@@ -182,6 +182,64 @@ def test_accumulated_m1_planes_switch_the_lazy_rotation_off():
     single.close()
 
 
+@pytest.mark.parametrize("lateral", [False, True])
+@pytest.mark.parametrize("nx,ny", GRIDS[:2])
+def test_one_rank_communicator(nx, ny, lateral):
+    """(c2) rh_run_steps_dist with a one-rank RCCL communicator: every slot equals the reference fed by single steps (more than one
+    rank: tests/test_hip_ranks_observers.py)."""
+    from roger_amd import _native as native
+
+    interval, n_slots = INTERVALS[0]
+    ref, _ = stepwise(nx, ny, lateral, interval, n_slots)
+    ctx, _ = make_ctx(nx, ny, lateral)
+    ctx.comm_init(native.comm_unique_id(), 1, 0)
+    ctx.diag_configure(rate=RATE, collect=COLLECT, n_slots=n_slots)
+    ctx.diag_set_interval(interval)
+    ctx.run_steps_dist(len(ref.log))
+    assert ctx.sparse_steps() > 0
+    assert_all_slots(ctx, ref, f"rh_run_steps_dist, one rank, {nx} x {ny} lateral={lateral}")
+    ctx.close()
+
+
+def test_routed_steps(monkeypatch):
+    """(c3) The routed step on the smallest routing golden (4 x 6), hourly slots: rh_step_routed step by step against the host
+    accumulator fed the context's own planes after every step, then the device-driven routed steps of rh_run_steps (and
+    RH_ROUTED_BY_ROUTINE=1) against those slots.  140 steps: 120 of ten minutes, four hourly, a daily one, fifteen of ten minutes."""
+    import hip_util as H
+    from golden_util import ROUTING_CASES, load_case
+    from test_hip_routing import routed_ctx
+
+    from roger_amd import _native as native
+
+    g, names_all, forcing = load_case(ROUTING_CASES[0])
+    rate, collect, nsteps, interval, n_slots = ("prec", "q_sur_out", "aet", "q_ss"), ("S", "z0"), 140, 3600, 5
+    ctx = routed_ctx(native, g, names_all)
+    ctx.diag_configure(rate=rate, collect=collect, n_slots=n_slots)
+    ctx.diag_set_interval(interval)
+    ref = HostAccumulator(rate, collect, n_slots, ctx.n, interval=interval)
+    drv = H.HipForcingDriver(ctx, forcing)
+    for k in range(nsteps):
+        ctx.step_routed(drv.before_step())
+        s = ctx.get_scalars()
+        slot, _ = feed(ref, ctx, s)     # (sanity_ok is not asserted: the reference's own water balance check fails on routed runs)
+        assert_slot(ctx, ref, slot, f"rh_step_routed step {k + 1}")
+    assert ref.step_classes() == {600, 3600, 86400} and ref.slots_reused() and ref.intervals_never_started() and all(np.any(ref.data[v] != 0) for v in rate + collect)
+    assert_all_slots(ctx, ref, "rh_step_routed")
+    ctx.close()
+    for by_routine in (False, True):
+        if by_routine:
+            monkeypatch.setenv("RH_ROUTED_BY_ROUTINE", "1")
+        else:
+            monkeypatch.delenv("RH_ROUTED_BY_ROUTINE", raising=False)
+        ctx = routed_ctx(native, g, names_all)
+        ctx.set_forcing_series(forcing)
+        ctx.diag_configure(rate=rate, collect=collect, n_slots=n_slots)
+        ctx.diag_set_interval(interval)
+        ctx.run_steps(nsteps)
+        assert_all_slots(ctx, ref, f"rh_run_steps on a routing context, by_routine={by_routine}")
+        ctx.close()
+
+
 def same_interval_steps(ctx, drv, ref, iv):
     """Steps until the next one would begin in another interval; yields (k, slot, planes of the step, scalars)."""
     s = ctx.get_scalars()

@@ -260,6 +260,60 @@ def test_per_cell_forcing(nx, ny, front, monkeypatch):
     ctx.close()
 
 
+@pytest.mark.parametrize("nx,ny,lateral", CASES[2:])
+def test_one_rank_communicator(nx, ny, lateral):
+    """7. rh_run_steps_dist with a one-rank RCCL communicator (more than one rank: tests/test_hip_ranks_observers.py)."""
+    from roger_amd import _native as native
+
+    ref = reference(nx, ny, lateral)
+    ctx, _ = configured(nx, ny, lateral)
+    ctx.comm_init(native.comm_unique_id(), 1, 0)
+    ctx.run_steps_dist(NSTEPS)
+    assert ctx.sparse_steps() > 0
+    assert_state(ctx, whole(ref), f"rh_run_steps_dist, one rank, {nx} x {ny} lateral={lateral}")
+    ctx.close()
+
+
+def test_routed_steps(monkeypatch):
+    """8. The routed step on the smallest routing golden (4 x 6): rh_step_routed step by step against the restatement of the context's
+    own planes and scalars after every step, then the device-driven routed steps of rh_run_steps (and RH_ROUTED_BY_ROUTINE=1) against
+    that state.  140 steps: event 1 (120 steps of ten minutes), four hourly steps and a daily one outside, the beginning of event 2."""
+    import hip_util as H
+    from golden_util import ROUTING_CASES, load_case
+    from test_hip_routing import routed_ctx
+
+    from roger_amd import _native as native
+
+    g, names_all, forcing = load_case(ROUTING_CASES[0])
+    names, kinds, nsteps = ("prec", "q_sur_out", "aet", "S", "q_ss", "z0"), (SUM, SUM, PEAK, FIRST, SUM, LAST), 140
+    ctx = routed_ctx(native, g, names_all)
+    ctx.events_configure(names, kinds, 4)
+    h = HostEvents(kinds, ctx.n, 4)
+    drv = H.HipForcingDriver(ctx, forcing)
+    outside = set()
+    for _ in range(nsteps):
+        ctx.step_routed(drv.before_step())
+        s = ctx.get_scalars()
+        h.add(s.event_id[1], s.time - s.dt_secs, s.time, s.dt, [ctx.download(v) for v in names])
+        if s.event_id[1] == 0:
+            outside.add(int(s.dt_secs))
+    assert (h.hdr[1:3, 0] == (1, 2)).all() and h.hdr[1, 4] == 120 and outside == {3600, 86400} and not h.lost
+    assert all(np.any(h.values[:, j] != 0) for j in range(len(names))), "a routed item never held a value"
+    assert_state(ctx, h, "rh_step_routed")
+    ctx.close()
+    for by_routine in (False, True):
+        if by_routine:
+            monkeypatch.setenv("RH_ROUTED_BY_ROUTINE", "1")
+        else:
+            monkeypatch.delenv("RH_ROUTED_BY_ROUTINE", raising=False)
+        ctx = routed_ctx(native, g, names_all)
+        ctx.set_forcing_series(forcing)
+        ctx.events_configure(names, kinds, 4)
+        ctx.run_steps(nsteps)
+        assert_state(ctx, h, f"rh_run_steps on a routing context, by_routine={by_routine}")
+        ctx.close()
+
+
 def test_script_on_the_device_writes_what_the_routine_by_routine_step_writes(tmp_path, monkeypatch):
     """End to end: a RogerSetup script with the reference's hook bodies and `state.events` writes the same `.events.nc` on the device
     rounds (one round holds the whole run: sixteen slots) as the same script stepped routine by routine with ONE slot (read out when an
