@@ -72,6 +72,19 @@ static Switches read_switches(const rh_config &cfg) {
     return s;
 }
 
+// A ring of `cap` rows on the device and the rows' headers (3 int64 each) beside it: what the points, the totals and the zonal totals
+// record into after every step.  cap 0: the observer is off.
+struct ObsRing {
+    DevBuf<double> buf;
+    DevBuf<long long> hdr_buf;
+    int64_t cap = 0;
+    hipError_t release() {
+        cap = 0;
+        const hipError_t e = buf.release(), h = hdr_buf.release();
+        return e != hipSuccess ? e : h;
+    }
+};
+
 struct rh_ctx {
     Stream stream;                   // first member: destroyed last, after everything that was enqueued on it has been released
     rh_config cfg = {};
@@ -96,7 +109,7 @@ struct rh_ctx {
     DeviceHolds held;
     Switches sw;                     // the environment as rh_create found it
     int n_groups = 1;                // fused kernel: completion groups (about 64 workgroups each, at most RH_DONE_GROUPS)
-    bool obs_reads_m1 = false;       // an observer (accumulators, points, totals) was given an X_m1 plane: the fused kernel does not skip those stores
+    bool obs_reads_m1 = false;       // one of the six observers was given an X_m1 plane: the fused kernel does not skip those stores
     bool obs_reads_sparse = false;   // an observer was given a plane the sparse kernel leaves out (its KEEP variant stores those); both
                                      // formed by observers_changed from the union of the observers' planes, and by nobody else
     int64_t t_end = -1;              // rh_set_time_limit (host copy of DevState::t_end)
@@ -106,25 +119,22 @@ struct rh_ctx {
     long long diag_interval = 86400;
     int diag_n = 0, diag_slots = 0;
     int diag_planes[32] = {};        // host copy of DevState::diag_planes (diag_n of them)
-    // time series at observation columns (rh_points_configure): the ring of points_cap rows and its headers
-    DevBuf<double> points_buf;
-    DevBuf<long long> points_hdr_buf;
+    // time series at observation columns (rh_points_configure): the ring and its headers
+    ObsRing points;
     int points_ncells = 0, points_nplanes = 0;   // both 0: not configured, no k_points launch
-    int64_t points_cap = 0;
     int points_planes[RH_POINTS_MAX_PLANES] = {};
     // catchment totals (rh_totals_configure): the ring and its headers, the tiles' partials, the mask (not held: every column)
-    DevBuf<double> totals_buf, totals_part_buf;
-    DevBuf<long long> totals_hdr_buf;
+    ObsRing totals;
+    DevBuf<double> totals_part_buf;
     DevBuf<unsigned char> totals_mask_buf;
     int totals_nplanes = 0;          // 0: not configured, no k_totals_* launch
-    int64_t totals_cap = 0, totals_ncells = 0;   // rows resident; columns inside the mask
+    int64_t totals_ncells = 0;       // columns inside the mask
     int totals_planes[RH_POINTS_MAX_PLANES] = {};
     // zonal totals (rh_zonal_configure): the ring and its headers, the (tile, zone) partials, the zone map and the index over it
-    DevBuf<double> zonal_buf, zonal_part_buf;
-    DevBuf<long long> zonal_hdr_buf;
+    ObsRing zonal;
+    DevBuf<double> zonal_part_buf;
     DevBuf<int> zonal_index_buf;     // zone[n], tile_ptr[ntiles + 1], tile_zone[S], acc_ptr[Z * 256 + 1], acc_slot[S] in one allocation
     int zonal_nplanes = 0, zonal_nzones = 0;   // 0: not configured, no k_zonal_* launch
-    int64_t zonal_cap = 0;
     int zonal_planes[RH_POINTS_MAX_PLANES] = {};
     std::vector<int64_t> zonal_ncells;         // columns of every zone on this rank
     // scores against observed series (rh_scores_configure): the moments, the observations, the series map (not held: every column
@@ -134,12 +144,12 @@ struct rh_ctx {
     DevBuf<unsigned char> scores_closed_buf;
     int scores_nitems = 0;           // 0: not configured, no k_scores launch
     int64_t scores_nintervals = 0;
-    int scores_planes[16] = {};      // RH_SCORES_MAX_ITEMS
+    int scores_planes[RH_SCORES_MAX_ITEMS] = {};
     // event outputs (rh_events_configure): the slots' maps, their headers and the per-workgroup copies of the slots' ids
     DevBuf<double> events_buf;
     DevBuf<long long> events_hdr_buf, events_ids_buf;
     int events_nitems = 0, events_nslots = 0;   // 0: not configured, no k_events launch
-    int events_planes[16] = {};      // RH_EVENTS_MAX_ITEMS
+    int events_planes[RH_EVENTS_MAX_ITEMS] = {};
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

@@ -1,9 +1,13 @@
 // rh_host.h -- host-side owners of what a context holds on the device (roger_hip.hip, rh_sas.hip): each releases what it holds in
-// its destructor, so a context is torn down by `delete ctx` and a member that was never allocated costs nothing.  Host code only.
+// its destructor, so a context is torn down by `delete ctx` and a member that was never allocated costs nothing; and the rules of a
+// ring of rows that the observers of both contexts share (at the end).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
+#include <cstdint>
+#include <string>
 #include <vector>
 
 // One hipMalloc allocation, move-only.  Converts to the pointer it holds, so it is passed to HIP calls and kernels like one.
@@ -133,3 +137,36 @@ struct EventPool {
         return hipSuccess;
     }
 };
+
+// ---- a ring of rows: row r of `total` recorded ones lives in slot r mod cap, the last cap of them are resident.  Neither context type
+// appears here, so both libraries' observers share these; each reports a refusal through its own fail / sfail.
+// The refusal of a capacity that a configure call was given, behind `prefix` ("<function>: "), or an empty string.  max_rows: 0 where
+// the caller bounds the ring's bytes itself.
+static inline std::string ring_capacity_refusal(const std::string &prefix, int64_t capacity, int64_t max_rows) {
+    if (capacity < 1) return prefix + "capacity = " + std::to_string(capacity) + " (at least one row)";
+    if (max_rows && capacity > max_rows) return prefix + "capacity = " + std::to_string(capacity) + " rows is beyond any device";
+    return std::string();
+}
+// The refusal of a read of rows [first_row, first_row + n_rows) by the function `who`, or an empty string: the rows are recorded and
+// still resident, or there are none.
+static inline std::string ring_range_refusal(const char *who, int64_t first_row, int64_t n_rows, int64_t total, int64_t cap) {
+    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
+        return std::string(who) + ": rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
+               " have not been recorded (" + std::to_string(total) + " rows so far)";
+    if (n_rows && first_row < total - cap)
+        return std::string(who) + ": rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
+               " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " + std::to_string(total) + " rows)";
+    return std::string();
+}
+// The at most two pieces of an accepted range -- it may straddle the ring's wrap: piece(done, slot, m) for m rows from slot `slot` on,
+// `done` rows into the range; the first piece that returns non-zero ends the walk with that value.
+template <class F>
+static inline int ring_pieces(int64_t first_row, int64_t n_rows, int64_t cap, F &&piece) {
+    for (int64_t done = 0; done < n_rows;) {
+        const int64_t slot = (first_row + done) % cap;
+        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
+        if (const int rc = piece(done, slot, m)) return rc;
+        done += m;
+    }
+    return 0;
+}

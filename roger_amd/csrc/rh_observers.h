@@ -2,10 +2,11 @@
 // (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*), the scores against observed series
 // (rh_scores_*) and the event outputs (rh_events_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
 #pragma once
-// The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure): what the fused kernel must
-// leave in memory after every step, from the UNION of the accumulators', the points', the totals' and the zonal totals' planes.  A plane the sparse kernel leaves out -- a pure output, or one of the
-// five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in DevState::keep: the KEEP
-// variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
+// The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure, rh_scores_configure,
+// rh_events_configure): what the fused kernel must leave in memory after every step, from the UNION of the planes of all six -- the
+// accumulators, the points, the totals, the zonal totals, the scores and the event outputs.  A plane the sparse kernel leaves out -- a
+// pure output, or one of the five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in
+// DevState::keep: the KEEP variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
 static int observers_changed(rh_ctx *ctx) {
     unsigned long long keep[(RH_NPLANES + 63) / 64] = {};
     bool reads_sparse = false, reads_m1 = false;
@@ -60,6 +61,44 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     if (ctx->scores_nitems) hipLaunchKernelGGL(k_scores, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->events_nitems) hipLaunchKernelGGL(k_events, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     CHECK_LAUNCH(ctx);
+    return RH_OK;
+}
+
+// ---- what the configure and the read calls below share; the rules of a ring itself are rh_host.h's ----
+// `planes` into `out`: every id names a plane that this context holds, and a float64 one.  prefix: "<function>: "; tail: FLOAT64_IDS
+// for the scores and the event outputs, whose texts end in it
+static const char *const FLOAT64_IDS = " (plane ids must name float64 planes)";
+static int check_planes(rh_ctx *ctx, const std::string &prefix, const int *planes, int n, int *out, const char *tail = nullptr) {
+    for (int j = 0; j < n; ++j) {
+        if (planes[j] < 0 || planes[j] >= ctx->planes_held)
+            return fail(ctx, RH_ERR_ARG, prefix + "plane id " + std::to_string(planes[j]) + " is not held by this context" + (tail ? tail : ""));
+        if (PLANE_IS_INT[planes[j]])
+            return fail(ctx, RH_ERR_ARG, prefix + "plane " + PLANE_NAMES[planes[j]] + " is int32" + (tail ? tail : " (float64 planes only)"));
+        out[j] = planes[j];
+    }
+    return RH_OK;
+}
+static int check_capacity(rh_ctx *ctx, const std::string &prefix, int64_t capacity) {
+    const std::string why = ring_capacity_refusal(prefix, capacity, (int64_t)1 << 40);
+    return why.empty() ? RH_OK : fail(ctx, RH_ERR_ARG, why);
+}
+// the rows recorded into `ring` so far (DevState::X_rows), for the function `who`; RH_ERR_STATE unless `configure` has switched it on
+static int ring_rows(rh_ctx *ctx, const char *who, const ObsRing &ring, const char *configure, long long DevState::*member, long long *rows) {
+    if (!ring.cap) return fail(ctx, RH_ERR_STATE, std::string(who) + ": " + configure + " has not been called");
+    HIPCHK(ctx, hipMemcpyAsync(rows, &(ctx->dev.get()->*member), sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+// the rows of an accepted range, nv values each, and their headers to the host.  Synchronises.
+static int ring_download(rh_ctx *ctx, const ObsRing &ring, size_t nv, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values) {
+    const int rc = ring_pieces(first_row, n_rows, ring.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
+        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ring.buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ring.hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        return RH_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
 
@@ -187,15 +226,8 @@ int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const in
     int plane_list[RH_POINTS_MAX_PLANES] = {};
     if (!off) {
         if (!cells || !planes) return fail(ctx, RH_ERR_ARG, "rh_points_configure: null pointer");
-        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_points_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
-        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_points_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
-        for (int j = 0; j < n_planes; ++j) {
-            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
-                return fail(ctx, RH_ERR_ARG, "rh_points_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
-            if (PLANE_IS_INT[planes[j]])
-                return fail(ctx, RH_ERR_ARG, std::string("rh_points_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
-            plane_list[j] = planes[j];
-        }
+        if (int rc = check_capacity(ctx, "rh_points_configure: ", capacity)) return rc;
+        if (int rc = check_planes(ctx, "rh_points_configure: ", planes, n_planes, plane_list)) return rc;
         std::vector<int64_t> seen(cells, cells + n_cells);
         std::sort(seen.begin(), seen.end());
         for (int c = 0; c < n_cells; ++c) {
@@ -206,22 +238,20 @@ int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const in
         }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
-    HIPCHK(ctx, ctx->points_buf.release());
-    HIPCHK(ctx, ctx->points_hdr_buf.release());
+    HIPCHK(ctx, ctx->points.release());
     ctx->points_ncells = ctx->points_nplanes = 0;
-    ctx->points_cap = 0;
     if (!off) {
         const size_t nv = (size_t)n_cells * n_planes;
-        HIPCHK(ctx, ctx->points_buf.alloc((size_t)capacity * nv * sizeof(double)));
-        HIPCHK(ctx, ctx->points_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        HIPCHK(ctx, ctx->points.buf.alloc((size_t)capacity * nv * sizeof(double)));
+        HIPCHK(ctx, ctx->points.hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
         ctx->points_ncells = n_cells;
         ctx->points_nplanes = n_planes;
-        ctx->points_cap = capacity;
+        ctx->points.cap = capacity;
         std::memcpy(ctx->points_planes, plane_list, sizeof(plane_list));
     }
-    const long long zero = 0, cap = (long long)ctx->points_cap;
-    HIPCHK(ctx, dev_put(ctx, &DevState::points, *ctx->points_buf.addr()));
-    HIPCHK(ctx, dev_put(ctx, &DevState::points_hdr, *ctx->points_hdr_buf.addr()));
+    const long long zero = 0, cap = (long long)ctx->points.cap;
+    HIPCHK(ctx, dev_put(ctx, &DevState::points, *ctx->points.buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::points_hdr, *ctx->points.hdr_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::points_rows, zero));
     HIPCHK(ctx, dev_put(ctx, &DevState::points_cap, cap));
     HIPCHK(ctx, dev_put(ctx, &DevState::points_ncells, ctx->points_ncells));
@@ -230,45 +260,24 @@ int rh_points_configure(rh_ctx *ctx, const int64_t *cells, int n_cells, const in
     HIPCHK(ctx, dev_put(ctx, &DevState::points_cells, cell_list));
     return observers_changed(ctx);   // synchronises: the sources above are stack locals
 }
-static int points_rows(rh_ctx *ctx, const char *who, long long *rows) {
-    if (!ctx->points_ncells) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_points_configure has not been called");
-    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->points_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RH_OK;
-}
 int rh_points_count(rh_ctx *ctx, int64_t *rows_total) {
     if (!ctx) return RH_ERR_ARG;
     if (!rows_total) return fail(ctx, RH_ERR_ARG, "rh_points_count: null pointer");
     long long rows = 0;
-    if (int rc = points_rows(ctx, "rh_points_count", &rows)) return rc;
+    if (int rc = ring_rows(ctx, "rh_points_count", ctx->points, "rh_points_configure", &DevState::points_rows, &rows)) return rc;
     *rows_total = (int64_t)rows;
     return RH_OK;
 }
 int rh_points_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
     if (!ctx) return RH_ERR_ARG;
     long long total = 0;
-    if (int rc = points_rows(ctx, "rh_points_read", &total)) return rc;
+    if (int rc = ring_rows(ctx, "rh_points_read", ctx->points, "rh_points_configure", &DevState::points_rows, &total)) return rc;
     const size_t nv = (size_t)ctx->points_ncells * ctx->points_nplanes;
-    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
-        return fail(ctx, RH_ERR_ARG, "rh_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
-                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
-    if (n_rows && first_row < total - ctx->points_cap)
-        return fail(ctx, RH_ERR_ARG, "rh_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->points_cap - 1) +
-                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->points_cap) + " of " +
-                                     std::to_string(total) + " rows)");
+    const std::string why = ring_range_refusal("rh_points_read", first_row, n_rows, total, ctx->points.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
     if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
         return fail(ctx, RH_ERR_ARG, "rh_points_read: size mismatch (n_rows x n_planes x n_cells float64)");
-    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
-        const int64_t slot = (first_row + done) % ctx->points_cap;
-        const int64_t m = std::min<int64_t>(n_rows - done, ctx->points_cap - slot);
-        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->points_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        done += m;
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RH_OK;
+    return ring_download(ctx, ctx->points, nv, first_row, n_rows, hdr, values);
 }
 
 // ---- catchment totals (include/roger_hip.h) ----
@@ -281,15 +290,8 @@ int rh_totals_configure(rh_ctx *ctx, const unsigned char *mask, const int *plane
     int64_t ncells = ctx->n;
     if (!off) {
         if (!planes) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: null pointer");
-        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
-        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_totals_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
-        for (int j = 0; j < n_planes; ++j) {
-            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
-                return fail(ctx, RH_ERR_ARG, "rh_totals_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
-            if (PLANE_IS_INT[planes[j]])
-                return fail(ctx, RH_ERR_ARG, std::string("rh_totals_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
-            plane_list[j] = planes[j];
-        }
+        if (int rc = check_capacity(ctx, "rh_totals_configure: ", capacity)) return rc;
+        if (int rc = check_planes(ctx, "rh_totals_configure: ", planes, n_planes, plane_list)) return rc;
         if (mask) {
             ncells = 0;
             for (int64_t i = 0; i < ctx->n; ++i) ncells += mask[i] != 0;
@@ -297,30 +299,29 @@ int rh_totals_configure(rh_ctx *ctx, const unsigned char *mask, const int *plane
         }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
-    HIPCHK(ctx, ctx->totals_buf.release());
-    HIPCHK(ctx, ctx->totals_hdr_buf.release());
+    HIPCHK(ctx, ctx->totals.release());
     HIPCHK(ctx, ctx->totals_part_buf.release());
     HIPCHK(ctx, ctx->totals_mask_buf.release());
     ctx->totals_nplanes = 0;
-    ctx->totals_cap = ctx->totals_ncells = 0;
+    ctx->totals_ncells = 0;
     const int ntiles = (int)grid_for(ctx->n);
     if (!off) {
-        HIPCHK(ctx, ctx->totals_buf.alloc((size_t)capacity * n_planes * 3 * sizeof(double)));
-        HIPCHK(ctx, ctx->totals_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        HIPCHK(ctx, ctx->totals.buf.alloc((size_t)capacity * n_planes * 3 * sizeof(double)));
+        HIPCHK(ctx, ctx->totals.hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
         HIPCHK(ctx, ctx->totals_part_buf.alloc((size_t)n_planes * 3 * ntiles * sizeof(double)));
         if (mask) {
             HIPCHK(ctx, ctx->totals_mask_buf.alloc((size_t)ctx->n));
             HIPCHK(ctx, hipMemcpyAsync(ctx->totals_mask_buf, mask, (size_t)ctx->n, hipMemcpyHostToDevice, ctx->stream));
         }
         ctx->totals_nplanes = n_planes;
-        ctx->totals_cap = capacity;
+        ctx->totals.cap = capacity;
         ctx->totals_ncells = ncells;
     }
     std::memcpy(ctx->totals_planes, plane_list, sizeof(plane_list));
-    const long long zero = 0, cap = (long long)ctx->totals_cap;
+    const long long zero = 0, cap = (long long)ctx->totals.cap;
     const unsigned char *const mask_dev = ctx->totals_mask_buf;
-    HIPCHK(ctx, dev_put(ctx, &DevState::totals, *ctx->totals_buf.addr()));
-    HIPCHK(ctx, dev_put(ctx, &DevState::totals_hdr, *ctx->totals_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals, *ctx->totals.buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::totals_hdr, *ctx->totals.hdr_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::totals_part, *ctx->totals_part_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::totals_mask, mask_dev));
     HIPCHK(ctx, dev_put(ctx, &DevState::totals_rows, zero));
@@ -330,17 +331,11 @@ int rh_totals_configure(rh_ctx *ctx, const unsigned char *mask, const int *plane
     HIPCHK(ctx, dev_put(ctx, &DevState::totals_planes, plane_list));
     return observers_changed(ctx);   // synchronises: the sources above are stack locals (and the caller's mask)
 }
-static int totals_rows(rh_ctx *ctx, const char *who, long long *rows) {
-    if (!ctx->totals_nplanes) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_totals_configure has not been called");
-    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->totals_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RH_OK;
-}
 int rh_totals_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
     if (!ctx) return RH_ERR_ARG;
     if (!rows_total || !ncells) return fail(ctx, RH_ERR_ARG, "rh_totals_count: null pointer");
     long long rows = 0;
-    if (int rc = totals_rows(ctx, "rh_totals_count", &rows)) return rc;
+    if (int rc = ring_rows(ctx, "rh_totals_count", ctx->totals, "rh_totals_configure", &DevState::totals_rows, &rows)) return rc;
     *rows_total = (int64_t)rows;
     *ncells = ctx->totals_ncells;
     return RH_OK;
@@ -348,28 +343,13 @@ int rh_totals_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
 int rh_totals_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
     if (!ctx) return RH_ERR_ARG;
     long long total = 0;
-    if (int rc = totals_rows(ctx, "rh_totals_read", &total)) return rc;
+    if (int rc = ring_rows(ctx, "rh_totals_read", ctx->totals, "rh_totals_configure", &DevState::totals_rows, &total)) return rc;
     const size_t nv = (size_t)ctx->totals_nplanes * 3;
-    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
-        return fail(ctx, RH_ERR_ARG, "rh_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
-                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
-    if (n_rows && first_row < total - ctx->totals_cap)
-        return fail(ctx, RH_ERR_ARG, "rh_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->totals_cap - 1) +
-                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->totals_cap) + " of " +
-                                     std::to_string(total) + " rows)");
+    const std::string why = ring_range_refusal("rh_totals_read", first_row, n_rows, total, ctx->totals.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
     if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
         return fail(ctx, RH_ERR_ARG, "rh_totals_read: size mismatch (n_rows x n_planes x 3 float64)");
-    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
-        const int64_t slot = (first_row + done) % ctx->totals_cap;
-        const int64_t m = std::min<int64_t>(n_rows - done, ctx->totals_cap - slot);
-        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->totals_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->totals_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        done += m;
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RH_OK;
+    return ring_download(ctx, ctx->totals, nv, first_row, n_rows, hdr, values);
 }
 
 // ---- zonal totals (include/roger_hip.h; the kernels and the order: rh_zonal.h) ----
@@ -423,16 +403,9 @@ int rh_zonal_configure(rh_ctx *ctx, const int32_t *zone, int n_zones, const int 
         if (!planes || !zone) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: null pointer");
         if (n_zones < 1 || n_zones > RH_ZONAL_MAX_ZONES)
             return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_ZONAL_MAX_ZONES) + ")");
-        if (capacity < 1) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: capacity = " + std::to_string(capacity) + " (at least one row)");
-        if (capacity > (int64_t)1 << 40) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: capacity = " + std::to_string(capacity) + " rows is beyond any device");
+        if (int rc = check_capacity(ctx, "rh_zonal_configure: ", capacity)) return rc;
         if (ctx->n >= (int64_t)1 << 31) return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: " + std::to_string(ctx->n) + " columns (the index holds int32 slots)");
-        for (int j = 0; j < n_planes; ++j) {
-            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
-                return fail(ctx, RH_ERR_ARG, "rh_zonal_configure: plane id " + std::to_string(planes[j]) + " is not held by this context");
-            if (PLANE_IS_INT[planes[j]])
-                return fail(ctx, RH_ERR_ARG, std::string("rh_zonal_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (float64 planes only)");
-            plane_list[j] = planes[j];
-        }
+        if (int rc = check_planes(ctx, "rh_zonal_configure: ", planes, n_planes, plane_list)) return rc;
         ncells.assign((size_t)n_zones, 0);
         int64_t inside = 0;
         for (int64_t i = 0; i < ctx->n; ++i) {
@@ -448,31 +421,29 @@ int rh_zonal_configure(rh_ctx *ctx, const int32_t *zone, int n_zones, const int 
         S = zonal_index(zone, ctx->n, n_zones, index, at);
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
-    HIPCHK(ctx, ctx->zonal_buf.release());
-    HIPCHK(ctx, ctx->zonal_hdr_buf.release());
+    HIPCHK(ctx, ctx->zonal.release());
     HIPCHK(ctx, ctx->zonal_part_buf.release());
     HIPCHK(ctx, ctx->zonal_index_buf.release());
     ctx->zonal_nplanes = ctx->zonal_nzones = 0;
-    ctx->zonal_cap = 0;
     ctx->zonal_ncells.clear();
     if (!off) {
-        HIPCHK(ctx, ctx->zonal_buf.alloc((size_t)capacity * n_zones * n_planes * 3 * sizeof(double)));
-        HIPCHK(ctx, ctx->zonal_hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
+        HIPCHK(ctx, ctx->zonal.buf.alloc((size_t)capacity * n_zones * n_planes * 3 * sizeof(double)));
+        HIPCHK(ctx, ctx->zonal.hdr_buf.alloc((size_t)capacity * 3 * sizeof(long long)));
         HIPCHK(ctx, ctx->zonal_part_buf.alloc((size_t)S * n_planes * 3 * sizeof(double)));
         HIPCHK(ctx, ctx->zonal_index_buf.alloc(index.size() * sizeof(int)));
         HIPCHK(ctx, hipMemcpyAsync(ctx->zonal_index_buf, index.data(), index.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         ctx->zonal_nplanes = n_planes;
         ctx->zonal_nzones = n_zones;
-        ctx->zonal_cap = capacity;
+        ctx->zonal.cap = capacity;
         ctx->zonal_ncells = ncells;
     }
     std::memcpy(ctx->zonal_planes, plane_list, sizeof(plane_list));
-    const long long zero = 0, cap = (long long)ctx->zonal_cap;
+    const long long zero = 0, cap = (long long)ctx->zonal.cap;
     const int *const base = ctx->zonal_index_buf;
     const int *const part[5] = {base, base ? base + at[1] : nullptr, base ? base + at[2] : nullptr, base ? base + at[3] : nullptr,
                                 base ? base + at[4] : nullptr};
-    HIPCHK(ctx, dev_put(ctx, &DevState::zonal, *ctx->zonal_buf.addr()));
-    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_hdr, *ctx->zonal_hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal, *ctx->zonal.buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::zonal_hdr, *ctx->zonal.hdr_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::zonal_part, *ctx->zonal_part_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::zonal_zone, part[0]));
     HIPCHK(ctx, dev_put(ctx, &DevState::zonal_tile_ptr, part[1]));
@@ -486,17 +457,11 @@ int rh_zonal_configure(rh_ctx *ctx, const int32_t *zone, int n_zones, const int 
     HIPCHK(ctx, dev_put(ctx, &DevState::zonal_planes, plane_list));
     return observers_changed(ctx);   // synchronises: the sources above are locals
 }
-static int zonal_rows(rh_ctx *ctx, const char *who, long long *rows) {
-    if (!ctx->zonal_nplanes) return fail(ctx, RH_ERR_STATE, std::string(who) + ": rh_zonal_configure has not been called");
-    HIPCHK(ctx, hipMemcpyAsync(rows, &ctx->dev->zonal_rows, sizeof(*rows), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RH_OK;
-}
 int rh_zonal_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
     if (!ctx) return RH_ERR_ARG;
     if (!rows_total || !ncells) return fail(ctx, RH_ERR_ARG, "rh_zonal_count: null pointer");
     long long rows = 0;
-    if (int rc = zonal_rows(ctx, "rh_zonal_count", &rows)) return rc;
+    if (int rc = ring_rows(ctx, "rh_zonal_count", ctx->zonal, "rh_zonal_configure", &DevState::zonal_rows, &rows)) return rc;
     *rows_total = (int64_t)rows;
     std::copy(ctx->zonal_ncells.begin(), ctx->zonal_ncells.end(), ncells);
     return RH_OK;
@@ -504,28 +469,13 @@ int rh_zonal_count(rh_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
 int rh_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
     if (!ctx) return RH_ERR_ARG;
     long long total = 0;
-    if (int rc = zonal_rows(ctx, "rh_zonal_read", &total)) return rc;
+    if (int rc = ring_rows(ctx, "rh_zonal_read", ctx->zonal, "rh_zonal_configure", &DevState::zonal_rows, &total)) return rc;
     const size_t nv = (size_t)ctx->zonal_nzones * ctx->zonal_nplanes * 3;
-    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
-        return fail(ctx, RH_ERR_ARG, "rh_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
-                                     " have not been recorded (" + std::to_string(total) + " rows so far)");
-    if (n_rows && first_row < total - ctx->zonal_cap)
-        return fail(ctx, RH_ERR_ARG, "rh_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - ctx->zonal_cap - 1) +
-                                     " have been overwritten (the ring holds the last " + std::to_string(ctx->zonal_cap) + " of " +
-                                     std::to_string(total) + " rows)");
+    const std::string why = ring_range_refusal("rh_zonal_read", first_row, n_rows, total, ctx->zonal.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
     if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
         return fail(ctx, RH_ERR_ARG, "rh_zonal_read: size mismatch (n_rows x n_zones x n_planes x 3 float64)");
-    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
-        const int64_t slot = (first_row + done) % ctx->zonal_cap;
-        const int64_t m = std::min<int64_t>(n_rows - done, ctx->zonal_cap - slot);
-        HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->zonal_buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ctx->zonal_hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        done += m;
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RH_OK;
+    return ring_download(ctx, ctx->zonal, nv, first_row, n_rows, hdr, values);
 }
 
 // ---- scores against observed series (include/roger_hip.h; the kernel and the rule: rh_scores.h) ----
@@ -562,14 +512,10 @@ int rh_scores_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_
         if (t_first < 0 || t_first % interval_seconds)
             return fail(ctx, RH_ERR_ARG, "rh_scores_configure: t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
                                          std::to_string(interval_seconds) + " s)");
-        for (int j = 0; j < n_items; ++j) {
-            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
-                return fail(ctx, RH_ERR_ARG, "rh_scores_configure: plane id " + std::to_string(planes[j]) + " is not held by this context (plane ids must name float64 planes)");
-            if (PLANE_IS_INT[planes[j]])
-                return fail(ctx, RH_ERR_ARG, std::string("rh_scores_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (plane ids must name float64 planes)");
+        for (int j = 0; j < n_items; ++j) {   // (item by item: an item's plane is refused before its kind, both before the next item)
+            if (int rc = check_planes(ctx, "rh_scores_configure: ", planes + j, 1, plane_list + j, FLOAT64_IDS)) return rc;
             if (kinds[j] != RH_SCORES_SUM && kinds[j] != RH_SCORES_LAST)
                 return fail(ctx, RH_ERR_ARG, "rh_scores_configure: kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: LAST)");
-            plane_list[j] = planes[j];
             kind_list[j] = kinds[j];
         }
         if (series)
@@ -653,14 +599,10 @@ int rh_events_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_
         if (!planes || !kinds) return fail(ctx, RH_ERR_ARG, "rh_events_configure: null pointer");
         if (n_slots < 1 || n_slots > RH_EVENTS_MAX_SLOTS)
             return fail(ctx, RH_ERR_ARG, "rh_events_configure: n_slots = " + std::to_string(n_slots) + " (1 ... " + std::to_string(RH_EVENTS_MAX_SLOTS) + ")");
-        for (int j = 0; j < n_items; ++j) {
-            if (planes[j] < 0 || planes[j] >= ctx->planes_held)
-                return fail(ctx, RH_ERR_ARG, "rh_events_configure: plane id " + std::to_string(planes[j]) + " is not held by this context (plane ids must name float64 planes)");
-            if (PLANE_IS_INT[planes[j]])
-                return fail(ctx, RH_ERR_ARG, std::string("rh_events_configure: plane ") + PLANE_NAMES[planes[j]] + " is int32 (plane ids must name float64 planes)");
+        for (int j = 0; j < n_items; ++j) {   // (item by item, as for the scores)
+            if (int rc = check_planes(ctx, "rh_events_configure: ", planes + j, 1, plane_list + j, FLOAT64_IDS)) return rc;
             if (kinds[j] < RH_EVENTS_SUM || kinds[j] > RH_EVENTS_LAST)
                 return fail(ctx, RH_ERR_ARG, "rh_events_configure: kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: PEAK, 2: FIRST, 3: LAST)");
-            plane_list[j] = planes[j];
             kind_list[j] = kinds[j];
         }
     }

@@ -76,6 +76,22 @@ __global__ void k_selftest_pow(const double *x, const double *k, double *out, in
 // ---------------------------------------------------------------------------------------------
 // host side: context and C ABI
 // ---------------------------------------------------------------------------------------------
+// A ring of `cap` rows of row_elems float64 on the device, row r at r mod cap, and the rows' tags in a host ring of the same capacity:
+// what the points, the totals and the zonal totals record into.  The host enqueues every row, so it counts them.  cap 0: the observer is off.
+struct SasRing {
+    DevBuf<double> ring;
+    std::unique_ptr<int64_t[]> tags;
+    int64_t cap = 0, row_elems = 0, rows = 0;
+    bool on() const { return cap != 0; }
+    double *next_row() const { return ring + (size_t)(rows % cap) * (size_t)row_elems; }
+    void enqueued(int64_t tag) { tags[(size_t)(rows++ % cap)] = tag; }   // (the launches into next_row() are in the stream)
+    hipError_t release() {
+        tags.reset();
+        cap = row_elems = rows = 0;
+        return ring.release();
+    }
+};
+
 struct rh_sas_ctx {
     Stream stream;                   // first member: destroyed last, after everything that was enqueued on it has been released
     rh_sas_config cfg = {};
@@ -84,38 +100,32 @@ struct rh_sas_ctx {
     DevBuf<int> unsupported;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the day's launch
-    // time series at observation columns (rh_sas_points_configure): a ring of points_cap rows of points_row_elems float64 on the device,
-    // row r at r mod points_cap, and the rows' tags in a host ring of the same capacity.  The host enqueues every row, so it counts them.
-    DevBuf<double> points_ring;
+    // time series at observation columns (rh_sas_points_configure): the ring (off: no k_sas_points launch) and what the kernel is told
+    SasRing points;
     DevBuf<SasPointsDev> points_cfg;
-    std::unique_ptr<int64_t[]> points_tags;
-    int points_ncells = 0;           // 0: not configured, no k_sas_points launch
     int points_blocks = 0;           // workgroups of one row's launch
-    int64_t points_cap = 0, points_row_elems = 0, points_rows = 0;
-    // catchment totals (rh_sas_totals_configure): the ring and its tags as for the points; the width-1 partials, the two level buffers
-    // of the age rule (rh_sas_totals.h), the mask on the device, and the host's copy of what the kernels are told
-    DevBuf<double> totals_ring, totals_part, totals_lvl[2];
+    // catchment totals (rh_sas_totals_configure): the ring (off: no launches); the width-1 partials, the two level buffers of the age
+    // rule (rh_sas_totals.h), the mask on the device, and the host's copy of what the kernels are told
+    SasRing totals;
+    DevBuf<double> totals_part, totals_lvl[2];
     DevBuf<SasTotalsDev> totals_cfg;
     DevBuf<unsigned char> totals_mask;
-    std::unique_ptr<int64_t[]> totals_tags;
     SasTotalsDev totals_host = {};
-    int totals_items = 0;            // 0: not configured, no launches
     int totals_width[RH_SAS_TOTALS_MAX_ITEMS] = {};
     const double *totals_src[RH_SAS_TOTALS_MAX_ITEMS] = {};   // the age items' arrays
-    int64_t totals_cap = 0, totals_row_elems = 0, totals_rows = 0, totals_ncells = 0;
-    // zonal totals (rh_sas_zonal_configure): the ring and its tags as for the totals; the slots' width-1 partials, the ONE level-1 buffer
-    // of the age rule, the index over the zone map (rh_sas_zonal.h) and where its parts start
-    DevBuf<double> zonal_ring, zonal_part, zonal_lvl;
+    int64_t totals_ncells = 0;
+    // zonal totals (rh_sas_zonal_configure): the ring (off: no launches); the slots' width-1 partials, the ONE level-1 buffer of the age
+    // rule, the index over the zone map (rh_sas_zonal.h) and where its parts start
+    SasRing zonal;
+    DevBuf<double> zonal_part, zonal_lvl;
     DevBuf<SasZonalDev> zonal_cfg;
     DevBuf<int> zonal_index;
-    std::unique_ptr<int64_t[]> zonal_tags;
     SasZonalDev zonal_host = {};
-    int zonal_items = 0;             // 0: not configured, no launches
     int zonal_nzones = 0;
     int zonal_width[RH_SAS_TOTALS_MAX_ITEMS] = {};
     const double *zonal_src[RH_SAS_TOTALS_MAX_ITEMS] = {};
     int64_t zonal_at[SZ_PARTS] = {};
-    int64_t zonal_cap = 0, zonal_row_elems = 0, zonal_rows = 0, zonal_ntiles = 0;
+    int64_t zonal_ntiles = 0;
     std::vector<int64_t> zonal_ncells;   // cells of every zone
     // scores against observed samples (rh_sas_scores_configure): the moments, the observations and the series map on the device; the
     // windows, the day count, the window the count stands in or before, and the closed flags are the host's (rh_sas_scores.h)
@@ -158,6 +168,32 @@ static int64_t sas_elems(const rh_sas_config &c, int a) {
     case K_MASK: return c.n_cells;
     }
     return 0;
+}
+
+// ---- what the observers' calls further down share; the rules of a ring itself are rh_host.h's ----
+static int sas_check_capacity(rh_sas_ctx *ctx, const std::string &who, int64_t capacity) {
+    const std::string why = ring_capacity_refusal(who, capacity, 0);   // (every configure call bounds its ring's bytes itself)
+    return why.empty() ? RH_OK : sfail(ctx, RH_ERR_ARG, why);
+}
+// RH_ERR_STATE for the function `who` unless `configure` has switched its observer on
+static int sas_on(rh_sas_ctx *ctx, bool on, const char *who, const char *configure) {
+    return on ? RH_OK : sfail(ctx, RH_ERR_STATE, std::string(who) + ": " + configure + " has not been called");
+}
+// rows [first_row, first_row + n_rows) of a ring that is on and their tags to the host, for the function `who`.  Synchronises.
+static int sas_ring_read(rh_sas_ctx *ctx, const char *who, const SasRing &r, int64_t first_row, int64_t n_rows, int64_t *tags, double *values,
+                         size_t value_bytes) {
+    const size_t nv = (size_t)r.row_elems;
+    const std::string why = ring_range_refusal(who, first_row, n_rows, r.rows, r.cap);
+    if (!why.empty()) return sfail(ctx, RH_ERR_ARG, why);
+    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return sfail(ctx, RH_ERR_ARG, std::string(who) + ": size mismatch (n_rows x row_elems float64)");
+    const int rc = ring_pieces(first_row, n_rows, r.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
+        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, r.ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+        std::copy(r.tags.get() + slot, r.tags.get() + slot + m, tags + done);
+        return RH_OK;
+    });
+    return rc ? rc : rh_sas_sync(ctx);
 }
 
 extern "C" {
@@ -400,12 +436,10 @@ int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
 // ---- time series at observation columns (include/roger_hip_sas.h) ----
 // one row behind what the stream holds so far: the gather into the ring's next slot, the tag beside it
 static int sas_points_enqueue(rh_sas_ctx *ctx, int64_t tag) {
-    const int64_t slot = ctx->points_rows % ctx->points_cap;
     hipLaunchKernelGGL(k_sas_points, dim3((unsigned)ctx->points_blocks), dim3(SAS_POINTS_BLOCK), 0, ctx->stream, ctx->points_cfg.get(),
-                       ctx->points_ring + (size_t)slot * (size_t)ctx->points_row_elems);
+                       ctx->points.next_row());
     SHIPCHK(ctx, hipGetLastError());
-    ctx->points_tags[(size_t)slot] = tag;
-    ++ctx->points_rows;
+    ctx->points.enqueued(tag);
     return RH_OK;
 }
 
@@ -416,9 +450,9 @@ static int sas_scores_enqueue(rh_sas_ctx *ctx, int64_t day);
 // a whole day and, with points, totals, zonal totals or scores configured, their rows and the day's scoring
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
-    if (!rc && ctx->points_ncells) rc = sas_points_enqueue(ctx, day);
-    if (!rc && ctx->totals_items) rc = sas_totals_enqueue(ctx, day, day);
-    if (!rc && ctx->zonal_items) rc = sas_zonal_enqueue(ctx, day, day);
+    if (!rc && ctx->points.on()) rc = sas_points_enqueue(ctx, day);
+    if (!rc && ctx->totals.on()) rc = sas_totals_enqueue(ctx, day, day);
+    if (!rc && ctx->zonal.on()) rc = sas_zonal_enqueue(ctx, day, day);
     if (!rc && ctx->scores_items) rc = sas_scores_enqueue(ctx, day);
     return rc;
 }
@@ -450,7 +484,7 @@ int rh_sas_points_configure(rh_sas_ctx *ctx, const int64_t *cells, int n_cells, 
     int64_t row_elems = 0;
     if (!off) {
         if (!cells || !arrays) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
-        if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (int rc = sas_check_capacity(ctx, who, capacity)) return rc;
         for (int j = 0; j < n_arrays; ++j) {
             const int a = arrays[j];
             if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
@@ -482,30 +516,25 @@ int rh_sas_points_configure(rh_sas_ctx *ctx, const int64_t *cells, int n_cells, 
                                               " float64 are a ring above 2 GiB");
     }
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
-    SHIPCHK(ctx, ctx->points_ring.release());
+    SHIPCHK(ctx, ctx->points.release());
     SHIPCHK(ctx, ctx->points_cfg.release());
-    ctx->points_tags.reset();
-    ctx->points_ncells = ctx->points_blocks = 0;
-    ctx->points_cap = ctx->points_row_elems = ctx->points_rows = 0;
+    ctx->points_blocks = 0;
     if (off) return RH_OK;
     std::unique_ptr<int64_t[]> tags(new (std::nothrow) int64_t[(size_t)capacity]);
     if (!tags) return sfail(ctx, RH_ERR_ARG, who + "out of host memory for the tags of " + std::to_string(capacity) + " rows");
-    SHIPCHK(ctx, ctx->points_ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
+    SHIPCHK(ctx, ctx->points.ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
     SHIPCHK(ctx, ctx->points_cfg.alloc(sizeof(SasPointsDev)));
     SHIPCHK(ctx, hipMemcpyAsync(ctx->points_cfg, &P, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the source is a local)
-    ctx->points_tags = std::move(tags);
+    ctx->points.tags = std::move(tags);
     ctx->points_blocks = P.first_block[n_arrays];
-    ctx->points_cap = capacity;
-    ctx->points_row_elems = row_elems;
-    ctx->points_ncells = n_cells;
+    ctx->points.row_elems = row_elems;
+    ctx->points.cap = capacity;
     return RH_OK;
 }
 
 static int sas_points_on(rh_sas_ctx *ctx, const char *who) {
-    if (!ctx) return RH_ERR_ARG;
-    if (!ctx->points_ncells) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_points_configure has not been called");
-    return RH_OK;
+    return ctx ? sas_on(ctx, ctx->points.on(), who, "rh_sas_points_configure") : RH_ERR_ARG;
 }
 
 int rh_sas_points_record(rh_sas_ctx *ctx, int64_t tag) {
@@ -516,48 +545,29 @@ int rh_sas_points_record(rh_sas_ctx *ctx, int64_t tag) {
 int rh_sas_points_count(rh_sas_ctx *ctx, int64_t *rows_total) {
     if (int rc = sas_points_on(ctx, "rh_sas_points_count")) return rc;
     if (!rows_total) return sfail(ctx, RH_ERR_ARG, "rh_sas_points_count: null pointer");
-    *rows_total = ctx->points_rows;
+    *rows_total = ctx->points.rows;
     return RH_OK;
 }
 
 int rh_sas_points_row_elems(const rh_sas_ctx *ctx, int64_t *elems) {
     if (int rc = sas_points_on(const_cast<rh_sas_ctx *>(ctx), "rh_sas_points_row_elems")) return rc;
     if (!elems) return RH_ERR_ARG;
-    *elems = ctx->points_row_elems;
+    *elems = ctx->points.row_elems;
     return RH_OK;
 }
 
 int rh_sas_points_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes) {
     if (int rc = sas_points_on(ctx, "rh_sas_points_read")) return rc;
-    const int64_t total = ctx->points_rows, cap = ctx->points_cap;
-    const size_t nv = (size_t)ctx->points_row_elems;
-    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
-                                          " have not been recorded (" + std::to_string(total) + " rows so far)");
-    if (n_rows && first_row < total - cap)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_points_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
-                                          " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " +
-                                          std::to_string(total) + " rows)");
-    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_points_read: size mismatch (n_rows x row_elems float64)");
-    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
-        const int64_t slot = (first_row + done) % cap;
-        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
-        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->points_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        std::copy(ctx->points_tags.get() + slot, ctx->points_tags.get() + slot + m, tags + done);
-        done += m;
-    }
-    return rh_sas_sync(ctx);
+    return sas_ring_read(ctx, "rh_sas_points_read", ctx->points, first_row, n_rows, tags, values, value_bytes);
 }
 
 // ---- catchment totals (include/roger_hip_sas.h; kernels and orders: rh_sas_totals.h) ----
 // one row behind what the stream holds so far: the width-1 statistics of every item, then the age items one after another
 static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
-    const int64_t slot = ctx->totals_rows % ctx->totals_cap, n = ctx->cfg.n_cells;
+    const int64_t n = ctx->cfg.n_cells;
     const int64_t day_off = day < 0 ? -1 : (day % ctx->cfg.forcing_days) * n;
     const SasTotalsDev &P = ctx->totals_host;
-    double *row = ctx->totals_ring + (size_t)slot * (size_t)ctx->totals_row_elems;
+    double *row = ctx->totals.next_row();
     hipLaunchKernelGGL(k_sas_totals_tiles, dim3((unsigned)P.ntiles), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->totals_cfg.get(), day_off);
     hipLaunchKernelGGL(k_sas_totals_finish, dim3((unsigned)P.n_items), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->totals_cfg.get(), row);
     for (int j = 0; j < P.n_items; ++j) {
@@ -582,8 +592,7 @@ static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
         }
     }
     SHIPCHK(ctx, hipGetLastError());
-    ctx->totals_tags[(size_t)slot] = tag;
-    ++ctx->totals_rows;
+    ctx->totals.enqueued(tag);
     return RH_OK;
 }
 
@@ -632,7 +641,7 @@ int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh
     int wmax = 0;
     if (n_items) {
         if (!items) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
-        if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (int rc = sas_check_capacity(ctx, who, capacity)) return rc;
         if (int rc = sas_totals_items(ctx, who, items, n_items, P.val, P.wgt, P.off, P.val_daily, width, srcs, &row_elems, &wmax)) return rc;
         if (mask) {
             ncells = 0;
@@ -644,21 +653,19 @@ int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh
                                               " float64 are a ring above 2 GiB");
     }
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
-    SHIPCHK(ctx, ctx->totals_ring.release());
+    SHIPCHK(ctx, ctx->totals.release());
     SHIPCHK(ctx, ctx->totals_part.release());
     SHIPCHK(ctx, ctx->totals_lvl[0].release());
     SHIPCHK(ctx, ctx->totals_lvl[1].release());
     SHIPCHK(ctx, ctx->totals_cfg.release());
     SHIPCHK(ctx, ctx->totals_mask.release());
-    ctx->totals_tags.reset();
-    ctx->totals_items = 0;
-    ctx->totals_cap = ctx->totals_row_elems = ctx->totals_rows = ctx->totals_ncells = 0;
+    ctx->totals_ncells = 0;
     if (!n_items) return RH_OK;
     std::unique_ptr<int64_t[]> tags(new (std::nothrow) int64_t[(size_t)capacity]);
     if (!tags) return sfail(ctx, RH_ERR_ARG, who + "out of host memory for the tags of " + std::to_string(capacity) + " rows");
     const int64_t ntiles = (n + SAS_TOTALS_BLOCK - 1) / SAS_TOTALS_BLOCK, runs1 = (n + SAS_TOTALS_RUN - 1) / SAS_TOTALS_RUN;
     const int64_t runs2 = (runs1 + SAS_TOTALS_RUN - 1) / SAS_TOTALS_RUN;
-    SHIPCHK(ctx, ctx->totals_ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
+    SHIPCHK(ctx, ctx->totals.ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
     SHIPCHK(ctx, ctx->totals_part.alloc((size_t)n_items * SAS_TOTALS_NSTAT * (size_t)ntiles * sizeof(double)));
     if (wmax && runs1 > 1) {
         SHIPCHK(ctx, ctx->totals_lvl[0].alloc((size_t)runs1 * (size_t)wmax * sizeof(double)));
@@ -679,18 +686,15 @@ int rh_sas_totals_configure(rh_sas_ctx *ctx, const unsigned char *mask, const rh
     ctx->totals_host = P;
     std::copy(width, width + RH_SAS_TOTALS_MAX_ITEMS, ctx->totals_width);
     std::copy(srcs, srcs + RH_SAS_TOTALS_MAX_ITEMS, ctx->totals_src);
-    ctx->totals_tags = std::move(tags);
-    ctx->totals_cap = capacity;
-    ctx->totals_row_elems = row_elems;
+    ctx->totals.tags = std::move(tags);
+    ctx->totals.row_elems = row_elems;
     ctx->totals_ncells = ncells;
-    ctx->totals_items = n_items;
+    ctx->totals.cap = capacity;
     return RH_OK;
 }
 
 static int sas_totals_on(rh_sas_ctx *ctx, const char *who) {
-    if (!ctx) return RH_ERR_ARG;
-    if (!ctx->totals_items) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_totals_configure has not been called");
-    return RH_OK;
+    return ctx ? sas_on(ctx, ctx->totals.on(), who, "rh_sas_totals_configure") : RH_ERR_ARG;
 }
 
 int rh_sas_totals_record(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
@@ -701,7 +705,7 @@ int rh_sas_totals_record(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
 int rh_sas_totals_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
     if (int rc = sas_totals_on(ctx, "rh_sas_totals_count")) return rc;
     if (!rows_total || !ncells) return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_count: null pointer");
-    *rows_total = ctx->totals_rows;
+    *rows_total = ctx->totals.rows;
     *ncells = ctx->totals_ncells;
     return RH_OK;
 }
@@ -709,43 +713,24 @@ int rh_sas_totals_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
 int rh_sas_totals_row_elems(const rh_sas_ctx *ctx, int64_t *elems) {
     if (int rc = sas_totals_on(const_cast<rh_sas_ctx *>(ctx), "rh_sas_totals_row_elems")) return rc;
     if (!elems) return RH_ERR_ARG;
-    *elems = ctx->totals_row_elems;
+    *elems = ctx->totals.row_elems;
     return RH_OK;
 }
 
 int rh_sas_totals_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes) {
     if (int rc = sas_totals_on(ctx, "rh_sas_totals_read")) return rc;
-    const int64_t total = ctx->totals_rows, cap = ctx->totals_cap;
-    const size_t nv = (size_t)ctx->totals_row_elems;
-    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
-                                          " have not been recorded (" + std::to_string(total) + " rows so far)");
-    if (n_rows && first_row < total - cap)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
-                                          " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " +
-                                          std::to_string(total) + " rows)");
-    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_totals_read: size mismatch (n_rows x row_elems float64)");
-    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
-        const int64_t slot = (first_row + done) % cap;
-        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
-        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->totals_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        std::copy(ctx->totals_tags.get() + slot, ctx->totals_tags.get() + slot + m, tags + done);
-        done += m;
-    }
-    return rh_sas_sync(ctx);
+    return sas_ring_read(ctx, "rh_sas_totals_read", ctx->totals, first_row, n_rows, tags, values, value_bytes);
 }
 
 // ---- zonal totals (include/roger_hip_sas.h; kernels, index and orders: rh_sas_zonal.h) ----
 // one row behind what the stream holds so far: every item's width-1 statistics for every zone, then the age items one after another
 static int sas_zonal_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
-    const int64_t slot = ctx->zonal_rows % ctx->zonal_cap, n = ctx->cfg.n_cells;
+    const int64_t n = ctx->cfg.n_cells;
     const int64_t day_off = day < 0 ? -1 : (day % ctx->cfg.forcing_days) * n;
     const SasZonalDev &P = ctx->zonal_host;
     const int *ix = ctx->zonal_index.get();
     const int64_t *at = ctx->zonal_at;
-    double *row = ctx->zonal_ring + (size_t)slot * (size_t)ctx->zonal_row_elems;
+    double *row = ctx->zonal.next_row();
     const unsigned ntiles = (unsigned)ctx->zonal_ntiles, nz = (unsigned)ctx->zonal_nzones;
     hipLaunchKernelGGL(k_sas_zonal_tiles, dim3(ntiles), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->zonal_cfg.get(), day_off);
     hipLaunchKernelGGL(k_sas_zonal_finish, dim3(nz), dim3(SAS_TOTALS_BLOCK), 0, ctx->stream, ctx->zonal_cfg.get(), row);
@@ -761,8 +746,7 @@ static int sas_zonal_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
                            ix + at[SZ_RUN_PTR], ix + at[SZ_RUN_SLOT], ix + at[SZ_SLOT_TILE], row + P.off[j] + 2, P.zone_elems);
     }
     SHIPCHK(ctx, hipGetLastError());
-    ctx->zonal_tags[(size_t)slot] = tag;
-    ++ctx->zonal_rows;
+    ctx->zonal.enqueued(tag);
     return RH_OK;
 }
 
@@ -783,7 +767,7 @@ int rh_sas_zonal_configure(rh_sas_ctx *ctx, const int32_t *zone, int n_zones, co
         if (!items || !zone) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
         if (n_zones < 1 || n_zones > RH_SAS_ZONAL_MAX_ZONES)
             return sfail(ctx, RH_ERR_ARG, who + "n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_SAS_ZONAL_MAX_ZONES) + ")");
-        if (capacity < 1) return sfail(ctx, RH_ERR_ARG, who + "capacity = " + std::to_string(capacity) + " (at least one row)");
+        if (int rc = sas_check_capacity(ctx, who, capacity)) return rc;
         if (int rc = sas_totals_items(ctx, who, items, n_items, P.val, P.wgt, P.off, P.val_daily, width, srcs, &zone_elems, &wmax)) return rc;
         ncells.assign((size_t)n_zones, 0);
         int64_t inside = 0;
@@ -806,20 +790,19 @@ int rh_sas_zonal_configure(rh_sas_ctx *ctx, const int32_t *zone, int n_zones, co
                                               " float64 are a level-1 buffer above 2 GiB");
     }
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
-    SHIPCHK(ctx, ctx->zonal_ring.release());
+    SHIPCHK(ctx, ctx->zonal.release());
     SHIPCHK(ctx, ctx->zonal_part.release());
     SHIPCHK(ctx, ctx->zonal_lvl.release());
     SHIPCHK(ctx, ctx->zonal_cfg.release());
     SHIPCHK(ctx, ctx->zonal_index.release());
-    ctx->zonal_tags.reset();
-    ctx->zonal_items = ctx->zonal_nzones = 0;
-    ctx->zonal_cap = ctx->zonal_row_elems = ctx->zonal_rows = ctx->zonal_ntiles = 0;
+    ctx->zonal_nzones = 0;
+    ctx->zonal_ntiles = 0;
     ctx->zonal_ncells.clear();
     if (!n_items) return RH_OK;
     std::unique_ptr<int64_t[]> tags(new (std::nothrow) int64_t[(size_t)capacity]);
     if (!tags) return sfail(ctx, RH_ERR_ARG, who + "out of host memory for the tags of " + std::to_string(capacity) + " rows");
     const int64_t row_elems = zone_elems * n_zones;
-    SHIPCHK(ctx, ctx->zonal_ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
+    SHIPCHK(ctx, ctx->zonal.ring.alloc((size_t)capacity * (size_t)row_elems * sizeof(double)));
     SHIPCHK(ctx, ctx->zonal_part.alloc((size_t)S * (size_t)n_items * SAS_TOTALS_NSTAT * sizeof(double)));
     if (wmax) SHIPCHK(ctx, ctx->zonal_lvl.alloc((size_t)S * (size_t)wmax * sizeof(double)));
     SHIPCHK(ctx, ctx->zonal_index.alloc(index.size() * sizeof(int)));
@@ -841,20 +824,17 @@ int rh_sas_zonal_configure(rh_sas_ctx *ctx, const int32_t *zone, int n_zones, co
     std::copy(width, width + RH_SAS_TOTALS_MAX_ITEMS, ctx->zonal_width);
     std::copy(srcs, srcs + RH_SAS_TOTALS_MAX_ITEMS, ctx->zonal_src);
     std::copy(at, at + SZ_PARTS, ctx->zonal_at);
-    ctx->zonal_tags = std::move(tags);
-    ctx->zonal_cap = capacity;
-    ctx->zonal_row_elems = row_elems;
+    ctx->zonal.tags = std::move(tags);
+    ctx->zonal.row_elems = row_elems;
     ctx->zonal_ntiles = (n + SAS_TOTALS_BLOCK - 1) / SAS_TOTALS_BLOCK;
     ctx->zonal_ncells = std::move(ncells);
     ctx->zonal_nzones = n_zones;
-    ctx->zonal_items = n_items;
+    ctx->zonal.cap = capacity;
     return RH_OK;
 }
 
 static int sas_zonal_on(rh_sas_ctx *ctx, const char *who) {
-    if (!ctx) return RH_ERR_ARG;
-    if (!ctx->zonal_items) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_zonal_configure has not been called");
-    return RH_OK;
+    return ctx ? sas_on(ctx, ctx->zonal.on(), who, "rh_sas_zonal_configure") : RH_ERR_ARG;
 }
 
 int rh_sas_zonal_record(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
@@ -865,7 +845,7 @@ int rh_sas_zonal_record(rh_sas_ctx *ctx, int64_t tag, int64_t day) {
 int rh_sas_zonal_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
     if (int rc = sas_zonal_on(ctx, "rh_sas_zonal_count")) return rc;
     if (!rows_total || !ncells) return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_count: null pointer");
-    *rows_total = ctx->zonal_rows;
+    *rows_total = ctx->zonal.rows;
     std::copy(ctx->zonal_ncells.begin(), ctx->zonal_ncells.end(), ncells);
     return RH_OK;
 }
@@ -873,32 +853,13 @@ int rh_sas_zonal_count(rh_sas_ctx *ctx, int64_t *rows_total, int64_t *ncells) {
 int rh_sas_zonal_row_elems(const rh_sas_ctx *ctx, int64_t *elems) {
     if (int rc = sas_zonal_on(const_cast<rh_sas_ctx *>(ctx), "rh_sas_zonal_row_elems")) return rc;
     if (!elems) return RH_ERR_ARG;
-    *elems = ctx->zonal_row_elems;
+    *elems = ctx->zonal.row_elems;
     return RH_OK;
 }
 
 int rh_sas_zonal_read(rh_sas_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *tags, double *values, size_t value_bytes) {
     if (int rc = sas_zonal_on(ctx, "rh_sas_zonal_read")) return rc;
-    const int64_t total = ctx->zonal_rows, cap = ctx->zonal_cap;
-    const size_t nv = (size_t)ctx->zonal_row_elems;
-    if (first_row < 0 || n_rows < 0 || first_row > total || n_rows > total - first_row)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(first_row + n_rows - 1) +
-                                          " have not been recorded (" + std::to_string(total) + " rows so far)");
-    if (n_rows && first_row < total - cap)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_read: rows " + std::to_string(first_row) + " ... " + std::to_string(total - cap - 1) +
-                                          " have been overwritten (the ring holds the last " + std::to_string(cap) + " of " +
-                                          std::to_string(total) + " rows)");
-    if ((n_rows && (!tags || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_zonal_read: size mismatch (n_rows x row_elems float64)");
-    for (int64_t done = 0; done < n_rows;) {   // at most two pieces: the range may straddle the ring's wrap
-        const int64_t slot = (first_row + done) % cap;
-        const int64_t m = std::min<int64_t>(n_rows - done, cap - slot);
-        SHIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ctx->zonal_ring + (size_t)slot * nv, (size_t)m * nv * sizeof(double),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        std::copy(ctx->zonal_tags.get() + slot, ctx->zonal_tags.get() + slot + m, tags + done);
-        done += m;
-    }
-    return rh_sas_sync(ctx);
+    return sas_ring_read(ctx, "rh_sas_zonal_read", ctx->zonal, first_row, n_rows, tags, values, value_bytes);
 }
 
 // ---- scores against observed samples (include/roger_hip_sas.h; the kernel and the rule: rh_sas_scores.h) ----
@@ -1028,9 +989,7 @@ int rh_sas_scores_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, in
 }
 
 static int sas_scores_on(rh_sas_ctx *ctx, const char *who) {
-    if (!ctx) return RH_ERR_ARG;
-    if (!ctx->scores_items) return sfail(ctx, RH_ERR_STATE, std::string(who) + ": rh_sas_scores_configure has not been called");
-    return RH_OK;
+    return ctx ? sas_on(ctx, ctx->scores_items != 0, who, "rh_sas_scores_configure") : RH_ERR_ARG;
 }
 
 int rh_sas_scores_record(rh_sas_ctx *ctx, int64_t day) {
