@@ -60,6 +60,31 @@ typedef struct oc_sas {
     int64_t solver;
 } oc_sas;
 
+/* CLIP AND SNAP MARGIN (oc_sas_step_margin): how far a column's day stayed from every decision that the last bit of
+ * an operand can flip -- the clips of a class to its own water, the snaps to zero, the bounds of the delta notation.  One number per
+ * column, the minimum of the relative distances met during the day; it only observes, the arithmetic of the step is untouched.  A class
+ * that is exactly empty contributes nothing: its increment of Omega is exactly 0 in every summation order. */
+static _Thread_local double *oc_mg = NULL, *oc_mg_clip = NULL;   /* all terms; all but the bounds of the delta notation */
+static void mg_term(double term) {
+    if (oc_mg && term < *oc_mg) *oc_mg = term;
+    if (oc_mg_clip && term < *oc_mg_clip) *oc_mg_clip = term;
+}
+static void mg_delta_term(double term) {
+    if (oc_mg && term < *oc_mg) *oc_mg = term;
+}
+/* `take > have` (or have - take < 0) decides: 1 - take / have for a class that holds something */
+static void mg_clip(double take, double have) {
+    if (oc_mg && have > 0) mg_term(1. - take / have);
+}
+/* a snap `x < 1e-8 -> 0` */
+static void mg_snap8(double x) {
+    if (oc_mg && x > 0) mg_term(fabs(x / 1e-8 - 1.));
+}
+/* update_sa's snap `-1e-5 < v < 0 -> 0`: a remainder below 1e-9 of either sign, or a negative one, is a residue */
+static void mg_residue(double v) {
+    if (oc_mg && ((v != 0 && fabs(v) < 1e-9) || v < 0)) mg_term(0.);
+}
+
 /* numpy pairwise add.reduce (see svat_oracle.c) */
 static double np_pairwise(const double *a, int64_t n) {
     if (n < 8) {
@@ -94,6 +119,7 @@ static double np_max(const double *a, int64_t n) {
 /* transport.py:315-340 */
 static double conc_to_delta(const oc_sas *P, double conc) {
     double d = 1000. * (conc / (P->vsmow * (1. - conc)) - 1.);
+    if (oc_mg && !isnan(d)) mg_delta_term(fmin(fabs(d - P->d18O_min), fabs(d - P->d18O_max)) / (P->d18O_max - P->d18O_min));
     return ((d < P->d18O_min) || (d > P->d18O_max)) ? NAN : d;
 }
 
@@ -102,7 +128,9 @@ static double conc_to_delta(const oc_sas *P, double conc) {
  * which of them produces the device's residue ties:
  *   bit 0: the cumulative sums over the age axis in the association of the kernel's wave scan (one age class per lane, ages <= 63:
  *          the shape the small golden cases run in) instead of numpy's running sum;
- *   bit 1: the sub-step distributions accumulated directly (ttn += tti) instead of diff(cumsum(tti)) accumulated and differenced. */
+ *   bit 1: the sub-step distributions accumulated directly (ttn += tti) instead of diff(cumsum(tti)) accumulated and differenced;
+ *   bit 2: the reversed exponential (code 52) selects nothing, as in the kernel, which does not evaluate it (FAM_NONE).  Bits 0 and 1
+ *          alone are what tools/sas_tie_causes.py measured and stay as they were. */
 static int oc_device_order(void) {
     static int v = -1;
     if (v < 0) {
@@ -228,6 +256,10 @@ static void sas_omega(double *Om, const double *SA, int64_t nages, double *p, do
     } else if (code == 52) { /* exponential, age order reversed (preference for old water), sas.py:186-190: Omega then
                               * DEcreases from 1 to 0 along the age axis and calc_tt clips every difference to 0 */
         const double S = Smax * mk;
+        /* the kernel does not evaluate this family: every difference is clipped to 0, so it selects nothing (rh_sas_kernels.h, FAM_NONE).
+         * In the wave scan's order the cumulative StorAge of an exactly empty class is an ulp off its neighbour's, and the zero
+         * increment that its mirror class owes to x + 0 == x would become +-1e-16: the device-order stand-in follows the kernel */
+        if (oc_device_order() & 4) return;
         for (int64_t k = 0; k < nages; ++k) {
             const double x = SA[nages - 1 - k];
             Om[k] = (x > 0 ? (x < S ? 1 - exp(p[1] * (-1) * (x / S)) : 1.) : 0.) * mk;
@@ -266,6 +298,7 @@ static void calc_tt(const oc_sas *P, double *tt, const double *SA, const double 
             double d = TTi[k + 1] - TTi[k];
             double t = (d >= 0 ? d : 0);
             double q = (flux * t * h > san[k] ? san[k] : flux * t * h);
+            mg_clip(flux * t * h, san[k]);
             t = (flux * h > 0 ? q / (flux * h) : 0);
             tti[k] = t;
             san[k] += -t * flux * h;
@@ -282,6 +315,7 @@ static void calc_tt(const oc_sas *P, double *tt, const double *SA, const double 
         for (int64_t k = 0; k < A; ++k) {
             double t = ttn_direct[k] / (double)N;
             double q = (flux * t > sa[k] ? sa[k] : flux * t);
+            mg_clip(flux * t, sa[k]);
             tt[k] = (flux > 0 ? q / flux : 0);
         }
         return;
@@ -289,6 +323,7 @@ static void calc_tt(const oc_sas *P, double *tt, const double *SA, const double 
     for (int64_t k = 0; k < A; ++k) {
         double t = TT[k + 1] - TT[k];
         double q = (flux * t > sa[k] ? sa[k] : flux * t);
+        mg_clip(flux * t, sa[k]);
         tt[k] = (flux > 0 ? q / flux : 0);
     }
 }
@@ -332,6 +367,7 @@ static void outflux(const oc_sas *P, int64_t i, int f, double flux, double *sa, 
     }
     for (int64_t k = 0; k < A; ++k) { /* update_sa :599-619 */
         double v = sa[k] + -flux * tt[k];
+        mg_residue(v);
         v = ((v > -1e-5) && (v < 0)) ? 0 : v;
         sa[k] = v * mk;
     }
@@ -373,6 +409,7 @@ static void outflux_anion(const oc_sas *P, int64_t i, int f, double flux, double
         for (int64_t k = 0; k < A; ++k) {
             double m = (sa[k] > 0 ? msa[k] / sa[k] : 0) * alpha * tt[k] * flux;
             m = (m <= 0 ? 0 : m);
+            mg_clip(m, msa[k]);
             m = (m > msa[k] ? msa[k] : m);
             mtt[k] = m * mk;
         }
@@ -382,6 +419,7 @@ static void outflux_anion(const oc_sas *P, int64_t i, int f, double flux, double
     }
     for (int64_t k = 0; k < A; ++k) { /* update_sa :599-619 */
         double v = sa[k] + -flux * tt[k];
+        mg_residue(v);
         v = ((v > -1e-5) && (v < 0)) ? 0 : v;
         sa[k] = v * mk;
     }
@@ -403,6 +441,7 @@ static void ageing_anion(double *sa, double *msa, int64_t A) {
     sa[0] = 0;
     msa[0] = 0;
     sa[A - 1] += sa_last;
+    mg_snap8(sa[A - 1]);
     sa[A - 1] = (sa[A - 1] < 1e-8 ? 0 : sa[A - 1]);
     msa[A - 1] += msa_last;
 }
@@ -428,6 +467,7 @@ static void step_anion(const oc_sas *P, int64_t i, double *work) {
     outflux_anion(P, i, 0, P->evap_soil[i], 1.0, P->tracer == 3 ? 0 : 1, sa_rz, msa_rz, NULL, NULL, mk, work);
     {   /* crop solute uptake stops above 80 % saturation: evapotranspiration.py:932-939 */
         const int crop = (P->lu_id[i] > 500) && (P->lu_id[i] < 599) && (np_sum(sa_rz, A) >= 0.8 * P->S_sat_rz[i]);
+        if ((P->lu_id[i] > 500) && (P->lu_id[i] < 599) && P->S_sat_rz[i] > 0) mg_term(fabs(np_sum(sa_rz, A) / (0.8 * P->S_sat_rz[i]) - 1.));
         const double alpha = (crop ? 0 : P->alpha_transp[i]) * mk;
         outflux_anion(P, i, 1, P->transp[i], alpha, 0, sa_rz, msa_rz, NULL, NULL, mk, work);
     }
@@ -449,6 +489,7 @@ static void storages_anion(const oc_sas *P, int64_t i, double *work) {
     const int64_t A = P->ages;
     const double mk = (double)P->maskCatch[i];
     double *sa_rz = P->sa_rz + i * A, *msa_rz = P->msa_rz + i * A, *sa_ss = P->sa_ss + i * A, *msa_ss = P->msa_ss + i * A;
+    for (int64_t k = 0; k < A; ++k) mg_snap8(sa_rz[k]);
     for (int64_t k = 0; k < A; ++k) sa_rz[k] = (sa_rz[k] < 1e-8 ? 0 : sa_rz[k]);
     for (int64_t k = 0; k < A; ++k) msa_rz[k] = (sa_rz[k] <= 0 ? 0 : msa_rz[k]);
     P->M_rz[i] = np_nansum(msa_rz, A, work) * mk;
@@ -456,6 +497,7 @@ static void storages_anion(const oc_sas *P, int64_t i, double *work) {
         const double S = np_sum(sa_rz, A);
         P->C_rz[i] = (S > 0 ? P->M_rz[i] / S : 0);
     }
+    for (int64_t k = 0; k < A; ++k) mg_snap8(sa_ss[k]);
     for (int64_t k = 0; k < A; ++k) sa_ss[k] = (sa_ss[k] < 1e-8 ? 0 : sa_ss[k]);
     for (int64_t k = 0; k < A; ++k) msa_ss[k] = (sa_ss[k] <= 0 ? 0 : msa_ss[k]);
     P->M_ss[i] = np_nansum(msa_ss, A, work) * mk;
@@ -526,6 +568,7 @@ static void ageing(double *sa, double *msa, int64_t A, double *scratch) {
     }
     sa[0] = 0;
     sa[A - 1] += sam1[A - 1];
+    mg_snap8(sa[A - 1]);
     sa[A - 1] = (sa[A - 1] < 1e-8 ? 0 : sa[A - 1]);
     msa[A - 1] = (sa[A - 1] <= 0 ? NAN : msa[A - 1]);
 }
@@ -604,9 +647,11 @@ static void storages_iso(const oc_sas *P, int64_t i, double *work) {
     const double mk = (double)P->maskCatch[i];
     double *sa_rz = P->sa_rz + i * A, *msa_rz = P->msa_rz + i * A, *sa_ss = P->sa_ss + i * A, *msa_ss = P->msa_ss + i * A;
     double *sa_s = P->sa_s + i * A, *msa_s = P->msa_s + i * A;
+    for (int64_t k = 0; k < A; ++k) mg_snap8(sa_rz[k]);
     for (int64_t k = 0; k < A; ++k) sa_rz[k] = (sa_rz[k] < 1e-8 ? 0 : sa_rz[k]);
     P->C_rz[i] = conc_storage(sa_rz, msa_rz, A, work) * mk;
     P->C_iso_rz[i] = conc_to_delta(P, P->C_rz[i]) * mk;
+    for (int64_t k = 0; k < A; ++k) mg_snap8(sa_ss[k]);
     for (int64_t k = 0; k < A; ++k) sa_ss[k] = (sa_ss[k] < 1e-8 ? 0 : sa_ss[k]);
     P->C_ss[i] = conc_storage(sa_ss, msa_ss, A, work) * mk;
     P->C_iso_ss[i] = conc_to_delta(P, P->C_ss[i]) * mk;
@@ -644,6 +689,7 @@ static void euler_tt(const oc_sas *P, double *TT, double *tt, const double *SA, 
     for (int64_t k = 0; k < A; ++k) {
         const double sa_d = SA[k + 1] - SA[k], ttq = (Om[k + 1] - Om[k]) * flux_h;
         double v = (sa_d + ttq < 0) ? -sa_d : ttq;
+        mg_clip(-ttq, sa_d);
         v = (v == 0) ? 0.0 : v;   /* where(x == -0, 0, x) */
         nn[k] = v;
     }
@@ -706,6 +752,7 @@ static void anion_mtt(double *mtt, const double *sa, const double *msa, const do
     for (int64_t k = 0; k < A; ++k) {
         double m = (sa[k] > 0 ? msa[k] / sa[k] : 0) * alpha * tt[k] * flux_h;
         m = (m <= 0 ? 0 : m);
+        mg_clip(m, msa[k]);
         mtt[k] = (m > msa[k] ? msa[k] : m);
     }
 }
@@ -730,11 +777,15 @@ static void explicit_update_anion(const oc_sas *P, int64_t i, double h, int rk4)
 #define NZ(x) (isnan(x) ? 0 : (x))
     for (int64_t k = 0; k < A; ++k) {
         double dsa_rz = rk4 ? (ev * tt_ev[k] - tr * tt_tr[k] - qrz * tt_qrz[k]) * h : (cpr * tt_cpr[k] - ev * tt_ev[k] - tr * tt_tr[k] - qrz * tt_qrz[k]) * h;
+        mg_clip(-dsa_rz, sa_rz[k]);
         dsa_rz = (sa_rz[k] + dsa_rz < 0) ? -sa_rz[k] : dsa_rz;
         double dsa_ss = (qrz * tt_qrz[k] - cpr * tt_cpr[k] - qss * tt_qss[k]) * h;
+        mg_clip(-dsa_ss, sa_ss[k]);
         dsa_ss = (sa_ss[k] + dsa_ss < 0) ? -sa_ss[k] : dsa_ss;
         double dmsa_rz = NZ(mtt_cpr[k]) - NZ(mtt_tr[k]) - NZ(mtt_qrz[k]);
         double dmsa_ss = NZ(mtt_qrz[k]) - NZ(mtt_cpr[k]) - NZ(mtt_qss[k]);
+        mg_clip(-dmsa_rz, msa_rz[k]);
+        mg_clip(-dmsa_ss, msa_ss[k]);
         dmsa_rz = (msa_rz[k] + dmsa_rz < 0) ? 0 : dmsa_rz;
         dmsa_ss = (msa_ss[k] + dmsa_ss < 0) ? 0 : dmsa_ss;
         sa_rz[k] += dsa_rz;
@@ -785,8 +836,10 @@ static void euler_update(const oc_sas *P, int64_t i, double h) {
     const double *mtt_qrz = P->mtt[2] + i * A, *mtt_cpr = P->mtt[4] + i * A;
     for (int64_t k = 0; k < A; ++k) {
         double dsa_rz = (cpr * tt_cpr[k] - ev * tt_ev[k] - tr * tt_tr[k] - qrz * tt_qrz[k]) * h;
+        mg_clip(-dsa_rz, sa_rz[k]);
         dsa_rz = (sa_rz[k] + dsa_rz < 0) ? -sa_rz[k] : dsa_rz;
         double dsa_ss = (qrz * tt_qrz[k] - cpr * tt_cpr[k] - qss * tt_qss[k]) * h;
+        mg_clip(-dsa_ss, sa_ss[k]);
         dsa_ss = (sa_ss[k] + dsa_ss < 0) ? -sa_ss[k] : dsa_ss;
         const double dsa_rz1 = (cpr * tt_cpr[k]) * h;
         const double dmsa_rz1 = (isnan(mtt_cpr[k]) ? 0 : mtt_cpr[k]) * (dsa_rz1 > 0 ? ((cpr * tt_cpr[k] * h) / dsa_rz1) : 0);
@@ -882,6 +935,8 @@ static void rk4_substep(const oc_sas *P, int64_t i, double h, double *work) {
                 d_rz = d_rz / 2;
                 d_ss = d_ss / 2;
             }
+            mg_clip(stage == 2 ? d_rz : -d_rz, s_rz[k]);
+            mg_clip(stage == 2 ? d_ss : -d_ss, s_ss[k]);
             if (stage == 2) { /* as written: `sarkn - dsarkn < 0` */
                 d_rz = (s_rz[k] - d_rz < 0) ? -s_rz[k] : d_rz;
                 d_ss = (s_ss[k] - d_ss < 0) ? -s_ss[k] : d_ss;
@@ -920,7 +975,7 @@ static void rk4_substep(const oc_sas *P, int64_t i, double h, double *work) {
 
 /* one day of svat_transport_model_deterministic for all columns; columns are independent and run on all host threads
  * once there are enough of them (bench.py's cpu_baseline) */
-void oc_sas_step(const oc_sas *P) {
+static void step_all(const oc_sas *P, double *margin, double *clip_only) {
     const int64_t A = P->ages, NA = A + 1;
 #pragma omp parallel if (P->n >= 256)
     {
@@ -930,6 +985,10 @@ void oc_sas_step(const oc_sas *P) {
         const double mk = (double)P->maskCatch[i];
         double *sa_rz = P->sa_rz + i * A, *msa_rz = P->msa_rz + i * A, *sa_ss = P->sa_ss + i * A, *msa_ss = P->msa_ss + i * A;
         double *sa_s = P->sa_s + i * A;
+        if (margin) margin[i] = 1.0;
+        if (clip_only) clip_only[i] = 1.0;
+        oc_mg = margin ? margin + i : NULL;
+        oc_mg_clip = (margin && clip_only) ? clip_only + i : NULL;
         if (P->tracer != 0 && P->solver == 0) {
             step_anion(P, i, work);
             goto statistics;
@@ -990,6 +1049,11 @@ void oc_sas_step(const oc_sas *P) {
         ageing(sa_rz, msa_rz, A, work);
         ageing(sa_ss, msa_ss, A, work);
     }
+    oc_mg = oc_mg_clip = NULL;
     free(work);
     }
 }
+void oc_sas_step(const oc_sas *P) { step_all(P, NULL, NULL); }
+/* the same day, and per column (n doubles) the clip and snap margin it kept (1 where nothing came near a decision); clip_only (or
+ * NULL): the same without the distance of the delta values from their bounds */
+void oc_sas_step_margin(const oc_sas *P, double *margin, double *clip_only) { step_all(P, margin, clip_only); }

@@ -152,8 +152,16 @@ class SasState:
             s.M_rz, s.M_ss, s.M_s = (_ptr(self.out[k]) for k in ("M_rz", "M_ss", "M_s"))
         return s
 
-    def step_oracle(self):
-        lib().oc_sas_step(C.byref(self.struct()))
+    def step_oracle(self, margin=False):
+        """One day.  With margin=True returns, per column, how far the day stayed from every decision that a last bit can
+        flip (the clip and snap margin of oracle/sas_oracle.c; 1 where nothing came near one); the results are the same."""
+        if not margin:
+            lib().oc_sas_step(C.byref(self.struct()))
+            return None
+        m, clip = np.ones(self.n, dtype=np.float64), np.ones(self.n, dtype=np.float64)
+        lib().oc_sas_step_margin(C.byref(self.struct()), _ptr(m), _ptr(clip))
+        self.clip_margin = clip      # the margin without the distance of the delta values from [dmin, dmax]
+        return m
 
     def rescale_oracle(self):
         lib().oc_sas_rescale(C.byref(self.struct()))

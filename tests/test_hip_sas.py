@@ -3,7 +3,8 @@ include/roger_hip_sas.h) against the reference's golden vectors and against the 
 
 Tolerance (fp64): rtol 1e-10, atol 1e-12 on every output, NaN patterns identical.  The kernel keeps
 the reference's operation order per element; its prefix sums and reductions over the age axis are
-parallel (rounding-level differences), `pow` is the device library's."""
+parallel (rounding-level differences), `pow` is the kernel's own (rh_sas_dev.h: sas_pow with its square-root and fifth-root paths,
+test_power_function_accuracy).  Columns that cannot tie are held without any allowance in tests/test_hip_sas_tiefree.py."""
 import os
 
 import numpy as np
@@ -71,12 +72,35 @@ def test_single_days_from_reference_states(case):
     ctx.close()
 
 
+def step_fused_and_staged(fused, split):
+    """One day on `fused` in one launch and on `split` one stage per launch, then every array both hold: bit for bit.  Returns how
+    many arrays were compared."""
+    from roger_amd._native import SAS_STAGES
+
+    fused.step(0)
+    for name in ("INF_RZ", "EVAP", "TRANSP", "Q_RZ", "INF_SS", "Q_SS", "CPR", "STORAGE", "AGEING"):
+        split.stages(0, SAS_STAGES[name])
+    compared = 0
+    for nm in fused.names:
+        try:
+            a = fused.download(nm)
+        except Exception:
+            continue
+        b = split.download(nm)
+        compared += 1
+        if nm[:2] in ("tt", "rt") and a.ndim == 1:
+            # statistics of a launch of their own read TT back from HBM, where the value at a thread's lower
+            # edge is the neighbour's upper edge instead of the scan's own (one rounding apart)
+            assert np.allclose(a, b, rtol=1e-12, atol=0, equal_nan=True), nm
+        else:
+            assert np.array_equal(a, b, equal_nan=True), nm
+    return compared
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_stage_by_stage_equals_fused(case):
     """The reference's kernels one launch at a time (state in HBM in between) give bit for bit the
     fused step."""
-    from roger_amd._native import SAS_STAGES
-
     g = SasGolden(case)
     st = g.new_state()
     fused, split = make_ctx(st), make_ctx(st)
@@ -85,21 +109,7 @@ def test_stage_by_stage_equals_fused(case):
     g.load_inputs(st, d)
     push(fused, st)
     push(split, st)
-    fused.step(0)
-    for name in ("INF_RZ", "EVAP", "TRANSP", "Q_RZ", "INF_SS", "Q_SS", "CPR", "STORAGE", "AGEING"):
-        split.stages(0, SAS_STAGES[name])
-    for nm in fused.names:
-        try:
-            a = fused.download(nm)
-        except Exception:
-            continue
-        b = split.download(nm)
-        if nm[:2] in ("tt", "rt") and a.ndim == 1:
-            # statistics of a launch of their own read TT back from HBM, where the value at a thread's lower
-            # edge is the neighbour's upper edge instead of the scan's own (one rounding apart)
-            assert np.allclose(a, b, rtol=1e-12, atol=0, equal_nan=True), nm
-        else:
-            assert np.array_equal(a, b, equal_nan=True), nm
+    step_fused_and_staged(fused, split)
     fused.close()
     split.close()
 
@@ -204,11 +214,8 @@ def test_random_columns_against_oracle(n, ages, substeps, stats):
     ctx.close()
 
 
-def test_fifth_root_fallback_inside_the_kernel():
-    """The benchmark's exponents with quotients SA / S below the fifth-root path's range (2^-127): the youngest classes hold 1e-45 mm
-    (the residue of a residue), nothing infiltrates, so Omega's first arguments under soil evaporation (k = 0.2) are ~1e-47 and the
-    wave that owns them takes the general path for its classes (the ballot in sas_omega) -- in the benchmark's shape (k_sas8<2>) and in a
-    four-class shape.  Against the oracle: no NaN or garbage, every column within the loose bound of a residue tie, most at 1e-10."""
+def fifth_root_problems():
+    """(n, ages, problem, the columns with tiny youngest classes) of test_fifth_root_fallback_inside_the_kernel."""
     for n, ages in ((48, 1000), (48, 200)):
         st = random_problem(n, ages, 6, seed=7 + ages, stats=True)
         for f, k in zip(FLUXES, (0.2, 0.5, 1.5, 1.5, 0.2)):   # SVATOXYGEN18_benchmark.py:129-138
@@ -224,6 +231,39 @@ def test_fifth_root_fallback_inside_the_kernel():
         st.inp["evap_soil"][:] = 0.4 + 0.01 * np.arange(n)
         st.inp["cpr_rz"][:] = 0.2
         st.maskCatch[:] = 1
+        yield n, ages, st, tiny
+
+
+def gamma_problems():
+    """(n, ages, problem) of test_gamma_and_reversed_exponential_against_oracle."""
+    for n, ages, substeps in ((128, 1000, 3), (200, 100, 4), (60, 2200, 2), (150, 30, 5)):
+        st = random_problem(n, ages, substeps, seed=ages)
+        rng = np.random.default_rng(ages + 1)
+        for f in FLUXES:
+            p = st.sas[f]
+            p[:, 0] = rng.choice([4, 4, 4, 52], n)
+            p[:, 1] = np.where(p[:, 0] == 4, rng.choice([0.2, 0.5, 1.0, 1.7, 3.0, 8.0, 25.0], n), rng.uniform(0.5, 5, n))
+            p[:, 2] = rng.choice([0.3, 1.0, 2.0, 5.0, 12.0, 40.0], n)
+        yield n, ages, st
+
+
+def closed_form_problems():
+    """(n, ages, problem) of test_closed_form_exponents_against_oracle."""
+    for n, ages, substeps in ((160, 1000, 6), (200, 90, 3), (64, 2100, 2)):
+        st = random_problem(n, ages, substeps, seed=7 + ages, stats=True)
+        rng = np.random.default_rng(ages)
+        for f in FLUXES:
+            st.sas[f][:, 0] = 6
+            st.sas[f][:, 1] = rng.choice([0.5, 1.5, 1.0, 0.2], n)
+        yield n, ages, st
+
+
+def test_fifth_root_fallback_inside_the_kernel():
+    """The benchmark's exponents with quotients SA / S below the fifth-root path's range (2^-127): the youngest classes hold 1e-45 mm
+    (the residue of a residue), nothing infiltrates, so Omega's first arguments under soil evaporation (k = 0.2) are ~1e-47 and the
+    wave that owns them takes the general path for its classes (the ballot in sas_omega) -- in the benchmark's shape (k_sas8<2>) and in a
+    four-class shape.  Against the oracle: no NaN or garbage, every column within the loose bound of a residue tie, most at 1e-10."""
+    for n, ages, st, tiny in fifth_root_problems():
         ref = clone(st)
         ctx = make_ctx(st)
         push(ctx, st)
@@ -295,14 +335,7 @@ def test_unknown_family_is_reported():
 def test_gamma_and_reversed_exponential_against_oracle():
     """Codes 4 and 52 on random columns of every workgroup shape: a wide range of shapes / scales for the incomplete
     gamma function (series and continued-fraction branch), against the oracle's own evaluation."""
-    for n, ages, substeps in ((128, 1000, 3), (200, 100, 4), (60, 2200, 2), (150, 30, 5)):
-        st = random_problem(n, ages, substeps, seed=ages)
-        rng = np.random.default_rng(ages + 1)
-        for f in FLUXES:
-            p = st.sas[f]
-            p[:, 0] = rng.choice([4, 4, 4, 52], n)
-            p[:, 1] = np.where(p[:, 0] == 4, rng.choice([0.2, 0.5, 1.0, 1.7, 3.0, 8.0, 25.0], n), rng.uniform(0.5, 5, n))
-            p[:, 2] = rng.choice([0.3, 1.0, 2.0, 5.0, 12.0, 40.0], n)
+    for n, ages, st in gamma_problems():
         ref = clone(st)
         ctx = make_ctx(st)
         push(ctx, st)
@@ -476,12 +509,7 @@ def test_hoisted_division_is_ieee_division():
 def test_closed_form_exponents_against_oracle():
     """Power-law exponents 0.5, 1.5 and 1 (the benchmark's 0.5 / 1.5 among them) take the square-root path of the kernel
     instead of exp2(k * log2 .): same results as the oracle's pow within the usual bounds, on every workgroup shape."""
-    for n, ages, substeps in ((160, 1000, 6), (200, 90, 3), (64, 2100, 2)):
-        st = random_problem(n, ages, substeps, seed=7 + ages, stats=True)
-        rng = np.random.default_rng(ages)
-        for f in FLUXES:
-            st.sas[f][:, 0] = 6
-            st.sas[f][:, 1] = rng.choice([0.5, 1.5, 1.0, 0.2], n)
+    for n, ages, st in closed_form_problems():
         ref = clone(st)
         ctx = make_ctx(st)
         push(ctx, st)
