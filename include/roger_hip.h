@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 14  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost */
+#define RH_ABI_VERSION 15  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -514,6 +514,35 @@ int rh_events_headers(rh_ctx *ctx, int64_t *hdr /* (n_slots, 6) */, size_t bytes
 int rh_events_download(rh_ctx *ctx, int item, int slot, double *host, size_t bytes);
 int rh_events_set_drained(rh_ctx *ctx, int64_t event_id);
 int rh_events_lost(rh_ctx *ctx, int *lost);
+
+/* ---- duration curves: per column the histogram of a plane's interval values, their exact extremes and the run lengths of a spell ----
+ * After rh_durations_configure every step, wherever the accumulators' kernel is launched, is followed by one more launch over all
+ * columns (k_durations, roger_amd/csrc/rh_durations.h, which states the rule in full).  With (t0, t1] the step, iv = interval_seconds:
+ *   first = t0 % iv == 0;  closes = t1 % iv == 0 && t1 - t0 <= iv;  k = t1 / iv - 1 - t_first / iv;  counted = closes && k >= 0
+ * Per item, v the plane's value after the step: kind 0 (SUM) acc = first ? v : acc + v on every step, s = acc; kind 1 (LAST) s = v on a
+ * counted step.  On a counted step, with the item's edges e_0 < ... < e_{m-1}: the bin is m + 1 for a NaN s, else #{q : e_q <= s} (a
+ * value on an edge goes up), and its uint32 counter gains 1; mn = s < mn ? s : mn, mx = s > mx ? s : mx from +inf / -inf; with a
+ * threshold (not NaN) in = side == 0 ? s < thr : s >= thr, run = in ? run + 1 : 0, n_spells += in && run == 1, longest = max(longest,
+ * run).  Spells run over consecutive counted intervals: an hourly or ten-minute interval under a longer step is never started, it is
+ * neither counted nor does it break a run.  An interval under way at the configuration (t_first at or before it) sums what is seen
+ * from then on.
+ *   planes, kinds, n_edges:  n_items (at most 16) float64 planes, their kinds and their numbers of edges (0 ... 63 each)
+ *   edges:                   the items' edges one behind the other, finite and strictly ascending within an item
+ *   thresholds, sides:       per item the spell's threshold (NaN: no spell) and side (0: BELOW, 1: AT_OR_ABOVE)
+ *   mask:                    a byte per column (0: the column loads and stores nothing) or null: every column
+ *   interval_seconds:        86400, 3600 or 600;  t_first: a multiple of it, the start of the first counted interval
+ * n_items == 0 releases the buffers and stops the launches.  Every other accepted call clears the counters.  RH_ERR_ARG (rh_last_error
+ * names the item and the value) leaves the previous configuration working: more than 16 items, more than 63 edges, an edge that is not
+ * finite, edges not strictly ascending, an int32 plane or one the context does not hold, a kind or side out of range, an interval
+ * outside the step classes, a t_first that is not a multiple of it, a size beyond any device.
+ *   rh_durations_read   counts (sum of the items' m + 2, n) uint32, item by item, the NaN bin last; values (n_items, 3, n) float64
+ *                       {acc, min, max}; spells (n_items, 3, n) uint32 {run, longest, n_spells}.  Synchronises; RH_ERR_STATE before
+ *                       rh_durations_configure (or after it released the buffers). */
+int rh_durations_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 LAST */, const int *n_edges, int n_items,
+                           const double *edges, const double *thresholds, const int *sides /* 0 BELOW, 1 AT_OR_ABOVE */,
+                           const unsigned char *mask, int64_t interval_seconds, int64_t t_first);
+int rh_durations_read(rh_ctx *ctx, uint32_t *counts, size_t count_bytes, double *values /* (n_items, 3, n) */, size_t value_bytes,
+                      uint32_t *spells /* (n_items, 3, n) */, size_t spell_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 14  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 15  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -171,6 +171,8 @@ def load():
     lib.rh_events_download.argtypes = [vp, i32, i32, vp, C.c_size_t]
     lib.rh_events_set_drained.argtypes = [vp, i64]
     lib.rh_events_lost.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.rh_durations_configure.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, i64]
+    lib.rh_durations_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -638,6 +640,7 @@ DECLARED_SYMBOLS = (
     "rh_zonal_configure", "rh_zonal_count", "rh_zonal_read",
     "rh_scores_configure", "rh_scores_read",
     "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
+    "rh_durations_configure", "rh_durations_read",
 )
 
 
@@ -1066,6 +1069,47 @@ class Context:
     def events_set_drained(self, event_id):
         """Publish the highest event id that has been read out: the slots of the events up to it may be taken again."""
         self._check(self._lib.rh_events_set_drained(self._h, int(event_id)), "rh_events_set_drained")
+
+    # -- duration curves (rh_durations_*) ------------------------------------------------------------
+    def durations_configure(self, names, kinds=(), edges=(), spells=(), mask=None, interval=86400, t_first=0):
+        """After every step aggregate `names` (float64 planes; kinds: 0 sum over the interval, 1 value at its end) to the interval and, at
+        every counted interval's end, count the value into the column's histogram over `edges[j]` (ascending, finite, at most 63; shared by
+        all columns), keep its extremes and, with spells[j] = (side, threshold) (side 0: below, 1: at or above; None: no spell), the run
+        lengths.  `mask`: a byte per interior column of this context's block (C order, 0: not counted), None: every column.  The first
+        counted interval starts at t_first.  No names: release the buffers and stop."""
+        names = list(names)
+        ni = len(names)
+        edges = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in edges]
+        spells = list(spells) if len(spells) else [None] * ni
+        if len(kinds) != ni or len(edges) != ni or len(spells) != ni:
+            raise ValueError(f"durations_configure: {len(kinds)} kinds, {len(edges)} edge lists and {len(spells)} spells for {ni} items")
+        ids = (C.c_int * max(1, ni))(*[self.index[n] for n in names])
+        kd = (C.c_int * max(1, ni))(*[int(k) for k in kinds])
+        ne = (C.c_int * max(1, ni))(*[int(e.size) for e in edges])
+        sd = (C.c_int * max(1, ni))(*[0 if s is None else int(s[0]) for s in spells])
+        thr = np.array([np.nan if s is None else float(s[1]) for s in spells] or [np.nan], dtype=np.float64)
+        flat = np.ascontiguousarray(np.concatenate(edges + [np.zeros(1)]), dtype=np.float64)
+        mk = None
+        if names and mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if mk.size != self.n:
+                raise ValueError(f"durations_configure: the mask has {mk.size} values, the context {self.n} columns")
+        self._check(self._lib.rh_durations_configure(self._h, ids, kd, ne, ni, flat.ctypes.data_as(C.c_void_p), thr.ctypes.data_as(C.c_void_p), sd,
+                                                     None if mk is None else mk.ctypes.data_as(C.c_void_p), int(interval), int(t_first)),
+                    "rh_durations_configure")
+        self._durations_shape = (ni, [int(e.size) for e in edges])   # (a refused configuration leaves the previous one)
+
+    def durations_read(self):
+        """(counts: one uint32 (m_j + 2, n) per item, the NaN bin last; values float64 (n_items, 3, n): acc, min, max; spells uint32
+        (n_items, 3, n): run, longest, n_spells).  Synchronises."""
+        ni, ms = getattr(self, "_durations_shape", (0, []))
+        counts = np.empty((sum(m + 2 for m in ms), self.n), dtype=np.uint32)
+        values = np.empty((ni, 3, self.n), dtype=np.float64)
+        spells = np.empty((ni, 3, self.n), dtype=np.uint32)
+        self._check(self._lib.rh_durations_read(self._h, counts.ctypes.data_as(C.c_void_p), counts.nbytes, values.ctypes.data_as(C.c_void_p),
+                                                values.nbytes, spells.ctypes.data_as(C.c_void_p), spells.nbytes), "rh_durations_read")
+        offs = np.concatenate([[0], np.cumsum([m + 2 for m in ms])]).astype(int)
+        return [counts[offs[j]:offs[j + 1]] for j in range(ni)], values, spells
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

@@ -150,6 +150,13 @@ struct rh_ctx {
     DevBuf<long long> events_hdr_buf, events_ids_buf;
     int events_nitems = 0, events_nslots = 0;   // 0: not configured, no k_events launch
     int events_planes[RH_EVENTS_MAX_ITEMS] = {};
+    // duration curves (rh_durations_configure): the counters, the float planes, the spell planes, the edges and the mask (not held:
+    // every column)
+    DevBuf<unsigned> durations_counts_buf, durations_spells_buf;
+    DevBuf<double> durations_vals_buf, durations_edges_buf;
+    DevBuf<unsigned char> durations_mask_buf;
+    int durations_nitems = 0, durations_nbins = 0;   // 0: not configured, no k_durations launch; nbins: the sum of the items' m + 2
+    int durations_planes[RH_DURATIONS_MAX_ITEMS] = {};
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

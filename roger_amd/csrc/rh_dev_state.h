@@ -170,6 +170,20 @@ struct DevState {
     long long events_drained, events_running;
     int events_lost, events_nitems, events_nslots, events_nblk;
     int events_planes[16], events_kinds[16];   // RH_EVENTS_MAX_ITEMS; kinds: 0 SUM, 1 PEAK, 2 FIRST, 3 LAST
+
+    // duration curves (rh_durations_configure; k_durations in rh_durations.h): durations_counts (bin, n) uint32, item j's m_j + 2 bins
+    // (the NaN bin last) from durations_bin_off[j]; durations_vals (item, {acc, mn, mx}, n) float64; durations_spells (item, {run,
+    // longest, n_spells}, n) uint32; durations_edges: the items' edges one behind the other, item j's durations_nedges[j] from
+    // durations_edge_off[j]; durations_mask: a byte per column (0: not counted) or null; durations_thr: NaN for an item without a
+    // spell; durations_nsum: SUM items among them.  (Behind everything else: no member another kernel addresses moves.)
+    unsigned *durations_counts, *durations_spells;
+    double *durations_vals;
+    const double *durations_edges;
+    const unsigned char *durations_mask;
+    long long durations_interval, durations_t_first;
+    int durations_nitems, durations_nsum;
+    int durations_planes[16], durations_kinds[16], durations_nedges[16], durations_edge_off[16], durations_bin_off[16], durations_sides[16];
+    double durations_thr[16];   // RH_DURATIONS_MAX_ITEMS; kinds: 0 SUM, 1 LAST; sides: 0 BELOW, 1 AT_OR_ABOVE
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

@@ -1,10 +1,12 @@
 // rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
 // (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*), the scores against observed series
-// (rh_scores_*) and the event outputs (rh_events_*).  Part of the one translation unit roger_hip.hip, behind rh_context.h.
+// (rh_scores_*), the event outputs (rh_events_*) and the duration curves (rh_durations_*).  Part of the one translation unit
+// roger_hip.hip, behind rh_context.h.
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure, rh_scores_configure,
-// rh_events_configure): what the fused kernel must leave in memory after every step, from the UNION of the planes of all six -- the
-// accumulators, the points, the totals, the zonal totals, the scores and the event outputs.  A plane the sparse kernel leaves out -- a
+// rh_events_configure, rh_durations_configure): what the fused kernel must leave in memory after every step, from the UNION of the planes
+// of all seven -- the accumulators, the points, the totals, the zonal totals, the scores, the event outputs and the duration curves.
+// A plane the sparse kernel leaves out -- a
 // pure output, or one of the five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in
 // DevState::keep: the KEEP variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
 static int observers_changed(rh_ctx *ctx) {
@@ -28,6 +30,7 @@ static int observers_changed(rh_ctx *ctx) {
     add(ctx->zonal_planes, ctx->zonal_nplanes);
     add(ctx->scores_planes, ctx->scores_nitems);
     add(ctx->events_planes, ctx->events_nitems);
+    add(ctx->durations_planes, ctx->durations_nitems);
     const int any = reads_sparse ? 1 : 0;
     HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
     HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
@@ -42,9 +45,11 @@ static int observers_changed(rh_ctx *ctx) {
 // workgroup more with RH_TAIL_PRE; 0: one workgroup per RH_BLOCK columns), then the points' row -- ONE workgroup (at most 8 192 values),
 // then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them -- then the zonal totals' row: a
 // workgroup per RH_BLOCK columns and one per zone (rh_zonal.h) -- then the scores' moments over all columns, on the accumulators' grid
-// (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h).  after_fused: rh_control.h, k_diag.
+// (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h) -- then the duration curves, on the same grid
+// (rh_durations.h).  after_fused: rh_control.h, k_diag.
 static bool has_observers(const rh_ctx *ctx) {
-    return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems;
+    return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems ||
+           ctx->durations_nitems;
 }
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
@@ -60,6 +65,7 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     }
     if (ctx->scores_nitems) hipLaunchKernelGGL(k_scores, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->events_nitems) hipLaunchKernelGGL(k_events, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    if (ctx->durations_nitems) hipLaunchKernelGGL(k_durations, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -677,6 +683,136 @@ int rh_events_lost(rh_ctx *ctx, int *lost) {
     if (int rc = events_check(ctx, "rh_events_lost")) return rc;
     if (!lost) return fail(ctx, RH_ERR_ARG, "rh_events_lost: null pointer");
     HIPCHK(ctx, hipMemcpyAsync(lost, &ctx->dev->events_lost, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+
+// ---- duration curves (include/roger_hip.h; the kernel and the rule: rh_durations.h) ----
+// the buffers, cleared: counters and spells to 0, acc to +0.0, mn / mx to +inf / -inf
+static int durations_alloc(rh_ctx *ctx, int n_items, int n_bins, const double *edges, int n_edges, const unsigned char *mask) {
+    const size_t n = (size_t)ctx->n, cb = (size_t)n_bins * n * sizeof(unsigned), vb = (size_t)n_items * 3 * n * sizeof(double),
+                 sb = (size_t)n_items * 3 * n * sizeof(unsigned);
+    HIPCHK(ctx, ctx->durations_counts_buf.alloc(cb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->durations_counts_buf, 0, cb, ctx->stream));
+    HIPCHK(ctx, ctx->durations_spells_buf.alloc(sb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->durations_spells_buf, 0, sb, ctx->stream));
+    HIPCHK(ctx, ctx->durations_vals_buf.alloc(vb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->durations_vals_buf, 0, vb, ctx->stream));
+    std::vector<double> init(2 * n, HUGE_VAL);   // one item's mn and mx planes
+    std::fill(init.begin() + n, init.end(), -HUGE_VAL);
+    for (int j = 0; j < n_items; ++j)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->durations_vals_buf + ((size_t)j * 3 + 1) * n, init.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, ctx->durations_edges_buf.alloc((size_t)(n_edges ? n_edges : 1) * sizeof(double)));
+    if (n_edges) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->durations_edges_buf, edges, (size_t)n_edges * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (mask) {
+        HIPCHK(ctx, ctx->durations_mask_buf.alloc(n));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->durations_mask_buf, mask, n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (`init` is a local)
+    return RH_OK;
+}
+int rh_durations_configure(rh_ctx *ctx, const int *planes, const int *kinds, const int *n_edges, int n_items, const double *edges,
+                           const double *thresholds, const int *sides, const unsigned char *mask, int64_t interval_seconds, int64_t t_first) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_DURATIONS_MAX_ITEMS)
+        return fail(ctx, RH_ERR_ARG, "rh_durations_configure: n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_DURATIONS_MAX_ITEMS) + ")");
+    const bool off = n_items == 0;
+    int plane_list[RH_DURATIONS_MAX_ITEMS] = {}, kind_list[RH_DURATIONS_MAX_ITEMS] = {}, m_list[RH_DURATIONS_MAX_ITEMS] = {},
+        edge_off[RH_DURATIONS_MAX_ITEMS] = {}, bin_off[RH_DURATIONS_MAX_ITEMS] = {}, side_list[RH_DURATIONS_MAX_ITEMS] = {};
+    double thr_list[RH_DURATIONS_MAX_ITEMS];
+    std::fill(thr_list, thr_list + RH_DURATIONS_MAX_ITEMS, std::nan(""));
+    int total_edges = 0, total_bins = 0, n_sum = 0;
+    if (!off) {
+        if (!planes || !kinds || !n_edges || !thresholds || !sides) return fail(ctx, RH_ERR_ARG, "rh_durations_configure: null pointer");
+        if (interval_seconds != 86400 && interval_seconds != 3600 && interval_seconds != 600)
+            return fail(ctx, RH_ERR_ARG, "rh_durations_configure: interval_seconds = " + std::to_string(interval_seconds) +
+                                         " (the interval is a day, an hour or ten minutes: the step classes)");
+        if (t_first < 0 || t_first % interval_seconds)
+            return fail(ctx, RH_ERR_ARG, "rh_durations_configure: t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
+                                         std::to_string(interval_seconds) + " s)");
+        for (int j = 0; j < n_items; ++j) {   // (item by item, as for the scores)
+            const std::string item = " of item " + std::to_string(j);
+            if (int rc = check_planes(ctx, "rh_durations_configure: item " + std::to_string(j) + ": ", planes + j, 1, plane_list + j, FLOAT64_IDS)) return rc;
+            if (kinds[j] != RH_DURATIONS_SUM && kinds[j] != RH_DURATIONS_LAST)
+                return fail(ctx, RH_ERR_ARG, "rh_durations_configure: kind " + std::to_string(kinds[j]) + item + " (0: SUM, 1: LAST)");
+            if (n_edges[j] < 0 || n_edges[j] > RH_DURATIONS_MAX_EDGES)
+                return fail(ctx, RH_ERR_ARG, "rh_durations_configure: " + std::to_string(n_edges[j]) + " edges" + item + " (0 ... " +
+                                             std::to_string(RH_DURATIONS_MAX_EDGES) + ")");
+            if (n_edges[j] && !edges) return fail(ctx, RH_ERR_ARG, "rh_durations_configure: null pointer");
+            for (int q = 0; q < n_edges[j]; ++q) {
+                const double e = edges[total_edges + q];
+                if (!std::isfinite(e))
+                    return fail(ctx, RH_ERR_ARG, "rh_durations_configure: edge " + std::to_string(q) + item + " is not finite");
+                if (q && !(edges[total_edges + q - 1] < e))
+                    return fail(ctx, RH_ERR_ARG, "rh_durations_configure: the edges" + item + " are not strictly ascending (edge " + std::to_string(q) + ")");
+            }
+            if (thresholds[j] == thresholds[j] && sides[j] != RH_DURATIONS_BELOW && sides[j] != RH_DURATIONS_AT_OR_ABOVE)
+                return fail(ctx, RH_ERR_ARG, "rh_durations_configure: side " + std::to_string(sides[j]) + item + " (0: BELOW, 1: AT_OR_ABOVE)");
+            kind_list[j] = kinds[j];
+            m_list[j] = n_edges[j];
+            edge_off[j] = total_edges;
+            bin_off[j] = total_bins;
+            thr_list[j] = thresholds[j];
+            side_list[j] = thresholds[j] == thresholds[j] ? sides[j] : 0;
+            total_edges += n_edges[j];
+            total_bins += n_edges[j] + 2;
+            n_sum += kinds[j] == RH_DURATIONS_SUM;
+        }
+        // the capacity rule of the rings, on the words per column: 4 per bin, 36 per item
+        const int64_t words = ((int64_t)total_bins + 9 * (int64_t)n_items) * ctx->n;
+        if (int rc = check_capacity(ctx, "rh_durations_configure: " + std::to_string(total_bins) + " bins and " + std::to_string(n_items) +
+                                             " items over " + std::to_string(ctx->n) + " columns, in 4-byte words: ", words)) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that count into the old buffers)
+    HIPCHK(ctx, ctx->durations_counts_buf.release());
+    HIPCHK(ctx, ctx->durations_spells_buf.release());
+    HIPCHK(ctx, ctx->durations_vals_buf.release());
+    HIPCHK(ctx, ctx->durations_edges_buf.release());
+    HIPCHK(ctx, ctx->durations_mask_buf.release());
+    ctx->durations_nitems = ctx->durations_nbins = 0;
+    if (int rc = off ? RH_OK : durations_alloc(ctx, n_items, total_bins, edges, total_edges, mask)) {   // refused: the observer is off
+        const std::string why = ctx->err;
+        (void)rh_durations_configure(ctx, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0);
+        return fail(ctx, rc, why);
+    }
+    if (!off) {
+        ctx->durations_nitems = n_items;
+        ctx->durations_nbins = total_bins;
+    }
+    std::memcpy(ctx->durations_planes, plane_list, sizeof(plane_list));
+    const long long iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first;
+    const double *const edges_dev = ctx->durations_edges_buf;
+    const unsigned char *const mask_dev = ctx->durations_mask_buf;
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_counts, *ctx->durations_counts_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_spells, *ctx->durations_spells_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_vals, *ctx->durations_vals_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_edges, edges_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_mask, mask_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_interval, iv));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_t_first, tf));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_nitems, ctx->durations_nitems));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_nsum, n_sum));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_planes, plane_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_kinds, kind_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_nedges, m_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_edge_off, edge_off));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_bin_off, bin_off));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_sides, side_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::durations_thr, thr_list));
+    return observers_changed(ctx);   // synchronises: the sources above are locals
+}
+int rh_durations_read(rh_ctx *ctx, uint32_t *counts, size_t count_bytes, double *values, size_t value_bytes, uint32_t *spells, size_t spell_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->durations_nitems) return fail(ctx, RH_ERR_STATE, "rh_durations_read: rh_durations_configure has not been called");
+    const size_t n = (size_t)ctx->n, ni = (size_t)ctx->durations_nitems;
+    if (!counts || !values || !spells || count_bytes != (size_t)ctx->durations_nbins * n * sizeof(uint32_t) || value_bytes != ni * 3 * n * sizeof(double) ||
+        spell_bytes != ni * 3 * n * sizeof(uint32_t))
+        return fail(ctx, RH_ERR_ARG, "rh_durations_read: size mismatch (n_bins x n uint32, n_items x 3 x n float64, n_items x 3 x n uint32)");
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->durations_counts_buf, count_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(values, ctx->durations_vals_buf, value_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(spells, ctx->durations_spells_buf, spell_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }

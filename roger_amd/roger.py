@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, events, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
+from . import diagnostics, distributed, durations, events, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -157,6 +157,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             zonal_totals.initialize(state)
             scores.initialize(state)
             events.initialize(state)
+            durations.initialize(state)
             sas_points.initialize(state)
             sas_totals.initialize(state)
             sas_zonal_totals.initialize(state)
@@ -167,6 +168,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             restart.read_restart(state)   # roger/roger.py:324-326
             scores.start(state)           # (the clock is known: a continued run scores from the next interval boundary)
             events.start(state)           # (the event ids are known: an event that is running now keeps event_start = -1)
+            durations.start(state)        # (the clock is known: a continued run counts from the next interval boundary)
             if offline and state.settings.warmup_done:
                 sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
                 sas_totals.start(state)
@@ -466,6 +468,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         zonal_totals.close(self.state)
         scores.close(self.state)
         events.close(self.state)
+        durations.close(self.state)
         sas_points.close(self.state)
         sas_totals.close(self.state)
         sas_zonal_totals.close(self.state)

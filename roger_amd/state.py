@@ -360,6 +360,9 @@ class RogerState:
         from .events import Events
 
         self.events = Events()              # per-column sums, peaks, first and last values of every rainfall event (roger_amd/events.py)
+        from .durations import Durations
+
+        self.durations = Durations()        # per-column histograms, extremes and spells of interval values (roger_amd/durations.py)
         from .sas_totals import TransportTotals
 
         self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
