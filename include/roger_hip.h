@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 15  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read */
+#define RH_ABI_VERSION 16  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -543,6 +543,34 @@ int rh_durations_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0
                            const unsigned char *mask, int64_t interval_seconds, int64_t t_first);
 int rh_durations_read(rh_ctx *ctx, uint32_t *counts, size_t count_bytes, double *values /* (n_items, 3, n) */, size_t value_bytes,
                       uint32_t *spells /* (n_items, 3, n) */, size_t spell_bytes);
+
+/* ---- ensemble bands: per interval the exact quantiles ACROSS the columns of a plane's interval values, a ring on the device ----
+ * After rh_bands_configure every step, wherever the accumulators' kernel is launched, is followed by one launch over all columns
+ * (k_bands) and six small ones (k_bands_select; roger_amd/csrc/rh_bands.h states the rule and the selection in full).  The clock and
+ * the aggregation are the duration curves': first, closes, k and counted as above; kind 0 (SUM) acc = first ? v : acc + v on every step,
+ * kind 1 (LAST) the value on a counted step.  On a counted step the interval value of a column is s = (SUM ? acc : v) + 0.0 (a -0.0
+ * becomes +0.0); a NaN s is counted in n_nan and left out, +-inf are ordinary values, m is the number of masked-in columns that are
+ * left.  Per probability p the rank is r = clamp((int64)ceil(p * (double)m) - 1, 0, m - 1) and the result the r-th smallest s, the
+ * bits of np.sort(s)[r] (the "inverted CDF" quantile; p = 0 the minimum, p = 1 the maximum); NaN where m == 0.  One row per counted
+ * interval: header int64 {k, t1, then per item m, n_nan}, values (n_items, n_probs) float64.
+ *   planes, kinds:     n_items (at most 8) float64 planes and their kinds
+ *   probs:             n_probs (1 ... 8) probabilities within [0, 1], shared by the items
+ *   interval_seconds:  86400, 3600 or 600;  t_first: a multiple of it, the start of the first counted interval
+ *   mask:              a byte per column (0: the column takes no part) or null: every column
+ *   capacity:          rows resident on the device, row r at r mod capacity
+ * n_items == 0 releases the buffers and stops the launches.  Every other accepted call starts a new series from row 0 and clears the
+ * accumulators.  RH_ERR_ARG (rh_last_error names the item and the value) leaves the previous configuration working: more than 8 items
+ * or probabilities, a probability outside [0, 1], an int32 plane or one the context does not hold, a kind out of range, an interval
+ * outside the step classes, a t_first that is not a multiple of it, 2^31 columns or more, a capacity below 1 or beyond any device.
+ *   rh_bands_count   rows recorded since the configuration
+ *   rh_bands_read    rows [first_row, first_row + n_rows): hdr (n_rows, 2 + 2 * n_items) int64, values (n_rows, n_items, n_probs) float64;
+ *                    RH_ERR_ARG for rows not yet recorded or already overwritten, as rh_totals_read.
+ * Both synchronise; RH_ERR_STATE before rh_bands_configure (or after it released the buffers).  Order statistics of blocks do not
+ * merge: with several ranks a rank's rows are the bands of its own block. */
+int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 LAST */, int n_items, const double *probs, int n_probs,
+                       int64_t interval_seconds, int64_t t_first, const unsigned char *mask, int64_t capacity);
+int rh_bands_count(rh_ctx *ctx, int64_t *rows_total);
+int rh_bands_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

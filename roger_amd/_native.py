@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 15  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 16  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -173,6 +173,9 @@ def load():
     lib.rh_events_lost.argtypes = [vp, C.POINTER(C.c_int)]
     lib.rh_durations_configure.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, i64]
     lib.rh_durations_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    lib.rh_bands_configure.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i64]
+    lib.rh_bands_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_bands_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -641,6 +644,7 @@ DECLARED_SYMBOLS = (
     "rh_scores_configure", "rh_scores_read",
     "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
     "rh_durations_configure", "rh_durations_read",
+    "rh_bands_configure", "rh_bands_count", "rh_bands_read",
 )
 
 
@@ -1110,6 +1114,45 @@ class Context:
                                                 values.nbytes, spells.ctypes.data_as(C.c_void_p), spells.nbytes), "rh_durations_read")
         offs = np.concatenate([[0], np.cumsum([m + 2 for m in ms])]).astype(int)
         return [counts[offs[j]:offs[j + 1]] for j in range(ni)], values, spells
+
+    # -- ensemble bands (rh_bands_*) -------------------------------------------------------------------
+    def bands_configure(self, names, kinds=(), probs=(0.05, 0.5, 0.95), interval=86400, t_first=0, mask=None, capacity=4096):
+        """After every step aggregate `names` (at most 8 float64 planes; kinds: 0 sum over the interval, 1 value at its end) to the
+        interval and, at every counted interval's end, record the exact quantiles ACROSS the columns of `mask` (a byte per interior column
+        of this context's block, C order; None: every column) at `probs` (at most 8, within [0, 1]) as one row of a ring of `capacity`
+        rows on the device.  The first counted interval starts at t_first.  No names: release the buffers and stop."""
+        names = list(names)
+        ni = len(names)
+        if len(kinds) != ni:
+            raise ValueError(f"bands_configure: {len(kinds)} kinds for {ni} items")
+        pr = np.ascontiguousarray(np.asarray(list(probs) or [0.0], dtype=np.float64).reshape(-1))
+        ids = (C.c_int * max(1, ni))(*[self.index[n] for n in names])
+        kd = (C.c_int * max(1, ni))(*[int(k) for k in kinds])
+        mk = None
+        if names and mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if mk.size != self.n:
+                raise ValueError(f"bands_configure: the mask has {mk.size} values, the context {self.n} columns")
+        self._check(self._lib.rh_bands_configure(self._h, ids, kd, ni, pr.ctypes.data_as(C.c_void_p), len(list(probs)), int(interval), int(t_first),
+                                                 None if mk is None else mk.ctypes.data_as(C.c_void_p), int(capacity)), "rh_bands_configure")
+        self._bands_shape = (ni, len(list(probs)) if ni else 0)   # (a refused configuration leaves the previous one)
+
+    def bands_count(self):
+        """Rows recorded since bands_configure."""
+        n = C.c_int64()
+        self._check(self._lib.rh_bands_count(self._h, C.byref(n)), "rh_bands_count")
+        return n.value
+
+    def bands_read(self, first, n):
+        """Rows [first, first + n) of the ring: (hdr int64 (n, 2 + 2 * items): k, t1, then per item m and n_nan; values float64
+        (n, items, probs))."""
+        n = int(n)
+        ni, nq = getattr(self, "_bands_shape", (0, 0))
+        hdr = np.empty((n, 2 + 2 * ni), dtype=np.int64)
+        values = np.empty((n, ni, nq), dtype=np.float64)
+        self._check(self._lib.rh_bands_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                            values.nbytes), "rh_bands_read")
+        return hdr, values
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

@@ -1,0 +1,264 @@
+// rh_bands.h -- ensemble bands (rh_bands_configure): after every step a variable is aggregated to an interval per column, and at every
+// interval's end the exact quantiles ACROSS the columns -- the 5 % / 50 % / 95 % prediction band of a parameter study -- go into one row
+// of a ring on the device.  A selection, not a reduction: integer counters over bit patterns, so a row is np.sort(...)[r] bit for bit.
+// Part of the one translation unit roger_hip.hip, behind rh_durations.h.
+//
+// The clock is k_durations' (uniform over the grid, from D->S): t1 = S.time, t0 = t1 - S.dt_secs, iv the interval in seconds (86400, 3600
+// or 600);
+//   first   = t0 % iv == 0
+//   closes  = t1 % iv == 0 && t1 - t0 <= iv     (a step longer than the interval never closes one)
+//   k       = t1 / iv - 1 - t_first / iv
+//   counted = closes && k >= 0                  (no upper bound on k)
+// after_fused && D->skipped ends every launch as for every other observer.
+//
+// Items.  At most 8 float64 planes, each SUM or LAST; column i with mask[i] == 0 (a mask is optional) loads and stores nothing.  v the
+// plane's value after the step:
+//   SUM:   acc = first ? v : acc + v on every step (k_durations' rule, the same order of additions)
+//   LAST:  nothing on a step that is not counted
+// Interval value.  On a counted step s = (SUM ? acc : v) + 0.0 -- the addition turns -0.0 into +0.0, so equal zeros have one bit pattern
+// and the result has no freedom left.  A NaN s is counted in n_nan and takes no further part; +-inf are ordinary values.  m is the
+// number of masked-in columns whose s is not a NaN.
+// Probabilities.  At most 8 probabilities p in [0, 1], shared by the items.  r = clamp((int64)ceil(p * (double)m) - 1, 0, m - 1) -- one
+// double multiplication and one ceil, the same on host and device -- and the result is the r-th smallest s (from 0): np.sort(s)[r],
+// the "inverted CDF" quantile; p = 0 is the minimum, p = 1 the maximum.  With m == 0 the row holds NaN.
+// Ring.  One row per counted interval, row q at q mod bands_cap (the one ring rule of rh_observers.h): header int64 {k, t1} and per item
+// {m, n_nan}; values (item, probability) float64.
+//
+// Keys.  k_bands (a workgroup per RH_BLOCK columns, after every step) does the SUM accumulation -- 24 B per SUM item and column; it ends
+// after the scalar loads when the step is not counted and there is no SUM item -- and on a counted step stores the order-preserving
+// key of s into the item's key plane: u = bits(s), key = u ^ (u >> 63 ? ~0 : 1 << 63); unsigned comparison of keys is < on the values.
+// Validity is part of the key plane, not a plane of its own: a NaN s stores RH_BANDS_KEY_NAN (~0 - 1), and a masked-out column keeps
+// RH_BANDS_KEY_MASKED (~0), which the configuration wrote once.  Both are the keys of NaN bit patterns, so no value's key equals them
+// (the largest value's key, +inf's, is 0xfff0000000000000); the selection skips every key >= RH_BANDS_KEY_NAN and counts the first.
+//
+// Selection.  A radix selection on the keys, most significant digit first, for all (item, probability) pairs at once, in
+// RH_BANDS_PASSES launches of k_bands_select<P> behind k_bands.  The host cannot know whether a step closes an interval (dt is the
+// device's), so the launches follow every step and end after the scalar loads on a step that is not counted.
+//   digits     11 bits: six passes over 11, 11, 11, 11, 11 and 9 bits.  8 bits would need eight passes.  A launch-bound grid (80 x 53
+//              columns, 21 us per step) pays per launch, a large grid per pass over the keys (8 B per column): both favour fewer
+//              passes, and 8 KiB of LDS per pair is there to be had -- a workgroup holds the 8 probabilities of ONE item (64 KiB) and
+//              takes the items one after the other, each from its own key plane.
+//   histogram  a workgroup strides over the tiles of RH_BLOCK keys (eight tiles in flight per thread) and counts the digit of every key
+//              whose higher digits equal the pair's prefix into an LDS histogram (uint32, LDS atomics).  In pass 0 all probabilities
+//              of an item share one histogram: there is no prefix yet.
+//   merge      the workgroup adds its NON-ZERO bins to the global histogram bands_hist [item][probability][2048] with integer atomic
+//              adds at device scope.  Integer adds commute: the sum does not depend on their order.  This is the one place where the
+//              project's "no atomics" habit, which is about floating-point sums, does not apply.  Device-scope atomics on one cache
+//              line are served one after the other (~ 25 ns each), so the grid is at most RH_BANDS_MAX_GRID
+//              workgroups (one per CU) however many tiles there are, and after pass 0 nearly every bin is empty.
+//   pick       the work of the workgroup that finishes last (k_step's tail pattern, one counter: the grid is small).  Its invariant
+//              is kept: a thread's adds are RETURNING atomics whose results feed an LDS add in front of the workgroup's barrier, and
+//              only behind that barrier does thread 0 count the workgroup done (a returning device-scope add on bands_done); the
+//              last workgroup reads the histograms with device-scope loads.  A wavefront per pair scans the bins -- 64 at a time, all
+//              loads requested first -- for the digit at which the cumulative count passes the remaining rank, appends it to the
+//              pair's prefix and subtracts the count below it from the rank (bands_prefix, bands_rank: device memory, read by the
+//              next launch).  Pass 0 also fixes m (the histogram's total), n_nan and r.  Then the workgroup clears the histograms
+//              and the counter with device-scope stores.
+//   row        after the last pass the prefix IS the key: inverted (key >> 63 ? key ^ 1 << 63 : ~key) it is the value.  Thread 0 writes
+//              the header and advances bands_rows last.
+// Cost.  A step that is not counted: as k_durations' (24 B per SUM item and column), and six launches that end after the scalar loads.
+// A counted step: k_bands' 8 B store per item and column, and six passes x 8 B per item and column of key reads.
+#pragma once
+
+#define RH_BANDS_MAX_ITEMS 8
+#define RH_BANDS_MAX_PROBS 8
+#define RH_BANDS_SUM 0
+#define RH_BANDS_LAST 1
+#define RH_BANDS_NBINS 2048   // 11-bit digits
+#define RH_BANDS_PASSES 6
+#define RH_BANDS_MAX_GRID 256   // workgroups of k_bands_select
+#define RH_BANDS_KEY_MASKED (~0ull)
+#define RH_BANDS_KEY_NAN (~0ull - 1ull)
+
+struct BandsClock {
+    bool first, counted;
+    long long k, t1;
+};
+RH_DEV BandsClock bands_clock(const DevState *D) {
+    const int64_t t1 = D->S.time, t0 = t1 - D->S.dt_secs, iv = D->bands_interval;
+    BandsClock c;
+    c.first = (t0 % iv) == 0;
+    c.k = t1 / iv - 1 - D->bands_t_first / iv;
+    c.counted = (t1 % iv) == 0 && t1 - t0 <= iv && c.k >= 0;
+    c.t1 = t1;
+    return c;
+}
+
+__global__ __launch_bounds__(RH_BLOCK) void k_bands(Arena a, DevState *D, int after_fused) {
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted && !D->bands_nsum) return;   // (uniform over the grid)
+    const int64_t i = (int64_t)blockIdx.x * RH_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned char *mask = D->bands_mask;
+    if (mask && !mask[i]) return;
+    const size_t n = (size_t)a.n;
+    const int ni = D->bands_nitems;
+    for (int j = 0; j < ni; ++j) {
+        const bool sum = D->bands_kinds[j] == RH_BANDS_SUM;
+        if (!sum && !c.counted) continue;   // LAST: only the value at a counted interval's end
+        double v;
+        rh_ld(a, D->bands_planes[j], i, v);
+        double s = v;
+        if (sum) {
+            double *p = D->bands_acc + (size_t)j * n + i;
+            if (!c.first) s = *p + v;
+            *p = s;
+        }
+        if (!c.counted) continue;
+        s = s + 0.0;
+        const unsigned long long u = (unsigned long long)__double_as_longlong(s);
+        D->bands_keys[(size_t)j * n + i] = s != s ? RH_BANDS_KEY_NAN : u ^ ((u >> 63) ? ~0ull : 1ull << 63);
+    }
+}
+
+// pass P of the selection: digit bits [shift, shift + width) of the key; the bits above them are the prefix
+template <int P>
+struct BandsPass {
+    static constexpr int shift = P < 5 ? 53 - 11 * P : 0, width = P < 5 ? 11 : 9, nb = 1 << width, high = shift + width;
+};
+RH_DEV unsigned bands_wave_scan(unsigned x) {   // inclusive, over the 64 lanes
+    const int lane = threadIdx.x & 63;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+template <int P>
+__global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D, int after_fused) {
+    using PS = BandsPass<P>;
+    constexpr int NB = PS::nb, NC = NB / 64, U = 8;
+    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_BANDS_NBINS];
+    __shared__ unsigned nan_count, posted, is_last;
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;   // (uniform over the grid)
+    const int ni = D->bands_nitems, np = D->bands_nprobs, nh = P == 0 ? 1 : np;
+    const int64_t n = a.n, ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    unsigned dep = 0;
+    if (threadIdx.x == 0) posted = 0;
+    for (int j = 0; j < ni; ++j) {
+        for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) hist[b] = 0;
+        if (threadIdx.x == 0) nan_count = 0;
+        __syncthreads();
+        unsigned long long pre[RH_BANDS_MAX_PROBS];
+#pragma unroll
+        for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q) pre[q] = (P > 0 && q < np) ? D->bands_prefix[j * RH_BANDS_MAX_PROBS + q] : 0ull;
+        const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
+        for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
+            unsigned long long key[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = (t + (int64_t)u * gridDim.x) * RH_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
+                key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_BANDS_KEY_MASKED;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (key[u] >= RH_BANDS_KEY_NAN) {
+                    if (P == 0 && key[u] == RH_BANDS_KEY_NAN) atomicAdd(&nan_count, 1u);
+                    continue;
+                }
+                const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
+                if (P == 0) {
+                    atomicAdd(&hist[d], 1u);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q)
+                        if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        unsigned *g = D->bands_hist + (size_t)j * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS;
+        for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) {
+            const unsigned cnt = hist[b];
+            if (cnt) dep |= __hip_atomic_fetch_add(g + (b / NB) * RH_BANDS_NBINS + (b % NB), cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
+        }
+        if (P == 0 && threadIdx.x == 0 && nan_count)
+            dep |= __hip_atomic_fetch_add(&D->bands_nan_count[j], nan_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
+        __syncthreads();   // (the next item clears the histogram)
+    }
+    // Completion: every thread's adds have returned before its LDS add (dep is 0: a count stays below 2^31), the barrier follows, and only
+    // then is the workgroup counted done.
+    atomicAdd(&posted, dep);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        is_last = __hip_atomic_fetch_add(&D->bands_done, 1u + posted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!is_last) return;
+
+    const int lane = threadIdx.x & 63;
+    const long long row = D->bands_rows;
+    const long long slot = row % D->bands_cap;
+    for (int pair = threadIdx.x >> 6; pair < ni * np; pair += RH_BLOCK / 64) {   // (uniform over the wavefront)
+        const int j = pair / np, q = pair - j * np, at = j * RH_BANDS_MAX_PROBS + q;
+        const unsigned *h = D->bands_hist + (size_t)(j * RH_BANDS_MAX_PROBS + (P == 0 ? 0 : q)) * RH_BANDS_NBINS;
+        unsigned v[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k] = __hip_atomic_load(h + k * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        long long m, r;
+        if (P == 0) {
+            unsigned tot = 0;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) tot += v[k];
+            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
+            m = (long long)tot;
+            r = (long long)ceil(D->bands_probs[q] * (double)m) - 1;
+            r = r > m - 1 ? m - 1 : r;
+            r = r < 0 ? 0 : r;
+        } else {
+            m = D->bands_m[j];
+            r = D->bands_rank[at];
+        }
+        long long base = 0, below = 0;
+        int digit = 0;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const unsigned incl = bands_wave_scan(v[k]);
+            const long long chunk = (long long)__shfl(incl, 63);
+            if (!found && base + chunk > r) {
+                const unsigned long long hit = __ballot(base + (long long)incl > r);
+                const int l = __ffsll((long long)hit) - 1;
+                digit = k * 64 + l;
+                below = base + (long long)__shfl(incl - v[k], l);
+                found = true;
+            }
+            base += chunk;
+        }
+        const unsigned long long prefix = (P == 0 ? 0ull : D->bands_prefix[at] << PS::width) | (unsigned long long)digit;
+        if (lane == 0) {
+            D->bands_prefix[at] = prefix;
+            D->bands_rank[at] = r - below;
+            if (P == 0 && q == 0) {
+                D->bands_m[j] = m;
+                D->bands_nan[j] = (long long)__hip_atomic_load(&D->bands_nan_count[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&D->bands_nan_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (P == RH_BANDS_PASSES - 1) {
+                const unsigned long long u = (prefix >> 63) ? prefix ^ (1ull << 63) : ~prefix;
+                D->bands[(size_t)slot * ni * np + j * np + q] = m ? __longlong_as_double((long long)u) : __builtin_nan("");
+            }
+        }
+    }
+    __syncthreads();   // (in pass 0 the pairs of an item read one histogram)
+    for (int b = threadIdx.x; b < ni * nh * NB; b += RH_BLOCK) {
+        const int jq = b / NB;
+        __hip_atomic_store(D->bands_hist + (size_t)((jq / nh) * RH_BANDS_MAX_PROBS + jq % nh) * RH_BANDS_NBINS + b % NB, 0u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&D->bands_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (P == RH_BANDS_PASSES - 1) {
+            long long *hd = D->bands_hdr + (size_t)slot * (2 + 2 * ni);
+            hd[0] = c.k;
+            hd[1] = c.t1;
+            for (int j = 0; j < ni; ++j) {
+                hd[2 + 2 * j] = D->bands_m[j];
+                hd[3 + 2 * j] = D->bands_nan[j];
+            }
+            D->bands_rows = row + 1;
+        }
+    }
+}

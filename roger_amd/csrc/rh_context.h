@@ -72,8 +72,8 @@ static Switches read_switches(const rh_config &cfg) {
     return s;
 }
 
-// A ring of `cap` rows on the device and the rows' headers (3 int64 each) beside it: what the points, the totals and the zonal totals
-// record into after every step.  cap 0: the observer is off.
+// A ring of `cap` rows on the device and the rows' headers (3 int64 each; the bands': 2 + 2 per item) beside it: what the points, the
+// totals and the zonal totals record into after every step, and the bands after every counted interval.  cap 0: the observer is off.
 struct ObsRing {
     DevBuf<double> buf;
     DevBuf<long long> hdr_buf;
@@ -109,7 +109,7 @@ struct rh_ctx {
     DeviceHolds held;
     Switches sw;                     // the environment as rh_create found it
     int n_groups = 1;                // fused kernel: completion groups (about 64 workgroups each, at most RH_DONE_GROUPS)
-    bool obs_reads_m1 = false;       // one of the six observers was given an X_m1 plane: the fused kernel does not skip those stores
+    bool obs_reads_m1 = false;       // one of the observers was given an X_m1 plane: the fused kernel does not skip those stores
     bool obs_reads_sparse = false;   // an observer was given a plane the sparse kernel leaves out (its KEEP variant stores those); both
                                      // formed by observers_changed from the union of the observers' planes, and by nobody else
     int64_t t_end = -1;              // rh_set_time_limit (host copy of DevState::t_end)
@@ -157,6 +157,15 @@ struct rh_ctx {
     DevBuf<unsigned char> durations_mask_buf;
     int durations_nitems = 0, durations_nbins = 0;   // 0: not configured, no k_durations launch; nbins: the sum of the items' m + 2
     int durations_planes[RH_DURATIONS_MAX_ITEMS] = {};
+    // ensemble bands (rh_bands_configure): the ring and its headers (2 + 2 * bands_nitems int64 a row), the SUM accumulators, the key
+    // planes, the digit histograms and the mask (not held: every column)
+    ObsRing bands;
+    DevBuf<double> bands_acc_buf;
+    DevBuf<unsigned long long> bands_keys_buf;
+    DevBuf<unsigned> bands_hist_buf;
+    DevBuf<unsigned char> bands_mask_buf;
+    int bands_nitems = 0, bands_nprobs = 0;   // 0: not configured, no k_bands* launch
+    int bands_planes[RH_BANDS_MAX_ITEMS] = {};
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

@@ -184,6 +184,27 @@ struct DevState {
     int durations_nitems, durations_nsum;
     int durations_planes[16], durations_kinds[16], durations_nedges[16], durations_edge_off[16], durations_bin_off[16], durations_sides[16];
     double durations_thr[16];   // RH_DURATIONS_MAX_ITEMS; kinds: 0 SUM, 1 LAST; sides: 0 BELOW, 1 AT_OR_ABOVE
+
+    // ensemble bands (rh_bands_configure; k_bands, k_bands_select in rh_bands.h): a ring of bands_cap rows, row r at r mod bands_cap --
+    // bands (row, item, probability) float64 and bands_hdr (row, 2 + 2 * items) int64 {k, t1, then per item m, n_nan}.  bands_acc (item,
+    // n) float64: the SUM accumulators; bands_keys (item, n) uint64: the keys of the interval values (~0: masked out, ~0 - 1: NaN);
+    // bands_hist [item][8][2048] uint32: the digit histograms of the pass under way, all zeros between two launches; bands_done: the
+    // workgroups of the pass that have finished, likewise 0; bands_nan_count: the NaN keys pass 0 met.  Per (item, probability) at
+    // [item * 8 + probability]: bands_prefix, the digits picked so far, and bands_rank, the rank that remains among the keys with that
+    // prefix; per item bands_m and bands_nan, fixed by pass 0.  (Behind everything else: no member another kernel addresses moves.)
+    double *bands, *bands_acc;
+    long long *bands_hdr;
+    unsigned long long *bands_keys;
+    unsigned *bands_hist;
+    const unsigned char *bands_mask;
+    long long bands_rows, bands_cap, bands_interval, bands_t_first;
+    int bands_nitems, bands_nprobs, bands_nsum;
+    unsigned bands_done;
+    unsigned bands_nan_count[8];
+    int bands_planes[8], bands_kinds[8];   // RH_BANDS_MAX_ITEMS; kinds: 0 SUM, 1 LAST
+    double bands_probs[8];                 // RH_BANDS_MAX_PROBS
+    unsigned long long bands_prefix[64];
+    long long bands_rank[64], bands_m[8], bands_nan[8];
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

@@ -1,11 +1,12 @@
 // rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
 // (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*), the scores against observed series
-// (rh_scores_*), the event outputs (rh_events_*) and the duration curves (rh_durations_*).  Part of the one translation unit
-// roger_hip.hip, behind rh_context.h.
+// (rh_scores_*), the event outputs (rh_events_*), the duration curves (rh_durations_*) and the ensemble bands (rh_bands_*).  Part of the
+// one translation unit roger_hip.hip, behind rh_context.h.
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure, rh_scores_configure,
-// rh_events_configure, rh_durations_configure): what the fused kernel must leave in memory after every step, from the UNION of the planes
-// of all seven -- the accumulators, the points, the totals, the zonal totals, the scores, the event outputs and the duration curves.
+// rh_events_configure, rh_durations_configure, rh_bands_configure): what the fused kernel must leave in memory after every step, from
+// the UNION of the planes of all eight -- the accumulators, the points, the totals, the zonal totals, the scores, the event outputs, the
+// duration curves and the ensemble bands.
 // A plane the sparse kernel leaves out -- a
 // pure output, or one of the five the next lazy step derives itself, which the storage stage computes all the same -- gets its bit in
 // DevState::keep: the KEEP variant stores it after all.  An X_m1 plane switches the lazy rotation off.  Synchronises.
@@ -31,6 +32,7 @@ static int observers_changed(rh_ctx *ctx) {
     add(ctx->scores_planes, ctx->scores_nitems);
     add(ctx->events_planes, ctx->events_nitems);
     add(ctx->durations_planes, ctx->durations_nitems);
+    add(ctx->bands_planes, ctx->bands_nitems);
     const int any = reads_sparse ? 1 : 0;
     HIPCHK(ctx, dev_put(ctx, &DevState::keep, keep));
     HIPCHK(ctx, dev_put(ctx, &DevState::keep_any, any));
@@ -46,10 +48,11 @@ static int observers_changed(rh_ctx *ctx) {
 // then the totals' row -- a workgroup per RH_BLOCK columns for the partials and ONE that combines them -- then the zonal totals' row: a
 // workgroup per RH_BLOCK columns and one per zone (rh_zonal.h) -- then the scores' moments over all columns, on the accumulators' grid
 // (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h) -- then the duration curves, on the same grid
-// (rh_durations.h).  after_fused: rh_control.h, k_diag.
+// (rh_durations.h) -- then the ensemble bands: the keys on the same grid, and the six passes of the selection on at most
+// RH_BANDS_MAX_GRID workgroups that stride over the tiles (rh_bands.h).  after_fused: rh_control.h, k_diag.
 static bool has_observers(const rh_ctx *ctx) {
     return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems ||
-           ctx->durations_nitems;
+           ctx->durations_nitems || ctx->bands_nitems;
 }
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
@@ -66,6 +69,16 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     if (ctx->scores_nitems) hipLaunchKernelGGL(k_scores, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->events_nitems) hipLaunchKernelGGL(k_events, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->durations_nitems) hipLaunchKernelGGL(k_durations, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    if (ctx->bands_nitems) {
+        const dim3 sel(std::min<unsigned>(grid_for(ctx->n), RH_BANDS_MAX_GRID));
+        hipLaunchKernelGGL(k_bands, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_bands_select<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_bands_select<1>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_bands_select<2>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_bands_select<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_bands_select<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        hipLaunchKernelGGL(k_bands_select<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    }
     CHECK_LAUNCH(ctx);
     return RH_OK;
 }
@@ -95,12 +108,12 @@ static int ring_rows(rh_ctx *ctx, const char *who, const ObsRing &ring, const ch
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
 }
-// the rows of an accepted range, nv values each, and their headers to the host.  Synchronises.
-static int ring_download(rh_ctx *ctx, const ObsRing &ring, size_t nv, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values) {
+// the rows of an accepted range, nv values each, and their headers (nh int64 each) to the host.  Synchronises.
+static int ring_download(rh_ctx *ctx, const ObsRing &ring, size_t nv, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t nh = 3) {
     const int rc = ring_pieces(first_row, n_rows, ring.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
         HIPCHK(ctx, hipMemcpyAsync(values + (size_t)done * nv, ring.buf + (size_t)slot * nv, (size_t)m * nv * sizeof(double), hipMemcpyDeviceToHost,
                                    ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(hdr + 3 * done, ring.hdr_buf + 3 * slot, (size_t)m * 3 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hdr + nh * done, ring.hdr_buf + nh * slot, (size_t)m * nh * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
         return RH_OK;
     });
     if (rc) return rc;
@@ -815,4 +828,118 @@ int rh_durations_read(rh_ctx *ctx, uint32_t *counts, size_t count_bytes, double 
     HIPCHK(ctx, hipMemcpyAsync(spells, ctx->durations_spells_buf, spell_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RH_OK;
+}
+
+// ---- ensemble bands (include/roger_hip.h; the kernels, the rule and the selection: rh_bands.h) ----
+// the buffers: the ring, the accumulators at +0.0, every key "masked out" (a masked-in column stores its key on every counted step), the
+// histograms at 0
+static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned char *mask, int64_t capacity) {
+    const size_t n = (size_t)ctx->n, ab = (size_t)n_items * n * sizeof(double),
+                 hb = (size_t)n_items * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS * sizeof(unsigned);
+    HIPCHK(ctx, ctx->bands.buf.alloc((size_t)capacity * n_items * n_probs * sizeof(double)));
+    HIPCHK(ctx, ctx->bands.hdr_buf.alloc((size_t)capacity * (2 + 2 * (size_t)n_items) * sizeof(long long)));
+    HIPCHK(ctx, ctx->bands_acc_buf.alloc(ab));
+    HIPCHK(ctx, hipMemsetAsync(ctx->bands_acc_buf, 0, ab, ctx->stream));
+    HIPCHK(ctx, ctx->bands_keys_buf.alloc(ab));
+    HIPCHK(ctx, hipMemsetAsync(ctx->bands_keys_buf, 0xff, ab, ctx->stream));   // RH_BANDS_KEY_MASKED
+    HIPCHK(ctx, ctx->bands_hist_buf.alloc(hb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->bands_hist_buf, 0, hb, ctx->stream));
+    if (mask) {
+        HIPCHK(ctx, ctx->bands_mask_buf.alloc(n));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->bands_mask_buf, mask, n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return RH_OK;
+}
+int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs, int64_t interval_seconds,
+                       int64_t t_first, const unsigned char *mask, int64_t capacity) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_BANDS_MAX_ITEMS)
+        return fail(ctx, RH_ERR_ARG, "rh_bands_configure: n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_BANDS_MAX_ITEMS) + ")");
+    const bool off = n_items == 0;
+    int plane_list[RH_BANDS_MAX_ITEMS] = {}, kind_list[RH_BANDS_MAX_ITEMS] = {}, n_sum = 0;
+    double prob_list[RH_BANDS_MAX_PROBS] = {};
+    if (!off) {
+        if (!planes || !kinds || !probs) return fail(ctx, RH_ERR_ARG, "rh_bands_configure: null pointer");
+        if (n_probs < 1 || n_probs > RH_BANDS_MAX_PROBS)
+            return fail(ctx, RH_ERR_ARG, "rh_bands_configure: n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_BANDS_MAX_PROBS) + ")");
+        for (int q = 0; q < n_probs; ++q) {
+            if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+                return fail(ctx, RH_ERR_ARG, "rh_bands_configure: probability " + std::to_string(q) + " = " + std::to_string(probs[q]) + " (within [0, 1])");
+            prob_list[q] = probs[q];
+        }
+        if (interval_seconds != 86400 && interval_seconds != 3600 && interval_seconds != 600)
+            return fail(ctx, RH_ERR_ARG, "rh_bands_configure: interval_seconds = " + std::to_string(interval_seconds) +
+                                         " (the interval is a day, an hour or ten minutes: the step classes)");
+        if (t_first < 0 || t_first % interval_seconds)
+            return fail(ctx, RH_ERR_ARG, "rh_bands_configure: t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
+                                         std::to_string(interval_seconds) + " s)");
+        for (int j = 0; j < n_items; ++j) {   // (item by item, as for the scores)
+            if (int rc = check_planes(ctx, "rh_bands_configure: item " + std::to_string(j) + ": ", planes + j, 1, plane_list + j, FLOAT64_IDS)) return rc;
+            if (kinds[j] != RH_BANDS_SUM && kinds[j] != RH_BANDS_LAST)
+                return fail(ctx, RH_ERR_ARG, "rh_bands_configure: kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: LAST)");
+            kind_list[j] = kinds[j];
+            n_sum += kinds[j] == RH_BANDS_SUM;
+        }
+        if (ctx->n >= (int64_t)1 << 31) return fail(ctx, RH_ERR_ARG, "rh_bands_configure: " + std::to_string(ctx->n) + " columns (the histograms hold uint32 counts)");
+        if (int rc = check_capacity(ctx, "rh_bands_configure: ", capacity)) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    HIPCHK(ctx, ctx->bands.release());
+    HIPCHK(ctx, ctx->bands_acc_buf.release());
+    HIPCHK(ctx, ctx->bands_keys_buf.release());
+    HIPCHK(ctx, ctx->bands_hist_buf.release());
+    HIPCHK(ctx, ctx->bands_mask_buf.release());
+    ctx->bands_nitems = ctx->bands_nprobs = 0;
+    if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, capacity)) {   // refused: the observer is off
+        const std::string why = ctx->err;
+        (void)rh_bands_configure(ctx, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, 0);
+        return fail(ctx, rc, why);
+    }
+    if (!off) {
+        ctx->bands_nitems = n_items;
+        ctx->bands_nprobs = n_probs;
+        ctx->bands.cap = capacity;
+    }
+    std::memcpy(ctx->bands_planes, plane_list, sizeof(plane_list));
+    const long long zero = 0, cap = (long long)ctx->bands.cap, iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first;
+    const unsigned none = 0, no_nan[RH_BANDS_MAX_ITEMS] = {};
+    const unsigned char *const mask_dev = ctx->bands_mask_buf;
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands, *ctx->bands.buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_hdr, *ctx->bands.hdr_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_acc, *ctx->bands_acc_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_keys, *ctx->bands_keys_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_hist, *ctx->bands_hist_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_mask, mask_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_rows, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_cap, cap));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_interval, iv));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_t_first, tf));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_nitems, ctx->bands_nitems));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_nprobs, ctx->bands_nprobs));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_nsum, n_sum));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_done, none));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_nan_count, no_nan));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_planes, plane_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_kinds, kind_list));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_probs, prob_list));
+    return observers_changed(ctx);   // synchronises: the sources above are locals (and the caller's mask)
+}
+int rh_bands_count(rh_ctx *ctx, int64_t *rows_total) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!rows_total) return fail(ctx, RH_ERR_ARG, "rh_bands_count: null pointer");
+    long long rows = 0;
+    if (int rc = ring_rows(ctx, "rh_bands_count", ctx->bands, "rh_bands_configure", &DevState::bands_rows, &rows)) return rc;
+    *rows_total = (int64_t)rows;
+    return RH_OK;
+}
+int rh_bands_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = ring_rows(ctx, "rh_bands_read", ctx->bands, "rh_bands_configure", &DevState::bands_rows, &total)) return rc;
+    const size_t nv = (size_t)ctx->bands_nitems * ctx->bands_nprobs;
+    const std::string why = ring_range_refusal("rh_bands_read", first_row, n_rows, total, ctx->bands.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
+    if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_bands_read: size mismatch (n_rows x n_items x n_probs float64)");
+    return ring_download(ctx, ctx->bands, nv, first_row, n_rows, hdr, values, 2 + 2 * (size_t)ctx->bands_nitems);
 }

@@ -42,6 +42,7 @@
 #include "rh_scores.h"   // (last: the kernels in front of it keep their places in the code object)
 #include "rh_events.h"   // (behind it, for the same reason)
 #include "rh_durations.h"   // (and behind that)
+#include "rh_bands.h"   // (and behind that)
 
 // The host side, one file per concern.  The entry points get their C linkage from their declarations in roger_hip.h.
 #include "rh_host_kernels.h"

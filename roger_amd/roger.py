@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import diagnostics, distributed, durations, events, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
+from . import bands, diagnostics, distributed, durations, events, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -158,6 +158,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             scores.initialize(state)
             events.initialize(state)
             durations.initialize(state)
+            bands.initialize(state)
             sas_points.initialize(state)
             sas_totals.initialize(state)
             sas_zonal_totals.initialize(state)
@@ -169,6 +170,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             scores.start(state)           # (the clock is known: a continued run scores from the next interval boundary)
             events.start(state)           # (the event ids are known: an event that is running now keeps event_start = -1)
             durations.start(state)        # (the clock is known: a continued run counts from the next interval boundary)
+            bands.start(state)            # (likewise)
             if offline and state.settings.warmup_done:
                 sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
                 sas_totals.start(state)
@@ -225,6 +227,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 points.drain(state)            # (rows not yet drained are drained before a restart file is written)
                 totals.drain(state)
                 zonal_totals.drain(state)
+                bands.drain(state)
                 restart.write_restart(state)   # roger/roger.py:385-386
         with state.timers["main"]:
             with state.timers["read data"]:
@@ -271,6 +274,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         points.stepped(state)    # the points' ring is drained every `capacity` step calls
         totals.stepped(state)    # ... and the totals'
         zonal_totals.stepped(state)
+        bands.stepped(state)     # ... and the bands'
         events.stepped(state)    # completed events are read out when the event id changes
         if rs.profile_mode:
             state.backend_context.sync()
@@ -392,6 +396,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     n = min(n, int(state.totals.capacity))   # (... nor than the totals')
                 if state.zonal_totals._on:
                     n = min(n, int(state.zonal_totals.capacity))
+                if state.bands._on:
+                    n = min(n, int(state.bands.capacity))
                 self.run_device(int(n), final=False)
                 first = False
         finally:
@@ -411,7 +417,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(state._diag_active) or state.points.active or state.totals.active or state.zonal_totals.active or state.events.active
+        diag = bool(state._diag_active) or state.points.active or state.totals.active or state.zonal_totals.active or state.events.active or state.bands.active
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -457,6 +463,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                     points.drain(self.state)
                     totals.drain(self.state)
                     zonal_totals.drain(self.state)
+                    bands.drain(self.state)
                     sas_points.drain(self.state)
                     sas_totals.drain(self.state)
                     sas_zonal_totals.drain(self.state)
@@ -469,6 +476,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         scores.close(self.state)
         events.close(self.state)
         durations.close(self.state)
+        bands.close(self.state)
         sas_points.close(self.state)
         sas_totals.close(self.state)
         sas_zonal_totals.close(self.state)
@@ -523,9 +531,11 @@ class RogerSetup(metaclass=abc.ABCMeta):
         points.check_call(self.state, nsteps)   # (before anything is enqueued)
         totals.check_call(self.state, nsteps)
         zonal_totals.check_call(self.state, nsteps)
+        bands.check_call(self.state, nsteps)
         points.drain(self.state)
         totals.drain(self.state)
         zonal_totals.drain(self.state)
+        bands.drain(self.state)
         vs.flush_to_device()
         ctx = self.state.backend_context
         engine = stepping.engine(self._facts())
@@ -541,6 +551,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         points.drain(self.state, final=final)
         totals.drain(self.state, final=final)
         zonal_totals.drain(self.state, final=final)
+        bands.drain(self.state, final=final)
         events.drain(self.state, write=final)   # (completed events; the running one stays on the device until it ends or run() does)
         if self.state._diag_active:
             diagnostics.output(self.state, final=final)

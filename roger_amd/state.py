@@ -363,6 +363,9 @@ class RogerState:
         from .durations import Durations
 
         self.durations = Durations()        # per-column histograms, extremes and spells of interval values (roger_amd/durations.py)
+        from .bands import Bands
+
+        self.bands = Bands()                # per-interval exact quantiles across the columns (roger_amd/bands.py)
         from .sas_totals import TransportTotals
 
         self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
