@@ -411,6 +411,16 @@ class SasContext:
         self._check(self._lib.rh_sas_timing_summary(self._h, C.byref(ms), C.byref(cnt)), "rh_sas_timing_summary")
         return ms.value, cnt.value
 
+    def _ring_read(self, what, first, n):
+        """(n, tags (n,) int64, values float64 (n, row elements)) of the rows [first, first + n) of the ring rh_sas_<what>_*."""
+        n = int(n)
+        elems = C.c_int64()
+        self._check(getattr(self._lib, f"rh_sas_{what}_row_elems")(self._h, C.byref(elems)), f"rh_sas_{what}_row_elems")
+        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
+        self._check(getattr(self._lib, f"rh_sas_{what}_read")(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p),
+                                                               values.ctypes.data_as(C.c_void_p), values.nbytes), f"rh_sas_{what}_read")
+        return n, tags, values
+
     # -- time series at observation columns (rh_sas_points_*) -----------------------------------
     def points_configure(self, cells, names, capacity=4096):
         """Record `names` (arrays of the registry) at the local cells `cells` after every day into a ring of `capacity` rows; empty
@@ -438,12 +448,7 @@ class SasContext:
 
     def points_read(self, first, n):
         """(tags (n,) int64, {name: (n, K) or (n, K, width) float64}) of the rows [first, first + n) that are still resident."""
-        n = int(n)
-        elems = C.c_int64()
-        self._check(self._lib.rh_sas_points_row_elems(self._h, C.byref(elems)), "rh_sas_points_row_elems")
-        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
-        self._check(self._lib.rh_sas_points_read(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                                 values.nbytes), "rh_sas_points_read")
+        n, tags, values = self._ring_read("points", first, n)
         out, off, K = {}, 0, self._points_ncells
         for v, w in zip(self._points_names, self._points_widths):
             block = values[:, off:off + K * w]
@@ -482,12 +487,7 @@ class SasContext:
     def totals_read(self, first, n):
         """(tags (n,) int64, {item: {"wsum", "count", "sum"[, "min", "max"]}}) of the rows [first, first + n) that are still resident;
         an item's key is `<array>` or `<array>_by_<weight>`, its statistics are (n,) float64, "sum" of an age item (n, width)."""
-        n = int(n)
-        elems = C.c_int64()
-        self._check(self._lib.rh_sas_totals_row_elems(self._h, C.byref(elems)), "rh_sas_totals_row_elems")
-        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
-        self._check(self._lib.rh_sas_totals_read(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                                 values.nbytes), "rh_sas_totals_read")
+        n, tags, values = self._ring_read("totals", first, n)
         out, off = {}, 0
         for key, w in self._totals_items:
             d = {"wsum": values[:, off].copy(), "count": values[:, off + 1].copy()}
@@ -533,13 +533,8 @@ class SasContext:
     def zonal_read(self, first, n):
         """(tags (n,) int64, {item: {"wsum", "count", "sum"[, "min", "max"]}}) of the rows [first, first + n) that are still resident;
         the statistics are (n, Z) float64, "sum" of an age item (n, Z, width)."""
-        n = int(n)
-        elems = C.c_int64()
-        self._check(self._lib.rh_sas_zonal_row_elems(self._h, C.byref(elems)), "rh_sas_zonal_row_elems")
-        tags, values = np.empty(n, dtype=np.int64), np.empty((n, elems.value), dtype=np.float64)
-        self._check(self._lib.rh_sas_zonal_read(self._h, int(first), n, tags.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                                values.nbytes), "rh_sas_zonal_read")
-        values = values.reshape(n, self._zonal_nzones, elems.value // self._zonal_nzones)
+        n, tags, values = self._ring_read("zonal", first, n)
+        values = values.reshape(n, self._zonal_nzones, values.shape[1] // self._zonal_nzones)
         out, off = {}, 0
         for key, w in self._zonal_items:
             d = {"wsum": values[:, :, off].copy(), "count": values[:, :, off + 1].copy()}
@@ -910,6 +905,16 @@ class Context:
     def diag_device_ptr(self, name, slot):
         return self._lib.rh_diag_device_ptr(self._h, self._diag_names.index(name), int(slot))
 
+    def _ring_read(self, fn, first, n, hdr_width, shape):
+        """Rows [first, first + n) of an observer's ring through its read entry point `fn`: (hdr int64 (n, hdr_width), values float64
+        (n,) + shape)."""
+        n = int(n)
+        hdr = np.empty((n, hdr_width), dtype=np.int64)
+        values = np.empty((n,) + tuple(shape), dtype=np.float64)
+        self._check(getattr(self._lib, fn)(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                                           values.nbytes), fn)
+        return hdr, values
+
     # -- time series at observation columns (rh_points_*) ---------------------------------------
     def points_configure(self, cells, names, capacity=4096):
         """Record `names` (float64 planes) at `cells` (interior indices of this context's block, C order) after every step, in a ring of
@@ -929,13 +934,7 @@ class Context:
 
     def points_read(self, first, n):
         """Rows [first, first + n) of the ring: (hdr int64 (n, 3): itt, time at the end of the step, dt_secs; values float64 (n, V, K))."""
-        n = int(n)
-        nv, nc = getattr(self, "_points_shape", (0, 0))
-        hdr = np.empty((n, 3), dtype=np.int64)
-        values = np.empty((n, nv, nc), dtype=np.float64)
-        self._check(self._lib.rh_points_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                             values.nbytes), "rh_points_read")
-        return hdr, values
+        return self._ring_read("rh_points_read", first, n, 3, getattr(self, "_points_shape", (0, 0)))
 
     # -- catchment totals (rh_totals_*) ----------------------------------------------------------
     def totals_configure(self, names, mask=None, capacity=4096):
@@ -962,12 +961,7 @@ class Context:
     def totals_read(self, first, n):
         """Rows [first, first + n) of the ring: (hdr int64 (n, 3): itt, time at the end of the step, dt_secs; values float64 (n, V, 3):
         sum, min, max)."""
-        n = int(n)
-        hdr = np.empty((n, 3), dtype=np.int64)
-        values = np.empty((n, getattr(self, "_totals_nv", 0), 3), dtype=np.float64)
-        self._check(self._lib.rh_totals_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                             values.nbytes), "rh_totals_read")
-        return hdr, values
+        return self._ring_read("rh_totals_read", first, n, 3, (getattr(self, "_totals_nv", 0), 3))
 
     # -- zonal totals (rh_zonal_*) ---------------------------------------------------------------
     def zonal_configure(self, names, zones=None, n_zones=0, capacity=4096):
@@ -995,13 +989,7 @@ class Context:
     def zonal_read(self, first, n):
         """Rows [first, first + n) of the ring: (hdr int64 (n, 3): itt, time at the end of the step, dt_secs; values float64
         (n, Z, V, 3): sum, min, max)."""
-        n = int(n)
-        nz, nv = getattr(self, "_zonal_shape", (0, 0))
-        hdr = np.empty((n, 3), dtype=np.int64)
-        values = np.empty((n, nz, nv, 3), dtype=np.float64)
-        self._check(self._lib.rh_zonal_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                            values.nbytes), "rh_zonal_read")
-        return hdr, values
+        return self._ring_read("rh_zonal_read", first, n, 3, getattr(self, "_zonal_shape", (0, 0)) + (3,))
 
     # -- scores against observed series (rh_scores_*) ------------------------------------------------
     def scores_configure(self, names, kinds=(), obs=None, series=None, interval=86400, t_first=0):
@@ -1146,13 +1134,8 @@ class Context:
     def bands_read(self, first, n):
         """Rows [first, first + n) of the ring: (hdr int64 (n, 2 + 2 * items): k, t1, then per item m and n_nan; values float64
         (n, items, probs))."""
-        n = int(n)
-        ni, nq = getattr(self, "_bands_shape", (0, 0))
-        hdr = np.empty((n, 2 + 2 * ni), dtype=np.int64)
-        values = np.empty((n, ni, nq), dtype=np.float64)
-        self._check(self._lib.rh_bands_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
-                                            values.nbytes), "rh_bands_read")
-        return hdr, values
+        shape = getattr(self, "_bands_shape", (0, 0))
+        return self._ring_read("rh_bands_read", first, n, 2 + 2 * shape[0], shape)
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

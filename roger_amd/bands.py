@@ -34,15 +34,11 @@ is a one-rank run.
 Start and restart.  `start` is a multiple of `frequency`.  If the model's clock is past `start` when the run begins -- after a restart --
 the next interval boundary starts the first counted interval.  The ring and the accumulators are NOT part of restart files: a continued
 run starts a new series there.  The host drains the ring as it drains the totals' (roger_amd/totals.py)."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
-from .points import DAY, WRITE_BYTES, claim_output_file, output_file_name
+from .observers import DAY, RingSeries, check_mask, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file
 from .scores import FILL, default_kind
-from .totals import local_mask
 
 MAX_VARIABLES = 8                 # roger_amd/csrc/rh_bands.h: RH_BANDS_MAX_ITEMS
 MAX_PROBABILITIES = 8             # ... RH_BANDS_MAX_PROBS
@@ -50,54 +46,79 @@ FREQUENCIES = (DAY, 3600, 600)    # the step classes
 KINDS = {"sum": 0, "last": 1}
 
 
-class Bands:
+class Bands(RingSeries):
     """`state.bands`: what the script sets (variables, aggregation, probabilities, frequency, start, mask, capacity, base_output_path)
-    and the rows drained so far."""
+    and the rows drained so far: headers (n, 2 + 2 V) int64 and values (n, V, P) float64."""
+
+    label = attribute = "bands"
 
     def __init__(self):
+        super().__init__()
         self.variables = []
         self.aggregation = {}
         self.probabilities = (0.05, 0.5, 0.95)
         self.frequency = DAY
         self.start = 0
         self.mask = None
-        self.capacity = 4096
         self.base_output_path = None
         self.output_path = "{identifier}.bands.nc"
         self._state = None
-        self._on = False         # start() configured the device (this rank holds at least one masked-in column)
         self._names = []
         self._kinds = []
         self._probs = ()
         self._local = None       # the mask of this rank's block, or None
         self._t_first = 0        # the start of the first counted interval on the device
-        self._hdr = []           # drained headers, arrays (n, 2 + 2 V) int64
-        self._values = []        # drained rows, arrays (n, V, P) float64
-        self._read = 0           # rows of the device's series read so far
-        self._steps = 0          # host-loop steps since the last drain
-        self._unwritten = 0      # bytes drained since the last write
-        self._path = None
 
     @property
     def active(self):
         return bool(self.variables)
-
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
 
     def read(self):
         """Synchronise, drain and return {"interval": (n,) int64, "time": (n,) int64 seconds, "<v>": (n, P) float64 with NaN where no
         column took part, "<v>_n", "<v>_nan": (n,) int64}; None while nothing is configured on this rank."""
         if not self._on:
             return None
-        drain(self._state)
-        hdr, values = _rows(self)
+        self.drain(self._state)
+        hdr, values = self._all_rows()
         out = {"interval": hdr[:, 0].copy(), "time": hdr[:, 1].copy()}
         for j, v in enumerate(self._names):
             out[v] = values[:, j].copy()
             out[f"{v}_n"] = hdr[:, 2 + 2 * j].copy()
             out[f"{v}_nan"] = hdr[:, 3 + 2 * j].copy()
         return out
+
+    def _count(self, ctx):
+        return ctx.bands_count()
+
+    def _rows(self, ctx, first, n):
+        return ctx.bands_read(first, n)
+
+    def _all_rows(self):
+        nv, npr = len(self._names), len(self._probs)
+        if not self._hdr:
+            return np.empty((0, 2 + 2 * nv), dtype=np.int64), np.empty((0, nv, npr))
+        return np.concatenate(self._hdr), np.concatenate(self._values)
+
+    def _write(self, state):
+        from .diagnostics import _UNITS
+
+        settings = state.settings
+        hdr, values = self._all_rows()
+        variables = {
+            "Time": (("Time",), hdr[:, 1] / float(DAY), {"long_name": "Time at the end of the interval", "units": "days", "time_origin": str(settings.time_origin)}),
+            "interval": (("Time",), hdr[:, 0].astype(np.int64), {"long_name": "number of the interval, from the first counted one", "units": ""}),
+            "probability": (("probability",), np.asarray(self._probs, dtype=np.float64), {"long_name": "non-exceedance probability", "units": ""}),
+        }
+        for j, v in enumerate(self._names):
+            kind = "sum over the interval" if self._kinds[j] == 0 else "value at the end of the interval"
+            q = np.ascontiguousarray(values[:, j])
+            variables[v] = (("Time", "probability"), np.where(np.isnan(q), FILL, q),
+                            {"_FillValue": np.float64(FILL), "long_name": f"{v} ({kind}): quantiles across the columns, sorted[ceil(p n) - 1]", "units": _UNITS.get(v, "")})
+            variables[f"{v}_n"] = (("Time",), np.ascontiguousarray(hdr[:, 2 + 2 * j]), {"long_name": f"{v}: columns that took part", "units": ""})
+            variables[f"{v}_nan"] = (("Time",), np.ascontiguousarray(hdr[:, 3 + 2 * j]), {"long_name": f"{v}: masked-in columns with a NaN", "units": ""})
+        write_file(self._path, {"Time": None, "probability": len(self._probs)}, variables, global_attributes(
+            settings.identifier, "Exact quantiles across the columns of interval values, one record per counted interval.",
+            {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}, lead={"columns": "this rank's block"}))
 
 
 def initialize(state):
@@ -107,9 +128,8 @@ def initialize(state):
     if not b.active:
         return
     settings = state.settings
-    if settings.enable_offline_transport:
-        raise NotImplementedError("bands: the offline transport model steps by the day over its own arrays; the quantiles of state.bands "
-                                  "belong to the SVAT / oneD step (a sibling for the transport model is not built)")
+    svat_only("bands", settings, " over its own arrays; the quantiles of state.bands belong to the SVAT / oneD step (a sibling for the "
+              "transport model is not built)")
     names = list(b.variables)
     if len(names) > MAX_VARIABLES:
         raise ValueError(f"bands: {len(names)} variables (at most {MAX_VARIABLES})")
@@ -132,16 +152,8 @@ def initialize(state):
             raise ValueError(f"bands: aggregation names {v!r}, which is not among the variables")
         if b.aggregation[v] not in KINDS:
             raise ValueError(f'bands: aggregation of {v!r} is {b.aggregation[v]!r} ("sum" or "last")')
-    for v in names:
-        meta = state.var_meta.get(v)
-        if meta is None or meta.plane is None or meta.dtype is not None:
-            raise NotImplementedError(f"bands: {v!r} is not a float64 (x, y) variable of the device arena")
-    if b.mask is not None:
-        m = np.asarray(b.mask)
-        if m.shape != (settings.nx, settings.ny):
-            raise ValueError(f"bands: the mask has shape {m.shape}, the grid {settings.nx} x {settings.ny} columns")
-        if not m.any():
-            raise ValueError("bands: the mask holds no column")
+    check_planes("bands", names, state)
+    check_mask("bands", b.mask, settings)
     b._names = names
     b._kinds = [KINDS[b.aggregation.get(v, default_kind(v))] for v in names]
     b._probs = probs
@@ -165,89 +177,10 @@ def start(state):
             return   # (several ranks: no masked-in column in this rank's block)
     vs.flush_to_device()
     state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, b._local, int(b.capacity))
-    b._on, b._read, b._steps, b._unwritten = True, 0, 0, 0
+    b._begin()
     b._hdr, b._values = [], []
     b._path = claim_output_file(b, state, "bands")
 
 
-def check_call(state, nsteps):
-    """Before a call that enqueues nsteps steps: a step closes at most one interval, more than the ring holds could overwrite rows nobody
-    has read."""
-    b = state.bands
-    if b._on and int(nsteps) > int(b.capacity):
-        raise RuntimeError(f"{int(nsteps)} steps in one call but only {int(b.capacity)} rows of the bands are resident on the device: "
-                           "call run_device() in shorter pieces, or raise state.bands.capacity")
-
-
-def drain(state, final=False):
-    """Read the rows the device recorded since the last drain."""
-    b = state.bands
-    if not b._on:
-        return
-    ctx = state.backend_context
-    total = int(ctx.bands_count())
-    n = total - b._read
-    if n > int(b.capacity):
-        raise RuntimeError(f"{n} rows of the bands recorded since the last drain but only {int(b.capacity)} are resident on the device")
-    if n > 0:
-        hdr, values = ctx.bands_read(b._read, n)
-        b._hdr.append(hdr)
-        b._values.append(values)
-        b._read = total
-        b._unwritten += values.nbytes + hdr.nbytes
-    b._steps = 0
-    if final or b._unwritten > WRITE_BYTES:
-        _write(state)
-
-
-def stepped(state):
-    """A host loop made one step call: drain when the calls since the last drain reach the capacity."""
-    b = state.bands
-    if not b._on:
-        return
-    b._steps += 1
-    if b._steps >= int(b.capacity):
-        drain(state)
-
-
 def close(state):
-    """End of run(): the rest of the ring, and the file."""
-    drain(state, final=True)
-
-
-def _rows(b):
-    nv, npr = len(b._names), len(b._probs)
-    if not b._hdr:
-        return np.empty((0, 2 + 2 * nv), dtype=np.int64), np.empty((0, nv, npr))
-    return np.concatenate(b._hdr), np.concatenate(b._values)
-
-
-def _write(state):
-    """The whole file from the rows held in memory, through roger_amd.nc4lite."""
-    from . import nc4lite
-    from .diagnostics import _UNITS
-
-    b = state.bands
-    b._unwritten = 0
-    if not b._path:
-        return
-    settings = state.settings
-    hdr, values = _rows(b)
-    variables = {
-        "Time": (("Time",), hdr[:, 1] / float(DAY), {"long_name": "Time at the end of the interval", "units": "days", "time_origin": str(settings.time_origin)}),
-        "interval": (("Time",), hdr[:, 0].astype(np.int64), {"long_name": "number of the interval, from the first counted one", "units": ""}),
-        "probability": (("probability",), np.asarray(b._probs, dtype=np.float64), {"long_name": "non-exceedance probability", "units": ""}),
-    }
-    for j, v in enumerate(b._names):
-        kind = "sum over the interval" if b._kinds[j] == 0 else "value at the end of the interval"
-        q = np.ascontiguousarray(values[:, j])
-        variables[v] = (("Time", "probability"), np.where(np.isnan(q), FILL, q),
-                        {"_FillValue": np.float64(FILL), "long_name": f"{v} ({kind}): quantiles across the columns, sorted[ceil(p n) - 1]", "units": _UNITS.get(v, "")})
-        variables[f"{v}_n"] = (("Time",), np.ascontiguousarray(hdr[:, 2 + 2 * j]), {"long_name": f"{v}: columns that took part", "units": ""})
-        variables[f"{v}_nan"] = (("Time",), np.ascontiguousarray(hdr[:, 3 + 2 * j]), {"long_name": f"{v}: masked-in columns with a NaN", "units": ""})
-    os.makedirs(os.path.dirname(os.path.abspath(b._path)), exist_ok=True)
-    nc4lite.write(b._path, {"Time": None, "probability": len(b._probs)}, variables, {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "Exact quantiles across the columns of interval values, one record per counted interval.",
-        "columns": "this rank's block", "setup_identifier": str(settings.identifier), "frequency_seconds": int(b.frequency),
-        "first_interval_starts_seconds": int(b._t_first)})
+    state.bands.close(state)

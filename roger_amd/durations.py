@@ -39,15 +39,11 @@ the last bin, and never above v_max.  `_FillValue` stands where v_n == 0 (min, m
 Start and restart.  `start` is a multiple of `frequency`.  If the model's clock is past `start` when the run begins -- after a restart
 -- the next interval boundary starts the first counted interval.  The counters are NOT part of restart files: a continued run counts
 from where it continues."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
-from .points import DAY, claim_output_file, output_file_name
+from .observers import DAY, Observer, check_mask, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file, xy_variables
 from .scores import FILL, default_kind
-from .totals import local_mask
 
 MAX_VARIABLES = 16                # roger_amd/csrc/rh_durations.h: RH_DURATIONS_MAX_ITEMS
 MAX_EDGES = 63                    # ... RH_DURATIONS_MAX_EDGES
@@ -104,7 +100,7 @@ def derive(counts, vals, edges, quantiles=(), spells=None):
     return out
 
 
-class Durations:
+class Durations(Observer):
     """`state.durations`: what the script sets (variables, aggregation, spells, frequency, start, mask, quantiles, base_output_path)."""
 
     def __init__(self):
@@ -131,15 +127,55 @@ class Durations:
     def active(self):
         return bool(self.variables)
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
-
     def read(self):
         """Synchronise and return {"<v>_<map>": array over this rank's block, (nx, ny) last}; None while nothing is configured on this
         rank."""
         if not self._on:
             return None
         return _maps(self._state)
+
+    def close(self, state):
+        """End of run(): the file."""
+        if not self._on or not self._path:
+            return
+        from .diagnostics import _UNITS
+
+        maps = _maps(state)
+        x, y, variables = xy_variables(state.variables)
+        dims = {"x": len(x), "y": len(y), "quantile": len(self._quantiles)}
+        variables["quantile"] = (("quantile",), np.asarray(self._quantiles, dtype=np.float64), {"long_name": "non-exceedance probability", "units": ""})
+        if self._local is not None:
+            variables["mask"] = (("y", "x"), np.ascontiguousarray(self._local.reshape(len(x), len(y)).T.astype(np.int32)),
+                                 {"long_name": "the column is counted", "units": ""})
+        fill = {"_FillValue": np.float64(FILL)}
+        for j, v in enumerate(self._names):
+            kind = "sum over the interval" if self._kinds[j] == 0 else "value at the end of the interval"
+            unit = _UNITS.get(v, "")
+            e = self._edges[j]
+
+            def t(key):   # (..., x, y) -> (..., y, x)
+                return np.ascontiguousarray(np.swapaxes(maps[f"{v}_{key}"], -1, -2))
+
+            dims[f"{v}_bin"] = e.size + 2
+            variables[f"{v}_count"] = ((f"{v}_bin", "y", "x"), t("count"), {"long_name": f"{v} ({kind}): intervals per bin, bin b holds edge b-1 <= value < edge b, the NaN bin last", "units": ""})
+            variables[f"{v}_n"] = (("y", "x"), t("n"), {"long_name": f"{v} ({kind}): counted intervals with a number", "units": ""})
+            variables[f"{v}_nan"] = (("y", "x"), t("nan"), {"long_name": f"{v} ({kind}): counted intervals with a NaN", "units": ""})
+            variables[f"{v}_min"] = (("y", "x"), t("min"), dict(fill, long_name=f"{v} ({kind}): smallest interval value", units=unit))
+            variables[f"{v}_max"] = (("y", "x"), t("max"), dict(fill, long_name=f"{v} ({kind}): largest interval value", units=unit))
+            variables[f"{v}_q"] = (("quantile", "y", "x"), t("q"), dict(fill, long_name=f"{v} ({kind}): quantiles of the interval values", units=unit))
+            if e.size:
+                dims[f"{v}_edge"] = e.size
+                variables[f"{v}_edges"] = ((f"{v}_edge",), e, {"long_name": f"{v}: bin edges", "units": unit})
+                variables[f"{v}_exceed"] = ((f"{v}_edge", "y", "x"), t("exceed"), dict(fill, long_name=f"{v} ({kind}): share of the intervals at or above the edge", units=""))
+            if self._spells[j] is not None:
+                side, thr = self._spells[j]
+                what = f"{v} ({kind}) {'<' if side == 0 else '>='} {thr!r}"
+                variables[f"{v}_longest"] = (("y", "x"), t("longest"), {"long_name": f"longest run of consecutive counted intervals with {what}", "units": ""})
+                variables[f"{v}_spells"] = (("y", "x"), t("spells"), {"long_name": f"number of runs with {what}", "units": ""})
+                variables[f"{v}_run"] = (("y", "x"), t("run"), {"long_name": f"the run with {what} under way at the end", "units": ""})
+        write_file(self._path, dims, variables, global_attributes(
+            state.settings.identifier, "Histograms of interval values per column, their extremes, exceedance shares, quantiles and threshold spells.",
+            {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}))
 
 
 def initialize(state):
@@ -149,9 +185,8 @@ def initialize(state):
     if not d.active:
         return
     settings = state.settings
-    if settings.enable_offline_transport:
-        raise NotImplementedError("durations: the offline transport model steps by the day over its own arrays; the histograms of "
-                                  "state.durations belong to the SVAT / oneD step (a sibling for the transport model is not built)")
+    svat_only("durations", settings, " over its own arrays; the histograms of state.durations belong to the SVAT / oneD step (a sibling for "
+              "the transport model is not built)")
     names = list(d.variables)
     if len(names) > MAX_VARIABLES:
         raise ValueError(f"durations: {len(names)} variables (at most {MAX_VARIABLES})")
@@ -176,9 +211,7 @@ def initialize(state):
         spells[v] = (SIDES[sp[0]], float(sp[1]))
     edges = []
     for v in names:
-        meta = state.var_meta.get(v)
-        if meta is None or meta.plane is None or meta.dtype is not None:
-            raise NotImplementedError(f"durations: {v!r} is not a float64 (x, y) variable of the device arena")
+        check_planes("durations", (v,), state)
         e = np.asarray(d.variables[v], dtype=np.float64)
         if e.ndim != 1:
             raise ValueError(f"durations: the edges of {v!r} have shape {e.shape} (one ascending list per variable, shared by all columns)")
@@ -189,12 +222,7 @@ def initialize(state):
         if not (np.diff(e) > 0).all():
             raise ValueError(f"durations: the edges of {v!r} are not strictly ascending")
         edges.append(np.ascontiguousarray(e))
-    if d.mask is not None:
-        m = np.asarray(d.mask)
-        if m.shape != (settings.nx, settings.ny):
-            raise ValueError(f"durations: the mask has shape {m.shape}, the grid {settings.nx} x {settings.ny} columns")
-        if not m.any():
-            raise ValueError("durations: the mask holds no column")
+    check_mask("durations", d.mask, settings)
     qs = tuple(float(p) for p in d.quantiles)
     if any(not 0.0 <= p <= 1.0 for p in qs):
         raise ValueError(f"durations: quantiles = {tuple(d.quantiles)!r} (each within [0, 1])")
@@ -236,56 +264,3 @@ def _maps(state):
         for key, a in derive(counts[j], vals[j], d._edges[j], d._quantiles, spells[j] if d._spells[j] is not None else None).items():
             out[f"{v}_{key}"] = a.reshape(a.shape[:-1] + (nxl, nyl))
     return out
-
-
-def close(state):
-    """End of run(): the file."""
-    d = state.durations
-    if not d._on or not d._path:
-        return
-    from . import nc4lite
-    from .diagnostics import _UNITS
-
-    vs, settings = state.variables, state.settings
-    maps = _maps(state)
-    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
-    dims = {"x": len(x), "y": len(y), "quantile": len(d._quantiles)}
-    variables = {
-        "x": (("x",), x, {"long_name": "x", "units": "m"}),
-        "y": (("y",), y, {"long_name": "y", "units": "m"}),
-        "quantile": (("quantile",), np.asarray(d._quantiles, dtype=np.float64), {"long_name": "non-exceedance probability", "units": ""}),
-    }
-    if d._local is not None:
-        variables["mask"] = (("y", "x"), np.ascontiguousarray(d._local.reshape(len(x), len(y)).T.astype(np.int32)),
-                             {"long_name": "the column is counted", "units": ""})
-    fill = {"_FillValue": np.float64(FILL)}
-    for j, v in enumerate(d._names):
-        kind = "sum over the interval" if d._kinds[j] == 0 else "value at the end of the interval"
-        unit = _UNITS.get(v, "")
-        e = d._edges[j]
-
-        def t(key):   # (..., x, y) -> (..., y, x)
-            return np.ascontiguousarray(np.swapaxes(maps[f"{v}_{key}"], -1, -2))
-
-        dims[f"{v}_bin"] = e.size + 2
-        variables[f"{v}_count"] = ((f"{v}_bin", "y", "x"), t("count"), {"long_name": f"{v} ({kind}): intervals per bin, bin b holds edge b-1 <= value < edge b, the NaN bin last", "units": ""})
-        variables[f"{v}_n"] = (("y", "x"), t("n"), {"long_name": f"{v} ({kind}): counted intervals with a number", "units": ""})
-        variables[f"{v}_nan"] = (("y", "x"), t("nan"), {"long_name": f"{v} ({kind}): counted intervals with a NaN", "units": ""})
-        variables[f"{v}_min"] = (("y", "x"), t("min"), dict(fill, long_name=f"{v} ({kind}): smallest interval value", units=unit))
-        variables[f"{v}_max"] = (("y", "x"), t("max"), dict(fill, long_name=f"{v} ({kind}): largest interval value", units=unit))
-        variables[f"{v}_q"] = (("quantile", "y", "x"), t("q"), dict(fill, long_name=f"{v} ({kind}): quantiles of the interval values", units=unit))
-        if e.size:
-            dims[f"{v}_edge"] = e.size
-            variables[f"{v}_edges"] = ((f"{v}_edge",), e, {"long_name": f"{v}: bin edges", "units": unit})
-            variables[f"{v}_exceed"] = ((f"{v}_edge", "y", "x"), t("exceed"), dict(fill, long_name=f"{v} ({kind}): share of the intervals at or above the edge", units=""))
-        if d._spells[j] is not None:
-            side, thr = d._spells[j]
-            what = f"{v} ({kind}) {'<' if side == 0 else '>='} {thr!r}"
-            variables[f"{v}_longest"] = (("y", "x"), t("longest"), {"long_name": f"longest run of consecutive counted intervals with {what}", "units": ""})
-            variables[f"{v}_spells"] = (("y", "x"), t("spells"), {"long_name": f"number of runs with {what}", "units": ""})
-            variables[f"{v}_run"] = (("y", "x"), t("run"), {"long_name": f"the run with {what} under way at the end", "units": ""})
-    os.makedirs(os.path.dirname(os.path.abspath(d._path)), exist_ok=True)
-    nc4lite.write(d._path, dims, variables, {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "Histograms of interval values per column, their extremes, exceedance shares, quantiles and threshold spells.",
-        "setup_identifier": str(settings.identifier), "frequency_seconds": int(d.frequency), "first_interval_starts_seconds": int(d._t_first)})

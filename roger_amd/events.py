@@ -24,21 +24,17 @@ name theirs.
 Start and restart.  An event that is already running when the observer is configured -- a run continued from a restart file written
 in mid-event -- is written with `event_start = -1`: its maps cover the steps from the configuration on.  The maps are NOT part of
 restart files."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
-from .points import DAY, claim_output_file, output_file_name
+from .observers import DAY, WRITE_BYTES, Observer, check_planes, claim_output_file, global_attributes, svat_only, write_file, xy_variables
 
 MAX_ITEMS = 16                    # roger_amd/csrc/rh_events.h: RH_EVENTS_MAX_ITEMS
 MAX_SLOTS = 65536                 # include/roger_hip.h: RH_EVENTS_MAX_SLOTS
 KINDS = {"sum": 0, "peak": 1, "first": 2, "last": 3}
-WRITE_BYTES = 32 << 20            # maps drained since the last write beyond which the file is written (as points.py)
 
 
-class Events:
+class Events(Observer):
     """`state.events`: what the script sets (items, n_slots, base_output_path) and the events drained so far."""
 
     def __init__(self):
@@ -59,8 +55,78 @@ class Events:
     def active(self):
         return bool(self.items)
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
+    def drain(self, state, final=False, end=False):
+        """Read out the completed events: every resident event but the one the last step belonged to (end, the end of run(): that one
+        too; it stays on the device until it ends or run() does).  final: the file is written now (otherwise when enough has been
+        read out)."""
+        if not self._on:
+            return
+        ctx = state.backend_context
+        hdr, _, lost = ctx.events_read(slots=())
+        if lost:
+            raise RuntimeError(f"events: more than {int(self.n_slots)} rainfall events passed between two read-outs and the device kept no "
+                               "slot for the last ones: raise state.events.n_slots (more slots), or call run_device() in shorter pieces")
+        current = 0 if end else int(ctx.get_scalars().event_id[1])
+        self._last_id = current
+        done = sorted((int(hdr[s, 0]), s) for s in range(hdr.shape[0])
+                      if hdr[s, 0] > 0 and int(hdr[s, 0]) != current and (self._drained is None or int(hdr[s, 0]) > self._drained))
+        if done:
+            _, values, _ = ctx.events_read(slots=[s for _, s in done])
+            for e, s in done:
+                self._hdr.append(hdr[s].copy())
+                self._values.append(values[s])
+                self._unwritten += values[s].nbytes
+            self._drained = done[-1][0]
+            ctx.events_set_drained(self._drained)
+        if end or final or self._unwritten > WRITE_BYTES:
+            self._unwritten = 0
+            if self._path:
+                self._write(state)
+
+    def stepped(self, state):
+        """A host loop made one step: read out when the step ran under another event id than the one before it (an event ended)."""
+        if not self._on:
+            return
+        e = int(state.variables._get_scalars().event_id[1])
+        if e != self._last_id:
+            if self._last_id > 0:
+                self.drain(state)
+            self._last_id = e
+
+    def close(self, state):
+        """End of run(): the event that is still running counts as complete, and the file."""
+        self.drain(state, end=True)
+
+    def _write(self, state):
+        """The whole file from the events held in memory, through roger_amd.nc4lite."""
+        from .diagnostics import _UNITS
+
+        settings = state.settings
+        nxl, nyl = settings.nx // rs.num_proc[0], settings.ny // rs.num_proc[1]
+        x, y, variables = xy_variables(state.variables)
+        hdr = np.stack(self._hdr) if self._hdr else np.zeros((0, 6), dtype=np.int64)
+        days = lambda t: np.where(t < 0, -1.0, t / float(DAY))   # noqa: E731  (-1: the event was running when the observer was configured)
+        time_attrs = {"units": "days", "time_origin": str(settings.time_origin)}
+        variables.update({
+            "event_id": (("event",), hdr[:, 0].astype(np.int64), {"long_name": "event id of the adaptive time stepping", "units": ""}),
+            "event_start": (("event",), days(hdr[:, 2].astype(np.float64)), dict(time_attrs, long_name="start of the event's first step (-1: before the run was (re)started)")),
+            "event_end": (("event",), days(hdr[:, 3].astype(np.float64)), dict(time_attrs, long_name="end of the event's last step")),
+            "event_steps": (("event",), hdr[:, 1].astype(np.int64), {"long_name": "time steps of the event", "units": ""}),
+            "event_steps_10min": (("event",), hdr[:, 4].astype(np.int64), {"long_name": "ten-minute steps of the event", "units": ""}),
+            "event_steps_hourly": (("event",), hdr[:, 5].astype(np.int64), {"long_name": "hourly steps of the event", "units": ""}),
+        })
+        long_names = {"sum": "sum over the event", "peak": "peak intensity of the event", "first": "value after the event's first step",
+                      "last": "value after the event's last step"}
+        for j, (v, kind) in enumerate(self._items):
+            a = np.stack([m[j].reshape(nxl, nyl).T for m in self._values]) if self._values else np.zeros((0, nyl, nxl))
+            unit = _UNITS.get(v, "")
+            if kind == "peak":
+                unit = "mm/h" if unit == "mm/dt" else (unit + "/h" if unit else "1/h")
+            elif kind == "sum" and unit == "mm/dt":
+                unit = "mm"
+            variables[f"{v}_{kind}"] = (("event", "y", "x"), np.ascontiguousarray(a), {"long_name": f"{v}: {long_names[kind]}", "units": unit})
+        write_file(self._path, {"event": None, "y": len(y), "x": len(x)}, variables, global_attributes(
+            settings.identifier, "One record per rainfall event of the adaptive time stepping, accumulated on the device after every step."))
 
 
 def initialize(state):
@@ -68,9 +134,7 @@ def initialize(state):
     ev = state.events
     if not ev.active:
         return
-    if state.settings.enable_offline_transport:
-        raise NotImplementedError("events: the offline transport model steps by the day and knows no rainfall events; the event "
-                                  "outputs belong to the SVAT / oneD step")
+    svat_only("events", state.settings, " and knows no rainfall events; the event outputs belong to the SVAT / oneD step")
     items = []
     for item in ev.items:
         if not isinstance(item, (tuple, list)) or len(item) != 2:
@@ -78,9 +142,7 @@ def initialize(state):
         v, kind = item
         if kind not in KINDS:
             raise ValueError(f"events: kind of {v!r} is {kind!r} (" + ", ".join(f'"{k}"' for k in KINDS) + ")")
-        meta = state.var_meta.get(v)
-        if meta is None or meta.plane is None or meta.dtype is not None:
-            raise NotImplementedError(f"events: {v!r} is not a float64 (x, y) variable of the device arena")
+        check_planes("events", (v,), state)
         if (v, kind) in items:
             raise ValueError(f"events: item ({v!r}, {kind!r}) is given twice")
         items.append((v, kind))
@@ -103,87 +165,9 @@ def start(state):
     ev._path = claim_output_file(ev, state, "events")
 
 
-def drain(state, final=False, write=False):
-    """Read out the completed events: every resident event but the one the last step belonged to (final, the end of run(): that one
-    too).  write: the file is written now (otherwise when enough has been read out)."""
-    ev = state.events
-    if not ev._on:
-        return
-    ctx = state.backend_context
-    hdr, _, lost = ctx.events_read(slots=())
-    if lost:
-        raise RuntimeError(f"events: more than {int(ev.n_slots)} rainfall events passed between two read-outs and the device kept no "
-                           "slot for the last ones: raise state.events.n_slots (more slots), or call run_device() in shorter pieces")
-    current = 0 if final else int(ctx.get_scalars().event_id[1])
-    ev._last_id = current
-    done = sorted((int(hdr[s, 0]), s) for s in range(hdr.shape[0])
-                  if hdr[s, 0] > 0 and int(hdr[s, 0]) != current and (ev._drained is None or int(hdr[s, 0]) > ev._drained))
-    if done:
-        _, values, _ = ctx.events_read(slots=[s for _, s in done])
-        for e, s in done:
-            ev._hdr.append(hdr[s].copy())
-            ev._values.append(values[s])
-            ev._unwritten += values[s].nbytes
-        ev._drained = done[-1][0]
-        ctx.events_set_drained(ev._drained)
-    if final or write or ev._unwritten > WRITE_BYTES:
-        _write(state)
-
-
-def stepped(state):
-    """A host loop made one step: read out when the step ran under another event id than the one before it (an event ended)."""
-    ev = state.events
-    if not ev._on:
-        return
-    e = int(state.variables._get_scalars().event_id[1])
-    if e != ev._last_id:
-        if ev._last_id > 0:
-            drain(state)
-        ev._last_id = e
+def drain(state, final=False):
+    state.events.drain(state, final=final)
 
 
 def close(state):
-    """End of run(): the event that is still running counts as complete, and the file."""
-    drain(state, final=True)
-
-
-def _write(state):
-    """The whole file from the events held in memory, through roger_amd.nc4lite."""
-    ev = state.events
-    ev._unwritten = 0
-    if not ev._path:
-        return
-    from . import nc4lite
-    from .diagnostics import _UNITS
-
-    vs, settings = state.variables, state.settings
-    nxl, nyl = settings.nx // rs.num_proc[0], settings.ny // rs.num_proc[1]
-    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
-    hdr = np.stack(ev._hdr) if ev._hdr else np.zeros((0, 6), dtype=np.int64)
-    days = lambda t: np.where(t < 0, -1.0, t / float(DAY))   # noqa: E731  (-1: the event was running when the observer was configured)
-    time_attrs = {"units": "days", "time_origin": str(settings.time_origin)}
-    variables = {
-        "x": (("x",), x, {"long_name": "x", "units": "m"}),
-        "y": (("y",), y, {"long_name": "y", "units": "m"}),
-        "event_id": (("event",), hdr[:, 0].astype(np.int64), {"long_name": "event id of the adaptive time stepping", "units": ""}),
-        "event_start": (("event",), days(hdr[:, 2].astype(np.float64)), dict(time_attrs, long_name="start of the event's first step (-1: before the run was (re)started)")),
-        "event_end": (("event",), days(hdr[:, 3].astype(np.float64)), dict(time_attrs, long_name="end of the event's last step")),
-        "event_steps": (("event",), hdr[:, 1].astype(np.int64), {"long_name": "time steps of the event", "units": ""}),
-        "event_steps_10min": (("event",), hdr[:, 4].astype(np.int64), {"long_name": "ten-minute steps of the event", "units": ""}),
-        "event_steps_hourly": (("event",), hdr[:, 5].astype(np.int64), {"long_name": "hourly steps of the event", "units": ""}),
-    }
-    long_names = {"sum": "sum over the event", "peak": "peak intensity of the event", "first": "value after the event's first step",
-                  "last": "value after the event's last step"}
-    for j, (v, kind) in enumerate(ev._items):
-        a = np.stack([m[j].reshape(nxl, nyl).T for m in ev._values]) if ev._values else np.zeros((0, nyl, nxl))
-        unit = _UNITS.get(v, "")
-        if kind == "peak":
-            unit = "mm/h" if unit == "mm/dt" else (unit + "/h" if unit else "1/h")
-        elif kind == "sum" and unit == "mm/dt":
-            unit = "mm"
-        variables[f"{v}_{kind}"] = (("event", "y", "x"), np.ascontiguousarray(a), {"long_name": f"{v}: {long_names[kind]}", "units": unit})
-    os.makedirs(os.path.dirname(os.path.abspath(ev._path)), exist_ok=True)
-    nc4lite.write(ev._path, {"event": None, "y": len(y), "x": len(x)}, variables, {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "One record per rainfall event of the adaptive time stepping, accumulated on the device after every step.",
-        "setup_identifier": str(settings.identifier)})
+    state.events.close(state)

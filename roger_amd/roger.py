@@ -21,7 +21,7 @@ ONE decision: roger_amd/stepping.py holds it as a truth table over the facts tha
 import abc
 import os
 
-from . import bands, diagnostics, distributed, durations, events, logger, points, restart, runtime_settings as rs, runtime_state as rst, sas_points, sas_scores, sas_totals, sas_zonal_totals, scores, stepping, totals, zonal_totals
+from . import diagnostics, distributed, logger, observers, restart, runtime_settings as rs, runtime_state as rst, stepping
 from . import settings as settings_mod
 from .routines import is_roger_routine, roger_routine, run_native
 from .state import RogerState
@@ -152,30 +152,15 @@ class RogerSetup(metaclass=abc.ABCMeta):
             state.diagnostics.update(diagnostics.create_default_diagnostics(state))   # roger/roger.py:296
             self.set_diagnostics(state)
             diagnostics.initialize(state)
-            points.initialize(state)
-            totals.initialize(state)
-            zonal_totals.initialize(state)
-            scores.initialize(state)
-            events.initialize(state)
-            durations.initialize(state)
-            bands.initialize(state)
-            sas_points.initialize(state)
-            sas_totals.initialize(state)
-            sas_zonal_totals.initialize(state)
-            sas_scores.initialize(state)
+            observers.initialize(state)
             self.set_boundary_conditions_setup(state)
             self.set_boundary_conditions(state)
             self.set_forcing_setup(state)
             restart.read_restart(state)   # roger/roger.py:324-326
-            scores.start(state)           # (the clock is known: a continued run scores from the next interval boundary)
-            events.start(state)           # (the event ids are known: an event that is running now keeps event_start = -1)
-            durations.start(state)        # (the clock is known: a continued run counts from the next interval boundary)
-            bands.start(state)            # (likewise)
+            observers.start(state, transport=False)   # (the clock and the event ids are known: a continued run counts from the next
+            # interval boundary, an event that is running now keeps event_start = -1)
             if offline and state.settings.warmup_done:
-                sas_points.start(state)   # (the file holds a warmed-up run: a restarted run starts a new series)
-                sas_totals.start(state)
-                sas_zonal_totals.start(state)
-                sas_scores.start(state)   # (the moments are not in the file: a continued run scores the windows that begin from here on)
+                observers.start(state, transport=True)   # (the file holds a warmed-up run: a restarted run starts a new series)
         self._setup_done = True
         if not state.settings.enable_offline_transport:   # roger/roger.py:324-327
             with state.settings.unlock():
@@ -202,10 +187,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         with self.state.settings.unlock():
             self.state.settings.warmup_done = True
         diagnostics.output_transport(self.state)   # initial values after the warm-up, roger/roger.py:515-521
-        sas_points.start(self.state)               # ... and record 0 of the transport points
-        sas_totals.start(self.state)
-        sas_zonal_totals.start(self.state)
-        sas_scores.start(self.state)               # ... and the day count of the transport scores starts with the next step
+        observers.start(self.state, transport=True)   # ... and record 0 of the transport model's observers
         if self.state.settings.enable_offline_transport and self.state.settings.write_restart:
             restart.write_restart(self.state, force=True)   # a warm-up that later runs can start from
 
@@ -224,10 +206,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
             return self._step_offline_transport(state)
         if facts.restart_every_step:
             with state.timers["diagnostics"]:
-                points.drain(state)            # (rows not yet drained are drained before a restart file is written)
-                totals.drain(state)
-                zonal_totals.drain(state)
-                bands.drain(state)
+                observers.drain_rings(state)   # (rows not yet drained are drained before a restart file is written)
                 restart.write_restart(state)   # roger/roger.py:385-386
         with state.timers["main"]:
             with state.timers["read data"]:
@@ -271,11 +250,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
     def _end_of_step(state):
         if state._diag_active:   # roger/roger.py:458-465: output at the end of the time step
             diagnostics.output(state)
-        points.stepped(state)    # the points' ring is drained every `capacity` step calls
-        totals.stepped(state)    # ... and the totals'
-        zonal_totals.stepped(state)
-        bands.stepped(state)     # ... and the bands'
-        events.stepped(state)    # completed events are read out when the event id changes
+        observers.stepped(state)   # (a ring is drained every `capacity` step calls)
         if rs.profile_mode:
             state.backend_context.sync()
             logger.info(" Time step took {:.2f}s".format(state.timers["main"].last_time))
@@ -287,9 +262,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         vs = state.variables
         if state.settings.restart_frequency > 0 and not self._in_warmup:
             with state.timers["diagnostics"]:
-                sas_points.drain(state)        # (rows not yet drained are drained before a restart file is written)
-                sas_totals.drain(state)
-                sas_zonal_totals.drain(state)
+                observers.drain_rings(state)   # (rows not yet drained are drained before a restart file is written)
                 restart.write_restart(state)   # at the start of a day step, as in step(); not during the warm-up runs
         with state.timers["main"]:
             with vs.unlock():
@@ -308,9 +281,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
                 with state.timers["StorAge selection"]:
                     transport.calculate_storage_selection(state)
                 diagnostics.output_transport(state)    # write_output, roger/core/transport.py:3399-3418
-                sas_points.stepped(state)              # (rh_sas_step recorded the day's row; the ring is drained every `capacity` steps)
-                sas_totals.stepped(state)
-                sas_zonal_totals.stepped(state)
+                observers.stepped(state, transport=True)   # (rh_sas_step recorded the day's row; a ring is drained every `capacity` steps)
         self.after_timestep(state)
         if rs.profile_mode:
             state.sas_context.sync()
@@ -373,6 +344,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         if state._diag_active and not state._diag_transport:
             slots, iv = state._diag_slots, state._diag_interval   # output intervals resident on the device; their length
         limit = stepping.time_limit(self._facts())   # (after enable_device_hooks: per-cell forcing is known)
+        capacity = observers.ring_capacity(state)    # (of what the script asked for: the same on every rank, as run_device is collective)
         try:
             steps0, first = int(vs.itt), True
             while True:
@@ -390,14 +362,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
                         n = max(n, int((t_round - now) / max(600.0, (now - start_time) / done) * 1.1) + 8)
                 elif slots is not None:
                     n = min(n, max(1, slots - 1))          # (a step starts at most one output interval)
-                if state.points.active:
-                    n = min(n, int(state.points.capacity))   # (a round never records more rows than the points' ring holds)
-                if state.totals.active:
-                    n = min(n, int(state.totals.capacity))   # (... nor than the totals')
-                if state.zonal_totals._on:
-                    n = min(n, int(state.zonal_totals.capacity))
-                if state.bands._on:
-                    n = min(n, int(state.bands.capacity))
+                if capacity is not None:
+                    n = min(n, capacity)                   # (a round never records more rows than a ring holds)
                 self.run_device(int(n), final=False)
                 first = False
         finally:
@@ -417,7 +383,7 @@ class RogerSetup(metaclass=abc.ABCMeta):
         front = [getattr(getattr(type(self), h), "__wrapped__", getattr(type(self), h))
                  for h in ("read_data", "set_boundary_conditions", "set_forcing")
                  if not (classes[h] and h != "set_forcing")]
-        diag = bool(state._diag_active) or state.points.active or state.totals.active or state.zonal_totals.active or state.events.active or state.bands.active
+        diag = bool(state._diag_active) or observers.needs_end_of_step(state)
         timer = state.timers["main"]
         with vs.unlock(), timer:
             s = vs._get_scalars()
@@ -460,27 +426,11 @@ class RogerSetup(metaclass=abc.ABCMeta):
             in_warmup = settings.enable_offline_transport and self._in_warmup
             if settings.write_restart and not in_warmup and not (failed and rst.proc_num > 1):   # roger/roger.py:577-579
                 if not failed:
-                    points.drain(self.state)
-                    totals.drain(self.state)
-                    zonal_totals.drain(self.state)
-                    bands.drain(self.state)
-                    sas_points.drain(self.state)
-                    sas_totals.drain(self.state)
-                    sas_zonal_totals.drain(self.state)
+                    observers.drain_rings(self.state)
                 restart.write_restart(self.state, force=True)
         (self.state.sas_context or self.state.backend_context).sync()
         diagnostics.close(self.state)
-        points.close(self.state)
-        totals.close(self.state)
-        zonal_totals.close(self.state)
-        scores.close(self.state)
-        events.close(self.state)
-        durations.close(self.state)
-        bands.close(self.state)
-        sas_points.close(self.state)
-        sas_totals.close(self.state)
-        sas_zonal_totals.close(self.state)
-        sas_scores.close(self.state)
+        observers.close(self.state)
 
     # -- fast path --------------------------------------------------------------------------------
     def enable_device_hooks(self):
@@ -528,14 +478,8 @@ class RogerSetup(metaclass=abc.ABCMeta):
         if not self._device_hooks:
             self.enable_device_hooks()
         vs = self.state.variables
-        points.check_call(self.state, nsteps)   # (before anything is enqueued)
-        totals.check_call(self.state, nsteps)
-        zonal_totals.check_call(self.state, nsteps)
-        bands.check_call(self.state, nsteps)
-        points.drain(self.state)
-        totals.drain(self.state)
-        zonal_totals.drain(self.state)
-        bands.drain(self.state)
+        observers.check_call(self.state, nsteps)   # (before anything is enqueued)
+        observers.drain_rings(self.state)
         vs.flush_to_device()
         ctx = self.state.backend_context
         engine = stepping.engine(self._facts())
@@ -548,10 +492,6 @@ class RogerSetup(metaclass=abc.ABCMeta):
         else:   # through torch.distributed: the summary word, or with per-cell forcing both predicate words (the three-phase protocol)
             self._stepper(one_exchange=engine == stepping.PHASED_ONE).run(nsteps)
         vs.mark_device_newer()
-        points.drain(self.state, final=final)
-        totals.drain(self.state, final=final)
-        zonal_totals.drain(self.state, final=final)
-        bands.drain(self.state, final=final)
-        events.drain(self.state, write=final)   # (completed events; the running one stays on the device until it ends or run() does)
+        observers.drain_round(self.state, final=final)   # (the rings, and what else is read out between rounds)
         if self.state._diag_active:
             diagnostics.output(self.state, final=final)

@@ -30,16 +30,12 @@ the step that follows carries itt + 1, so model day d is day d - (itt + 1) of th
 dropped (`observations_dropped` in the file): its first days were not seen.  Nothing is drained per step; `close` writes the file.  The
 moments are NOT part of restart files: a continued run scores from where it continues.  With several ranks a rank writes one file of
 its own for its block, named as the diagnostics name theirs."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
 from ._native import DAILY_INPUTS, SAS_SCORES_KINDS, totals_item_name
-from .points import claim_output_file, output_file_name
-from .scores import FILL, METRICS, MOMENTS, metrics
-from .totals import local_mask
+from .observers import Observer, claim_output_file, global_attributes, local_mask, write_file, xy_variables
+from .scores import FILL, METRIC_NAMES, METRICS, MOMENTS, check_series, map_variables, metrics
 
 MAX_ITEMS = 16                    # include/roger_hip_sas.h: RH_SAS_SCORES_MAX_ITEMS
 MAX_SERIES = 1024                 # RH_SAS_SCORES_MAX_SERIES
@@ -57,7 +53,7 @@ def derive(moments, series=None):
     return out
 
 
-class TransportScores:
+class TransportScores(Observer):
     """`state.transport_scores`: what the script sets (observations, aggregation, windows, series, base_output_path)."""
 
     def __init__(self):
@@ -82,8 +78,10 @@ class TransportScores:
     def active(self):
         return bool(self.observations)
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
+    def close(self, state):
+        """End of run(): the file."""
+        if self._on and self._path:
+            _write(self, state)
 
     def read(self):
         """Synchronise and return {"closed": (K,) uint8, "<item>_<map>": (nx, ny) of this rank's block}; None while nothing is
@@ -164,14 +162,7 @@ def initialize(state):
             raise ValueError(f"transport_scores: window {k} starts on day {first[k]}, window {k - 1} ends on day {last[k - 1]} "
                              "(windows are in increasing order and do not overlap)")
     if s.series is not None:
-        m = np.asarray(s.series)
-        if m.shape != (settings.nx, settings.ny):
-            raise ValueError(f"transport_scores: the series map has shape {m.shape}, the grid {settings.nx} x {settings.ny} columns")
-        if m.dtype.kind not in "iub":
-            raise ValueError(f"transport_scores: the series map holds {m.dtype} values (an integer series index per column, < 0: not scored)")
-        if int(m.max()) >= n_series:
-            raise ValueError(f"transport_scores: the series map names series {int(m.max())}, the observations hold {n_series} (0 ... {n_series - 1})")
-        if int(m.max()) < 0:
+        if int(check_series("transport_scores", s.series, n_series, settings).max()) < 0:
             raise ValueError("transport_scores: the series map scores no column")
     s._items, s._obs, s._first, s._last = items, np.ascontiguousarray(np.stack(obs)), first, last
 
@@ -215,43 +206,18 @@ def _maps(state):
     return out
 
 
-def close(state):
+def _write(s, state):
     """End of run(): the file."""
-    s = state.transport_scores
-    if not s._on or not s._path:
-        return
-    from . import nc4lite
-    from .diagnostics import _UNITS
-
-    vs, settings = state.variables, state.settings
     maps = _maps(state)
-    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
-    variables = {
-        "x": (("x",), x, {"long_name": "x", "units": "m"}),
-        "y": (("y",), y, {"long_name": "y", "units": "m"}),
-        "window_first": (("sample",), s._first.astype(np.int64), {"long_name": "first model day (itt) of the sample's window", "units": ""}),
-        "window_last": (("sample",), s._last.astype(np.int64), {"long_name": "last model day (itt) of the sample's window", "units": ""}),
-        "closed": (("sample",), maps["closed"].astype(np.int32), {"long_name": "the window's last day was stepped while it was open", "units": ""}),
-    }
-    if s._local is not None:
-        variables["series"] = (("y", "x"), np.ascontiguousarray(s._local.reshape(len(x), len(y)).T.astype(np.int32)),
-                               {"long_name": "series of the column (< 0: not scored)", "units": ""})
-    long_names = {"sum_sim": "sum of the simulated samples", "sum_sim2": "sum of their squares",
-                  "sum_simobs": "sum of simulated times observed", "sse": "sum of squared errors", "sum_obs": "sum of the observed samples",
-                  "sum_obs2": "sum of their squares", "n": "counted samples",
-                  "bias": "mean simulated minus mean observed", "rmse": "root mean squared error", "r": "Pearson correlation",
-                  "nse": "Nash-Sutcliffe efficiency", "kge": "Kling-Gupta efficiency (2009)"}
+    x, y, variables = xy_variables(state.variables)
+    variables["window_first"] = (("sample",), s._first.astype(np.int64), {"long_name": "first model day (itt) of the sample's window", "units": ""})
+    variables["window_last"] = (("sample",), s._last.astype(np.int64), {"long_name": "last model day (itt) of the sample's window", "units": ""})
+    variables["closed"] = (("sample",), maps["closed"].astype(np.int32), {"long_name": "the window's last day was stepped while it was open", "units": ""})
+    long_names = dict(METRIC_NAMES, sum_sim="sum of the simulated samples", sum_sim2="sum of their squares", sum_simobs="sum of simulated times observed",
+                      sse="sum of squared errors", sum_obs="sum of the observed samples", sum_obs2="sum of their squares", n="counted samples")
     kinds = {"bulk": "mean over the window weighted by {w}", "mean": "mean over the window's days", "last": "value on the window's last day"}
-    for v, w, kind in s._items:
-        name = totals_item_name(v, w)
-        for key in MOMENTS + OBS_MOMENTS + ("n",) + METRICS:
-            a = np.ascontiguousarray(maps[f"{name}_{key}"].T)
-            attrs = {"long_name": f"{v} ({kinds[kind].format(w=w)}): {long_names[key]}", "units": _UNITS.get(v, "") if key in ("bias", "rmse") else ""}
-            if key != "n":
-                attrs["_FillValue"] = np.float64(FILL)
-            variables[f"{name}_{key}"] = (("y", "x"), a, attrs)
-    os.makedirs(os.path.dirname(os.path.abspath(s._path)), exist_ok=True)
-    nc4lite.write(s._path, {"x": len(x), "y": len(y), "sample": len(s._first)}, variables, {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "Moments of simulated against observed samples per column and the metrics derived from them.",
-        "setup_identifier": str(settings.identifier), "first_scored_model_day": int(s._day0), "observations_dropped": int(s._dropped)})
+    map_variables(variables, maps, [(totals_item_name(v, w), v, kinds[kind].format(w=w)) for v, w, kind in s._items],
+                  MOMENTS + OBS_MOMENTS + ("n",) + METRICS, long_names, s._local, (len(x), len(y)))
+    write_file(s._path, {"x": len(x), "y": len(y), "sample": len(s._first)}, variables, global_attributes(
+        state.settings.identifier, "Moments of simulated against observed samples per column and the metrics derived from them.",
+        {"first_scored_model_day": int(s._day0), "observations_dropped": int(s._dropped)}))

@@ -24,45 +24,70 @@ record 0 takes the initial values, in which no day's flux exists yet: weighted i
 on the day's launch itself is followed by the row's.  The ring is drained every `capacity` steps, before a restart file is written and
 at the end of run().  With several ranks a rank records its own block and writes one file of its own (`.NNNN.nc`); a rank whose block
 holds no masked column writes none; `combine` merges the ranks' files."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
 from ._native import DAILY_INPUTS, totals_item_name
-from .points import DAY, MAX_VARIABLES, WRITE_BYTES, check_request, claim_output_file, output_file_name
-from .totals import local_mask
+from .observers import (DAY, MAX_VARIABLES, RingSeries, check_mask, check_request, claim_output_file, combined_from, global_attributes, local_mask,
+                        read_rank_files, time_variables, write_file)
 
 _GRIDS = (("x", "y"), ("x", "y", "timesteps"), ("x", "y", "ages"), ("x", "y", "nages"), ("x", "y", "timesteps", "ages"))
 _STATS = ("sum", "count", "wsum", "min", "max")
 
 
-class TransportTotals:
-    """`state.transport_totals`: what the script sets (mask, output_variables, base_output_path, capacity) and the rows drained so far."""
+def keep_item_rows(t, rows):
+    """Hold the rows {item: {stat: array}} a totals_read / zonal_read gave in t._values, item by item in the order of t._items; the
+    bytes they take."""
+    held_bytes = 0
+    for (v, w), stats in zip(t._items, rows.values()):
+        held = t._values[totals_item_name(v, w)]
+        for s, a in stats.items():
+            held.setdefault(s, []).append(a)
+            held_bytes += a.nbytes
+    return held_bytes
+
+
+def held_rows(t):
+    """(itt (n,), days (n,), [(name, weighted, {stat: array})]) of the rows held in t, as `_file_variables` takes them."""
+    hdr = np.array(t._hdr[:t._read], dtype=np.int64).reshape(-1, 2)
+    items = [(totals_item_name(v, w), w is not None, {s: np.concatenate(a) for s, a in t._values[totals_item_name(v, w)].items()})
+             for v, w in t._items]
+    return hdr[:, 0], hdr[:, 1] / float(DAY), items
+
+
+class TransportTotals(RingSeries):
+    """`state.transport_totals`: what the script sets (mask, output_variables, base_output_path, capacity) and the rows drained so far:
+    {item: {stat: [arrays (n,) or (n, width)]}}."""
+
+    label, attribute = "transport totals", "transport_totals"
+    context, host_header = "sas_context", True
 
     def __init__(self):
+        super().__init__()
         self.mask = None
         self.output_variables = []
         self.base_output_path = None
-        self.capacity = 4096
         self.output_path = "{identifier}.transport_totals.nc"
-        self._on = False         # start() configured the device (this rank holds at least one masked column)
         self._items = []         # [(value, weight or None)] as the script's names
         self._ncells = 0         # masked columns of this rank
-        self._hdr = []           # (itt, time) of every row: the drained ones, then the ones still on the device
-        self._values = {}        # {item: {stat: [arrays (n,) or (n, width)]}} drained so far
-        self._read = 0           # rows of the device's series read so far
-        self._steps = 0          # steps since the last drain
-        self._unwritten = 0      # bytes drained since the last write
-        self._path = None
+        self._values = {}
 
     @property
     def active(self):
         return bool(self.output_variables)
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
+    def _count(self, ctx):
+        return ctx.totals_count()[0]
+
+    def _rows(self, ctx, first, n):
+        return ctx.totals_read(first, n)
+
+    def _keep(self, state, tags, rows):
+        return keep_item_rows(self, rows)
+
+    def _write(self, state):
+        dims, variables = _file_variables(*held_rows(self), self._ncells, state.settings.time_origin, state.settings.ages)
+        _write_file(self._path, dims, variables, state.settings.identifier)
 
 
 def _items(output_variables, who="transport_totals"):
@@ -116,12 +141,7 @@ def initialize(state):
     if not settings.enable_offline_transport:
         raise NotImplementedError("transport_totals: the totals of the offline transport model; the SVAT / oneD step records through state.totals")
     items = check_items(state, t.output_variables, t.capacity)
-    if t.mask is not None:
-        mask = np.asarray(t.mask)
-        if mask.shape != (settings.nx, settings.ny):
-            raise ValueError(f"transport_totals: the mask has shape {mask.shape}, the grid {settings.nx} x {settings.ny} columns")
-        if not (mask != 0).any():
-            raise ValueError("transport_totals: the mask holds no column")
+    check_mask("transport_totals", t.mask, settings)
     t._items = items
 
 
@@ -144,53 +164,11 @@ def start(state):
     sas.totals_configure([(state.var_meta[v].sas, None if w is None else state.var_meta[w].sas) for v, w in t._items],
                          None if local.all() else local, int(t.capacity))
     sas.totals_record(int(vs.itt), day=-1)   # (the initial values: no day's flux yet)
-    t._on, t._read, t._steps, t._unwritten = True, 0, 0, 0
+    t._begin()
     t._hdr = [(int(vs.itt), int(vs.time))]
     t._values = {totals_item_name(v, w): {} for v, w in t._items}
     t._path = claim_output_file(t, state, "transport totals")
-    drain(state, final=True)
-
-
-def drain(state, final=False):
-    """Read the rows the device recorded since the last drain."""
-    t = state.transport_totals
-    if not t._on:
-        return
-    sas = state.sas_context
-    total = int(sas.totals_count()[0])
-    n = total - t._read
-    if n > int(t.capacity) or total != len(t._hdr):
-        raise RuntimeError(f"{n} rows of the transport totals recorded since the last drain ({total} in all, {len(t._hdr)} steps known "
-                           f"to the host) but only {int(t.capacity)} are resident on the device")
-    if n > 0:
-        _, rows = sas.totals_read(t._read, n)
-        for (v, w), stats in zip(t._items, rows.values()):
-            held = t._values[totals_item_name(v, w)]
-            for s, a in stats.items():
-                held.setdefault(s, []).append(a)
-                t._unwritten += a.nbytes
-        t._read = total
-    t._steps = 0
-    if final or t._unwritten > WRITE_BYTES:
-        _write(state)
-
-
-def stepped(state):
-    """_step_offline_transport made a step (rh_sas_step recorded its row): note its itt and time, drain when the steps since the last
-    drain reach the capacity."""
-    t = state.transport_totals
-    if not t._on:
-        return
-    vs = state.variables
-    t._hdr.append((int(vs.itt), int(vs.time)))
-    t._steps += 1
-    if t._steps >= int(t.capacity):
-        drain(state)
-
-
-def close(state):
-    """End of run(): the rest of the ring, and the file."""
-    drain(state, final=True)
+    t.drain(state, final=True)
 
 
 def _file_variables(hdr, days, items, ncells, time_origin, ages):
@@ -198,11 +176,8 @@ def _file_variables(hdr, days, items, ncells, time_origin, ages):
     from .diagnostics import _UNITS
 
     dims = {"Time": None}
-    variables = {
-        "Time": (("Time",), np.asarray(days, dtype=np.float64), {"long_name": "Time", "units": "days", "time_origin": str(time_origin)}),
-        "itt": (("Time",), np.asarray(hdr, dtype=np.int64), {"long_name": "time step", "units": ""}),
-        "ncells": ((), np.array(int(ncells), dtype=np.int64), {"long_name": "columns inside the mask", "units": ""}),
-    }
+    variables = time_variables(hdr, days, time_origin)
+    variables["ncells"] = ((), np.array(int(ncells), dtype=np.int64), {"long_name": "columns inside the mask", "units": ""})
     for name, weighted, stats in items:
         units = _UNITS.get(name.split("_by_")[0], "")
         total = np.asarray(stats["sum"], dtype=np.float64)
@@ -228,50 +203,16 @@ def _file_variables(hdr, days, items, ncells, time_origin, ages):
 
 
 def _write_file(path, dims, variables, identifier, extra=None):
-    from . import nc4lite
-
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    attributes = {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "First record contains the initial values of the run proper, in which no day's flux exists yet. "
-                   "Every further record is one day, Time at its end.",
-        "setup_identifier": str(identifier)}
-    attributes.update(extra or {})
-    nc4lite.write(path, dims, variables, attributes)
-
-
-def _write(state):
-    """The whole file from the rows held in memory, through roger_amd.nc4lite."""
-    t = state.transport_totals
-    t._unwritten = 0
-    if not t._path:
-        return
-    settings = state.settings
-    hdr = np.array(t._hdr[:t._read], dtype=np.int64).reshape(-1, 2)
-    items = [(totals_item_name(v, w), w is not None, {s: np.concatenate(a) for s, a in t._values[totals_item_name(v, w)].items()})
-             for v, w in t._items]
-    dims, variables = _file_variables(hdr[:, 0], hdr[:, 1] / float(DAY), items, t._ncells, settings.time_origin, settings.ages)
-    _write_file(t._path, dims, variables, settings.identifier)
+    write_file(path, dims, variables, global_attributes(
+        identifier, "First record contains the initial values of the run proper, in which no day's flux exists yet. "
+                    "Every further record is one day, Time at its end.", extra))
 
 
 def combine(paths, out):
     """The ranks' files `paths` (in rank order) as one: sums, wsums and counts added in rank order, minimum of the minima, maximum of
     the maxima, ncells added, means formed again.  Files whose itt or Time differ are refused."""
-    from . import nc4lite
-
-    paths = [str(p) for p in paths]
-    if not paths:
-        raise ValueError("sas_totals.combine: no files")
-    recs = [nc4lite.read(p) for p in paths]
+    paths, recs, names = read_rank_files("sas_totals", paths, ("itt", "Time"), what="items")
     first = recs[0]["variables"]
-    names = [k[:-4] for k in first if k.endswith("_sum")]
-    for p, rec in zip(paths[1:], recs[1:]):
-        v = rec["variables"]
-        if [k[:-4] for k in v if k.endswith("_sum")] != names:
-            raise ValueError(f"sas_totals.combine: {p} holds other items than {paths[0]}")
-        for key in ("itt", "Time"):
-            if not np.array_equal(np.asarray(v[key][1]), np.asarray(first[key][1])):
-                raise ValueError(f"sas_totals.combine: {key} of {p} differs from {paths[0]}")
     items, ages = [], 0
     for name in names:
         stats = {}
@@ -293,5 +234,4 @@ def combine(paths, out):
         items.append((name, "wsum" in stats, stats))
     ncells = sum(int(np.asarray(rec["variables"]["ncells"][1]).reshape(-1)[0]) for rec in recs)
     dims, variables = _file_variables(first["itt"][1], first["Time"][1], items, ncells, first["Time"][2].get("time_origin", ""), ages)
-    _write_file(str(out), dims, variables, recs[0]["attributes"].get("setup_identifier", ""),
-                {"combined_from": ", ".join(os.path.basename(p) for p in paths)})
+    _write_file(str(out), dims, variables, recs[0]["attributes"].get("setup_identifier", ""), combined_from(paths))

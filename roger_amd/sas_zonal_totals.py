@@ -25,48 +25,53 @@ the run proper, in which no day's flux exists yet; from then on the day's launch
 every `capacity` steps, before a restart file is written and at the end of run(); a restarted run starts a new series.  With several
 ranks a rank records its own block and writes one file of its own (`.NNNN.nc`) over the GLOBAL zone list; a rank whose block holds no
 column of any zone writes none; `combine` merges the ranks' files."""
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
 from ._native import totals_item_name
-from .points import DAY, WRITE_BYTES, claim_output_file, output_file_name
-from .sas_totals import _STATS, _write_file, check_items
-from .totals import local_mask
-from .zonal_totals import FILL, MAX_ZONES, RING_BYTES, zone_ids
+from .observers import RingSeries, claim_output_file, combined_from, local_mask, read_rank_files, time_variables
+from .sas_totals import _STATS, _write_file, check_items, held_rows, keep_item_rows
+from .zonal_totals import FILL, RING_BYTES, check_zones
 
 WHO = "transport_zonal_totals"
 
 
-class TransportZonalTotals:
+class TransportZonalTotals(RingSeries):
     """`state.transport_zonal_totals`: what the script sets (zones, output_variables, base_output_path, capacity) and the rows drained
-    so far."""
+    so far: {item: {stat: [arrays (n, Z) or (n, Z, width)]}}."""
+
+    label, attribute = "transport zonal totals", WHO
+    context, host_header = "sas_context", True
 
     def __init__(self):
+        super().__init__()
         self.zones = None
         self.output_variables = []
         self.base_output_path = None
         self.capacity = None
         self.output_path = "{identifier}.transport_zonal_totals.nc"
-        self._on = False         # start() configured the device (this rank holds at least one column of a zone)
         self._items = []         # [(value, weight or None)] as the script's names
         self._ids = np.zeros(0, dtype=np.int64)      # the zone ids as the script gave them, ascending (the GLOBAL list)
         self._index = None       # the map as indices into them over the GLOBAL interior (-1: outside)
         self._ncells = np.zeros(0, dtype=np.int64)   # columns of every zone on this rank
-        self._hdr = []           # (itt, time) of every row: the drained ones, then the ones still on the device
-        self._values = {}        # {item: {stat: [arrays (n, Z) or (n, Z, width)]}} drained so far
-        self._read = 0           # rows of the device's series read so far
-        self._steps = 0          # steps since the last drain
-        self._unwritten = 0      # bytes drained since the last write
-        self._path = None
+        self._values = {}
 
     @property
     def active(self):
         return bool(self.output_variables) and self.zones is not None
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
+    def _count(self, ctx):
+        return ctx.zonal_count()[0]
+
+    def _rows(self, ctx, first, n):
+        return ctx.zonal_read(first, n)
+
+    def _keep(self, state, tags, rows):
+        return keep_item_rows(self, rows)
+
+    def _write(self, state):
+        dims, variables = _file_variables(*held_rows(self), self._ids, self._ncells, state.settings.time_origin, state.settings.ages)
+        _write_file(self._path, dims, variables, state.settings.identifier)
 
 
 def default_capacity(n_zones, zone_elems):
@@ -84,14 +89,7 @@ def initialize(state):
         raise NotImplementedError(f"{WHO}: the zonal totals of the offline transport model; the SVAT / oneD step records through "
                                   "state.zonal_totals")
     items = check_items(state, t.output_variables, 1 if t.capacity is None else t.capacity, WHO)
-    zones = np.asarray(t.zones)
-    if zones.shape != (settings.nx, settings.ny):
-        raise ValueError(f"{WHO}: the zone map has shape {zones.shape}, the grid {settings.nx} x {settings.ny} columns")
-    ids, index = zone_ids(zones)
-    if not ids.size:
-        raise ValueError(f"{WHO}: the zone map holds no column in any zone (no value > 0)")
-    if ids.size > MAX_ZONES:
-        raise ValueError(f"{WHO}: {ids.size} zones (at most {MAX_ZONES})")
+    ids, index = check_zones(WHO, t.zones, settings)
     if t.capacity is None:
         width = {"ages": settings.ages, "nages": settings.ages + 1}
         elems = sum(next((2 + width[d] for d in state.var_meta[v].dims if d in width), 5) for v, _ in items)
@@ -117,53 +115,11 @@ def start(state):
     sas.zonal_configure([(state.var_meta[v].sas, None if w is None else state.var_meta[w].sas) for v, w in t._items],
                         local, int(t._ids.size), int(t.capacity))
     sas.zonal_record(int(vs.itt), day=-1)   # (the initial values: no day's flux yet)
-    t._on, t._read, t._steps, t._unwritten = True, 0, 0, 0
+    t._begin()
     t._hdr = [(int(vs.itt), int(vs.time))]
     t._values = {totals_item_name(v, w): {} for v, w in t._items}
     t._path = claim_output_file(t, state, "transport zonal totals")
-    drain(state, final=True)
-
-
-def drain(state, final=False):
-    """Read the rows the device recorded since the last drain."""
-    t = state.transport_zonal_totals
-    if not t._on:
-        return
-    sas = state.sas_context
-    total = int(sas.zonal_count()[0])
-    n = total - t._read
-    if n > int(t.capacity) or total != len(t._hdr):
-        raise RuntimeError(f"{n} rows of the transport zonal totals recorded since the last drain ({total} in all, {len(t._hdr)} steps "
-                           f"known to the host) but only {int(t.capacity)} are resident on the device")
-    if n > 0:
-        _, rows = sas.zonal_read(t._read, n)
-        for (v, w), stats in zip(t._items, rows.values()):
-            held = t._values[totals_item_name(v, w)]
-            for s, a in stats.items():
-                held.setdefault(s, []).append(a)
-                t._unwritten += a.nbytes
-        t._read = total
-    t._steps = 0
-    if final or t._unwritten > WRITE_BYTES:
-        _write(state)
-
-
-def stepped(state):
-    """_step_offline_transport made a step (rh_sas_step recorded its row): note its itt and time, drain when the steps since the last
-    drain reach the capacity."""
-    t = state.transport_zonal_totals
-    if not t._on:
-        return
-    vs = state.variables
-    t._hdr.append((int(vs.itt), int(vs.time)))
-    t._steps += 1
-    if t._steps >= int(t.capacity):
-        drain(state)
-
-
-def close(state):
-    """End of run(): the rest of the ring, and the file."""
-    drain(state, final=True)
+    t.drain(state, final=True)
 
 
 def _file_variables(hdr, days, items, ids, ncells, time_origin, ages):
@@ -171,10 +127,11 @@ def _file_variables(hdr, days, items, ids, ncells, time_origin, ages):
     from .diagnostics import _UNITS
 
     dims = {"Time": None, "zone": int(len(ids))}
+    tv = time_variables(hdr, days, time_origin)
     variables = {
-        "Time": (("Time",), np.asarray(days, dtype=np.float64), {"long_name": "Time", "units": "days", "time_origin": str(time_origin)}),
+        "Time": tv["Time"],
         "zone": (("zone",), np.asarray(ids, dtype=np.int64), {"long_name": "zone id of the zone map", "units": ""}),
-        "itt": (("Time",), np.asarray(hdr, dtype=np.int64), {"long_name": "time step", "units": ""}),
+        "itt": tv["itt"],
         "ncells": (("zone",), np.asarray(ncells, dtype=np.int64), {"long_name": "columns of the zone", "units": ""}),
     }
     for name, weighted, stats in items:
@@ -206,39 +163,12 @@ def _file_variables(hdr, days, items, ids, ncells, time_origin, ages):
     return dims, variables
 
 
-def _write(state):
-    """The whole file from the rows held in memory, through roger_amd.nc4lite."""
-    t = state.transport_zonal_totals
-    t._unwritten = 0
-    if not t._path:
-        return
-    settings = state.settings
-    hdr = np.array(t._hdr[:t._read], dtype=np.int64).reshape(-1, 2)
-    items = [(totals_item_name(v, w), w is not None, {s: np.concatenate(a) for s, a in t._values[totals_item_name(v, w)].items()})
-             for v, w in t._items]
-    dims, variables = _file_variables(hdr[:, 0], hdr[:, 1] / float(DAY), items, t._ids, t._ncells, settings.time_origin, settings.ages)
-    _write_file(t._path, dims, variables, settings.identifier)
-
-
 def combine(paths, out):
     """The ranks' files `paths` (in rank order) as one: per zone the sums, wsums and counts added in rank order, the minimum of the
     minima, the maximum of the maxima (a rank that counted nothing in the zone takes no part), ncells added, means formed again.  Files
     whose zone list, itt or Time differ are refused."""
-    from . import nc4lite
-
-    paths = [str(p) for p in paths]
-    if not paths:
-        raise ValueError("sas_zonal_totals.combine: no files")
-    recs = [nc4lite.read(p) for p in paths]
+    paths, recs, names = read_rank_files("sas_zonal_totals", paths, ("zone", "itt", "Time"), what="items")
     first = recs[0]["variables"]
-    names = [k[:-4] for k in first if k.endswith("_sum")]
-    for p, rec in zip(paths[1:], recs[1:]):
-        v = rec["variables"]
-        if [k[:-4] for k in v if k.endswith("_sum")] != names:
-            raise ValueError(f"sas_zonal_totals.combine: {p} holds other items than {paths[0]}")
-        for key in ("zone", "itt", "Time"):
-            if not np.array_equal(np.asarray(v[key][1]), np.asarray(first[key][1])):
-                raise ValueError(f"sas_zonal_totals.combine: {key} of {p} differs from {paths[0]}")
     items, ages = [], 0
     for name in names:
         stats = {}
@@ -262,5 +192,4 @@ def combine(paths, out):
     ncells = np.sum([np.asarray(rec["variables"]["ncells"][1], dtype=np.int64) for rec in recs], axis=0)
     dims, variables = _file_variables(first["itt"][1], first["Time"][1], items, first["zone"][1], ncells,
                                       first["Time"][2].get("time_origin", ""), ages)
-    _write_file(str(out), dims, variables, recs[0]["attributes"].get("setup_identifier", ""),
-                {"combined_from": ", ".join(os.path.basename(p) for p in paths)})
+    _write_file(str(out), dims, variables, recs[0]["attributes"].get("setup_identifier", ""), combined_from(paths))

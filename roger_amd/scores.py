@@ -35,14 +35,10 @@ that set in increasing k with plain sequential additions (not numpy.sum, whose p
 Start and restart.  `start` is a multiple of `frequency`.  If the model's clock is past `start` when the run begins -- after a restart --
 the next interval boundary becomes interval 0 and the observations before it are dropped.  The moments are NOT part of restart files: a
 continued run scores from where it continues."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
-from .points import DAY, claim_output_file, output_file_name
-from .totals import local_mask
+from .observers import DAY, Observer, check_map_shape, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file, xy_variables
 
 MAX_VARIABLES = 16                # roger_amd/csrc/rh_scores.h: RH_SCORES_MAX_ITEMS
 MAX_SERIES = 1024                 # include/roger_hip.h: RH_SCORES_MAX_SERIES
@@ -107,7 +103,38 @@ def metrics(m1, m2, m3, m4, n, so, soo, scored):
     return out
 
 
-class Scores:
+METRIC_NAMES = {"bias": "mean simulated minus mean observed", "rmse": "root mean squared error", "r": "Pearson correlation",
+                "nse": "Nash-Sutcliffe efficiency", "kge": "Kling-Gupta efficiency (2009)"}
+
+
+def check_series(what, series, n_series, settings):
+    """A series map over the global interior: of the grid's shape, integers, and none beyond the observations' series."""
+    m = np.asarray(series)
+    check_map_shape(what, "series map", m, settings)
+    if m.dtype.kind not in "iub":
+        raise ValueError(f"{what}: the series map holds {m.dtype} values (an integer series index per column, < 0: not scored)")
+    if int(m.max()) >= n_series:
+        raise ValueError(f"{what}: the series map names series {int(m.max())}, the observations hold {n_series} (0 ... {n_series - 1})")
+    return m
+
+
+def map_variables(variables, maps, items, keys, long_names, series, shape):
+    """Into `variables` the (y, x) maps of a scores file: the series of every column (where a map was given), then per item
+    (name, variable, kind sentence) its moments, count and metrics `keys`."""
+    from .diagnostics import _UNITS
+
+    if series is not None:
+        variables["series"] = (("y", "x"), np.ascontiguousarray(series.reshape(shape).T.astype(np.int32)),
+                               {"long_name": "series of the column (< 0: not scored)", "units": ""})
+    for name, v, kind in items:
+        for key in keys:
+            attrs = {"long_name": f"{v} ({kind}): {long_names[key]}", "units": _UNITS.get(v, "") if key in ("bias", "rmse") else ""}
+            if key != "n":
+                attrs["_FillValue"] = np.float64(FILL)
+            variables[f"{name}_{key}"] = (("y", "x"), np.ascontiguousarray(maps[f"{name}_{key}"].T), attrs)
+
+
+class Scores(Observer):
     """`state.scores`: what the script sets (observations, aggregation, frequency, start, series, base_output_path)."""
 
     def __init__(self):
@@ -132,15 +159,32 @@ class Scores:
     def active(self):
         return bool(self.observations)
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
-
     def read(self):
         """Synchronise and return {"closed": (n_intervals,) uint8, "<v>_<map>": (nx, ny) of this rank's block}; None while nothing is
         configured on this rank."""
         if not self._on:
             return None
         return _maps(self._state)
+
+    def close(self, state):
+        """End of run(): the file."""
+        if not self._on or not self._path:
+            return
+        settings = state.settings
+        maps = _maps(state)
+        x, y, variables = xy_variables(state.variables)
+        f = int(self.frequency)
+        ends = (self._t_first + (np.arange(len(maps["closed"]), dtype=np.float64) + 1.0) * f) / float(DAY)
+        variables["interval"] = (("interval",), ends, {"long_name": "end of the observation interval", "units": "days", "time_origin": str(settings.time_origin)})
+        variables["closed"] = (("interval",), maps["closed"].astype(np.int32), {"long_name": "the interval was closed by a step while it was scored", "units": ""})
+        long_names = dict(METRIC_NAMES, sum_sim="sum of the simulated interval values", sum_sim2="sum of their squares",
+                          sum_simobs="sum of simulated times observed", sse="sum of squared errors", n="scored intervals")
+        kinds = ("sum over the interval", "value at the end of the interval")
+        map_variables(variables, maps, [(v, v, kinds[k]) for v, k in zip(self._names, self._kinds)], MOMENTS + ("n",) + METRICS, long_names,
+                      self._local, (len(x), len(y)))
+        write_file(self._path, {"x": len(x), "y": len(y), "interval": len(ends)}, variables, global_attributes(
+            settings.identifier, "Moments of simulated against observed interval values per column and the metrics derived from them.",
+            {"frequency_seconds": int(f), "first_interval_starts_seconds": int(self._t_first), "observations_dropped": int(self._dropped)}))
 
 
 def default_kind(name):
@@ -156,10 +200,8 @@ def initialize(state):
     if not s.active:
         return
     settings = state.settings
-    if settings.enable_offline_transport:
-        raise NotImplementedError("scores: the offline transport model steps by the day and scores its tracers against bulk samples "
-                                  "over windows of days through state.transport_scores (roger_amd/sas_scores.py); the moments of "
-                                  "state.scores belong to the SVAT / oneD step")
+    svat_only("scores", settings, " and scores its tracers against bulk samples over windows of days through state.transport_scores "
+              "(roger_amd/sas_scores.py); the moments of state.scores belong to the SVAT / oneD step")
     names = list(s.observations)
     if len(names) > MAX_VARIABLES:
         raise ValueError(f"scores: {len(names)} variables (at most {MAX_VARIABLES})")
@@ -175,9 +217,7 @@ def initialize(state):
             raise ValueError(f'scores: aggregation of {v!r} is {s.aggregation[v]!r} ("sum" or "last")')
     obs = []
     for v in names:
-        meta = state.var_meta.get(v)
-        if meta is None or meta.plane is None or meta.dtype is not None:
-            raise NotImplementedError(f"scores: {v!r} is not a float64 (x, y) variable of the device arena")
+        check_planes("scores", (v,), state)
         o = np.asarray(s.observations[v], dtype=np.float64)
         if o.ndim not in (1, 2) or not o.size:
             raise ValueError(f"scores: the observations of {v!r} have shape {o.shape} ((n_intervals,) or (n_series, n_intervals))")
@@ -188,13 +228,7 @@ def initialize(state):
     if n_series > MAX_SERIES:
         raise ValueError(f"scores: {n_series} series (at most {MAX_SERIES})")
     if s.series is not None:
-        m = np.asarray(s.series)
-        if m.shape != (settings.nx, settings.ny):
-            raise ValueError(f"scores: the series map has shape {m.shape}, the grid {settings.nx} x {settings.ny} columns")
-        if m.dtype.kind not in "iub":
-            raise ValueError(f"scores: the series map holds {m.dtype} values (an integer series index per column, < 0: not scored)")
-        if int(m.max()) >= n_series:
-            raise ValueError(f"scores: the series map names series {int(m.max())}, the observations hold {n_series} (0 ... {n_series - 1})")
+        check_series("scores", s.series, n_series, settings)
     s._names = names
     s._kinds = [KINDS[s.aggregation.get(v, default_kind(v))] for v in names]
     s._obs = np.ascontiguousarray(np.stack(obs))
@@ -226,6 +260,10 @@ def start(state):
     s._path = claim_output_file(s, state, "scores")
 
 
+def close(state):
+    state.scores.close(state)
+
+
 def _maps(state):
     s = state.scores
     moments, closed = state.backend_context.scores_read()
@@ -235,45 +273,3 @@ def _maps(state):
         for key, a in derive(moments[j], closed, s._obs[j], s._local).items():
             out[f"{v}_{key}"] = a.reshape(nxl, nyl)
     return out
-
-
-def close(state):
-    """End of run(): the file."""
-    s = state.scores
-    if not s._on or not s._path:
-        return
-    from . import nc4lite
-    from .diagnostics import _UNITS
-
-    vs, settings = state.variables, state.settings
-    maps = _maps(state)
-    x, y = np.asarray(vs.x)[2:-2], np.asarray(vs.y)[2:-2]
-    f = int(s.frequency)
-    ends = (s._t_first + (np.arange(len(maps["closed"]), dtype=np.float64) + 1.0) * f) / float(DAY)
-    variables = {
-        "x": (("x",), x, {"long_name": "x", "units": "m"}),
-        "y": (("y",), y, {"long_name": "y", "units": "m"}),
-        "interval": (("interval",), ends, {"long_name": "end of the observation interval", "units": "days", "time_origin": str(settings.time_origin)}),
-        "closed": (("interval",), maps["closed"].astype(np.int32), {"long_name": "the interval was closed by a step while it was scored", "units": ""}),
-    }
-    if s._local is not None:
-        variables["series"] = (("y", "x"), np.ascontiguousarray(s._local.reshape(len(x), len(y)).T.astype(np.int32)),
-                               {"long_name": "series of the column (< 0: not scored)", "units": ""})
-    long_names = {"sum_sim": "sum of the simulated interval values", "sum_sim2": "sum of their squares",
-                  "sum_simobs": "sum of simulated times observed", "sse": "sum of squared errors", "n": "scored intervals",
-                  "bias": "mean simulated minus mean observed", "rmse": "root mean squared error", "r": "Pearson correlation",
-                  "nse": "Nash-Sutcliffe efficiency", "kge": "Kling-Gupta efficiency (2009)"}
-    for j, v in enumerate(s._names):
-        kind = "sum over the interval" if s._kinds[j] == 0 else "value at the end of the interval"
-        for key in MOMENTS + ("n",) + METRICS:
-            a = np.ascontiguousarray(maps[f"{v}_{key}"].T)
-            attrs = {"long_name": f"{v} ({kind}): {long_names[key]}", "units": _UNITS.get(v, "") if key in ("bias", "rmse") else ""}
-            if key != "n":
-                attrs["_FillValue"] = np.float64(FILL)
-            variables[f"{v}_{key}"] = (("y", "x"), a, attrs)
-    os.makedirs(os.path.dirname(os.path.abspath(s._path)), exist_ok=True)
-    nc4lite.write(s._path, {"x": len(x), "y": len(y), "interval": len(ends)}, variables, {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "Moments of simulated against observed interval values per column and the metrics derived from them.",
-        "setup_identifier": str(settings.identifier), "frequency_seconds": int(f), "first_interval_starts_seconds": int(s._t_first),
-        "observations_dropped": int(s._dropped)})

@@ -342,39 +342,9 @@ class RogerState:
         self._ctx = None
         self._sas_ctx = None             # the `_native.SasContext` of an offline-transport run
         self._diagnostics = {}
-        from .points import PointSeries
+        from . import observers
 
-        self.points = PointSeries()      # time series at observation columns (roger_amd/points.py); filled in by set_diagnostics
-        from .sas_points import TransportPointSeries
-
-        self.transport_points = TransportPointSeries()   # ... of the offline transport model (roger_amd/sas_points.py)
-        from .totals import AreaTotals
-
-        self.totals = AreaTotals()       # per-step sum, min and max over a masked area (roger_amd/totals.py)
-        from .zonal_totals import ZonalTotals
-
-        self.zonal_totals = ZonalTotals()   # ... for every zone of a zone map (roger_amd/zonal_totals.py)
-        from .scores import Scores
-
-        self.scores = Scores()              # per-column scores against observed series, moments on the device (roger_amd/scores.py)
-        from .events import Events
-
-        self.events = Events()              # per-column sums, peaks, first and last values of every rainfall event (roger_amd/events.py)
-        from .durations import Durations
-
-        self.durations = Durations()        # per-column histograms, extremes and spells of interval values (roger_amd/durations.py)
-        from .bands import Bands
-
-        self.bands = Bands()                # per-interval exact quantiles across the columns (roger_amd/bands.py)
-        from .sas_totals import TransportTotals
-
-        self.transport_totals = TransportTotals()        # ... of the offline transport model, flux-weighted (roger_amd/sas_totals.py)
-        from .sas_zonal_totals import TransportZonalTotals
-
-        self.transport_zonal_totals = TransportZonalTotals()   # ... for every zone of a zone map (roger_amd/sas_zonal_totals.py)
-        from .sas_scores import TransportScores
-
-        self.transport_scores = TransportScores()   # per-column scores of the transport model against observed samples (roger_amd/sas_scores.py)
+        observers.create(self)           # self.points ... self.transport_scores: what set_diagnostics fills in (roger_amd/observers.py: REGISTRY)
         # output (roger_amd/diagnostics.py: initialize): the active diagnostics; for the device-side accumulators their one output
         # interval, the number of resident slots and the last interval looked at; whether the transport model writes them per step
         self._diag_active = None

@@ -22,13 +22,11 @@ differ in the last bits.
 The host drains the ring as it drains the points' (roger_amd/points.py).  With several ranks a rank records its own block and writes
 one file of its own (`.0000.nc`); a rank whose block holds no masked column writes none; `combine` merges the ranks' files.
 Restart: a restarted run starts a new series."""
-import datetime
-import os
-
 import numpy as np
 
 from . import runtime_settings as rs
-from .points import DAY, MAX_VARIABLES, WRITE_BYTES, check_request, claim_output_file, output_file_name
+from .observers import (DAY, MAX_VARIABLES, RingSeries, check_mask, check_planes, check_request, claim_output_file, combined_from,  # noqa: F401
+                        global_attributes, interior_plane, local_mask, read_rank_files, svat_only, time_variables, write_file)
 
 TILE, WAVE = 256, 64
 STATS = ("sum", "min", "max")
@@ -64,38 +62,33 @@ def tree_totals(values, mask=None):
     return tuple(out)
 
 
-def local_mask(mask, nx, ny, num_proc, rank):
-    """The block of `rank` of a mask over the global interior, flat in C order over the block's (x, y).  Ranks x-fastest."""
-    px, py = int(num_proc[0]), int(num_proc[1])
-    nxl, nyl = int(nx) // px, int(ny) // py
-    bx, by = rank % px, rank // px
-    return np.ascontiguousarray(mask[bx * nxl:(bx + 1) * nxl, by * nyl:(by + 1) * nyl]).reshape(-1)
+class AreaTotals(RingSeries):
+    """`state.totals`: what the script sets (mask, output_variables, base_output_path, capacity) and the rows drained so far:
+    headers (n, 3) int64 itt, time, dt_secs and values (n, V, 3) float64."""
 
-
-class AreaTotals:
-    """`state.totals`: what the script sets (mask, output_variables, base_output_path, capacity) and the rows drained so far."""
+    label = attribute = "totals"
 
     def __init__(self):
+        super().__init__()
         self.mask = None
         self.output_variables = []
         self.base_output_path = None
-        self.capacity = 4096
         self.output_path = "{identifier}.totals.nc"
-        self._on = False         # initialize() configured the device (this rank holds at least one masked column)
         self._ncells = 0         # masked columns of this rank
-        self._hdr = []           # drained headers, arrays (n, 3) int64: itt, time, dt_secs
-        self._values = []        # drained rows, arrays (n, V, 3) float64
-        self._read = 0           # rows of the device's series read so far
-        self._steps = 0          # host-loop steps since the last drain
-        self._unwritten = 0      # bytes drained since the last write
-        self._path = None
 
     @property
     def active(self):
         return bool(self.output_variables)
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
+    def _count(self, ctx):
+        return ctx.totals_count()[0]
+
+    def _rows(self, ctx, first, n):
+        return ctx.totals_read(first, n)
+
+    def _write(self, state):
+        hdr, values = np.concatenate(self._hdr), np.concatenate(self._values)
+        _write_file(self._path, _file_variables(hdr, values, self.output_variables, self._ncells, state.settings.time_origin), state.settings.identifier)
 
 
 def initialize(state):
@@ -106,101 +99,41 @@ def initialize(state):
     if not t.active:
         return
     settings = state.settings
-    if settings.enable_offline_transport:
-        raise NotImplementedError("totals: the offline transport model steps by the day and its output is read after every step "
-                                  "(state.diagnostics); the recorder belongs to the SVAT / oneD step -- the transport model's own totals are "
-                                  "state.transport_totals (roger_amd/sas_totals.py)")
+    svat_only("totals", settings, " and its output is read after every step (state.diagnostics); the recorder belongs to the SVAT / oneD step "
+              "-- the transport model's own totals are state.transport_totals (roger_amd/sas_totals.py)")
     if len(t.output_variables) > MAX_VARIABLES:
         raise ValueError(f"totals: {len(t.output_variables)} variables (at most {MAX_VARIABLES})")
     check_request("totals", (), len(t.output_variables), t.capacity, settings)   # (no cells to check: the capacity)
-    for v in t.output_variables:
-        meta = state.var_meta.get(v)
-        if meta is None or meta.plane is None or meta.dtype is not None:
-            raise NotImplementedError(f"totals: {v!r} is not a float64 (x, y) variable of the device arena")
-    if t.mask is None:
-        mask = np.ones((settings.nx, settings.ny), dtype=bool)
-    else:
-        mask = np.asarray(t.mask)
-        if mask.shape != (settings.nx, settings.ny):
-            raise ValueError(f"totals: the mask has shape {mask.shape}, the grid {settings.nx} x {settings.ny} columns")
-        mask = mask != 0
-    if not mask.any():
-        raise ValueError("totals: the mask holds no column")
+    check_planes("totals", t.output_variables, state)
+    mask = np.ones((settings.nx, settings.ny), dtype=bool) if t.mask is None else check_mask("totals", t.mask, settings)
     local = local_mask(mask, settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
     t._ncells = int(local.sum())
     if not t._ncells:
         return   # (several ranks: no masked column in this rank's block)
-    ctx = state.backend_context
-    state.variables.flush_to_device()
-    ctx.totals_configure(list(t.output_variables), None if local.all() else local, int(t.capacity))
-    t._on, t._read, t._steps, t._unwritten = True, 0, 0, 0
     vs = state.variables
+    vs.flush_to_device()
+    state.backend_context.totals_configure(list(t.output_variables), None if local.all() else local, int(t.capacity))
+    t._begin()
     first = np.empty((1, len(t.output_variables), 3))
     for j, v in enumerate(t.output_variables):
-        a = np.asarray(getattr(vs, v))[2:-2, 2:-2]
-        if a.ndim == 3:
-            a = a[:, :, 1]
-        first[0, j] = tree_totals(a, local)
+        first[0, j] = tree_totals(interior_plane(vs, v), local)
     t._hdr = [np.array([[int(vs.itt), int(vs.time), 0]], dtype=np.int64)]
     t._values = [first]
     t._path = claim_output_file(t, state, "totals")
-    _write(state)
-
-
-def check_call(state, nsteps):
-    """Before a call that enqueues nsteps steps: more than the ring holds would overwrite rows nobody has read."""
-    t = state.totals
-    if t._on and int(nsteps) > int(t.capacity):
-        raise RuntimeError(f"{int(nsteps)} steps in one call but only {int(t.capacity)} rows of the totals are resident on the device: "
-                           "call run_device() in shorter pieces, or raise state.totals.capacity")
-
-
-def drain(state, final=False):
-    """Read the rows the device recorded since the last drain."""
-    t = state.totals
-    if not t._on:
-        return
-    ctx = state.backend_context
-    total = int(ctx.totals_count()[0])
-    n = total - t._read
-    if n > int(t.capacity):
-        raise RuntimeError(f"{n} rows of the totals recorded since the last drain but only {int(t.capacity)} are resident on the device")
-    if n > 0:
-        hdr, values = ctx.totals_read(t._read, n)
-        t._hdr.append(hdr)
-        t._values.append(values)
-        t._read = total
-        t._unwritten += values.nbytes + hdr.nbytes
-    t._steps = 0
-    if final or t._unwritten > WRITE_BYTES:
-        _write(state)
-
-
-def stepped(state):
-    """A host loop made one step call: drain when the calls since the last drain reach the capacity."""
-    t = state.totals
-    if not t._on:
-        return
-    t._steps += 1
-    if t._steps >= int(t.capacity):
-        drain(state)
+    t.write(state)
 
 
 def close(state):
-    """End of run(): the rest of the ring, and the file."""
-    drain(state, final=True)
+    state.totals.close(state)
 
 
-def _file_variables(hdr, values, names, ncells, time_origin):
-    """The variables of a totals file from headers (n, 3), values (n, V, 3) and the number of masked columns."""
+def _file_variables(hdr, values, names, ncells, time_origin, days=None):
+    """The variables of a totals file from headers (n, 3), values (n, V, 3) and the number of masked columns (`days`: the rows' Time
+    where the headers do not hold it)."""
     from .diagnostics import _UNITS
 
-    variables = {
-        "Time": (("Time",), hdr[:, 1] / float(DAY), {"long_name": "Time", "units": "days", "time_origin": str(time_origin)}),
-        "dt": (("Time",), hdr[:, 2].astype(np.float64), {"long_name": "length of the time step", "units": "s"}),
-        "itt": (("Time",), hdr[:, 0].astype(np.int64), {"long_name": "time step", "units": ""}),
-        "ncells": ((), np.array(int(ncells), dtype=np.int64), {"long_name": "columns inside the mask", "units": ""}),
-    }
+    variables = time_variables(hdr[:, 0], hdr[:, 1] / float(DAY) if days is None else days, time_origin, dt=hdr[:, 2])
+    variables["ncells"] = ((), np.array(int(ncells), dtype=np.int64), {"long_name": "columns inside the mask", "units": ""})
     for j, name in enumerate(names):
         units = _UNITS.get(name, "")
         for k, stat in enumerate(STATS):
@@ -211,48 +144,23 @@ def _file_variables(hdr, values, names, ncells, time_origin):
     return variables
 
 
-def _write_file(path, variables, identifier, extra=None):
-    from . import nc4lite
-
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    attributes = {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "First record (dt = 0) contains initial values. Every further record is one time step, Time at its end.",
-        "setup_identifier": str(identifier)}
-    attributes.update(extra or {})
-    nc4lite.write(path, {"Time": None}, variables, attributes)
+def _write_file(path, variables, identifier, extra=None, dims=None):
+    write_file(path, dims or {"Time": None}, variables, global_attributes(
+        identifier, "First record (dt = 0) contains initial values. Every further record is one time step, Time at its end.", extra))
 
 
-def _write(state):
-    """The whole file from the rows held in memory, through roger_amd.nc4lite."""
-    t = state.totals
-    t._unwritten = 0
-    if not t._path:
-        return
-    hdr, values = np.concatenate(t._hdr), np.concatenate(t._values)
-    _write_file(t._path, _file_variables(hdr, values, t.output_variables, t._ncells, state.settings.time_origin), state.settings.identifier)
+def rank_headers(first):
+    """The headers (n, 3) of the rows of a rank's file (its variables `first`); the time is left to the file's own days."""
+    itt = np.asarray(first["itt"][1], dtype=np.int64)
+    return np.stack([itt, np.zeros(len(itt), dtype=np.int64), np.asarray(first["dt"][1]).astype(np.int64)], axis=1)
 
 
 def combine(paths, out):
     """The ranks' files `paths` (in rank order) as one: sums added in rank order, minimum of the minima, maximum of the maxima, ncells
     added, means formed again.  Files whose itt or Time differ are refused."""
-    from . import nc4lite
-
-    paths = [str(p) for p in paths]
-    if not paths:
-        raise ValueError("totals.combine: no files")
-    recs = [nc4lite.read(p) for p in paths]
+    paths, recs, names = read_rank_files("totals", paths, ("itt", "Time", "dt"))
     first = recs[0]["variables"]
-    names = [k[:-4] for k in first if k.endswith("_sum")]
-    for p, rec in zip(paths[1:], recs[1:]):
-        v = rec["variables"]
-        if [k[:-4] for k in v if k.endswith("_sum")] != names:
-            raise ValueError(f"totals.combine: {p} holds other variables than {paths[0]}")
-        for key in ("itt", "Time", "dt"):
-            if not np.array_equal(np.asarray(v[key][1]), np.asarray(first[key][1])):
-                raise ValueError(f"totals.combine: {key} of {p} differs from {paths[0]}")
-    hdr = np.stack([np.asarray(first["itt"][1], dtype=np.int64), np.zeros(len(first["itt"][1]), dtype=np.int64),
-                    np.asarray(first["dt"][1]).astype(np.int64)], axis=1)
+    hdr = rank_headers(first)
     values = np.empty((len(hdr), len(names), 3))
     for j, name in enumerate(names):
         cols = [[np.asarray(rec["variables"][f"{name}_{stat}"][1], dtype=np.float64) for rec in recs] for stat in STATS]
@@ -263,6 +171,5 @@ def combine(paths, out):
         values[:, j, 1] = np.fmin.reduce(cols[1])
         values[:, j, 2] = np.fmax.reduce(cols[2])
     ncells = sum(int(np.asarray(rec["variables"]["ncells"][1]).reshape(-1)[0]) for rec in recs)
-    variables = _file_variables(hdr, values, names, ncells, first["Time"][2].get("time_origin", ""))
-    variables["Time"] = (("Time",), np.asarray(first["Time"][1], dtype=np.float64), variables["Time"][2])   # (the files' own days)
-    _write_file(str(out), variables, recs[0]["attributes"].get("setup_identifier", ""), {"combined_from": ", ".join(os.path.basename(p) for p in paths)})
+    variables = _file_variables(hdr, values, names, ncells, first["Time"][2].get("time_origin", ""), days=first["Time"][1])
+    _write_file(str(out), variables, recs[0]["attributes"].get("setup_identifier", ""), combined_from(paths))

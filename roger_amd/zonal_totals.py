@@ -24,14 +24,12 @@ The host drains the ring as it drains the totals'.  With several ranks a rank re
 (`.0000.nc`) over the GLOBAL zone list -- a zone without a column in the rank's block has ncells 0, sum 0 and `_FillValue` for minimum,
 maximum and mean; a rank whose block holds no column of any zone writes none; `combine` merges the ranks' files.
 Restart: a restarted run starts a new series."""
-import datetime
-import os
-
 import numpy as np
 
-from . import runtime_settings as rs
-from .points import DAY, MAX_VARIABLES, WRITE_BYTES, check_request, claim_output_file, output_file_name
-from .totals import STATS, TILE, _OPS, _tile_reduce, local_mask
+from . import runtime_settings as rs, totals
+from .observers import (DAY, MAX_VARIABLES, RingSeries, check_map_shape, check_planes, check_request, claim_output_file, combined_from,
+                        interior_plane, local_mask, read_rank_files, svat_only, time_variables)
+from .totals import STATS, TILE, _OPS, _tile_reduce
 
 MAX_ZONES = 1024                  # include/roger_hip.h: RH_ZONAL_MAX_ZONES
 RING_BYTES = 64 << 20             # what the default capacity keeps the device's ring under
@@ -79,31 +77,48 @@ def zone_totals(values, zone, n_zones):
     return out
 
 
-class ZonalTotals:
-    """`state.zonal_totals`: what the script sets (zones, output_variables, base_output_path, capacity) and the rows drained so far."""
+def check_zones(what, zones, settings):
+    """(ids, index) of a script's zone map (zone_ids), or the refusal: of the grid's shape, with a zone, and not too many."""
+    zones = np.asarray(zones)
+    check_map_shape(what, "zone map", zones, settings)
+    ids, index = zone_ids(zones)
+    if not ids.size:
+        raise ValueError(f"{what}: the zone map holds no column in any zone (no value > 0)")
+    if ids.size > MAX_ZONES:
+        raise ValueError(f"{what}: {ids.size} zones (at most {MAX_ZONES})")
+    return ids, index
+
+
+class ZonalTotals(RingSeries):
+    """`state.zonal_totals`: what the script sets (zones, output_variables, base_output_path, capacity) and the rows drained so far:
+    headers (n, 3) int64 itt, time, dt_secs and values (n, Z, V, 3) float64."""
+
+    label, attribute = "zonal totals", "zonal_totals"
 
     def __init__(self):
+        super().__init__()
         self.zones = None
         self.output_variables = []
         self.base_output_path = None
         self.capacity = None
         self.output_path = "{identifier}.zonal_totals.nc"
-        self._on = False         # initialize() configured the device (this rank holds at least one column of a zone)
         self._ids = np.zeros(0, dtype=np.int64)      # the zone ids as the script gave them, ascending (the GLOBAL list)
         self._ncells = np.zeros(0, dtype=np.int64)   # columns of every zone on this rank
-        self._hdr = []           # drained headers, arrays (n, 3) int64: itt, time, dt_secs
-        self._values = []        # drained rows, arrays (n, Z, V, 3) float64
-        self._read = 0           # rows of the device's series read so far
-        self._steps = 0          # host-loop steps since the last drain
-        self._unwritten = 0      # bytes drained since the last write
-        self._path = None
 
     @property
     def active(self):
         return bool(self.output_variables) and self.zones is not None
 
-    def get_output_file_name(self, state):
-        return output_file_name(self, state)
+    def _count(self, ctx):
+        return ctx.zonal_count()[0]
+
+    def _rows(self, ctx, first, n):
+        return ctx.zonal_read(first, n)
+
+    def _write(self, state):
+        hdr, values = np.concatenate(self._hdr), np.concatenate(self._values)
+        _write_file(self._path, _file_variables(hdr, values, self.output_variables, self._ids, self._ncells, state.settings.time_origin),
+                    state.settings.identifier)
 
 
 def default_capacity(n_zones, n_variables):
@@ -119,25 +134,13 @@ def initialize(state):
     if not t.active:
         return
     settings = state.settings
-    if settings.enable_offline_transport:
-        raise NotImplementedError("zonal totals: the offline transport model steps by the day and its output is read after every step "
-                                  "(state.diagnostics); the recorder belongs to the SVAT / oneD step -- the transport model's own totals are "
-                                  "state.transport_totals (roger_amd/sas_totals.py), per zone state.transport_zonal_totals "
-                                  "(roger_amd/sas_zonal_totals.py)")
+    svat_only("zonal totals", settings, " and its output is read after every step (state.diagnostics); the recorder belongs to the SVAT / oneD step "
+              "-- the transport model's own totals are state.transport_totals (roger_amd/sas_totals.py), per zone "
+              "state.transport_zonal_totals (roger_amd/sas_zonal_totals.py)")
     if len(t.output_variables) > MAX_VARIABLES:
         raise ValueError(f"zonal totals: {len(t.output_variables)} variables (at most {MAX_VARIABLES})")
-    zones = np.asarray(t.zones)
-    if zones.shape != (settings.nx, settings.ny):
-        raise ValueError(f"zonal totals: the zone map has shape {zones.shape}, the grid {settings.nx} x {settings.ny} columns")
-    ids, index = zone_ids(zones)
-    if not ids.size:
-        raise ValueError("zonal totals: the zone map holds no column in any zone (no value > 0)")
-    if ids.size > MAX_ZONES:
-        raise ValueError(f"zonal totals: {ids.size} zones (at most {MAX_ZONES})")
-    for v in t.output_variables:
-        meta = state.var_meta.get(v)
-        if meta is None or meta.plane is None or meta.dtype is not None:
-            raise NotImplementedError(f"zonal totals: {v!r} is not a float64 (x, y) variable of the device arena")
+    ids, index = check_zones("zonal totals", t.zones, settings)
+    check_planes("zonal totals", t.output_variables, state)
     if t.capacity is None:
         t.capacity = default_capacity(ids.size, len(t.output_variables))
     check_request("zonal totals", (), len(t.output_variables), t.capacity, settings)   # (no cells to check: the capacity)
@@ -146,78 +149,36 @@ def initialize(state):
     t._ncells = np.bincount(local[local >= 0], minlength=ids.size).astype(np.int64)
     if not t._ncells.any():
         return   # (several ranks: no column of any zone in this rank's block)
-    ctx = state.backend_context
-    state.variables.flush_to_device()
-    ctx.zonal_configure(list(t.output_variables), local, int(ids.size), int(t.capacity))
-    t._on, t._read, t._steps, t._unwritten = True, 0, 0, 0
     vs = state.variables
+    vs.flush_to_device()
+    state.backend_context.zonal_configure(list(t.output_variables), local, int(ids.size), int(t.capacity))
+    t._begin()
     first = np.empty((1, ids.size, len(t.output_variables), 3))
     for j, v in enumerate(t.output_variables):
-        a = np.asarray(getattr(vs, v))[2:-2, 2:-2]
-        if a.ndim == 3:
-            a = a[:, :, 1]
-        first[0, :, j] = zone_totals(a, local, ids.size)
+        first[0, :, j] = zone_totals(interior_plane(vs, v), local, ids.size)
     t._hdr = [np.array([[int(vs.itt), int(vs.time), 0]], dtype=np.int64)]
     t._values = [first]
     t._path = claim_output_file(t, state, "zonal totals")
-    _write(state)
-
-
-def check_call(state, nsteps):
-    """Before a call that enqueues nsteps steps: more than the ring holds would overwrite rows nobody has read."""
-    t = state.zonal_totals
-    if t._on and int(nsteps) > int(t.capacity):
-        raise RuntimeError(f"{int(nsteps)} steps in one call but only {int(t.capacity)} rows of the zonal totals are resident on the device: "
-                           "call run_device() in shorter pieces, or raise state.zonal_totals.capacity")
-
-
-def drain(state, final=False):
-    """Read the rows the device recorded since the last drain."""
-    t = state.zonal_totals
-    if not t._on:
-        return
-    ctx = state.backend_context
-    total = int(ctx.zonal_count()[0])
-    n = total - t._read
-    if n > int(t.capacity):
-        raise RuntimeError(f"{n} rows of the zonal totals recorded since the last drain but only {int(t.capacity)} are resident on the device")
-    if n > 0:
-        hdr, values = ctx.zonal_read(t._read, n)
-        t._hdr.append(hdr)
-        t._values.append(values)
-        t._read = total
-        t._unwritten += values.nbytes + hdr.nbytes
-    t._steps = 0
-    if final or t._unwritten > WRITE_BYTES:
-        _write(state)
-
-
-def stepped(state):
-    """A host loop made one step call: drain when the calls since the last drain reach the capacity."""
-    t = state.zonal_totals
-    if not t._on:
-        return
-    t._steps += 1
-    if t._steps >= int(t.capacity):
-        drain(state)
+    t.write(state)
 
 
 def close(state):
-    """End of run(): the rest of the ring, and the file."""
-    drain(state, final=True)
+    state.zonal_totals.close(state)
 
 
-def _file_variables(hdr, values, names, ids, ncells, time_origin):
-    """The variables of a zonal totals file from headers (n, 3), values (n, Z, V, 3), the zone ids and the columns of every zone."""
+def _file_variables(hdr, values, names, ids, ncells, time_origin, days=None):
+    """The variables of a zonal totals file from headers (n, 3), values (n, Z, V, 3), the zone ids and the columns of every zone
+    (`days`: the rows' Time where the headers do not hold it)."""
     from .diagnostics import _UNITS
 
     ncells = np.asarray(ncells, dtype=np.int64)
     empty = ncells == 0
+    tv = time_variables(hdr[:, 0], hdr[:, 1] / float(DAY) if days is None else days, time_origin, dt=hdr[:, 2])
     variables = {
-        "Time": (("Time",), hdr[:, 1] / float(DAY), {"long_name": "Time", "units": "days", "time_origin": str(time_origin)}),
+        "Time": tv["Time"],
         "zone": (("zone",), np.asarray(ids, dtype=np.int64), {"long_name": "zone id of the zone map", "units": ""}),
-        "dt": (("Time",), hdr[:, 2].astype(np.float64), {"long_name": "length of the time step", "units": "s"}),
-        "itt": (("Time",), hdr[:, 0].astype(np.int64), {"long_name": "time step", "units": ""}),
+        "dt": tv["dt"],
+        "itt": tv["itt"],
         "ncells": (("zone",), ncells, {"long_name": "columns of the zone", "units": ""}),
     }
     for j, name in enumerate(names):
@@ -237,49 +198,16 @@ def _file_variables(hdr, values, names, ids, ncells, time_origin):
 
 
 def _write_file(path, variables, identifier, extra=None):
-    from . import nc4lite
-
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    attributes = {
-        "date_created": datetime.datetime.today().isoformat(), "roger_version": "roger_amd (hip backend)",
-        "comment": "First record (dt = 0) contains initial values. Every further record is one time step, Time at its end.",
-        "setup_identifier": str(identifier)}
-    attributes.update(extra or {})
-    nc4lite.write(path, {"Time": None, "zone": int(len(variables["zone"][1]))}, variables, attributes)
-
-
-def _write(state):
-    """The whole file from the rows held in memory, through roger_amd.nc4lite."""
-    t = state.zonal_totals
-    t._unwritten = 0
-    if not t._path:
-        return
-    hdr, values = np.concatenate(t._hdr), np.concatenate(t._values)
-    _write_file(t._path, _file_variables(hdr, values, t.output_variables, t._ids, t._ncells, state.settings.time_origin),
-                state.settings.identifier)
+    totals._write_file(path, variables, identifier, extra, {"Time": None, "zone": int(len(variables["zone"][1]))})
 
 
 def combine(paths, out):
     """The ranks' files `paths` (in rank order) as one: per zone the sums added in rank order, the minimum of the minima, the maximum of
     the maxima (a rank without a column of the zone takes no part), ncells added, means formed again.  Files whose zone list, itt or Time
     differ are refused."""
-    from . import nc4lite
-
-    paths = [str(p) for p in paths]
-    if not paths:
-        raise ValueError("zonal_totals.combine: no files")
-    recs = [nc4lite.read(p) for p in paths]
+    paths, recs, names = read_rank_files("zonal_totals", paths, ("zone", "itt", "Time", "dt"))
     first = recs[0]["variables"]
-    names = [k[:-4] for k in first if k.endswith("_sum")]
-    for p, rec in zip(paths[1:], recs[1:]):
-        v = rec["variables"]
-        if [k[:-4] for k in v if k.endswith("_sum")] != names:
-            raise ValueError(f"zonal_totals.combine: {p} holds other variables than {paths[0]}")
-        for key in ("zone", "itt", "Time", "dt"):
-            if not np.array_equal(np.asarray(v[key][1]), np.asarray(first[key][1])):
-                raise ValueError(f"zonal_totals.combine: {key} of {p} differs from {paths[0]}")
-    hdr = np.stack([np.asarray(first["itt"][1], dtype=np.int64), np.zeros(len(first["itt"][1]), dtype=np.int64),
-                    np.asarray(first["dt"][1]).astype(np.int64)], axis=1)
+    hdr = totals.rank_headers(first)
     ids = np.asarray(first["zone"][1], dtype=np.int64)
     cells = [np.asarray(rec["variables"]["ncells"][1], dtype=np.int64) for rec in recs]
     values = np.empty((len(hdr), ids.size, len(names), 3))
@@ -291,6 +219,5 @@ def combine(paths, out):
                 a[:, c == 0] = identity
                 total = op(total, a)
             values[:, :, j, k] = total
-    variables = _file_variables(hdr, values, names, ids, np.sum(cells, axis=0), first["Time"][2].get("time_origin", ""))
-    variables["Time"] = (("Time",), np.asarray(first["Time"][1], dtype=np.float64), variables["Time"][2])   # (the files' own days)
-    _write_file(str(out), variables, recs[0]["attributes"].get("setup_identifier", ""), {"combined_from": ", ".join(os.path.basename(p) for p in paths)})
+    variables = _file_variables(hdr, values, names, ids, np.sum(cells, axis=0), first["Time"][2].get("time_origin", ""), days=first["Time"][1])
+    _write_file(str(out), variables, recs[0]["attributes"].get("setup_identifier", ""), combined_from(paths))
