@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 16  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read */
+#define RH_ABI_VERSION 17  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -571,6 +571,25 @@ int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM
                        int64_t interval_seconds, int64_t t_first, const unsigned char *mask, int64_t capacity);
 int rh_bands_count(rh_ctx *ctx, int64_t *rows_total);
 int rh_bands_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, double *values, size_t value_bytes);
+/* ... per zone: the same bands for every zone of a zone map in one run.  THE PROMISE: block z of a row is, bit for bit, the row
+ * rh_bands_configure records with mask = (zone == z) -- np.sort(s)[clamp(ceil(p m) - 1, 0, m - 1)] over the zone's columns, with the
+ * + 0.0 rule and the NaN rule above.  k_bands runs unchanged; ONE launch with a workgroup per (zone, item) selects in LDS in place of
+ * the six k_bands_select, and a one-thread launch writes the row's header (roger_amd/csrc/rh_bands.h).  One workgroup walks a zone,
+ * however large: a map with one dominant zone belongs to rh_bands_configure's mask.
+ *   zone:     an index 0 ... n_zones - 1 per column, negative: the column takes no part (the caller folds a mask into it)
+ *   n_zones:  1 ... 1024; it may name zones that no column has (those of other ranks): their blocks hold m = 0 and NaN
+ * Everything else is rh_bands_configure's, its refusals included; further RH_ERR_ARG: n_zones outside 1 ... 1024, a zone index
+ * >= n_zones, no participating column, a null pointer.  A zonal configuration replaces a plain one and the other way round;
+ * n_items == 0 releases the buffers.  rh_bands_count serves both.
+ *   rh_bands_zonal_read  rows [first_row, first_row + n_rows): hdr (n_rows, 2) int64 {k, t1}, counts (n_rows, n_items, n_zones, 2)
+ *                        int64 {m, n_nan}, values (n_rows, n_items, n_zones, n_probs) float64
+ * rh_bands_read on a zonal configuration and rh_bands_zonal_read on a plain one return RH_ERR_STATE and name the other call. */
+int rh_bands_configure_zonal(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 LAST */, int n_items, const double *probs, int n_probs,
+                             int64_t interval_seconds, int64_t t_first, const int32_t *zone /* [n]: index 0 .. n_zones-1, < 0: takes no part */,
+                             int n_zones, int64_t capacity);
+int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr /* (rows, 2) {k, t1} */,
+                        int64_t *counts /* (rows, n_items, n_zones, 2) {m, n_nan} */, size_t count_bytes,
+                        double *values /* (rows, n_items, n_zones, n_probs) */, size_t value_bytes);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 16  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 17  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -176,6 +176,8 @@ def load():
     lib.rh_bands_configure.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i64]
     lib.rh_bands_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.rh_bands_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
+    lib.rh_bands_configure_zonal.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i32, i64]
+    lib.rh_bands_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t, vp, C.c_size_t]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -639,7 +641,7 @@ DECLARED_SYMBOLS = (
     "rh_scores_configure", "rh_scores_read",
     "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
     "rh_durations_configure", "rh_durations_read",
-    "rh_bands_configure", "rh_bands_count", "rh_bands_read",
+    "rh_bands_configure", "rh_bands_count", "rh_bands_read", "rh_bands_configure_zonal", "rh_bands_zonal_read",
 )
 
 
@@ -1104,11 +1106,14 @@ class Context:
         return [counts[offs[j]:offs[j + 1]] for j in range(ni)], values, spells
 
     # -- ensemble bands (rh_bands_*) -------------------------------------------------------------------
-    def bands_configure(self, names, kinds=(), probs=(0.05, 0.5, 0.95), interval=86400, t_first=0, mask=None, capacity=4096):
+    def bands_configure(self, names, kinds=(), probs=(0.05, 0.5, 0.95), interval=86400, t_first=0, mask=None, capacity=4096, zones=None, n_zones=None):
         """After every step aggregate `names` (at most 8 float64 planes; kinds: 0 sum over the interval, 1 value at its end) to the
         interval and, at every counted interval's end, record the exact quantiles ACROSS the columns of `mask` (a byte per interior column
         of this context's block, C order; None: every column) at `probs` (at most 8, within [0, 1]) as one row of a ring of `capacity`
-        rows on the device.  The first counted interval starts at t_first.  No names: release the buffers and stop."""
+        rows on the device.  The first counted interval starts at t_first.  No names: release the buffers and stop.
+        `zones`: an index 0 ... n_zones - 1 per interior column (negative: the column takes no part; a `mask` is folded into it), and the
+        row holds the bands of every zone -- block z bit for bit what mask = (zones == z) gives (rh_bands_configure_zonal; read with
+        bands_zonal_read).  n_zones (default: the largest index + 1) may name zones that no column of this block has."""
         names = list(names)
         ni = len(names)
         if len(kinds) != ni:
@@ -1121,12 +1126,22 @@ class Context:
             mk = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
             if mk.size != self.n:
                 raise ValueError(f"bands_configure: the mask has {mk.size} values, the context {self.n} columns")
+        if names and zones is not None:
+            zn = np.asarray(zones).reshape(-1)
+            if zn.size != self.n:
+                raise ValueError(f"bands_configure: the zone map has {zn.size} values, the context {self.n} columns")
+            zn = np.ascontiguousarray(np.clip(zn, -1, 2 ** 31 - 1) if mk is None else np.where(mk != 0, np.clip(zn, -1, 2 ** 31 - 1), -1), dtype=np.int32)
+            nz = int(zn.max()) + 1 if n_zones is None else int(n_zones)
+            self._check(self._lib.rh_bands_configure_zonal(self._h, ids, kd, ni, pr.ctypes.data_as(C.c_void_p), len(list(probs)), int(interval),
+                                                           int(t_first), zn.ctypes.data_as(C.c_void_p), nz, int(capacity)), "rh_bands_configure_zonal")
+            self._bands_shape = (ni, nz, len(list(probs)))   # (a refused configuration leaves the previous one)
+            return
         self._check(self._lib.rh_bands_configure(self._h, ids, kd, ni, pr.ctypes.data_as(C.c_void_p), len(list(probs)), int(interval), int(t_first),
                                                  None if mk is None else mk.ctypes.data_as(C.c_void_p), int(capacity)), "rh_bands_configure")
         self._bands_shape = (ni, len(list(probs)) if ni else 0)   # (a refused configuration leaves the previous one)
 
     def bands_count(self):
-        """Rows recorded since bands_configure."""
+        """Rows recorded since bands_configure (with or without zones)."""
         n = C.c_int64()
         self._check(self._lib.rh_bands_count(self._h, C.byref(n)), "rh_bands_count")
         return n.value
@@ -1135,7 +1150,21 @@ class Context:
         """Rows [first, first + n) of the ring: (hdr int64 (n, 2 + 2 * items): k, t1, then per item m and n_nan; values float64
         (n, items, probs))."""
         shape = getattr(self, "_bands_shape", (0, 0))
+        shape = shape if len(shape) == 2 else (shape[0], shape[2])   # (configured per zone: the call refuses)
         return self._ring_read("rh_bands_read", first, n, 2 + 2 * shape[0], shape)
+
+    def bands_zonal_read(self, first, n):
+        """Rows [first, first + n) of the ring of a configuration with zones: (hdr int64 (n, 2): k, t1; counts int64 (n, items, zones, 2):
+        m, n_nan; values float64 (n, items, zones, probs))."""
+        n = int(n)
+        shape = getattr(self, "_bands_shape", (0, 0))
+        ni, nz, npr = shape if len(shape) == 3 else (shape[0], 0, shape[1])   # (configured without zones: the call refuses)
+        hdr = np.empty((n, 2), dtype=np.int64)
+        counts = np.empty((n, ni, nz, 2), dtype=np.int64)
+        values = np.empty((n, ni, nz, npr), dtype=np.float64)
+        self._check(self._lib.rh_bands_zonal_read(self._h, int(first), n, hdr.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), counts.nbytes,
+                                                  values.ctypes.data_as(C.c_void_p), values.nbytes), "rh_bands_zonal_read")
+        return hdr, counts, values
 
     def pure_output_planes(self):
         """Names of the planes the fused step of this context's model only produces (not stored by the steps of an rh_run_steps call

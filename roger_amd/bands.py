@@ -11,7 +11,8 @@ A setup script fills `state.bands` in `set_diagnostics`:
     state.bands.frequency     = 24 * 60 * 60                          # or 3600, 600
     state.bands.start         = 0                                     # seconds, a multiple of frequency
     state.bands.mask          = None                                  # or (nx, ny) over the GLOBAL interior, 0: column takes no part
-    state.bands.capacity      = 4096                                  # rows resident on the device
+    state.bands.zones         = None                                  # or int (nx, ny) over the GLOBAL interior, <= 0: outside every zone
+    state.bands.capacity      = 4096                                  # rows resident on the device; with zones at most what 64 MiB hold
     state.bands.base_output_path = ...                                # as for the diagnostics
 
 and gets `<identifier>.bands.nc`: dimensions Time (unlimited) and probability; `Time` in days at the END of each interval, `interval`
@@ -27,7 +28,20 @@ r = clamp(ceil(p * m) - 1, 0, m - 1) -- one double multiplication, one ceil -- a
 the "inverted CDF" quantile, bit for bit.  p = 0 is the minimum and p = 1 the maximum.  With m == 0 the row holds NaN and the file
 `_FillValue`.  An hourly or ten-minute interval under a longer step is never started: it has no row.
 
-Several ranks.  Order statistics of blocks do not merge, so there is no `combine`: a rank computes the bands of ITS OWN block and writes
+Zones.  With `zones` (the convention of `state.zonal_totals.zones`: the zone list is the distinct positive values in ascending order, at
+most 1024) one run records the band of EVERY zone: a column takes part iff its zone is > 0 and, where a mask is given as well, mask != 0;
+a zone that the mask empties stays in the list.  The file gains the dimension zone: `zone(zone)` the ids as given, `ncells(zone)` this
+rank's participating columns of each, and per variable `v(Time, zone, probability)`, `v_n(Time, zone)`, `v_nan(Time, zone)`, with
+`_FillValue` where a zone had no column with a number; `read()` returns the same arrays with the zone axis.  THE PROMISE: block z of a
+row is, bit for bit, the row `state.bands` records without zones and with mask = (zones == z) & mask -- np.sort(s)[clamp(ceil(p m) - 1,
+0, m - 1)] with the + 0.0 rule and the NaN rule below (roger_amd/csrc/rh_bands.h).  Without `zones` the file and `read()` are what they
+were.  A row is V Z P 8 + V Z 16 + 16 bytes (up to 0.6 MiB), so with zones `initialize` lowers `capacity` to the rows that 64 MiB hold
+(never below 1), from the GLOBAL zone list: the same number on every rank.  On the device ONE workgroup selects a zone's quantiles in its
+own LDS, so the largest zone sets the time of a counted step: a map with one dominant zone belongs to `mask`.
+
+Several ranks.  With zones a rank computes the bands of its own block over the GLOBAL zone list: a zone without a column in the block has
+v_n = 0 and fill values, and a rank whose block holds no participating column configures nothing and writes no file.  Order statistics
+of blocks do not merge, so there is no `combine`: a rank computes the bands of ITS OWN block and writes
 one file of its own, named as the diagnostics name theirs, with the global attribute columns = "this rank's block".  A parameter study
 is a one-rank run.
 
@@ -39,6 +53,7 @@ import numpy as np
 from . import runtime_settings as rs
 from .observers import DAY, RingSeries, check_mask, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file
 from .scores import FILL, default_kind
+from .zonal_totals import RING_BYTES, check_zones
 
 MAX_VARIABLES = 8                 # roger_amd/csrc/rh_bands.h: RH_BANDS_MAX_ITEMS
 MAX_PROBABILITIES = 8             # ... RH_BANDS_MAX_PROBS
@@ -47,8 +62,9 @@ KINDS = {"sum": 0, "last": 1}
 
 
 class Bands(RingSeries):
-    """`state.bands`: what the script sets (variables, aggregation, probabilities, frequency, start, mask, capacity, base_output_path)
-    and the rows drained so far: headers (n, 2 + 2 V) int64 and values (n, V, P) float64."""
+    """`state.bands`: what the script sets (variables, aggregation, probabilities, frequency, start, mask, zones, capacity,
+    base_output_path) and the rows drained so far: headers (n, 2 + 2 V) int64 and values (n, V, P) float64 -- with zones headers (n, 2),
+    counts (n, V, Z, 2) int64 and values (n, V, Z, P)."""
 
     label = attribute = "bands"
 
@@ -60,6 +76,7 @@ class Bands(RingSeries):
         self.frequency = DAY
         self.start = 0
         self.mask = None
+        self.zones = None
         self.base_output_path = None
         self.output_path = "{identifier}.bands.nc"
         self._state = None
@@ -68,6 +85,10 @@ class Bands(RingSeries):
         self._probs = ()
         self._local = None       # the mask of this rank's block, or None
         self._t_first = 0        # the start of the first counted interval on the device
+        self._ids = None         # zones: the ids as the script gave them, ascending (the GLOBAL list); None without zones
+        self._index = None       # ... the global map as indices into them (-1: outside, or masked out)
+        self._ncells = None      # ... this rank's participating columns of every zone
+        self._counts = []        # ... drained counts
 
     @property
     def active(self):
@@ -79,6 +100,14 @@ class Bands(RingSeries):
         if not self._on:
             return None
         self.drain(self._state)
+        if self._ids is not None:
+            hdr, counts, values = self._all_zonal_rows()
+            out = {"interval": hdr[:, 0].copy(), "time": hdr[:, 1].copy()}
+            for j, v in enumerate(self._names):
+                out[v] = values[:, j].copy()              # (n, Z, P)
+                out[f"{v}_n"] = counts[:, j, :, 0].copy()   # (n, Z)
+                out[f"{v}_nan"] = counts[:, j, :, 1].copy()
+            return out
         hdr, values = self._all_rows()
         out = {"interval": hdr[:, 0].copy(), "time": hdr[:, 1].copy()}
         for j, v in enumerate(self._names):
@@ -91,7 +120,14 @@ class Bands(RingSeries):
         return ctx.bands_count()
 
     def _rows(self, ctx, first, n):
-        return ctx.bands_read(first, n)
+        return ctx.bands_read(first, n) if self._ids is None else ctx.bands_zonal_read(first, n)
+
+    def _keep(self, state, hdr, *rest):
+        if self._ids is None:
+            return super()._keep(state, hdr, *rest)
+        counts, values = rest
+        self._counts.append(counts)
+        return super()._keep(state, hdr, values) + counts.nbytes
 
     def _all_rows(self):
         nv, npr = len(self._names), len(self._probs)
@@ -99,9 +135,17 @@ class Bands(RingSeries):
             return np.empty((0, 2 + 2 * nv), dtype=np.int64), np.empty((0, nv, npr))
         return np.concatenate(self._hdr), np.concatenate(self._values)
 
+    def _all_zonal_rows(self):
+        nv, nz, npr = len(self._names), len(self._ids), len(self._probs)
+        if not self._hdr:
+            return np.empty((0, 2), dtype=np.int64), np.empty((0, nv, nz, 2), dtype=np.int64), np.empty((0, nv, nz, npr))
+        return np.concatenate(self._hdr), np.concatenate(self._counts), np.concatenate(self._values)
+
     def _write(self, state):
         from .diagnostics import _UNITS
 
+        if self._ids is not None:
+            return self._write_zonal(state)
         settings = state.settings
         hdr, values = self._all_rows()
         variables = {
@@ -119,6 +163,37 @@ class Bands(RingSeries):
         write_file(self._path, {"Time": None, "probability": len(self._probs)}, variables, global_attributes(
             settings.identifier, "Exact quantiles across the columns of interval values, one record per counted interval.",
             {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}, lead={"columns": "this rank's block"}))
+
+
+    def _write_zonal(self, state):
+        from .diagnostics import _UNITS
+
+        settings = state.settings
+        hdr, counts, values = self._all_zonal_rows()
+        variables = {
+            "Time": (("Time",), hdr[:, 1] / float(DAY), {"long_name": "Time at the end of the interval", "units": "days", "time_origin": str(settings.time_origin)}),
+            "interval": (("Time",), hdr[:, 0].astype(np.int64), {"long_name": "number of the interval, from the first counted one", "units": ""}),
+            "probability": (("probability",), np.asarray(self._probs, dtype=np.float64), {"long_name": "non-exceedance probability", "units": ""}),
+            "zone": (("zone",), np.asarray(self._ids, dtype=np.int64), {"long_name": "zone id of the zone map", "units": ""}),
+            "ncells": (("zone",), np.asarray(self._ncells, dtype=np.int64), {"long_name": "columns of the zone that take part", "units": ""}),
+        }
+        for j, v in enumerate(self._names):
+            kind = "sum over the interval" if self._kinds[j] == 0 else "value at the end of the interval"
+            q = np.ascontiguousarray(values[:, j])
+            variables[v] = (("Time", "zone", "probability"), np.where(np.isnan(q), FILL, q),
+                            {"_FillValue": np.float64(FILL), "long_name": f"{v} ({kind}): quantiles across the columns of the zone, sorted[ceil(p n) - 1]",
+                             "units": _UNITS.get(v, "")})
+            variables[f"{v}_n"] = (("Time", "zone"), np.ascontiguousarray(counts[:, j, :, 0]), {"long_name": f"{v}: columns of the zone that took part", "units": ""})
+            variables[f"{v}_nan"] = (("Time", "zone"), np.ascontiguousarray(counts[:, j, :, 1]), {"long_name": f"{v}: participating columns of the zone with a NaN", "units": ""})
+        write_file(self._path, {"Time": None, "zone": len(self._ids), "probability": len(self._probs)}, variables, global_attributes(
+            settings.identifier, "Exact quantiles across the columns of every zone of interval values, one record per counted interval.",
+            {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}, lead={"columns": "this rank's block"}))
+
+
+def zonal_capacity(capacity, n_variables, n_zones, n_probabilities):
+    """The rows of V Z P 8 + V Z 16 + 16 bytes that RING_BYTES (64 MiB) hold, at most `capacity` and at least one."""
+    v, z, p = int(n_variables), int(n_zones), int(n_probabilities)
+    return int(max(1, min(int(capacity), RING_BYTES // (v * z * p * 8 + v * z * 16 + 16))))
 
 
 def initialize(state):
@@ -153,7 +228,13 @@ def initialize(state):
         if b.aggregation[v] not in KINDS:
             raise ValueError(f'bands: aggregation of {v!r} is {b.aggregation[v]!r} ("sum" or "last")')
     check_planes("bands", names, state)
-    check_mask("bands", b.mask, settings)
+    mask = check_mask("bands", b.mask, settings)
+    b._ids = b._index = None
+    if b.zones is not None:
+        ids, index = check_zones("bands", b.zones, settings)
+        b._ids = ids.astype(np.int64)
+        b._index = index if mask is None else np.where(mask, index, -1).astype(np.int32)   # (a zone the mask empties stays in the list)
+        b.capacity = zonal_capacity(b.capacity, len(names), ids.size, len(probs))
     b._names = names
     b._kinds = [KINDS[b.aggregation.get(v, default_kind(v))] for v in names]
     b._probs = probs
@@ -171,14 +252,23 @@ def start(state):
     f, now = int(b.frequency), int(vs.time)
     b._t_first = int(b.start) if now <= int(b.start) else -(-now // f) * f
     b._local = None
-    if b.mask is not None:
-        b._local = local_mask((np.asarray(b.mask) != 0).astype(np.uint8), settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
-        if not b._local.any():
-            return   # (several ranks: no masked-in column in this rank's block)
-    vs.flush_to_device()
-    state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, b._local, int(b.capacity))
+    if b._ids is not None:
+        b._local = local_mask(b._index, settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
+        b._ncells = np.bincount(b._local[b._local >= 0], minlength=b._ids.size).astype(np.int64)
+        if not b._ncells.any():
+            return   # (several ranks: no participating column in this rank's block)
+        vs.flush_to_device()
+        state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, None, int(b.capacity), zones=b._local,
+                                              n_zones=int(b._ids.size))
+    else:
+        if b.mask is not None:
+            b._local = local_mask((np.asarray(b.mask) != 0).astype(np.uint8), settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
+            if not b._local.any():
+                return   # (several ranks: no masked-in column in this rank's block)
+        vs.flush_to_device()
+        state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, b._local, int(b.capacity))
     b._begin()
-    b._hdr, b._values = [], []
+    b._hdr, b._values, b._counts = [], [], []
     b._path = claim_output_file(b, state, "bands")
 
 

@@ -58,6 +58,9 @@
 //              the header and advances bands_rows last.
 // Cost.  A step that is not counted: as k_durations' (24 B per SUM item and column), and six launches that end after the scalar loads.
 // A counted step: k_bands' 8 B store per item and column, and six passes x 8 B per item and column of key reads.
+//
+// Per zone (rh_bands_configure_zonal): the same rule for every zone of a zone map in one run -- block z of a row is, bit for bit, the row
+// above under mask = (zone == z) -- selected by one workgroup per (zone, item) in its own LDS: k_bands_zonal at the end of this file.
 #pragma once
 
 #define RH_BANDS_MAX_ITEMS 8
@@ -67,6 +70,7 @@
 #define RH_BANDS_NBINS 2048   // 11-bit digits
 #define RH_BANDS_PASSES 6
 #define RH_BANDS_MAX_GRID 256   // workgroups of k_bands_select
+#define RH_BANDS_MAX_ZONES 1024   // rh_bands_configure_zonal: a workgroup of k_bands_zonal per zone and item
 #define RH_BANDS_KEY_MASKED (~0ull)
 #define RH_BANDS_KEY_NAN (~0ull - 1ull)
 
@@ -124,6 +128,34 @@ RH_DEV unsigned bands_wave_scan(unsigned x) {   // inclusive, over the 64 lanes
         if (lane >= off) x += y;
     }
     return x;
+}
+// The pick of one wavefront: bin k * 64 + lane of a histogram in v[k]; the digit at which the cumulative count passes the rank r, and the
+// count below it.  (No bin passes it only where the histogram is empty: digit 0, below 0.)
+template <int NC>
+RH_DEV void bands_pick(const unsigned (&v)[NC], long long r, int &digit, long long &below) {
+    long long base = 0;
+    bool found = false;
+    digit = 0;
+    below = 0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const unsigned incl = bands_wave_scan(v[k]);
+        const long long chunk = (long long)__shfl(incl, 63);
+        if (!found && base + chunk > r) {
+            const unsigned long long hit = __ballot(base + (long long)incl > r);
+            const int l = __ffsll((long long)hit) - 1;
+            digit = k * 64 + l;
+            below = base + (long long)__shfl(incl - v[k], l);
+            found = true;
+        }
+        base += chunk;
+    }
+}
+// the rank of probability p among m values: one double multiplication, one ceil
+RH_DEV long long bands_rank_of(double p, long long m) {
+    long long r = (long long)ceil(p * (double)m) - 1;
+    r = r > m - 1 ? m - 1 : r;
+    return r < 0 ? 0 : r;
 }
 template <int P>
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D, int after_fused) {
@@ -204,29 +236,14 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
             for (int k = 0; k < NC; ++k) tot += v[k];
             for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
             m = (long long)tot;
-            r = (long long)ceil(D->bands_probs[q] * (double)m) - 1;
-            r = r > m - 1 ? m - 1 : r;
-            r = r < 0 ? 0 : r;
+            r = bands_rank_of(D->bands_probs[q], m);
         } else {
             m = D->bands_m[j];
             r = D->bands_rank[at];
         }
-        long long base = 0, below = 0;
-        int digit = 0;
-        bool found = false;
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            const unsigned incl = bands_wave_scan(v[k]);
-            const long long chunk = (long long)__shfl(incl, 63);
-            if (!found && base + chunk > r) {
-                const unsigned long long hit = __ballot(base + (long long)incl > r);
-                const int l = __ffsll((long long)hit) - 1;
-                digit = k * 64 + l;
-                below = base + (long long)__shfl(incl - v[k], l);
-                found = true;
-            }
-            base += chunk;
-        }
+        long long below;
+        int digit;
+        bands_pick<NC>(v, r, digit, below);
         const unsigned long long prefix = (P == 0 ? 0ull : D->bands_prefix[at] << PS::width) | (unsigned long long)digit;
         if (lane == 0) {
             D->bands_prefix[at] = prefix;
@@ -261,4 +278,138 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
             D->bands_rows = row + 1;
         }
     }
+}
+
+// ---- bands per zone (rh_bands_configure_zonal) ----
+// The promise.  Block z of a row is, bit for bit, the row the plain configuration records with mask = (zone == z): np.sort(s)[clamp(ceil(p
+// m) - 1, 0, m - 1)] over the zone's columns, with the + 0.0 rule and the NaN rule above.  k_bands runs unchanged (its byte mask is zone
+// >= 0, written at the configuration), so the clock, the SUM accumulation and the key planes are the plain path's own.
+// Column lists.  A stable counting sort on the host: bands_zone_off [n_zones + 1] and bands_zone_cols (int32 column indices, ascending
+// within a zone), uploaded once.
+// k_bands_zonal, ONE launch behind k_bands in place of the six k_bands_select: grid (n_zones, n_items).  A workgroup walks its zone's list
+// (eight columns in flight per thread), gathers keys[j * n + col] and runs all RH_BANDS_PASSES digit passes itself: one LDS histogram per
+// probability at the widths of BandsPass<P>; pass 0 is shared by the probabilities and yields m and n_nan; a wavefront per probability
+// picks the digit (bands_pick); prefixes and ranks stay in LDS between the passes.  The later passes read the keys again: L2 serves them.
+// LDS atomics only -- no device-scope atomic, no completion counter.  It writes its (item, zone) block of row bands_rows % bands_cap:
+// counts {m, n_nan} and the values, NaN with m == 0.  k_bands_zonal_row<<<1, 1>>> behind it in the same stream writes {k, t1} and advances
+// bands_rows: stream order stands where the plain path has its last-workgroup pattern.  Both end after the scalar loads on a step that
+// is not counted.
+// Load balance.  ONE workgroup walks a zone, however large: the largest zone sets the time of a counted step.  A map with one dominant
+// zone belongs to the plain configuration's mask, whose selection strides over the whole device.
+// Cost of a counted step: 8 B per item and participating column per pass gathered (six passes), 4 B per column of bands_zone_cols per pass,
+// 2 launches.
+template <int P>
+RH_DEV void bands_zonal_pass(const unsigned long long *keys, const int *cols, long long beg, long long end, int np, const double *probs, unsigned *hist,
+                             unsigned long long *s_prefix, long long *s_rank, long long *s_count, unsigned *s_nan) {
+    using PS = BandsPass<P>;
+    constexpr int NB = PS::nb, NC = NB / 64, U = 8;
+    const int nh = P == 0 ? 1 : np;
+    for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) hist[b] = 0;
+    if (P == 0 && threadIdx.x == 0) *s_nan = 0;
+    __syncthreads();
+    unsigned long long pre[RH_BANDS_MAX_PROBS];
+#pragma unroll
+    for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q) pre[q] = (P > 0 && q < np) ? s_prefix[q] : 0ull;
+    for (long long base = beg; base < end; base += (long long)RH_BLOCK * U) {
+        int col[U];
+        unsigned long long key[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long at = base + (long long)u * RH_BLOCK + threadIdx.x;
+            col[u] = at < end ? cols[at] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) key[u] = col[u] >= 0 ? keys[col[u]] : RH_BANDS_KEY_MASKED;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (key[u] >= RH_BANDS_KEY_NAN) {
+                if (P == 0 && key[u] == RH_BANDS_KEY_NAN) atomicAdd(s_nan, 1u);
+                continue;
+            }
+            const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
+            if (P == 0) {
+                atomicAdd(&hist[d], 1u);
+            } else {
+#pragma unroll
+                for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q)
+                    if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int q = threadIdx.x >> 6; q < np; q += RH_BLOCK / 64) {   // (uniform over the wavefront)
+        const unsigned *h = hist + (P == 0 ? 0 : q) * NB;
+        unsigned v[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k] = h[k * 64 + lane];
+        long long r;
+        if (P == 0) {
+            unsigned tot = 0;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) tot += v[k];
+            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
+            r = bands_rank_of(probs[q], (long long)tot);
+            if (q == 0 && lane == 0) {
+                s_count[0] = (long long)tot;
+                s_count[1] = (long long)*s_nan;
+            }
+        } else {
+            r = s_rank[q];
+        }
+        long long below;
+        int digit;
+        bands_pick<NC>(v, r, digit, below);
+        if (lane == 0) {
+            s_prefix[q] = (P == 0 ? 0ull : s_prefix[q] << PS::width) | (unsigned long long)digit;
+            s_rank[q] = r - below;
+        }
+    }
+    __syncthreads();   // (the next pass clears the histograms and reads the prefixes)
+}
+__global__ __launch_bounds__(RH_BLOCK) void k_bands_zonal(DevState *D, long long n, int after_fused) {
+    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_BANDS_NBINS];
+    __shared__ unsigned long long s_prefix[RH_BANDS_MAX_PROBS];
+    __shared__ long long s_rank[RH_BANDS_MAX_PROBS], s_count[2];
+    __shared__ unsigned s_nan;
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;   // (uniform over the grid)
+    const int z = blockIdx.x, j = blockIdx.y, nz = gridDim.x, ni = gridDim.y, np = D->bands_nprobs;
+    const long long beg = D->bands_zone_off[z], end = D->bands_zone_off[z + 1];
+    const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
+    const int *cols = D->bands_zone_cols;
+    const double *probs = D->bands_probs;
+    const size_t block = ((size_t)(D->bands_rows % D->bands_cap) * ni + j) * nz + z;
+    double *out = D->bands + block * np;
+    long long *counts = D->bands_counts + block * 2;
+    bands_zonal_pass<0>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
+    const long long m = s_count[0];
+    if (threadIdx.x == 0) {
+        counts[0] = m;
+        counts[1] = s_count[1];
+    }
+    if (m == 0) {   // (uniform over the workgroup)
+        if ((int)threadIdx.x < np) out[threadIdx.x] = __builtin_nan("");
+        return;
+    }
+    bands_zonal_pass<1>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
+    bands_zonal_pass<2>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
+    bands_zonal_pass<3>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
+    bands_zonal_pass<4>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
+    bands_zonal_pass<5>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
+    if ((int)threadIdx.x < np) {   // after the last pass the prefix IS the key
+        const unsigned long long prefix = s_prefix[threadIdx.x], u = (prefix >> 63) ? prefix ^ (1ull << 63) : ~prefix;
+        out[threadIdx.x] = __longlong_as_double((long long)u);
+    }
+}
+__global__ void k_bands_zonal_row(DevState *D, int after_fused) {
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;
+    const long long row = D->bands_rows;
+    long long *hd = D->bands_hdr + 2 * (row % D->bands_cap);
+    hd[0] = c.k;
+    hd[1] = c.t1;
+    D->bands_rows = row + 1;
 }

@@ -166,6 +166,11 @@ struct rh_ctx {
     DevBuf<unsigned char> bands_mask_buf;
     int bands_nitems = 0, bands_nprobs = 0;   // 0: not configured, no k_bands* launch
     int bands_planes[RH_BANDS_MAX_ITEMS] = {};
+    // ... per zone (rh_bands_configure_zonal): the rows' counts (item, zone, 2 int64 a row; the ring's headers are 2 int64 a row then), and
+    // zone_off[n_zones + 1] with the zones' column lists behind it in one allocation
+    DevBuf<long long> bands_counts_buf;
+    DevBuf<int> bands_zone_buf;
+    int bands_nzones = 0;            // 0: the plain configuration (k_bands_select); else k_bands_zonal on (bands_nzones, bands_nitems)
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

@@ -205,6 +205,12 @@ struct DevState {
     double bands_probs[8];                 // RH_BANDS_MAX_PROBS
     unsigned long long bands_prefix[64];
     long long bands_rank[64], bands_m[8], bands_nan[8];
+    // ... per zone (rh_bands_configure_zonal; k_bands_zonal, k_bands_zonal_row): bands is (row, item, zone, probability), bands_hdr (row,
+    // 2) {k, t1} and bands_counts (row, item, zone, 2) int64 {m, n_nan}; bands_mask is zone >= 0.  bands_zone_off [zones + 1] and
+    // bands_zone_cols: the columns of every zone, ascending within a zone.  Null without zones: the histograms and the members from
+    // bands_done on are the plain selection's alone.
+    long long *bands_counts;
+    const int *bands_zone_off, *bands_zone_cols;
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

@@ -49,7 +49,8 @@ static int observers_changed(rh_ctx *ctx) {
 // workgroup per RH_BLOCK columns and one per zone (rh_zonal.h) -- then the scores' moments over all columns, on the accumulators' grid
 // (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h) -- then the duration curves, on the same grid
 // (rh_durations.h) -- then the ensemble bands: the keys on the same grid, and the six passes of the selection on at most
-// RH_BANDS_MAX_GRID workgroups that stride over the tiles (rh_bands.h).  after_fused: rh_control.h, k_diag.
+// RH_BANDS_MAX_GRID workgroups that stride over the tiles -- per zone instead ONE launch with a workgroup per (zone, item) and a
+// one-thread launch for the row's header (rh_bands.h).  after_fused: rh_control.h, k_diag.
 static bool has_observers(const rh_ctx *ctx) {
     return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems ||
            ctx->durations_nitems || ctx->bands_nitems;
@@ -70,14 +71,19 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     if (ctx->events_nitems) hipLaunchKernelGGL(k_events, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->durations_nitems) hipLaunchKernelGGL(k_durations, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->bands_nitems) {
-        const dim3 sel(std::min<unsigned>(grid_for(ctx->n), RH_BANDS_MAX_GRID));
         hipLaunchKernelGGL(k_bands, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-        hipLaunchKernelGGL(k_bands_select<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-        hipLaunchKernelGGL(k_bands_select<1>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-        hipLaunchKernelGGL(k_bands_select<2>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-        hipLaunchKernelGGL(k_bands_select<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-        hipLaunchKernelGGL(k_bands_select<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-        hipLaunchKernelGGL(k_bands_select<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        if (ctx->bands_nzones) {   // per zone: one launch for the selection, one thread for the row's header
+            hipLaunchKernelGGL(k_bands_zonal, dim3(ctx->bands_nzones, ctx->bands_nitems), block, 0, ctx->stream, ctx->dev, (long long)ctx->n, after_fused);
+            hipLaunchKernelGGL(k_bands_zonal_row, dim3(1), dim3(1), 0, ctx->stream, ctx->dev, after_fused);
+        } else {
+            const dim3 sel(std::min<unsigned>(grid_for(ctx->n), RH_BANDS_MAX_GRID));
+            hipLaunchKernelGGL(k_bands_select<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select<1>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select<2>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        }
     }
     CHECK_LAUNCH(ctx);
     return RH_OK;
@@ -831,57 +837,98 @@ int rh_durations_read(rh_ctx *ctx, uint32_t *counts, size_t count_bytes, double 
 }
 
 // ---- ensemble bands (include/roger_hip.h; the kernels, the rule and the selection: rh_bands.h) ----
+// What a zonal configuration adds on the host: the byte mask zone >= 0 for k_bands, and zone_off[n_zones + 1] with the zones' column lists
+// behind it (a stable counting sort: ascending within a zone).
+struct BandsZones {
+    int n_zones = 0;
+    std::vector<unsigned char> mask;
+    std::vector<int> index;
+};
 // the buffers: the ring, the accumulators at +0.0, every key "masked out" (a masked-in column stores its key on every counted step), the
-// histograms at 0
-static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned char *mask, int64_t capacity) {
+// histograms at 0 (the plain selection's alone); per zone the counts and the column lists
+static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned char *mask, const BandsZones &zones, int64_t capacity) {
     const size_t n = (size_t)ctx->n, ab = (size_t)n_items * n * sizeof(double),
-                 hb = (size_t)n_items * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS * sizeof(unsigned);
-    HIPCHK(ctx, ctx->bands.buf.alloc((size_t)capacity * n_items * n_probs * sizeof(double)));
-    HIPCHK(ctx, ctx->bands.hdr_buf.alloc((size_t)capacity * (2 + 2 * (size_t)n_items) * sizeof(long long)));
+                 hb = (size_t)n_items * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS * sizeof(unsigned), nz = (size_t)zones.n_zones,
+                 blocks = (size_t)n_items * (nz ? nz : 1);
+    HIPCHK(ctx, ctx->bands.buf.alloc((size_t)capacity * blocks * n_probs * sizeof(double)));
+    HIPCHK(ctx, ctx->bands.hdr_buf.alloc((size_t)capacity * (nz ? 2 : 2 + 2 * (size_t)n_items) * sizeof(long long)));
     HIPCHK(ctx, ctx->bands_acc_buf.alloc(ab));
     HIPCHK(ctx, hipMemsetAsync(ctx->bands_acc_buf, 0, ab, ctx->stream));
     HIPCHK(ctx, ctx->bands_keys_buf.alloc(ab));
     HIPCHK(ctx, hipMemsetAsync(ctx->bands_keys_buf, 0xff, ab, ctx->stream));   // RH_BANDS_KEY_MASKED
-    HIPCHK(ctx, ctx->bands_hist_buf.alloc(hb));
-    HIPCHK(ctx, hipMemsetAsync(ctx->bands_hist_buf, 0, hb, ctx->stream));
+    if (nz) {
+        HIPCHK(ctx, ctx->bands_counts_buf.alloc((size_t)capacity * blocks * 2 * sizeof(long long)));
+        HIPCHK(ctx, ctx->bands_zone_buf.alloc(zones.index.size() * sizeof(int)));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->bands_zone_buf, zones.index.data(), zones.index.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        mask = zones.mask.data();
+    } else {
+        HIPCHK(ctx, ctx->bands_hist_buf.alloc(hb));
+        HIPCHK(ctx, hipMemsetAsync(ctx->bands_hist_buf, 0, hb, ctx->stream));
+    }
     if (mask) {
         HIPCHK(ctx, ctx->bands_mask_buf.alloc(n));
         HIPCHK(ctx, hipMemcpyAsync(ctx->bands_mask_buf, mask, n, hipMemcpyHostToDevice, ctx->stream));
     }
     return RH_OK;
 }
-int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs, int64_t interval_seconds,
-                       int64_t t_first, const unsigned char *mask, int64_t capacity) {
+// rh_bands_configure (zone == nullptr) and rh_bands_configure_zonal (mask == nullptr) under the name `who`
+static int bands_configure(rh_ctx *ctx, const std::string &who, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs,
+                           int64_t interval_seconds, int64_t t_first, const unsigned char *mask, const int32_t *zone, int n_zones, bool zonal,
+                           int64_t capacity) {
     if (!ctx) return RH_ERR_ARG;
     if (n_items < 0 || n_items > RH_BANDS_MAX_ITEMS)
-        return fail(ctx, RH_ERR_ARG, "rh_bands_configure: n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_BANDS_MAX_ITEMS) + ")");
+        return fail(ctx, RH_ERR_ARG, who + ": n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_BANDS_MAX_ITEMS) + ")");
     const bool off = n_items == 0;
     int plane_list[RH_BANDS_MAX_ITEMS] = {}, kind_list[RH_BANDS_MAX_ITEMS] = {}, n_sum = 0;
     double prob_list[RH_BANDS_MAX_PROBS] = {};
+    BandsZones zones;
     if (!off) {
-        if (!planes || !kinds || !probs) return fail(ctx, RH_ERR_ARG, "rh_bands_configure: null pointer");
+        if (!planes || !kinds || !probs || (zonal && !zone)) return fail(ctx, RH_ERR_ARG, who + ": null pointer");
         if (n_probs < 1 || n_probs > RH_BANDS_MAX_PROBS)
-            return fail(ctx, RH_ERR_ARG, "rh_bands_configure: n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_BANDS_MAX_PROBS) + ")");
+            return fail(ctx, RH_ERR_ARG, who + ": n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_BANDS_MAX_PROBS) + ")");
         for (int q = 0; q < n_probs; ++q) {
             if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
-                return fail(ctx, RH_ERR_ARG, "rh_bands_configure: probability " + std::to_string(q) + " = " + std::to_string(probs[q]) + " (within [0, 1])");
+                return fail(ctx, RH_ERR_ARG, who + ": probability " + std::to_string(q) + " = " + std::to_string(probs[q]) + " (within [0, 1])");
             prob_list[q] = probs[q];
         }
         if (interval_seconds != 86400 && interval_seconds != 3600 && interval_seconds != 600)
-            return fail(ctx, RH_ERR_ARG, "rh_bands_configure: interval_seconds = " + std::to_string(interval_seconds) +
+            return fail(ctx, RH_ERR_ARG, who + ": interval_seconds = " + std::to_string(interval_seconds) +
                                          " (the interval is a day, an hour or ten minutes: the step classes)");
         if (t_first < 0 || t_first % interval_seconds)
-            return fail(ctx, RH_ERR_ARG, "rh_bands_configure: t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
+            return fail(ctx, RH_ERR_ARG, who + ": t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
                                          std::to_string(interval_seconds) + " s)");
         for (int j = 0; j < n_items; ++j) {   // (item by item, as for the scores)
-            if (int rc = check_planes(ctx, "rh_bands_configure: item " + std::to_string(j) + ": ", planes + j, 1, plane_list + j, FLOAT64_IDS)) return rc;
+            if (int rc = check_planes(ctx, who + ": item " + std::to_string(j) + ": ", planes + j, 1, plane_list + j, FLOAT64_IDS)) return rc;
             if (kinds[j] != RH_BANDS_SUM && kinds[j] != RH_BANDS_LAST)
-                return fail(ctx, RH_ERR_ARG, "rh_bands_configure: kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: LAST)");
+                return fail(ctx, RH_ERR_ARG, who + ": kind " + std::to_string(kinds[j]) + " of item " + std::to_string(j) + " (0: SUM, 1: LAST)");
             kind_list[j] = kinds[j];
             n_sum += kinds[j] == RH_BANDS_SUM;
         }
-        if (ctx->n >= (int64_t)1 << 31) return fail(ctx, RH_ERR_ARG, "rh_bands_configure: " + std::to_string(ctx->n) + " columns (the histograms hold uint32 counts)");
-        if (int rc = check_capacity(ctx, "rh_bands_configure: ", capacity)) return rc;
+        if (ctx->n >= (int64_t)1 << 31) return fail(ctx, RH_ERR_ARG, who + ": " + std::to_string(ctx->n) + " columns (the histograms hold uint32 counts)");
+        if (int rc = check_capacity(ctx, who + ": ", capacity)) return rc;
+        if (zonal) {
+            if (n_zones < 1 || n_zones > RH_BANDS_MAX_ZONES)
+                return fail(ctx, RH_ERR_ARG, who + ": n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_BANDS_MAX_ZONES) + ")");
+            const size_t n = (size_t)ctx->n, nz = (size_t)n_zones;
+            std::vector<int> off_of(nz + 1, 0);
+            for (size_t i = 0; i < n; ++i) {
+                if (zone[i] >= n_zones)
+                    return fail(ctx, RH_ERR_ARG, who + ": zone index " + std::to_string(zone[i]) + " of column " + std::to_string(i) + " (n_zones = " +
+                                                 std::to_string(n_zones) + ")");
+                if (zone[i] >= 0) ++off_of[(size_t)zone[i] + 1];
+            }
+            for (size_t z = 0; z < nz; ++z) off_of[z + 1] += off_of[z];
+            if (!off_of[nz]) return fail(ctx, RH_ERR_ARG, who + ": no participating column (every zone index is negative)");
+            zones.n_zones = n_zones;
+            zones.mask.resize(n);
+            zones.index.assign(nz + 1 + (size_t)off_of[nz], 0);
+            std::copy(off_of.begin(), off_of.end(), zones.index.begin());
+            std::vector<int> next(off_of.begin(), off_of.end() - 1);
+            for (size_t i = 0; i < n; ++i) {
+                zones.mask[i] = zone[i] >= 0;
+                if (zone[i] >= 0) zones.index[nz + 1 + (size_t)next[(size_t)zone[i]]++] = (int)i;
+            }
+        }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
     HIPCHK(ctx, ctx->bands.release());
@@ -889,27 +936,34 @@ int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_i
     HIPCHK(ctx, ctx->bands_keys_buf.release());
     HIPCHK(ctx, ctx->bands_hist_buf.release());
     HIPCHK(ctx, ctx->bands_mask_buf.release());
-    ctx->bands_nitems = ctx->bands_nprobs = 0;
-    if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, capacity)) {   // refused: the observer is off
+    HIPCHK(ctx, ctx->bands_counts_buf.release());
+    HIPCHK(ctx, ctx->bands_zone_buf.release());
+    ctx->bands_nitems = ctx->bands_nprobs = ctx->bands_nzones = 0;
+    if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, zones, capacity)) {   // refused: the observer is off
         const std::string why = ctx->err;
-        (void)rh_bands_configure(ctx, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, 0);
+        (void)bands_configure(ctx, who, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0, false, 0);
         return fail(ctx, rc, why);
     }
     if (!off) {
         ctx->bands_nitems = n_items;
         ctx->bands_nprobs = n_probs;
+        ctx->bands_nzones = zones.n_zones;
         ctx->bands.cap = capacity;
     }
     std::memcpy(ctx->bands_planes, plane_list, sizeof(plane_list));
     const long long zero = 0, cap = (long long)ctx->bands.cap, iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first;
     const unsigned none = 0, no_nan[RH_BANDS_MAX_ITEMS] = {};
     const unsigned char *const mask_dev = ctx->bands_mask_buf;
+    const int *const zone_off = ctx->bands_zone_buf, *const zone_cols = zone_off ? zone_off + zones.n_zones + 1 : nullptr;
     HIPCHK(ctx, dev_put(ctx, &DevState::bands, *ctx->bands.buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_hdr, *ctx->bands.hdr_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_acc, *ctx->bands_acc_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_keys, *ctx->bands_keys_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_hist, *ctx->bands_hist_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_mask, mask_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_counts, *ctx->bands_counts_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_zone_off, zone_off));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_zone_cols, zone_cols));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_rows, zero));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_cap, cap));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_interval, iv));
@@ -924,6 +978,15 @@ int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_i
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_probs, prob_list));
     return observers_changed(ctx);   // synchronises: the sources above are locals (and the caller's mask)
 }
+int rh_bands_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs, int64_t interval_seconds,
+                       int64_t t_first, const unsigned char *mask, int64_t capacity) {
+    return bands_configure(ctx, "rh_bands_configure", planes, kinds, n_items, probs, n_probs, interval_seconds, t_first, mask, nullptr, 0, false, capacity);
+}
+int rh_bands_configure_zonal(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs, int64_t interval_seconds,
+                             int64_t t_first, const int32_t *zone, int n_zones, int64_t capacity) {
+    return bands_configure(ctx, "rh_bands_configure_zonal", planes, kinds, n_items, probs, n_probs, interval_seconds, t_first, nullptr, zone, n_zones, true,
+                           capacity);
+}
 int rh_bands_count(rh_ctx *ctx, int64_t *rows_total) {
     if (!ctx) return RH_ERR_ARG;
     if (!rows_total) return fail(ctx, RH_ERR_ARG, "rh_bands_count: null pointer");
@@ -936,10 +999,30 @@ int rh_bands_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, 
     if (!ctx) return RH_ERR_ARG;
     long long total = 0;
     if (int rc = ring_rows(ctx, "rh_bands_read", ctx->bands, "rh_bands_configure", &DevState::bands_rows, &total)) return rc;
+    if (ctx->bands_nzones) return fail(ctx, RH_ERR_STATE, "rh_bands_read: the bands are configured per zone (rh_bands_zonal_read reads their rows)");
     const size_t nv = (size_t)ctx->bands_nitems * ctx->bands_nprobs;
     const std::string why = ring_range_refusal("rh_bands_read", first_row, n_rows, total, ctx->bands.cap);
     if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
     if ((n_rows && (!hdr || !values)) || value_bytes != (size_t)n_rows * nv * sizeof(double))
         return fail(ctx, RH_ERR_ARG, "rh_bands_read: size mismatch (n_rows x n_items x n_probs float64)");
     return ring_download(ctx, ctx->bands, nv, first_row, n_rows, hdr, values, 2 + 2 * (size_t)ctx->bands_nitems);
+}
+int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr, int64_t *counts, size_t count_bytes, double *values,
+                        size_t value_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = ring_rows(ctx, "rh_bands_zonal_read", ctx->bands, "rh_bands_configure_zonal", &DevState::bands_rows, &total)) return rc;
+    if (!ctx->bands_nzones) return fail(ctx, RH_ERR_STATE, "rh_bands_zonal_read: the bands are configured without zones (rh_bands_read reads their rows)");
+    const size_t blocks = (size_t)ctx->bands_nitems * ctx->bands_nzones, nv = blocks * ctx->bands_nprobs, nc = blocks * 2;
+    const std::string why = ring_range_refusal("rh_bands_zonal_read", first_row, n_rows, total, ctx->bands.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
+    if ((n_rows && (!hdr || !counts || !values)) || count_bytes != (size_t)n_rows * nc * sizeof(int64_t) || value_bytes != (size_t)n_rows * nv * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_bands_zonal_read: size mismatch (n_rows x n_items x n_zones x 2 int64, n_rows x n_items x n_zones x n_probs float64)");
+    const int rc = ring_pieces(first_row, n_rows, ctx->bands.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
+        HIPCHK(ctx, hipMemcpyAsync(counts + (size_t)done * nc, ctx->bands_counts_buf + (size_t)slot * nc, (size_t)m * nc * sizeof(long long),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        return RH_OK;
+    });
+    if (rc) return rc;
+    return ring_download(ctx, ctx->bands, nv, first_row, n_rows, hdr, values, 2);
 }
