@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 17  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read */
+#define RH_ABI_VERSION 18  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -590,6 +590,36 @@ int rh_bands_configure_zonal(rh_ctx *ctx, const int *planes, const int *kinds /*
 int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr /* (rows, 2) {k, t1} */,
                         int64_t *counts /* (rows, n_items, n_zones, 2) {m, n_nan} */, size_t count_bytes,
                         double *values /* (rows, n_items, n_zones, n_probs) */, size_t value_bytes);
+
+/* ---- carrying the scores, the duration curves, the event outputs and the bands through a restart (ABI version 18) ----
+ * What the kernels keep between two launches is planes of plain data; these calls are copies, no kernel.  Reading: rh_scores_read and
+ * rh_durations_read return everything; the events add rh_events_state to rh_events_headers / _download / _lost; the bands add
+ * rh_bands_state to rh_bands_count.  Restoring: a fresh context is configured like the one that was read (the same items, sizes, maps and
+ * t_first), then ONE restore call replaces the state the configuration cleared.  A restore call is valid after the observer's configure
+ * call and before the next step: RH_ERR_STATE before the configuration and once a step has run behind it; it checks every size first
+ * (RH_ERR_ARG) and copies nothing when it refuses.  The copies are enqueued on the context's stream; the calls synchronise (the sources
+ * are the caller's).
+ *   rh_scores_restore     moments (n_items, 5, n), closed[n_intervals] as rh_scores_read gave them, and t_first, the carried start of
+ *                         interval 0 (a multiple of the interval, else RH_ERR_ARG): rh_scores_configure refuses a t_first behind the
+ *                         clock, a continued run configures with any boundary it accepts and carries the true one here.
+ *   rh_durations_restore  counts, values, spells as rh_durations_read gave them.
+ *   rh_events_state       ids[n_slots]: the event id every slot holds for the kernel (-1: none; workgroup 0's copy of DevState::events_ids,
+ *                         with which the copies of all workgroups that hold columns agree); *running, *drained: events_running, events_drained.
+ *   rh_events_restore     hdr (n_slots, 6) and ids[n_slots] (written to EVERY workgroup's copy), running, drained, lost, and the maps
+ *                         (n_maps, n_items, n) of the slots slots[0 ... n_maps): the slots of events that have not been read out; the maps of
+ *                         the other slots stay cleared (a slot's maps are overwritten by the first step of its next event).
+ *   rh_bands_state        acc (n_items, n): the SUM accumulators of the interval under way (plain and zonal configurations alike).
+ *   rh_bands_restore      acc, and rows: the rows recorded before the restart (rh_bands_count), so that the row numbering goes on; the
+ *                         rows themselves are not carried (the caller has drained them), rh_bands_read serves rows >= `rows` only. */
+int rh_scores_restore(rh_ctx *ctx, const double *moments, size_t moment_bytes, const unsigned char *closed, size_t closed_bytes, int64_t t_first);
+int rh_durations_restore(rh_ctx *ctx, const uint32_t *counts, size_t count_bytes, const double *values, size_t value_bytes, const uint32_t *spells,
+                         size_t spell_bytes);
+int rh_events_state(rh_ctx *ctx, int64_t *ids /* [n_slots] */, size_t id_bytes, int64_t *running, int64_t *drained);
+int rh_events_restore(rh_ctx *ctx, const int64_t *hdr /* (n_slots, 6) */, size_t hdr_bytes, const int64_t *ids /* [n_slots] */, size_t id_bytes,
+                      int64_t running, int64_t drained, int lost, const int *slots, int n_maps, const double *maps /* (n_maps, n_items, n) */,
+                      size_t map_bytes);
+int rh_bands_state(rh_ctx *ctx, double *acc /* (n_items, n) */, size_t acc_bytes);
+int rh_bands_restore(rh_ctx *ctx, const double *acc, size_t acc_bytes, int64_t rows);
 
 /* HIP-event timing of the fused per-cell kernel.  rh_enable_timing(ctx, 1) starts a new
  * measurement: every following step records an event pair around the kernel on the context's

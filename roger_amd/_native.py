@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 17  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 18  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -178,6 +178,12 @@ def load():
     lib.rh_bands_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_bands_configure_zonal.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i32, i64]
     lib.rh_bands_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t, vp, C.c_size_t]
+    lib.rh_scores_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i64]
+    lib.rh_durations_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    lib.rh_events_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.rh_events_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i64, i64, i32, vp, i32, vp, C.c_size_t]
+    lib.rh_bands_state.argtypes = [vp, vp, C.c_size_t]
+    lib.rh_bands_restore.argtypes = [vp, vp, C.c_size_t, i64]
     lib.rh_svat_step.argtypes = [vp, i32]
     lib.rh_svat_step_scalars.argtypes = [vp, i32, C.POINTER(RhScalars)]
     lib.rh_param_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -642,6 +648,7 @@ DECLARED_SYMBOLS = (
     "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
     "rh_durations_configure", "rh_durations_read",
     "rh_bands_configure", "rh_bands_count", "rh_bands_read", "rh_bands_configure_zonal", "rh_bands_zonal_read",
+    "rh_scores_restore", "rh_durations_restore", "rh_events_state", "rh_events_restore", "rh_bands_state", "rh_bands_restore",
 )
 
 
@@ -1029,6 +1036,14 @@ class Context:
                                              closed.nbytes), "rh_scores_read")
         return moments, closed
 
+    def scores_restore(self, moments, closed, t_first):
+        """Replace the moments and the closed flags (as scores_read gave them) and the start of interval 0 by those of an interrupted
+        run: after scores_configure, before the next step."""
+        m = np.ascontiguousarray(moments, dtype=np.float64)
+        c = np.ascontiguousarray(closed, dtype=np.uint8)
+        self._check(self._lib.rh_scores_restore(self._h, m.ctypes.data_as(C.c_void_p), m.nbytes, c.ctypes.data_as(C.c_void_p), c.nbytes, int(t_first)),
+                    "rh_scores_restore")
+
     # -- event outputs (rh_events_*) -----------------------------------------------------------------
     def events_configure(self, names, kinds=(), n_slots=1):
         """After every step of a rainfall event accumulate `names` (float64 planes; kinds: 0 sum, 1 peak of value / dt, 2 first, 3 last)
@@ -1063,6 +1078,25 @@ class Context:
     def events_set_drained(self, event_id):
         """Publish the highest event id that has been read out: the slots of the events up to it may be taken again."""
         self._check(self._lib.rh_events_set_drained(self._h, int(event_id)), "rh_events_set_drained")
+
+    def events_state(self):
+        """(ids int64 (n_slots,): the event id every slot holds for the kernel, -1: none; running; drained).  Synchronises."""
+        ids = np.empty(getattr(self, "_events_shape", (0, 0))[1], dtype=np.int64)
+        running, drained = C.c_int64(), C.c_int64()
+        self._check(self._lib.rh_events_state(self._h, ids.ctypes.data_as(C.c_void_p), ids.nbytes, C.byref(running), C.byref(drained)), "rh_events_state")
+        return ids, running.value, drained.value
+
+    def events_restore(self, hdr, ids, running, drained, lost=False, values=None):
+        """Replace the headers, the slots' ids, `running`, `drained`, `lost` and the maps {slot: (n_items, n)} of the events that were not
+        read out by those of an interrupted run: after events_configure, before the next step."""
+        h = np.ascontiguousarray(hdr, dtype=np.int64)
+        i = np.ascontiguousarray(ids, dtype=np.int64)
+        values = dict(values or {})
+        slots = np.ascontiguousarray(sorted(values), dtype=np.int32)
+        maps = np.ascontiguousarray(np.stack([np.asarray(values[s], dtype=np.float64) for s in sorted(values)])) if values else np.zeros((0,))
+        self._check(self._lib.rh_events_restore(self._h, h.ctypes.data_as(C.c_void_p), h.nbytes, i.ctypes.data_as(C.c_void_p), i.nbytes, int(running),
+                                                int(drained), int(bool(lost)), slots.ctypes.data_as(C.c_void_p) if values else None, len(values),
+                                                maps.ctypes.data_as(C.c_void_p) if values else None, maps.nbytes), "rh_events_restore")
 
     # -- duration curves (rh_durations_*) ------------------------------------------------------------
     def durations_configure(self, names, kinds=(), edges=(), spells=(), mask=None, interval=86400, t_first=0):
@@ -1105,6 +1139,15 @@ class Context:
         offs = np.concatenate([[0], np.cumsum([m + 2 for m in ms])]).astype(int)
         return [counts[offs[j]:offs[j + 1]] for j in range(ni)], values, spells
 
+    def durations_restore(self, counts, values, spells):
+        """Replace the counters, the float planes and the spell planes (as durations_read gave them) by those of an interrupted run:
+        after durations_configure, before the next step."""
+        c = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.uint32) for a in counts]), dtype=np.uint32)
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        sp = np.ascontiguousarray(spells, dtype=np.uint32)
+        self._check(self._lib.rh_durations_restore(self._h, c.ctypes.data_as(C.c_void_p), c.nbytes, v.ctypes.data_as(C.c_void_p), v.nbytes,
+                                                   sp.ctypes.data_as(C.c_void_p), sp.nbytes), "rh_durations_restore")
+
     # -- ensemble bands (rh_bands_*) -------------------------------------------------------------------
     def bands_configure(self, names, kinds=(), probs=(0.05, 0.5, 0.95), interval=86400, t_first=0, mask=None, capacity=4096, zones=None, n_zones=None):
         """After every step aggregate `names` (at most 8 float64 planes; kinds: 0 sum over the interval, 1 value at its end) to the
@@ -1145,6 +1188,18 @@ class Context:
         n = C.c_int64()
         self._check(self._lib.rh_bands_count(self._h, C.byref(n)), "rh_bands_count")
         return n.value
+
+    def bands_state(self):
+        """The SUM accumulators of the interval under way, float64 (n_items, n) (with or without zones).  Synchronises."""
+        acc = np.empty((getattr(self, "_bands_shape", (0, 0))[0], self.n), dtype=np.float64)
+        self._check(self._lib.rh_bands_state(self._h, acc.ctypes.data_as(C.c_void_p), acc.nbytes), "rh_bands_state")
+        return acc
+
+    def bands_restore(self, acc, rows):
+        """Replace the accumulators (as bands_state gave them) and the count of rows by those of an interrupted run: after
+        bands_configure, before the next step.  The rows before `rows` are not on the device: read from `rows` on."""
+        a = np.ascontiguousarray(acc, dtype=np.float64)
+        self._check(self._lib.rh_bands_restore(self._h, a.ctypes.data_as(C.c_void_p), a.nbytes, int(rows)), "rh_bands_restore")
 
     def bands_read(self, first, n):
         """Rows [first, first + n) of the ring: (hdr int64 (n, 2 + 2 * items): k, t1, then per item m and n_nan; values float64

@@ -46,12 +46,23 @@ one file of its own, named as the diagnostics name theirs, with the global attri
 is a one-rank run.
 
 Start and restart.  `start` is a multiple of `frequency`.  If the model's clock is past `start` when the run begins -- after a restart --
-the next interval boundary starts the first counted interval.  The ring and the accumulators are NOT part of restart files: a continued
-run starts a new series there.  The host drains the ring as it drains the totals' (roger_amd/totals.py)."""
+the next interval boundary starts the first counted interval.  Without `resume` the ring and the accumulators are not part of restart
+files: a continued run starts a new series there.  The host drains the ring as it drains the totals' (roger_amd/totals.py).
+
+Resuming.  With `state.bands.resume = True` every restart file that is written holds the group "hip_bands": the SUM accumulators of the
+interval under way, the start of the first counted interval, the number of rows recorded so far and the request.  The rows themselves do
+not go into the restart file: the ring is drained and `<identifier>.bands.nc` is written at that moment.  A run that reads such a file with
+`resume = True` and the same request -- variables and kinds, probabilities, frequency, start, mask, zone map, grid -- configures the
+device with the stored start, uploads the accumulators and goes on numbering rows and intervals where the interrupted run stopped: the
+interrupted run's rows followed by the continued run's are the uninterrupted run's, the interval that holds the restart among them, plain
+and per zone.  (The ring, the key planes and the selection's scratch are no state: they are rewritten or zero between two steps.)  A
+different request is a RuntimeError that names the first difference; a restart file without the group too (set `resume = False` to start a
+new series).  One rank only: `initialize` refuses `resume = True` with several ranks."""
 import numpy as np
 
 from . import runtime_settings as rs
-from .observers import DAY, RingSeries, check_mask, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file
+from .observers import (DAY, RingSeries, carried_group, check_mask, check_planes, check_resume, check_same_request, claim_output_file,
+                        global_attributes, local_mask, map_array, names_array, request_group, svat_only, write_file)
 from .scores import FILL, default_kind
 from .zonal_totals import RING_BYTES, check_zones
 
@@ -67,6 +78,7 @@ class Bands(RingSeries):
     counts (n, V, Z, 2) int64 and values (n, V, Z, P)."""
 
     label = attribute = "bands"
+    group = "hip_bands"
 
     def __init__(self):
         super().__init__()
@@ -115,6 +127,23 @@ class Bands(RingSeries):
             out[f"{v}_n"] = hdr[:, 2 + 2 * j].copy()
             out[f"{v}_nan"] = hdr[:, 3 + 2 * j].copy()
         return out
+
+    def _request(self, state):
+        """What a resumed run must ask for again (observers.check_same_request)."""
+        return {"variables": names_array(self._names), "kinds": np.asarray(self._kinds, dtype=np.int64),
+                "probabilities": np.asarray(self._probs, dtype=np.float64), "frequency": np.int64(self.frequency), "start": np.int64(self.start),
+                "mask": map_array(None if self.mask is None else np.asarray(self.mask) != 0, np.uint8), "zones": map_array(self.zones, np.int64),
+                "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
+
+    def restart_state(self, state):
+        """The group "hip_bands" of a restart file.  The ring is drained and the file written first; what is carried is the SUM
+        accumulators, the start of the first counted interval and the number of rows so far."""
+        if not self._on:
+            return None
+        self.drain(state, final=True)
+        ctx = state.backend_context
+        return dict(request_group(self._request(state)), acc=np.asarray(ctx.bands_state(), dtype=np.float64),
+                    scalars=np.asarray([self._t_first, ctx.bands_count()], dtype=np.int64))
 
     def _count(self, ctx):
         return ctx.bands_count()
@@ -203,6 +232,7 @@ def initialize(state):
     if not b.active:
         return
     settings = state.settings
+    check_resume("bands", b)
     svat_only("bands", settings, " over its own arrays; the quantiles of state.bands belong to the SVAT / oneD step (a sibling for the "
               "transport model is not built)")
     names = list(b.variables)
@@ -242,7 +272,8 @@ def initialize(state):
 
 def start(state):
     """Configure the device (after the restart file was read: the clock is known).  The first counted interval starts at `start`, or
-    at the next boundary if the clock is past it."""
+    at the next boundary if the clock is past it.  A resumed run (`resume`, and the restart file holds "hip_bands") takes the stored
+    start instead, the accumulators with it, and numbers its rows from the stored count on."""
     from . import runtime_state
 
     b = state.bands
@@ -251,6 +282,10 @@ def start(state):
     settings, vs = state.settings, state.variables
     f, now = int(b.frequency), int(vs.time)
     b._t_first = int(b.start) if now <= int(b.start) else -(-now // f) * f
+    held = carried_group("bands", b)
+    if held is not None:
+        check_same_request("bands", b, held, b._request(state))
+        b._t_first = int(held["scalars"][0])
     b._local = None
     if b._ids is not None:
         b._local = local_mask(b._index, settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
@@ -269,6 +304,10 @@ def start(state):
         state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, b._local, int(b.capacity))
     b._begin()
     b._hdr, b._values, b._counts = [], [], []
+    if held is not None:
+        rows = int(held["scalars"][1])
+        state.backend_context.bands_restore(held["acc"], rows)
+        b._read = rows   # (the rows before it are in the interrupted run's file)
     b._path = claim_output_file(b, state, "bands")
 
 

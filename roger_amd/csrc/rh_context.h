@@ -171,6 +171,11 @@ struct rh_ctx {
     DevBuf<long long> bands_counts_buf;
     DevBuf<int> bands_zone_buf;
     int bands_nzones = 0;            // 0: the plain configuration (k_bands_select); else k_bands_zonal on (bands_nzones, bands_nitems)
+    // carrying the four through a restart (ABI version 18, rh_*_restore): an observer is FRESH from its configure call until the first
+    // step that launches the observers -- only then may its state be replaced; scores_interval is the host copy the restore checks a
+    // carried t_first against
+    unsigned obs_fresh = 0;          // RH_FRESH_SCORES | _EVENTS | _DURATIONS | _BANDS
+    int64_t scores_interval = 0;
     int pred_blocks = 0;
     bool timing = false;
     EventPool events;                // pairs (start, stop) around the fused kernel, one per timed step

@@ -1,7 +1,8 @@
 // rh_observers.h -- what follows every step: the output accumulators (rh_diag_*), the time series at observation columns
 // (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*), the scores against observed series
 // (rh_scores_*), the event outputs (rh_events_*), the duration curves (rh_durations_*) and the ensemble bands (rh_bands_*).  Part of the
-// one translation unit roger_hip.hip, behind rh_context.h.
+// one translation unit roger_hip.hip, behind rh_context.h.  ABI version 18: the last four are carried through a restart by plain copies
+// (rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore); no kernel is involved.
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure, rh_scores_configure,
 // rh_events_configure, rh_durations_configure, rh_bands_configure): what the fused kernel must leave in memory after every step, from
@@ -55,8 +56,11 @@ static bool has_observers(const rh_ctx *ctx) {
     return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems ||
            ctx->durations_nitems || ctx->bands_nitems;
 }
+// What rh_*_restore may still replace: set by the observer's configure call, cleared by the first step behind it (launch_observers).
+enum { RH_FRESH_SCORES = 1, RH_FRESH_EVENTS = 2, RH_FRESH_DURATIONS = 4, RH_FRESH_BANDS = 8 };
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
+    ctx->obs_fresh = 0;   // (a step is enqueued: the observers' state is the run's from here on)
     if (ctx->diag_n) hipLaunchKernelGGL(k_diag, cells, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->points_ncells) hipLaunchKernelGGL(k_points, dim3(1), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
     if (ctx->totals_nplanes) {
@@ -564,6 +568,7 @@ int rh_scores_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_
     HIPCHK(ctx, ctx->scores_closed_buf.release());
     ctx->scores_nitems = 0;
     ctx->scores_nintervals = 0;
+    ctx->obs_fresh &= ~(unsigned)RH_FRESH_SCORES;
     if (int rc = off ? RH_OK : scores_alloc(ctx, n_items, obs, n_series, n_intervals, series)) {   // refused: the scores are off
         const std::string why = ctx->err;
         (void)rh_scores_configure(ctx, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0);
@@ -572,6 +577,8 @@ int rh_scores_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_
     if (!off) {
         ctx->scores_nitems = n_items;
         ctx->scores_nintervals = n_intervals;
+        ctx->scores_interval = interval_seconds;
+        ctx->obs_fresh |= RH_FRESH_SCORES;
     }
     std::memcpy(ctx->scores_planes, plane_list, sizeof(plane_list));
     const long long iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first, nk = (long long)ctx->scores_nintervals;
@@ -599,6 +606,28 @@ int rh_scores_read(rh_ctx *ctx, double *moments, size_t moment_bytes, unsigned c
     HIPCHK(ctx, hipMemcpyAsync(moments, ctx->scores_buf, moment_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(closed, ctx->scores_closed_buf, closed_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+// What the four restore calls check first: the observer is configured and no step has run since (RH_ERR_STATE otherwise).
+static int restore_check(rh_ctx *ctx, const char *who, const char *configure, int configured, unsigned fresh_bit) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!configured) return fail(ctx, RH_ERR_STATE, std::string(who) + ": " + configure + " has not been called");
+    if (!(ctx->obs_fresh & fresh_bit))
+        return fail(ctx, RH_ERR_STATE, std::string(who) + ": a step has run since " + configure + " (a restore follows the configuration, before the next step)");
+    return RH_OK;
+}
+int rh_scores_restore(rh_ctx *ctx, const double *moments, size_t moment_bytes, const unsigned char *closed, size_t closed_bytes, int64_t t_first) {
+    if (int rc = restore_check(ctx, "rh_scores_restore", "rh_scores_configure", ctx ? ctx->scores_nitems : 0, RH_FRESH_SCORES)) return rc;
+    if (!moments || !closed || moment_bytes != (size_t)ctx->scores_nitems * 5 * ctx->n * sizeof(double) || closed_bytes != (size_t)ctx->scores_nintervals)
+        return fail(ctx, RH_ERR_ARG, "rh_scores_restore: size mismatch (n_items x 5 x n float64, n_intervals bytes)");
+    if (t_first < 0 || t_first % ctx->scores_interval)
+        return fail(ctx, RH_ERR_ARG, "rh_scores_restore: t_first = " + std::to_string(t_first) + " is not a multiple of the interval (" +
+                                     std::to_string(ctx->scores_interval) + " s)");
+    const long long tf = (long long)t_first;   // (the carried start of interval 0 may lie behind the clock: that is what a restart is)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scores_buf, moments, moment_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scores_closed_buf, closed, closed_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::scores_t_first, tf));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's, and a stack local)
     return RH_OK;
 }
 
@@ -636,6 +665,7 @@ int rh_events_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_
     HIPCHK(ctx, ctx->events_hdr_buf.release());
     HIPCHK(ctx, ctx->events_ids_buf.release());
     ctx->events_nitems = ctx->events_nslots = 0;
+    ctx->obs_fresh &= ~(unsigned)RH_FRESH_EVENTS;
     const int nblk = (int)grid_for(ctx->n) + 1;   // (the fused launch's grid with RH_TAIL_PRE)
     if (int rc = off ? RH_OK : events_alloc(ctx, n_items, n_slots, nblk)) {   // refused: the event outputs are off
         const std::string why = ctx->err;
@@ -653,6 +683,7 @@ int rh_events_configure(rh_ctx *ctx, const int *planes, const int *kinds, int n_
         drained = (long long)(running > 0 ? running : S.event_id_counter) - 1;
         ctx->events_nitems = n_items;
         ctx->events_nslots = n_slots;
+        ctx->obs_fresh |= RH_FRESH_EVENTS;
     }
     std::memcpy(ctx->events_planes, plane_list, sizeof(plane_list));
     const int zero = 0;
@@ -703,6 +734,49 @@ int rh_events_lost(rh_ctx *ctx, int *lost) {
     if (!lost) return fail(ctx, RH_ERR_ARG, "rh_events_lost: null pointer");
     HIPCHK(ctx, hipMemcpyAsync(lost, &ctx->dev->events_lost, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_events_state(rh_ctx *ctx, int64_t *ids, size_t id_bytes, int64_t *running, int64_t *drained) {
+    if (int rc = events_check(ctx, "rh_events_state")) return rc;
+    if (!ids || !running || !drained || id_bytes != (size_t)ctx->events_nslots * sizeof(int64_t))
+        return fail(ctx, RH_ERR_ARG, "rh_events_state: size mismatch (n_slots int64) or null pointer");
+    // workgroup 0's copy of every slot's id: the copies of the workgroups that hold columns agree after every launch (rh_events.h)
+    const size_t nblk = (size_t)grid_for(ctx->n) + 1;
+    long long v[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpy2DAsync(ids, sizeof(int64_t), ctx->events_ids_buf, nblk * sizeof(long long), sizeof(long long), (size_t)ctx->events_nslots,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&v[0], &ctx->dev->events_running, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&v[1], &ctx->dev->events_drained, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *running = (int64_t)v[0];
+    *drained = (int64_t)v[1];
+    return RH_OK;
+}
+int rh_events_restore(rh_ctx *ctx, const int64_t *hdr, size_t hdr_bytes, const int64_t *ids, size_t id_bytes, int64_t running, int64_t drained, int lost,
+                      const int *slots, int n_maps, const double *maps, size_t map_bytes) {
+    if (int rc = restore_check(ctx, "rh_events_restore", "rh_events_configure", ctx ? ctx->events_nitems : 0, RH_FRESH_EVENTS)) return rc;
+    const size_t ns = (size_t)ctx->events_nslots, ni = (size_t)ctx->events_nitems, n = (size_t)ctx->n, nblk = (size_t)grid_for(ctx->n) + 1;
+    if (!hdr || !ids || hdr_bytes != ns * 6 * sizeof(int64_t) || id_bytes != ns * sizeof(int64_t))
+        return fail(ctx, RH_ERR_ARG, "rh_events_restore: size mismatch (n_slots x 6 int64 headers, n_slots int64 ids)");
+    if (n_maps < 0 || (size_t)n_maps > ns || (n_maps && (!slots || !maps)) || map_bytes != (size_t)n_maps * ni * n * sizeof(double))
+        return fail(ctx, RH_ERR_ARG, "rh_events_restore: size mismatch (the maps of n_maps <= n_slots slots, n_items x n float64 each)");
+    for (int k = 0; k < n_maps; ++k)
+        if (slots[k] < 0 || (size_t)slots[k] >= ns)
+            return fail(ctx, RH_ERR_ARG, "rh_events_restore: slot " + std::to_string(slots[k]) + " out of range (" + std::to_string(ns) + " slots)");
+    // every workgroup's copy of a slot's id (events_ids is (slot, workgroup)): all of them take the carried id
+    std::vector<long long> copies(ns * nblk);
+    for (size_t s = 0; s < ns; ++s) std::fill(copies.begin() + s * nblk, copies.begin() + (s + 1) * nblk, (long long)ids[s]);
+    const long long run = (long long)running, dr = (long long)drained;
+    const int was_lost = lost ? 1 : 0;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->events_hdr_buf, hdr, hdr_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->events_ids_buf, copies.data(), copies.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    for (int k = 0; k < n_maps; ++k)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->events_buf + (size_t)slots[k] * ni * n, maps + (size_t)k * ni * n, ni * n * sizeof(double), hipMemcpyHostToDevice,
+                                   ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_running, run));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_drained, dr));
+    HIPCHK(ctx, dev_put(ctx, &DevState::events_lost, was_lost));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and locals)
     return RH_OK;
 }
 
@@ -791,6 +865,7 @@ int rh_durations_configure(rh_ctx *ctx, const int *planes, const int *kinds, con
     HIPCHK(ctx, ctx->durations_edges_buf.release());
     HIPCHK(ctx, ctx->durations_mask_buf.release());
     ctx->durations_nitems = ctx->durations_nbins = 0;
+    ctx->obs_fresh &= ~(unsigned)RH_FRESH_DURATIONS;
     if (int rc = off ? RH_OK : durations_alloc(ctx, n_items, total_bins, edges, total_edges, mask)) {   // refused: the observer is off
         const std::string why = ctx->err;
         (void)rh_durations_configure(ctx, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0);
@@ -799,6 +874,7 @@ int rh_durations_configure(rh_ctx *ctx, const int *planes, const int *kinds, con
     if (!off) {
         ctx->durations_nitems = n_items;
         ctx->durations_nbins = total_bins;
+        ctx->obs_fresh |= RH_FRESH_DURATIONS;
     }
     std::memcpy(ctx->durations_planes, plane_list, sizeof(plane_list));
     const long long iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first;
@@ -833,6 +909,19 @@ int rh_durations_read(rh_ctx *ctx, uint32_t *counts, size_t count_bytes, double 
     HIPCHK(ctx, hipMemcpyAsync(values, ctx->durations_vals_buf, value_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(spells, ctx->durations_spells_buf, spell_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_durations_restore(rh_ctx *ctx, const uint32_t *counts, size_t count_bytes, const double *values, size_t value_bytes, const uint32_t *spells,
+                         size_t spell_bytes) {
+    if (int rc = restore_check(ctx, "rh_durations_restore", "rh_durations_configure", ctx ? ctx->durations_nitems : 0, RH_FRESH_DURATIONS)) return rc;
+    const size_t n = (size_t)ctx->n, ni = (size_t)ctx->durations_nitems;
+    if (!counts || !values || !spells || count_bytes != (size_t)ctx->durations_nbins * n * sizeof(uint32_t) || value_bytes != ni * 3 * n * sizeof(double) ||
+        spell_bytes != ni * 3 * n * sizeof(uint32_t))
+        return fail(ctx, RH_ERR_ARG, "rh_durations_restore: size mismatch (n_bins x n uint32, n_items x 3 x n float64, n_items x 3 x n uint32)");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->durations_counts_buf, counts, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->durations_vals_buf, values, value_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->durations_spells_buf, spells, spell_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's)
     return RH_OK;
 }
 
@@ -939,6 +1028,7 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
     HIPCHK(ctx, ctx->bands_counts_buf.release());
     HIPCHK(ctx, ctx->bands_zone_buf.release());
     ctx->bands_nitems = ctx->bands_nprobs = ctx->bands_nzones = 0;
+    ctx->obs_fresh &= ~(unsigned)RH_FRESH_BANDS;
     if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, zones, capacity)) {   // refused: the observer is off
         const std::string why = ctx->err;
         (void)bands_configure(ctx, who, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0, false, 0);
@@ -949,6 +1039,7 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
         ctx->bands_nprobs = n_probs;
         ctx->bands_nzones = zones.n_zones;
         ctx->bands.cap = capacity;
+        ctx->obs_fresh |= RH_FRESH_BANDS;
     }
     std::memcpy(ctx->bands_planes, plane_list, sizeof(plane_list));
     const long long zero = 0, cap = (long long)ctx->bands.cap, iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first;
@@ -1025,4 +1116,24 @@ int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t 
     });
     if (rc) return rc;
     return ring_download(ctx, ctx->bands, nv, first_row, n_rows, hdr, values, 2);
+}
+// the SUM accumulators of the interval under way, with or without zones (the ring's rows are the caller's already; the keys and the
+// selection's scratch are rewritten or zero between two launches)
+int rh_bands_state(rh_ctx *ctx, double *acc, size_t acc_bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->bands_nitems) return fail(ctx, RH_ERR_STATE, "rh_bands_state: rh_bands_configure has not been called");
+    if (!acc || acc_bytes != (size_t)ctx->bands_nitems * ctx->n * sizeof(double)) return fail(ctx, RH_ERR_ARG, "rh_bands_state: size mismatch (n_items x n float64)");
+    HIPCHK(ctx, hipMemcpyAsync(acc, ctx->bands_acc_buf, acc_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+int rh_bands_restore(rh_ctx *ctx, const double *acc, size_t acc_bytes, int64_t rows) {
+    if (int rc = restore_check(ctx, "rh_bands_restore", "rh_bands_configure", ctx ? ctx->bands_nitems : 0, RH_FRESH_BANDS)) return rc;
+    if (!acc || acc_bytes != (size_t)ctx->bands_nitems * ctx->n * sizeof(double)) return fail(ctx, RH_ERR_ARG, "rh_bands_restore: size mismatch (n_items x n float64)");
+    if (rows < 0) return fail(ctx, RH_ERR_ARG, "rh_bands_restore: rows = " + std::to_string(rows) + " (the rows recorded before the restart, at least 0)");
+    const long long r = (long long)rows;   // row r lands at r mod capacity: the numbering and the interval index k go on
+    HIPCHK(ctx, hipMemcpyAsync(ctx->bands_acc_buf, acc, acc_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_rows, r));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's, and a stack local)
+    return RH_OK;
 }

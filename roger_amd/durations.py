@@ -37,12 +37,21 @@ p = 0 is v_min and p = 1 is v_max.  Otherwise interpolate linearly inside [lo, h
 the last bin, and never above v_max.  `_FillValue` stands where v_n == 0 (min, max, exceed and the quantiles).
 
 Start and restart.  `start` is a multiple of `frequency`.  If the model's clock is past `start` when the run begins -- after a restart
--- the next interval boundary starts the first counted interval.  The counters are NOT part of restart files: a continued run counts
-from where it continues."""
+-- the next interval boundary starts the first counted interval.  Without `resume` the counters are not part of restart files: a
+continued run counts from where it continues.
+
+Resuming.  With `state.durations.resume = True` every restart file that is written holds the group "hip_durations": the counters, the
+float planes (the interval's sum under way, the extremes), the spell planes (the run under way, the longest, the number), the start of the
+first counted interval and the request.  A run that reads such a file with `resume = True` and the same request -- variables and kinds,
+frequency, start, edges, spells, mask, grid -- configures the device with the stored start and uploads the state: its
+`<identifier>.durations.nc` equals the uninterrupted run's bit for bit.  A different request is a RuntimeError that names the first
+difference; a restart file without the group too (set `resume = False` to count from where the run continues).  One rank only:
+`initialize` refuses `resume = True` with several ranks (restart files are gathered to rank 0, the counters are not)."""
 import numpy as np
 
 from . import runtime_settings as rs
-from .observers import DAY, Observer, check_mask, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file, xy_variables
+from .observers import (DAY, Observer, carried_group, check_mask, check_planes, check_resume, check_same_request, claim_output_file,
+                        global_attributes, local_mask, map_array, names_array, request_group, svat_only, write_file, xy_variables)
 from .scores import FILL, default_kind
 
 MAX_VARIABLES = 16                # roger_amd/csrc/rh_durations.h: RH_DURATIONS_MAX_ITEMS
@@ -101,7 +110,10 @@ def derive(counts, vals, edges, quantiles=(), spells=None):
 
 
 class Durations(Observer):
-    """`state.durations`: what the script sets (variables, aggregation, spells, frequency, start, mask, quantiles, base_output_path)."""
+    """`state.durations`: what the script sets (variables, aggregation, spells, frequency, start, mask, quantiles, base_output_path,
+    resume)."""
+
+    group = "hip_durations"
 
     def __init__(self):
         self.variables = {}
@@ -133,6 +145,25 @@ class Durations(Observer):
         if not self._on:
             return None
         return _maps(self._state)
+
+    def _request(self, state):
+        """What a resumed run must ask for again (observers.check_same_request)."""
+        spells = [(-1, np.nan) if sp is None else sp for sp in self._spells]
+        return {"variables": names_array(self._names), "kinds": np.asarray(self._kinds, dtype=np.int64), "frequency": np.int64(self.frequency),
+                "start": np.int64(self.start), "n_edges": np.asarray([e.size for e in self._edges], dtype=np.int64),
+                "edges": np.concatenate(list(self._edges) + [np.zeros(0)]), "sides": np.asarray([sp[0] for sp in spells], dtype=np.int64),
+                "thresholds": np.asarray([sp[1] for sp in spells], dtype=np.float64),
+                "mask": map_array(None if self.mask is None else np.asarray(self.mask) != 0, np.uint8),
+                "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
+
+    def restart_state(self, state):
+        """The group "hip_durations" of a restart file: the counters (the items' bins one behind the other), the float planes, the spell
+        planes, the start of the first counted interval and the request."""
+        if not self._on:
+            return None
+        counts, vals, spells = state.backend_context.durations_read()
+        return dict(request_group(self._request(state)), counts=np.concatenate([np.asarray(c, dtype=np.uint32) for c in counts]),
+                    values=np.asarray(vals, dtype=np.float64), spells=np.asarray(spells, dtype=np.uint32), t_first=np.int64(self._t_first))
 
     def close(self, state):
         """End of run(): the file."""
@@ -185,6 +216,7 @@ def initialize(state):
     if not d.active:
         return
     settings = state.settings
+    check_resume("durations", d)
     svat_only("durations", settings, " over its own arrays; the histograms of state.durations belong to the SVAT / oneD step (a sibling for "
               "the transport model is not built)")
     names = list(d.variables)
@@ -235,7 +267,8 @@ def initialize(state):
 
 def start(state):
     """Configure the device (after the restart file was read: the clock is known).  The first counted interval starts at `start`, or
-    at the next boundary if the clock is past it."""
+    at the next boundary if the clock is past it.  A resumed run (`resume`, and the restart file holds "hip_durations") takes the stored
+    start instead and the counters with it."""
     from . import runtime_state
 
     d = state.durations
@@ -244,6 +277,10 @@ def start(state):
     settings, vs = state.settings, state.variables
     f, now = int(d.frequency), int(vs.time)
     d._t_first = int(d.start) if now <= int(d.start) else -(-now // f) * f
+    held = carried_group("durations", d)
+    if held is not None:
+        check_same_request("durations", d, held, d._request(state))
+        d._t_first = int(held["t_first"])
     d._local = None
     if d.mask is not None:
         d._local = local_mask((np.asarray(d.mask) != 0).astype(np.uint8), settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
@@ -251,6 +288,9 @@ def start(state):
             return   # (several ranks: no counted column in this rank's block)
     vs.flush_to_device()
     state.backend_context.durations_configure(d._names, d._kinds, d._edges, d._spells, d._local, f, d._t_first)
+    if held is not None:
+        offs = np.concatenate([[0], np.cumsum([e.size + 2 for e in d._edges])]).astype(int)
+        state.backend_context.durations_restore([held["counts"][offs[j]:offs[j + 1]] for j in range(len(d._names))], held["values"], held["spells"])
     d._on = True
     d._path = claim_output_file(d, state, "durations")
 

@@ -22,12 +22,24 @@ with an error that names the remedy.  With several ranks a rank writes one file 
 name theirs.
 
 Start and restart.  An event that is already running when the observer is configured -- a run continued from a restart file written
-in mid-event -- is written with `event_start = -1`: its maps cover the steps from the configuration on.  The maps are NOT part of
-restart files."""
+in mid-event -- is written with `event_start = -1`: its maps cover the steps from the configuration on.  Without `resume` the maps are
+not part of restart files.
+
+Resuming.  With `state.events.resume = True` every restart file that is written holds the group "hip_events": the slots' headers and ids,
+`running`, `drained`, `lost`, the maps of the events that are not complete yet (the one that is running: the completed ones are read out
+and `<identifier>.events.nc` is written at that moment -- they can be many times the size of the arena and do not go into the restart
+file), the host's bookkeeping and the request.  A run that reads such a file with `resume = True` and the same request -- items, n_slots,
+grid -- uploads all of it: the event that was running at the restart appears ONCE, in the continued run's file, with its true
+`event_start` and its sums and peak over the whole event, and the interrupted run's file followed by the continued run's along the `event`
+axis is the uninterrupted run's.  A run whose last act is the restart file of the end of run() leaves the running event to the continued
+run: its own file ends with the last completed event.  A different request is a RuntimeError that names the first difference; a restart
+file without the group too (set `resume = False` for the behaviour above).  One rank only: `initialize` refuses `resume = True` with
+several ranks (restart files are gathered to rank 0, the maps are not)."""
 import numpy as np
 
 from . import runtime_settings as rs
-from .observers import DAY, WRITE_BYTES, Observer, check_planes, claim_output_file, global_attributes, svat_only, write_file, xy_variables
+from .observers import (DAY, WRITE_BYTES, Observer, carried_group, check_planes, check_resume, check_same_request, claim_output_file,
+                        global_attributes, names_array, request_group, svat_only, write_file, xy_variables)
 
 MAX_ITEMS = 16                    # roger_amd/csrc/rh_events.h: RH_EVENTS_MAX_ITEMS
 MAX_SLOTS = 65536                 # include/roger_hip.h: RH_EVENTS_MAX_SLOTS
@@ -35,7 +47,9 @@ KINDS = {"sum": 0, "peak": 1, "first": 2, "last": 3}
 
 
 class Events(Observer):
-    """`state.events`: what the script sets (items, n_slots, base_output_path) and the events drained so far."""
+    """`state.events`: what the script sets (items, n_slots, base_output_path, resume) and the events drained so far."""
+
+    group = "hip_events"
 
     def __init__(self):
         self.items = []
@@ -49,11 +63,35 @@ class Events(Observer):
         self._drained = None     # the highest event id read out (None: as the configuration left it)
         self._last_id = 0        # the event id of the last step a host loop looked at
         self._unwritten = 0
+        self._handed_over = None # resume: the time step at which the running event went into a restart file
         self._path = None
 
     @property
     def active(self):
         return bool(self.items)
+
+    def _request(self, state):
+        """What a resumed run must ask for again (observers.check_same_request)."""
+        return {"items": names_array(f"{v} {k}" for v, k in self._items), "n_slots": np.int64(self.n_slots),
+                "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
+
+    def restart_state(self, state):
+        """The group "hip_events" of a restart file.  The completed events are read out and the file is written first: what is left on
+        the device is the event that is running, and only its maps go into the restart file."""
+        if not self._on:
+            return None
+        self.drain(state, final=True)
+        ctx = state.backend_context
+        hdr, _, lost = ctx.events_read(slots=())
+        ids, running, drained = ctx.events_state()
+        live = [s for s in range(hdr.shape[0]) if int(hdr[s, 0]) > 0 and int(hdr[s, 0]) > int(drained)]
+        out = dict(request_group(self._request(state)), hdr=np.asarray(hdr, dtype=np.int64), ids=np.asarray(ids, dtype=np.int64),
+                   scalars=np.asarray([running, drained, int(bool(lost)), self._last_id], dtype=np.int64), slots=np.asarray(live, dtype=np.int32))
+        if live:
+            _, values, _ = ctx.events_read(slots=live)
+            out["maps"] = np.stack([values[s] for s in live])
+        self._handed_over = int(state.variables.itt)
+        return out
 
     def drain(self, state, final=False, end=False):
         """Read out the completed events: every resident event but the one the last step belonged to (end, the end of run(): that one
@@ -94,7 +132,10 @@ class Events(Observer):
             self._last_id = e
 
     def close(self, state):
-        """End of run(): the event that is still running counts as complete, and the file."""
+        """End of run(): the event that is still running counts as complete, and the file -- unless this very step's restart file took
+        the running event over (`resume`): then it belongs to the run that continues."""
+        if self.resume and self._on and self._handed_over is not None and self._handed_over == int(state.variables.itt):
+            return self.drain(state, final=True)
         self.drain(state, end=True)
 
     def _write(self, state):
@@ -134,6 +175,7 @@ def initialize(state):
     ev = state.events
     if not ev.active:
         return
+    check_resume("events", ev)
     svat_only("events", state.settings, " and knows no rainfall events; the event outputs belong to the SVAT / oneD step")
     items = []
     for item in ev.items:
@@ -154,14 +196,23 @@ def initialize(state):
 
 
 def start(state):
-    """Configure the device (after the restart file was read: an event that is running now keeps event_start = -1)."""
+    """Configure the device (after the restart file was read: an event that is running now keeps event_start = -1).  A resumed run
+    (`resume`, and the restart file holds "hip_events") uploads the slots as they were instead: the running event keeps its start."""
     ev = state.events
     if not ev.active or not ev._items:
         return
+    held = carried_group("events", ev)
+    if held is not None:
+        check_same_request("events", ev, held, ev._request(state))
     state.variables.flush_to_device()
     state.backend_context.events_configure([v for v, _ in ev._items], [KINDS[k] for _, k in ev._items], int(ev.n_slots))
-    ev._on, ev._hdr, ev._values, ev._drained, ev._unwritten = True, [], [], None, 0
+    ev._on, ev._hdr, ev._values, ev._drained, ev._unwritten, ev._handed_over = True, [], [], None, 0, None
     ev._last_id = int(state.backend_context.get_scalars().event_id[1])
+    if held is not None:
+        running, drained, lost, last_id = (int(v) for v in held["scalars"])
+        maps = {int(s): held["maps"][k] for k, s in enumerate(np.asarray(held["slots"]).reshape(-1))}
+        state.backend_context.events_restore(held["hdr"], held["ids"], running, drained, bool(lost), maps)
+        ev._drained, ev._last_id = drained, last_id
     ev._path = claim_output_file(ev, state, "events")
 
 

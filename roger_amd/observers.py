@@ -6,6 +6,11 @@ device is configured later than that, `start(state)`.  The ones that record a ro
 class from `RingSeries` and say how rows are counted, read and written; everything about when a ring is drained is here.  The ones
 that keep maps per column (scores, durations, events) derive from `Observer` and read out in their own `close`.
 
+Restart files.  An observer whose result accumulates over the whole run (scores, durations, events, bands) names a `group` and supplies
+`restart_state`; with `resume = True` on its object restart.py writes that group (`restart_groups`) and tells the observer of the file a
+run continues from (`restart_read`), and the module's `start` reinstates the state (`carried_group`, `check_same_request`).  One rank
+only (`check_resume`).
+
 Adding an observer: derive its class from `RingSeries` or `Observer`, add one `Entry` to `REGISTRY`.  Nothing in roger.py changes.
 """
 import collections
@@ -31,9 +36,19 @@ class Observer:
     output_path = None
     _on = False
     _path = None
+    # carrying the observer's state through restart files (scores, durations, events, bands): `resume` is what a script sets, `group` the
+    # restart file's group of the observer; `restart_read` notes the file a run was continued from and the group it held
+    resume = False
+    group = None
+    _restart_file = None
+    _carried = None
 
     def get_output_file_name(self, state):
         return output_file_name(self, state)
+
+    def restart_state(self, state):
+        """{name: array} for the observer's group of a restart file that is being written, or None (nothing to carry)."""
+        return None
 
 
 class RingSeries(Observer):
@@ -171,6 +186,70 @@ def check_request(what, cells, n_variables, capacity, settings):
     if int(capacity) < 1:
         raise ValueError(f"{what}: capacity = {capacity} (at least one row resident on the device)")
     return cells
+
+
+# -- resuming from a restart file ----------------------------------------------------------------------------------------------------
+def check_resume(what, obs):
+    """`initialize`: carrying an observer through restart files is a one-rank feature, as the output accumulators' group is."""
+    from . import runtime_state
+
+    if obs.resume and runtime_state.proc_num > 1:
+        raise NotImplementedError(f"{what}: resume = True with {runtime_state.proc_num} ranks: restart files are gathered to rank 0 and the "
+                                  f"observers' state is not (as for the output accumulators); set state.{what}.resume = False")
+
+
+def carried_group(what, obs):
+    """`start`: the observer's group of the restart file the run continues from; None for a run that does not resume (resume = False,
+    or no restart file was read).  A file without the group is an error: the script asked to resume and there is nothing to resume from."""
+    if not obs.resume or obs._restart_file is None:
+        return None
+    if obs._carried is None:
+        raise RuntimeError(f"{what}: resume = True, but the restart file {obs._restart_file} holds no group {obs.group!r} (it was written "
+                           f"without state.{what}.resume = True); set state.{what}.resume = False to start the observer anew from here, "
+                           "as a run without resume does")
+    return obs._carried
+
+
+def names_array(names):
+    """A list of names as bytes (restart files hold numbers only)."""
+    return np.frombuffer("\n".join(str(v) for v in names).encode(), dtype=np.uint8).copy()
+
+
+def map_array(a, dtype):
+    """A map of a request, or an empty array for None."""
+    return np.zeros(0, dtype=dtype) if a is None else np.ascontiguousarray(np.asarray(a).astype(dtype))
+
+
+def _shown(key, a):
+    a = np.asarray(a)
+    if key in ("variables", "items"):
+        return repr(bytes(a.astype(np.uint8)).decode().split("\n"))
+    if a.size == 0:
+        return "None"
+    return repr(a.tolist()) if a.size <= 8 else f"an array of shape {a.shape}"
+
+
+def request_group(request):
+    """The request {key: array} as datasets of the observer's group: `request_<key>`."""
+    return {f"request_{k}": np.asarray(v) for k, v in request.items()}
+
+
+def check_same_request(what, obs, group, request):
+    """The request of this run equals the one the restart file was written with, key by key in the request's order (NaN equals NaN)."""
+    for key, want in request.items():
+        want, have = np.asarray(want), group.get(f"request_{key}")
+        same = have is not None and np.asarray(have).shape == want.shape and np.array_equal(
+            np.asarray(have).astype(want.dtype), want, equal_nan=want.dtype.kind == "f")
+        if same:
+            continue
+        was = "nothing" if have is None else _shown(key, have)
+        where = ""
+        if have is not None and np.asarray(have).shape == want.shape and want.size > 8:
+            h, w = np.asarray(have).astype(want.dtype).reshape(-1), want.reshape(-1)
+            differs = ~((h == w) | ((h != h) & (w != w)))
+            where = f", first difference at flat index {int(np.flatnonzero(differs)[0])}"
+        raise RuntimeError(f"{what}: resume = True, but the restart file {obs._restart_file} was written with {key} = {was} and this run asks "
+                           f"for {key} = {_shown(key, want)}{where}: a resumed observer takes the same request")
 
 
 def _block(nx, ny, num_proc, rank):
@@ -322,6 +401,24 @@ def start(state, transport):
     for e in REGISTRY:
         if e.transport == transport and hasattr(_module(e), "start"):
             _module(e).start(state)
+
+
+def restart_groups(state):
+    """{group: {name: array}} of the observers that carry their state through the restart file that is being written (`resume`)."""
+    out = {}
+    for e in REGISTRY:
+        o = getattr(state, e.attribute)
+        held = o.restart_state(state) if o.resume and o.group else None
+        if held:
+            out[o.group] = held
+    return out
+
+
+def restart_read(state, fname, groups):
+    """A restart file was read: every observer learns of it and of its own group in it; `start` takes it from there."""
+    for e in REGISTRY:
+        o = getattr(state, e.attribute)
+        o._restart_file, o._carried = fname, (groups.get(o.group) if o.group else None)
 
 
 def check_call(state, nsteps):

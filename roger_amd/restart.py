@@ -11,6 +11,11 @@ roger/restart.py:32-67, 129-174), so that states can go back and forth between t
   the reference in both directions: tests/test_restart_interchange.py.
 * The device-side output accumulators (rh_diag_*) go into the group "hip_diag": a restart in the middle of an output interval keeps
   the partial sums.
+* The observers that accumulate over the whole run -- state.scores, state.durations, state.events, state.bands -- go, where the script
+  sets `state.<observer>.resume = True`, into the groups "hip_scores", "hip_durations", "hip_events", "hip_bands": their device state
+  and the few host numbers that reinstate it (Observer.restart_state / the modules' `start`, walked over observers.REGISTRY: this module
+  names no observer).  The reference's reader opens "core" and the groups of its own diagnostics and nothing else, so these groups, like
+  "hip_core" and "hip_diag", leave the file readable for it.  One rank only, as "hip_diag".  Without `resume` nothing is written.
 * Several ranks (num_proc = (px, py)): the blocks are gathered to rank 0, which writes ONE file with the global arrays like the
   reference's MPI-IO write (roger/restart.py:43-64); every rank reads its own chunk, ghost frame included (`get_chunk_slices(...,
   include_overlap=True)`, :20-24).
@@ -46,7 +51,7 @@ import os
 
 import numpy as np
 
-from . import distributed, h5lite, logger, runtime_settings as rs, runtime_state as rst
+from . import distributed, h5lite, logger, observers, runtime_settings as rs, runtime_state as rst
 
 # roger/variables.py: the variables with write_to_restart=True that exist on this path (the others belong to modules that are out of
 # scope: crops, film flow, groundwater, routing, transport)
@@ -197,6 +202,9 @@ def collect(state):
         t0, t1 = ctx.diag_slot_times(slot)
         groups["hip_diag"] = {nm: ctx.diag_download(nm, slot) for nm in names}
         groups["hip_diag"]["slot_state"] = np.array([slot, ctx.diag_steps(slot), t0, t1, state._diag_written_day], dtype=np.int64)
+    # the observers a script set `resume` on: one group each ("hip_scores", "hip_durations", "hip_events", "hip_bands"), next to the two
+    # above and like them never opened by the reference's reader; nothing without `resume` (roger_amd/observers.py: restart_groups)
+    groups.update(observers.restart_groups(state))
     return groups
 
 
@@ -519,4 +527,5 @@ def read_restart(state, filename=None):
                 ctx.diag_upload(nm, slot, groups["hip_diag"][nm])
         ctx.diag_set_slot_state(slot, steps, t0, t1)
         state._diag_written_day = written
+    observers.restart_read(state, fname, groups)   # (their `start` follows: roger.py)
     return fname

@@ -33,12 +33,21 @@ that set in increasing k with plain sequential additions (not numpy.sum, whose p
 `_FillValue` stands where the column is not scored, where n < 2, or where a denominator is zero.
 
 Start and restart.  `start` is a multiple of `frequency`.  If the model's clock is past `start` when the run begins -- after a restart --
-the next interval boundary becomes interval 0 and the observations before it are dropped.  The moments are NOT part of restart files: a
-continued run scores from where it continues."""
+the next interval boundary becomes interval 0 and the observations before it are dropped.  Without `resume` the moments are not part
+of restart files: a continued run scores from where it continues.
+
+Resuming.  With `state.scores.resume = True` every restart file that is written (restart_frequency, and at the end of run()) holds the
+group "hip_scores": the moments, the closed flags, the start of interval 0 and the request.  A run that reads such a file with
+`resume = True` and the same request -- variables and kinds, frequency, start, the observations' shape, the series map, the grid --
+configures the device with the stored start of interval 0, drops no observation and uploads the moments: its `<identifier>.scores.nc`
+equals the uninterrupted run's bit for bit, `closed` included.  A different request is a RuntimeError that names the first difference; a
+restart file without the group too (set `resume = False` to score from where the run continues).  One rank only: `initialize` refuses
+`resume = True` with several ranks (restart files are gathered to rank 0, the moments are not)."""
 import numpy as np
 
 from . import runtime_settings as rs
-from .observers import DAY, Observer, check_map_shape, check_planes, claim_output_file, global_attributes, local_mask, svat_only, write_file, xy_variables
+from .observers import (DAY, Observer, carried_group, check_map_shape, check_planes, check_resume, check_same_request, claim_output_file,
+                        global_attributes, local_mask, map_array, names_array, request_group, svat_only, write_file, xy_variables)
 
 MAX_VARIABLES = 16                # roger_amd/csrc/rh_scores.h: RH_SCORES_MAX_ITEMS
 MAX_SERIES = 1024                 # include/roger_hip.h: RH_SCORES_MAX_SERIES
@@ -135,7 +144,9 @@ def map_variables(variables, maps, items, keys, long_names, series, shape):
 
 
 class Scores(Observer):
-    """`state.scores`: what the script sets (observations, aggregation, frequency, start, series, base_output_path)."""
+    """`state.scores`: what the script sets (observations, aggregation, frequency, start, series, base_output_path, resume)."""
+
+    group = "hip_scores"
 
     def __init__(self):
         self.observations = {}
@@ -153,6 +164,7 @@ class Scores(Observer):
         self._local = None       # the series of every column of this rank's block, or None
         self._t_first = 0        # the start of interval 0 on the device
         self._dropped = 0        # observations before it
+        self._shape = (0, 0)     # (n_series, n_intervals) of the observations as the script gave them
         self._path = None
 
     @property
@@ -165,6 +177,20 @@ class Scores(Observer):
         if not self._on:
             return None
         return _maps(self._state)
+
+    def _request(self, state):
+        """What a resumed run must ask for again (observers.check_same_request)."""
+        return {"variables": names_array(self._names), "kinds": np.asarray(self._kinds, dtype=np.int64), "frequency": np.int64(self.frequency),
+                "start": np.int64(self.start), "observations_shape": np.asarray(self._shape, dtype=np.int64),
+                "series": map_array(self.series, np.int32), "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
+
+    def restart_state(self, state):
+        """The group "hip_scores" of a restart file: the moments, the closed flags, the start of interval 0 and the request."""
+        if not self._on:
+            return None
+        moments, closed = state.backend_context.scores_read()
+        return dict(request_group(self._request(state)), moments=np.asarray(moments, dtype=np.float64), closed=np.asarray(closed, dtype=np.uint8),
+                    t_first=np.int64(self._t_first))
 
     def close(self, state):
         """End of run(): the file."""
@@ -200,6 +226,7 @@ def initialize(state):
     if not s.active:
         return
     settings = state.settings
+    check_resume("scores", s)
     svat_only("scores", settings, " and scores its tracers against bulk samples over windows of days through state.transport_scores "
               "(roger_amd/sas_scores.py); the moments of state.scores belong to the SVAT / oneD step")
     names = list(s.observations)
@@ -232,11 +259,13 @@ def initialize(state):
     s._names = names
     s._kinds = [KINDS[s.aggregation.get(v, default_kind(v))] for v in names]
     s._obs = np.ascontiguousarray(np.stack(obs))
+    s._shape = tuple(s._obs.shape[1:])
 
 
 def start(state):
     """Configure the device (after the restart file was read: the clock is known).  Interval 0 starts at `start`, or at the next
-    boundary if the clock is past it; the observations before it are dropped."""
+    boundary if the clock is past it; the observations before it are dropped.  A resumed run (`resume`, and the restart file holds
+    "hip_scores") takes the stored start of interval 0 instead and the moments with it."""
     from . import runtime_state
 
     s = state.scores
@@ -245,6 +274,10 @@ def start(state):
     settings, vs = state.settings, state.variables
     f, now = int(s.frequency), int(vs.time)
     t_first = int(s.start) if now <= int(s.start) else -(-now // f) * f
+    held = carried_group("scores", s)
+    if held is not None:
+        check_same_request("scores", s, held, s._request(state))
+        boundary, t_first = max(t_first, int(held["t_first"])), int(held["t_first"])
     s._t_first, s._dropped = t_first, (t_first - int(s.start)) // f
     s._local = None
     if s.series is not None:
@@ -255,7 +288,12 @@ def start(state):
         return       # (a continued run beyond the last observation)
     s._obs = np.ascontiguousarray(s._obs[:, :, s._dropped:])
     vs.flush_to_device()
-    state.backend_context.scores_configure(s._names, s._kinds, s._obs, s._local, f, t_first)
+    if held is not None:
+        # rh_scores_configure takes no start of interval 0 behind the clock: any boundary it accepts, then the stored one with the moments
+        state.backend_context.scores_configure(s._names, s._kinds, s._obs, s._local, f, boundary)
+        state.backend_context.scores_restore(held["moments"], held["closed"], t_first)
+    else:
+        state.backend_context.scores_configure(s._names, s._kinds, s._obs, s._local, f, t_first)
     s._on = True
     s._path = claim_output_file(s, state, "scores")
 
