@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 18  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore */
+#define RH_ABI_VERSION 19  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore; 19: rh_bands_configure_weighted / rh_bands_weight_sums */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -590,6 +590,31 @@ int rh_bands_configure_zonal(rh_ctx *ctx, const int *planes, const int *kinds /*
 int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *hdr /* (rows, 2) {k, t1} */,
                         int64_t *counts /* (rows, n_items, n_zones, 2) {m, n_nan} */, size_t count_bytes,
                         double *values /* (rows, n_items, n_zones, n_probs) */, size_t value_bytes);
+/* ... likelihood-weighted (ABI version 19): the GLUE band, column i counting as w_i identical members.  Everything is the plain bands'
+ * rule except what is named here: clock, SUM / LAST aggregation, s = (acc or v) + 0.0, NaN handling, keys.
+ *   Weights.  Integer weights w_i, one uint16 per column, in 0 ... 65535: the type is the bound.  A column with w_i == 0 takes no part,
+ *   exactly as a masked-out column: it is in neither m nor n_nan.
+ *   Counts.  m is the number of participating columns whose s is not a NaN, n_nan the number whose s is a NaN: column counts, as above.
+ *   New: W = sum of w_i over the m columns, an int64; W < 2^47, since n < 2^31, so (double)W is exact.
+ *   Target and result.  For a probability p: T = clamp((int64)ceil(p * (double)W), 1, W) -- one double multiplication, one ceil -- and
+ *   the result is the smallest s with sum_{s_i <= s} w_i >= T: with o = np.argsort(s, kind="stable") and cw = np.cumsum(w[o]) it is
+ *   s[o][np.searchsorted(cw, T, side="left")], equivalently np.sort(np.repeat(s, w))[T - 1], bit for bit.  p = 0 is the participants'
+ *   minimum, p = 1 their maximum.  With m == 0 the row holds NaN and W = 0.
+ *   Consequence.  With every weight in {0, 1}, T - 1 = clamp(ceil(p m) - 1, 0, m - 1): the row is bit for bit the row rh_bands_configure
+ *   records with mask = (w != 0), header and values, and W == m.
+ * k_bands runs unchanged (its byte mask is w != 0); six launches of k_bands_select_w take the place of the six k_bands_select: the bins
+ * gain w_i instead of 1, the global histograms and the pick are 64-bit, and the grid bounds a workgroup to 65 536 columns so that its
+ * uint32 LDS bins cannot overflow (roger_amd/csrc/rh_bands.h).  The refusals are rh_bands_configure's; in addition a null weight pointer
+ * and no column with a positive weight are RH_ERR_ARG.  rh_bands_count, rh_bands_read, rh_bands_state and rh_bands_restore serve a
+ * weighted configuration unchanged.  A weighted configuration replaces a plain or a zonal one and the other way round; n_items == 0
+ * releases the weight plane, the 64-bit histograms and the ring of weight sums with the rest.
+ *   rh_bands_weight_sums  W per item of the rows [first_row, first_row + n_rows): wsum (n_rows, n_items) int64; the row range is checked
+ *                         as in rh_bands_read.  Synchronises.
+ * rh_bands_weight_sums on a configuration without weights and rh_bands_zonal_read on a weighted one return RH_ERR_STATE and name the
+ * right call. */
+int rh_bands_configure_weighted(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 LAST */, int n_items, const double *probs, int n_probs,
+                                int64_t interval_seconds, int64_t t_first, const uint16_t *weight /* [n], 0: takes no part */, int64_t capacity);
+int rh_bands_weight_sums(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *wsum /* (rows, n_items) */, size_t bytes);
 
 /* ---- carrying the scores, the duration curves, the event outputs and the bands through a restart (ABI version 18) ----
  * What the kernels keep between two launches is planes of plain data; these calls are copies, no kernel.  Reading: rh_scores_read and

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 18  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 19  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -178,6 +178,8 @@ def load():
     lib.rh_bands_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t]
     lib.rh_bands_configure_zonal.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i32, i64]
     lib.rh_bands_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t, vp, C.c_size_t]
+    lib.rh_bands_configure_weighted.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i64]
+    lib.rh_bands_weight_sums.argtypes = [vp, i64, i64, vp, C.c_size_t]
     lib.rh_scores_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i64]
     lib.rh_durations_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
     lib.rh_events_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -648,6 +650,7 @@ DECLARED_SYMBOLS = (
     "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
     "rh_durations_configure", "rh_durations_read",
     "rh_bands_configure", "rh_bands_count", "rh_bands_read", "rh_bands_configure_zonal", "rh_bands_zonal_read",
+    "rh_bands_configure_weighted", "rh_bands_weight_sums",
     "rh_scores_restore", "rh_durations_restore", "rh_events_state", "rh_events_restore", "rh_bands_state", "rh_bands_restore",
 )
 
@@ -1149,14 +1152,17 @@ class Context:
                                                    sp.ctypes.data_as(C.c_void_p), sp.nbytes), "rh_durations_restore")
 
     # -- ensemble bands (rh_bands_*) -------------------------------------------------------------------
-    def bands_configure(self, names, kinds=(), probs=(0.05, 0.5, 0.95), interval=86400, t_first=0, mask=None, capacity=4096, zones=None, n_zones=None):
+    def bands_configure(self, names, kinds=(), probs=(0.05, 0.5, 0.95), interval=86400, t_first=0, mask=None, capacity=4096, zones=None, n_zones=None, weights=None):
         """After every step aggregate `names` (at most 8 float64 planes; kinds: 0 sum over the interval, 1 value at its end) to the
         interval and, at every counted interval's end, record the exact quantiles ACROSS the columns of `mask` (a byte per interior column
         of this context's block, C order; None: every column) at `probs` (at most 8, within [0, 1]) as one row of a ring of `capacity`
         rows on the device.  The first counted interval starts at t_first.  No names: release the buffers and stop.
         `zones`: an index 0 ... n_zones - 1 per interior column (negative: the column takes no part; a `mask` is folded into it), and the
         row holds the bands of every zone -- block z bit for bit what mask = (zones == z) gives (rh_bands_configure_zonal; read with
-        bands_zonal_read).  n_zones (default: the largest index + 1) may name zones that no column of this block has."""
+        bands_zonal_read).  n_zones (default: the largest index + 1) may name zones that no column of this block has.
+        `weights`: a uint16 per interior column of this block, and the row holds the likelihood-weighted quantiles -- column i counts as
+        weights[i] identical members, 0: the column takes no part (a `mask` is folded into it) -- with the rows' weight sums beside them
+        (rh_bands_configure_weighted; bands_read, bands_weight_sums).  Not together with `zones`."""
         names = list(names)
         ni = len(names)
         if len(kinds) != ni:
@@ -1169,6 +1175,19 @@ class Context:
             mk = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
             if mk.size != self.n:
                 raise ValueError(f"bands_configure: the mask has {mk.size} values, the context {self.n} columns")
+        if names and weights is not None:
+            if zones is not None:
+                raise ValueError("bands_configure: weights with zones is not built")
+            wt = np.asarray(weights).reshape(-1)
+            if wt.size != self.n:
+                raise ValueError(f"bands_configure: the weights have {wt.size} values, the context {self.n} columns")
+            if wt.dtype.kind not in "iu" or (wt.size and (int(wt.min()) < 0 or int(wt.max()) > 65535)):
+                raise ValueError(f"bands_configure: the weights are integers 0 ... 65535 (got dtype {wt.dtype}, {wt.min()} ... {wt.max()})")
+            wt = np.ascontiguousarray(wt if mk is None else np.where(mk != 0, wt, 0), dtype=np.uint16)
+            self._check(self._lib.rh_bands_configure_weighted(self._h, ids, kd, ni, pr.ctypes.data_as(C.c_void_p), len(list(probs)), int(interval),
+                                                              int(t_first), wt.ctypes.data_as(C.c_void_p), int(capacity)), "rh_bands_configure_weighted")
+            self._bands_shape = (ni, len(list(probs)))   # (a refused configuration leaves the previous one)
+            return
         if names and zones is not None:
             zn = np.asarray(zones).reshape(-1)
             if zn.size != self.n:
@@ -1207,6 +1226,14 @@ class Context:
         shape = getattr(self, "_bands_shape", (0, 0))
         shape = shape if len(shape) == 2 else (shape[0], shape[2])   # (configured per zone: the call refuses)
         return self._ring_read("rh_bands_read", first, n, 2 + 2 * shape[0], shape)
+
+    def bands_weight_sums(self, first, n):
+        """The weight sums W of the rows [first, first + n) of a configuration with weights: int64 (n, items)."""
+        n = int(n)
+        shape = getattr(self, "_bands_shape", (0, 0))
+        wsum = np.empty((n, shape[0]), dtype=np.int64)
+        self._check(self._lib.rh_bands_weight_sums(self._h, int(first), n, wsum.ctypes.data_as(C.c_void_p), wsum.nbytes), "rh_bands_weight_sums")
+        return wsum
 
     def bands_zonal_read(self, first, n):
         """Rows [first, first + n) of the ring of a configuration with zones: (hdr int64 (n, 2): k, t1; counts int64 (n, items, zones, 2):

@@ -12,6 +12,7 @@ A setup script fills `state.bands` in `set_diagnostics`:
     state.bands.start         = 0                                     # seconds, a multiple of frequency
     state.bands.mask          = None                                  # or (nx, ny) over the GLOBAL interior, 0: column takes no part
     state.bands.zones         = None                                  # or int (nx, ny) over the GLOBAL interior, <= 0: outside every zone
+    state.bands.weights       = None                                  # or (nx, ny) over the GLOBAL interior: likelihood weights, the GLUE band
     state.bands.capacity      = 4096                                  # rows resident on the device; with zones at most what 64 MiB hold
     state.bands.base_output_path = ...                                # as for the diagnostics
 
@@ -39,6 +40,27 @@ were.  A row is V Z P 8 + V Z 16 + 16 bytes (up to 0.6 MiB), so with zones `init
 (never below 1), from the GLOBAL zone list: the same number on every rank.  On the device ONE workgroup selects a zone's quantiles in its
 own LDS, so the largest zone sets the time of a counted step: a map with one dominant zone belongs to `mask`.
 
+Weights.  A GLUE band is not the plain quantile over the behavioural sets but the likelihood-weighted one: each column carries a weight,
+for example max(NSE, 0) from `<identifier>.scores.nc`, and the 5 % / 95 % bounds are the values at which the cumulative weight passes
+5 % / 95 % of the total.  `weights` is None (every masked-in column counts the same: everything above) or an (nx, ny) array over the
+GLOBAL interior.  An integer dtype is taken as it is; a value outside 0 ... 65535 is a ValueError that names it.  A float dtype must be
+finite and >= 0 with a positive maximum, and is turned into np.rint(w / w.max() * 65535.0).astype(np.uint16), the maximum taken over the
+global array, so that every rank forms the same integers: A COLUMN WHOSE WEIGHT ROUNDS TO 0 TAKES NO PART.  A `mask` on top is folded in
+on the host: a column takes part iff mask != 0 and its integer weight is > 0; no participating column anywhere is a ValueError, none in
+this rank's block means the rank configures nothing and writes no file, like a mask.  `weights` with `zones` is refused: it is not
+built.  The device rule (roger_amd/csrc/rh_bands.h) -- everything is the rule above except what is named here: clock, aggregation,
+s = (sum or value) + 0.0, NaN handling.  Integer weights w_i, one uint16 per column; a column with w_i == 0 takes no part, exactly as a
+masked-out column, and is in neither v_n nor v_nan.  m is the number of participating columns whose s is not a NaN, n_nan the number
+whose s is a NaN: column counts, as above.  New: W = sum of w_i over the m columns, an int64 (W < 2^47, so float(W) is exact).  For a
+probability p the target is T = clamp(ceil(p * W), 1, W) -- one double multiplication, one ceil -- and the result is the smallest s with
+sum_{s_i <= s} w_i >= T:
+    o = np.argsort(s, kind="stable");  cw = np.cumsum(w[o].astype(np.int64));  value = s[o][np.searchsorted(cw, T, side="left")]
+equivalently np.sort(np.repeat(s, w))[T - 1], bit for bit: column i counts as w_i identical members.  p = 0 is the participants'
+minimum and p = 1 their maximum; with m == 0 the row holds NaN and W = 0.  With every weight in {0, 1} the row is bit for bit the row
+without weights under mask = (w != 0), and W == m.  `read()` gains "<v>_w", an (n,) int64, and the file `v_w(Time)` and the global
+attribute weights = "integer 0 ... 65535: rint(w / max(w) * 65535)".  Without weights `read()` and the file are byte for byte what
+they were.
+
 Several ranks.  With zones a rank computes the bands of its own block over the GLOBAL zone list: a zone without a column in the block has
 v_n = 0 and fill values, and a rank whose block holds no participating column configures nothing and writes no file.  Order statistics
 of blocks do not merge, so there is no `combine`: a rank computes the bands of ITS OWN block and writes
@@ -52,7 +74,8 @@ files: a continued run starts a new series there.  The host drains the ring as i
 Resuming.  With `state.bands.resume = True` every restart file that is written holds the group "hip_bands": the SUM accumulators of the
 interval under way, the start of the first counted interval, the number of rows recorded so far and the request.  The rows themselves do
 not go into the restart file: the ring is drained and `<identifier>.bands.nc` is written at that moment.  A run that reads such a file with
-`resume = True` and the same request -- variables and kinds, probabilities, frequency, start, mask, zone map, grid -- configures the
+`resume = True` and the same request -- variables and kinds, probabilities, frequency, start, mask, zone map, grid and, where weights are
+given, their integer map (a file written with weights resumed without them, or the other way round, is the same error) -- configures the
 device with the stored start, uploads the accumulators and goes on numbering rows and intervals where the interrupted run stopped: the
 interrupted run's rows followed by the continued run's are the uninterrupted run's, the interval that holds the restart among them, plain
 and per zone.  (The ring, the key planes and the selection's scratch are no state: they are rewritten or zero between two steps.)  A
@@ -61,21 +84,23 @@ new series).  One rank only: `initialize` refuses `resume = True` with several r
 import numpy as np
 
 from . import runtime_settings as rs
-from .observers import (DAY, RingSeries, carried_group, check_mask, check_planes, check_resume, check_same_request, claim_output_file,
+from .observers import (DAY, RingSeries, carried_group, check_map_shape, check_mask, check_planes, check_resume, check_same_request, claim_output_file,
                         global_attributes, local_mask, map_array, names_array, request_group, svat_only, write_file)
 from .scores import FILL, default_kind
 from .zonal_totals import RING_BYTES, check_zones
 
 MAX_VARIABLES = 8                 # roger_amd/csrc/rh_bands.h: RH_BANDS_MAX_ITEMS
 MAX_PROBABILITIES = 8             # ... RH_BANDS_MAX_PROBS
+MAX_WEIGHT = 65535                # the weight plane is uint16
+WEIGHTS_ATTRIBUTE = "integer 0 ... 65535: rint(w / max(w) * 65535)"
 FREQUENCIES = (DAY, 3600, 600)    # the step classes
 KINDS = {"sum": 0, "last": 1}
 
 
 class Bands(RingSeries):
-    """`state.bands`: what the script sets (variables, aggregation, probabilities, frequency, start, mask, zones, capacity,
+    """`state.bands`: what the script sets (variables, aggregation, probabilities, frequency, start, mask, zones, weights, capacity,
     base_output_path) and the rows drained so far: headers (n, 2 + 2 V) int64 and values (n, V, P) float64 -- with zones headers (n, 2),
-    counts (n, V, Z, 2) int64 and values (n, V, Z, P)."""
+    counts (n, V, Z, 2) int64 and values (n, V, Z, P); with weights the weight sums (n, V) int64 beside the headers."""
 
     label = attribute = "bands"
     group = "hip_bands"
@@ -89,6 +114,7 @@ class Bands(RingSeries):
         self.start = 0
         self.mask = None
         self.zones = None
+        self.weights = None
         self.base_output_path = None
         self.output_path = "{identifier}.bands.nc"
         self._state = None
@@ -101,6 +127,8 @@ class Bands(RingSeries):
         self._index = None       # ... the global map as indices into them (-1: outside, or masked out)
         self._ncells = None      # ... this rank's participating columns of every zone
         self._counts = []        # ... drained counts
+        self._weights = None     # weights: the GLOBAL integer map, uint16 (nx, ny), as quantised by `initialize`; None without weights
+        self._wsum = []          # ... drained weight sums
 
     @property
     def active(self):
@@ -108,7 +136,8 @@ class Bands(RingSeries):
 
     def read(self):
         """Synchronise, drain and return {"interval": (n,) int64, "time": (n,) int64 seconds, "<v>": (n, P) float64 with NaN where no
-        column took part, "<v>_n", "<v>_nan": (n,) int64}; None while nothing is configured on this rank."""
+        column took part, "<v>_n", "<v>_nan": (n,) int64 and, with weights, "<v>_w": (n,) int64}; None while nothing is configured on
+        this rank."""
         if not self._on:
             return None
         self.drain(self._state)
@@ -126,14 +155,19 @@ class Bands(RingSeries):
             out[v] = values[:, j].copy()
             out[f"{v}_n"] = hdr[:, 2 + 2 * j].copy()
             out[f"{v}_nan"] = hdr[:, 3 + 2 * j].copy()
+            if self._weights is not None:
+                out[f"{v}_w"] = self._all_wsum()[:, j].copy()
         return out
 
     def _request(self, state):
         """What a resumed run must ask for again (observers.check_same_request)."""
-        return {"variables": names_array(self._names), "kinds": np.asarray(self._kinds, dtype=np.int64),
-                "probabilities": np.asarray(self._probs, dtype=np.float64), "frequency": np.int64(self.frequency), "start": np.int64(self.start),
-                "mask": map_array(None if self.mask is None else np.asarray(self.mask) != 0, np.uint8), "zones": map_array(self.zones, np.int64),
-                "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
+        request = {"variables": names_array(self._names), "kinds": np.asarray(self._kinds, dtype=np.int64),
+                   "probabilities": np.asarray(self._probs, dtype=np.float64), "frequency": np.int64(self.frequency), "start": np.int64(self.start),
+                   "mask": map_array(None if self.mask is None else np.asarray(self.mask) != 0, np.uint8), "zones": map_array(self.zones, np.int64),
+                   "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
+        if self._weights is not None:   # (only then: the groups of runs without weights stay what they were)
+            request["weights"] = map_array(self._weights, np.int64)
+        return request
 
     def restart_state(self, state):
         """The group "hip_bands" of a restart file.  The ring is drained and the file written first; what is carried is the SUM
@@ -149,9 +183,15 @@ class Bands(RingSeries):
         return ctx.bands_count()
 
     def _rows(self, ctx, first, n):
+        if self._weights is not None:
+            return ctx.bands_read(first, n) + (ctx.bands_weight_sums(first, n),)
         return ctx.bands_read(first, n) if self._ids is None else ctx.bands_zonal_read(first, n)
 
     def _keep(self, state, hdr, *rest):
+        if self._weights is not None:
+            values, wsum = rest
+            self._wsum.append(wsum)
+            return super()._keep(state, hdr, values) + wsum.nbytes
         if self._ids is None:
             return super()._keep(state, hdr, *rest)
         counts, values = rest
@@ -163,6 +203,9 @@ class Bands(RingSeries):
         if not self._hdr:
             return np.empty((0, 2 + 2 * nv), dtype=np.int64), np.empty((0, nv, npr))
         return np.concatenate(self._hdr), np.concatenate(self._values)
+
+    def _all_wsum(self):
+        return np.concatenate(self._wsum) if self._wsum else np.empty((0, len(self._names)), dtype=np.int64)
 
     def _all_zonal_rows(self):
         nv, nz, npr = len(self._names), len(self._ids), len(self._probs)
@@ -189,9 +232,15 @@ class Bands(RingSeries):
                             {"_FillValue": np.float64(FILL), "long_name": f"{v} ({kind}): quantiles across the columns, sorted[ceil(p n) - 1]", "units": _UNITS.get(v, "")})
             variables[f"{v}_n"] = (("Time",), np.ascontiguousarray(hdr[:, 2 + 2 * j]), {"long_name": f"{v}: columns that took part", "units": ""})
             variables[f"{v}_nan"] = (("Time",), np.ascontiguousarray(hdr[:, 3 + 2 * j]), {"long_name": f"{v}: masked-in columns with a NaN", "units": ""})
+            if self._weights is not None:
+                variables[f"{v}_w"] = (("Time",), np.ascontiguousarray(self._all_wsum()[:, j]),
+                                       {"long_name": f"{v}: sum of the integer weights of the columns that took part", "units": ""})
+        extra = {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}
+        if self._weights is not None:
+            extra["weights"] = WEIGHTS_ATTRIBUTE
         write_file(self._path, {"Time": None, "probability": len(self._probs)}, variables, global_attributes(
-            settings.identifier, "Exact quantiles across the columns of interval values, one record per counted interval.",
-            {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}, lead={"columns": "this rank's block"}))
+            settings.identifier, "Exact quantiles across the columns of interval values, one record per counted interval.", extra,
+            lead={"columns": "this rank's block"}))
 
 
     def _write_zonal(self, state):
@@ -223,6 +272,33 @@ def zonal_capacity(capacity, n_variables, n_zones, n_probabilities):
     """The rows of V Z P 8 + V Z 16 + 16 bytes that RING_BYTES (64 MiB) hold, at most `capacity` and at least one."""
     v, z, p = int(n_variables), int(n_zones), int(n_probabilities)
     return int(max(1, min(int(capacity), RING_BYTES // (v * z * p * 8 + v * z * 16 + 16))))
+
+
+def check_weights(weights, mask, settings):
+    """`state.bands.weights` as the GLOBAL integer map, uint16 (nx, ny): an integer array as it is, a float array as
+    rint(w / max(w) * 65535) with the maximum over the global array.  `mask`: booleans or None; at least one column takes part."""
+    w = np.asarray(weights)
+    check_map_shape("bands", "weights map", w, settings)
+    if w.dtype.kind in "iub":
+        bad = np.argwhere((w < 0) | (w > MAX_WEIGHT))
+        if bad.size:
+            ix, iy = (int(c) for c in bad[0])
+            raise ValueError(f"bands: weight {int(w[ix, iy])} at cell ({ix}, {iy}) (integer weights lie within 0 ... {MAX_WEIGHT})")
+        q = w.astype(np.uint16)
+    elif w.dtype.kind == "f":
+        w = w.astype(np.float64)
+        bad = np.argwhere(~(np.isfinite(w) & (w >= 0.0)))
+        if bad.size:
+            ix, iy = (int(c) for c in bad[0])
+            raise ValueError(f"bands: weight {float(w[ix, iy])!r} at cell ({ix}, {iy}) (weights are finite and >= 0)")
+        if not w.max() > 0.0:
+            raise ValueError("bands: every weight is 0 (the largest weight must be positive)")
+        q = np.rint(w / w.max() * float(MAX_WEIGHT)).astype(np.uint16)
+    else:
+        raise ValueError(f"bands: the weights have dtype {w.dtype} (an integer or a float array)")
+    if not ((q != 0) if mask is None else (q != 0) & mask).any():
+        raise ValueError("bands: no column takes part (a column takes part iff its integer weight is > 0" + (")" if mask is None else " and mask != 0)"))
+    return q
 
 
 def initialize(state):
@@ -259,7 +335,11 @@ def initialize(state):
             raise ValueError(f'bands: aggregation of {v!r} is {b.aggregation[v]!r} ("sum" or "last")')
     check_planes("bands", names, state)
     mask = check_mask("bands", b.mask, settings)
-    b._ids = b._index = None
+    b._ids = b._index = b._weights = None
+    if b.weights is not None:
+        if b.zones is not None:
+            raise ValueError("bands: weights with zones is not built (the per-zone selection counts in 32-bit histograms, one per zone)")
+        b._weights = check_weights(b.weights, mask, settings)
     if b.zones is not None:
         ids, index = check_zones("bands", b.zones, settings)
         b._ids = ids.astype(np.int64)
@@ -285,6 +365,9 @@ def start(state):
     held = carried_group("bands", b)
     if held is not None:
         check_same_request("bands", b, held, b._request(state))
+        if b._weights is None and held.get("request_weights") is not None:   # (the other direction is check_same_request's: a key the file lacks)
+            raise RuntimeError(f"bands: resume = True, but the restart file {b._restart_file} was written with weights = an array of shape "
+                               f"{np.asarray(held['request_weights']).shape} and this run asks for weights = None: a resumed observer takes the same request")
         b._t_first = int(held["scalars"][0])
     b._local = None
     if b._ids is not None:
@@ -295,6 +378,13 @@ def start(state):
         vs.flush_to_device()
         state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, None, int(b.capacity), zones=b._local,
                                               n_zones=int(b._ids.size))
+    elif b._weights is not None:
+        folded = b._weights if b.mask is None else np.where(np.asarray(b.mask) != 0, b._weights, 0).astype(np.uint16)
+        b._local = local_mask(folded, settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
+        if not b._local.any():
+            return   # (several ranks: no participating column in this rank's block)
+        vs.flush_to_device()
+        state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, None, int(b.capacity), weights=b._local)
     else:
         if b.mask is not None:
             b._local = local_mask((np.asarray(b.mask) != 0).astype(np.uint8), settings.nx, settings.ny, rs.num_proc, runtime_state.proc_rank)
@@ -303,7 +393,7 @@ def start(state):
         vs.flush_to_device()
         state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, b._local, int(b.capacity))
     b._begin()
-    b._hdr, b._values, b._counts = [], [], []
+    b._hdr, b._values, b._counts, b._wsum = [], [], [], []
     if held is not None:
         rows = int(held["scalars"][1])
         state.backend_context.bands_restore(held["acc"], rows)

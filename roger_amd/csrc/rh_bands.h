@@ -61,6 +61,9 @@
 //
 // Per zone (rh_bands_configure_zonal): the same rule for every zone of a zone map in one run -- block z of a row is, bit for bit, the row
 // above under mask = (zone == z) -- selected by one workgroup per (zone, item) in its own LDS: k_bands_zonal at the end of this file.
+//
+// Likelihood-weighted (rh_bands_configure_weighted): the GLUE band -- column i counts as w_i identical members.  k_bands runs unchanged
+// and k_bands_select_w<P> takes the place of the six k_bands_select<P>: behind k_bands_zonal in this file, the rule with it.
 #pragma once
 
 #define RH_BANDS_MAX_ITEMS 8
@@ -412,4 +415,212 @@ __global__ void k_bands_zonal_row(DevState *D, int after_fused) {
     hd[0] = c.k;
     hd[1] = c.t1;
     D->bands_rows = row + 1;
+}
+
+// ---- likelihood-weighted bands (rh_bands_configure_weighted) ----
+// The rule.  Everything is the plain bands' rule except what is named here: clock, SUM / LAST aggregation, s = (acc or v) + 0.0, NaN
+// handling, keys.
+// Weights.  Integer weights w_i, one uint16 per column, in 0 ... 65535: the type is the bound.  A column with w_i == 0 takes no part,
+// exactly as a masked-out column: it loads and stores nothing in k_bands (whose byte mask is w != 0, written at the configuration, as
+// the zonal path writes zone >= 0), it is in neither m nor n_nan, and its key stays RH_BANDS_KEY_MASKED.
+// Counts.  m is the number of participating columns whose s is not a NaN, n_nan the number whose s is a NaN: column counts, as in the
+// plain rule.  New: W = sum of w_i over the m columns, an int64.  W < 2^47, since n < 2^31, so (double)W is exact.
+// Target and result.  For a probability p: T = clamp((int64)ceil(p * (double)W), 1, W) -- one double multiplication, one ceil, the same
+// on host and device -- and the result is the smallest s with sum_{s_i <= s} w_i >= T.  In numpy:
+//     o = np.argsort(s, kind="stable");  cw = np.cumsum(w[o].astype(np.int64));  value = s[o][np.searchsorted(cw, T, side="left")]
+// equivalently np.sort(np.repeat(s, w))[T - 1].  p = 0 is the participants' minimum and p = 1 their maximum.  With m == 0 the row holds
+// NaN and W = 0.
+// Consequence.  With every weight in {0, 1}: T - 1 = clamp(ceil(p m) - 1, 0, m - 1), so the row is bit for bit the row of the plain
+// configuration with mask = (w != 0), header and values, and W == m.  In the selection r = T - 1 takes the place of the rank
+// (bands_rank_of(p, W) is T - 1): the pick is again "the digit at which the cumulative sum passes r", and r -= below.
+//
+// k_bands_select_w<P>: six launches, the digit widths of BandsPass<P>, the last-workgroup completion pattern of k_bands_select with its
+// invariant.  What differs:
+//   histogram  a key's bin gains w_i, not 1.  The weight plane (bands_weight, 2 B per column) is read in every pass, non-temporal, issued
+//              with the key loads.  A zero weight needs no test: such a column's key is RH_BANDS_KEY_MASKED.
+//   LDS bins   stay uint32 (64 KiB for eight probabilities).  A bin holds at most (columns the workgroup walks) x 65535, so a workgroup
+//              walks at most RH_BANDS_W_MAX_TILES = 256 tiles of RH_BLOCK = 256 columns: 65536 x 65535 < 2^32.  bands_weighted_grid
+//              derives the grid from that bound -- max(min(RH_BANDS_MAX_GRID, ntiles), ceil(ntiles / 256)) -- and is the one place that
+//              does; beyond 16.7 x 10^6 columns the grid grows past one workgroup per CU.  (The tile loop gives workgroup b the tiles
+//              t = b mod grid: ceil(ntiles / grid) of them at most.)
+//   merge      into bands_whist, uint64 [item][probability][2048] (1 MiB), with returning 64-bit device-scope integer adds of the non-zero
+//              bins (dep |= ret >> 63; a sum stays below 2^47).  The last workgroup clears it.
+//   counts     m is no longer the histogram's total: pass 0 counts the keys below RH_BANDS_KEY_NAN per item in LDS beside nan_count, and
+//              one returning device-scope add per workgroup and item takes it to bands_m_count.  W is the pass-0 histogram's total.
+//   pick       bands_wave_scan64 / bands_pick64 over unsigned long long bins: the 32-bit forms above, which k_bands_select and
+//              k_bands_zonal call, are as they were.
+//   row        header {k, t1, m, n_nan per item} as in the plain path; W per item goes into a ring of its own, bands_wsum [cap][items]
+//              int64, written with the header before bands_rows advances.
+// No counter overflows for any configuration the configure call accepts (n < 2^31): LDS bins by the bound above, the global bins and W
+// below 2^31 x 65535 < 2^47, m and n_nan below 2^31, bands_done at most 2^15 workgroups.  Integer atomics only.
+// Cost of a counted step: the plain path's, plus 2 B per column, item and pass of weights, plus 64-bit merges (8 B a bin, not 4).
+#define RH_BANDS_W_MAX_TILES 256   // tiles of RH_BLOCK columns one workgroup of k_bands_select_w may walk
+static_assert((unsigned long long)RH_BANDS_W_MAX_TILES * RH_BLOCK * 65535ull < (1ull << 32), "a uint32 LDS bin holds a workgroup's weights");
+static inline unsigned bands_weighted_grid(long long n) {
+    const long long ntiles = (n + RH_BLOCK - 1) / RH_BLOCK, few = ntiles < RH_BANDS_MAX_GRID ? ntiles : RH_BANDS_MAX_GRID,
+                    bound = (ntiles + RH_BANDS_W_MAX_TILES - 1) / RH_BANDS_W_MAX_TILES;
+    return (unsigned)(few > bound ? few : bound);
+}
+RH_DEV unsigned long long bands_wave_scan64(unsigned long long x) {   // inclusive, over the 64 lanes
+    const int lane = threadIdx.x & 63;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+// bands_pick over 64-bit bins (sums of weights, below 2^47)
+template <int NC>
+RH_DEV void bands_pick64(const unsigned long long (&v)[NC], long long r, int &digit, long long &below) {
+    long long base = 0;
+    bool found = false;
+    digit = 0;
+    below = 0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const unsigned long long incl = bands_wave_scan64(v[k]);
+        const long long chunk = (long long)__shfl(incl, 63);
+        if (!found && base + chunk > r) {
+            const unsigned long long hit = __ballot(base + (long long)incl > r);
+            const int l = __ffsll((long long)hit) - 1;
+            digit = k * 64 + l;
+            below = base + (long long)__shfl(incl - v[k], l);
+            found = true;
+        }
+        base += chunk;
+    }
+}
+template <int P>
+__global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *D, int after_fused) {
+    using PS = BandsPass<P>;
+    constexpr int NB = PS::nb, NC = NB / 64, U = 8;
+    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_BANDS_NBINS];
+    __shared__ unsigned nan_count, num_count, posted, is_last;
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;   // (uniform over the grid)
+    const int ni = D->bands_nitems, np = D->bands_nprobs, nh = P == 0 ? 1 : np;
+    const int64_t n = a.n, ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    const unsigned short *wts = D->bands_weight;
+    unsigned dep = 0;
+    if (threadIdx.x == 0) posted = 0;
+    for (int j = 0; j < ni; ++j) {
+        for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) hist[b] = 0;
+        if (threadIdx.x == 0) nan_count = num_count = 0;
+        __syncthreads();
+        unsigned long long pre[RH_BANDS_MAX_PROBS];
+#pragma unroll
+        for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q) pre[q] = (P > 0 && q < np) ? D->bands_prefix[j * RH_BANDS_MAX_PROBS + q] : 0ull;
+        const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
+        unsigned mine = 0;   // pass 0: the keys of numbers this thread met
+        for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
+            unsigned long long key[U];
+            unsigned w[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = (t + (int64_t)u * gridDim.x) * RH_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
+                key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_BANDS_KEY_MASKED;
+                w[u] = i < n ? (unsigned)__builtin_nontemporal_load(wts + i) : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (key[u] >= RH_BANDS_KEY_NAN) {
+                    if (P == 0 && key[u] == RH_BANDS_KEY_NAN) atomicAdd(&nan_count, 1u);
+                    continue;
+                }
+                const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
+                if (P == 0) {
+                    ++mine;
+                    atomicAdd(&hist[d], w[u]);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q)
+                        if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], w[u]);
+                }
+            }
+        }
+        if (P == 0 && mine) atomicAdd(&num_count, mine);
+        __syncthreads();
+        unsigned long long *g = D->bands_whist + (size_t)j * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS;
+        for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) {
+            const unsigned cnt = hist[b];
+            if (cnt)
+                dep |= (unsigned)(__hip_atomic_fetch_add(g + (b / NB) * RH_BANDS_NBINS + (b % NB), (unsigned long long)cnt, __ATOMIC_RELAXED,
+                                                         __HIP_MEMORY_SCOPE_AGENT) >> 63);
+        }
+        if (P == 0 && threadIdx.x == 0) {
+            if (nan_count) dep |= __hip_atomic_fetch_add(&D->bands_nan_count[j], nan_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
+            if (num_count) dep |= __hip_atomic_fetch_add(&D->bands_m_count[j], num_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
+        }
+        __syncthreads();   // (the next item clears the histogram)
+    }
+    // Completion, as in k_bands_select: every thread's adds have returned before its LDS add (dep is 0: a sum stays below 2^47, a count
+    // below 2^31), the barrier follows, and only then is the workgroup counted done.
+    atomicAdd(&posted, dep);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        is_last = __hip_atomic_fetch_add(&D->bands_done, 1u + posted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!is_last) return;
+
+    const int lane = threadIdx.x & 63;
+    const long long row = D->bands_rows;
+    const long long slot = row % D->bands_cap;
+    for (int pair = threadIdx.x >> 6; pair < ni * np; pair += RH_BLOCK / 64) {   // (uniform over the wavefront)
+        const int j = pair / np, q = pair - j * np, at = j * RH_BANDS_MAX_PROBS + q;
+        const unsigned long long *h = D->bands_whist + (size_t)(j * RH_BANDS_MAX_PROBS + (P == 0 ? 0 : q)) * RH_BANDS_NBINS;
+        unsigned long long v[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k] = __hip_atomic_load(h + k * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        long long wsum = 0, r;
+        if (P == 0) {
+            unsigned long long tot = 0;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) tot += v[k];
+            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
+            wsum = (long long)tot;
+            r = bands_rank_of(D->bands_probs[q], wsum);   // T - 1
+        } else {
+            r = D->bands_rank[at];
+        }
+        long long below;
+        int digit;
+        bands_pick64<NC>(v, r, digit, below);
+        const unsigned long long prefix = (P == 0 ? 0ull : D->bands_prefix[at] << PS::width) | (unsigned long long)digit;
+        if (lane == 0) {
+            D->bands_prefix[at] = prefix;
+            D->bands_rank[at] = r - below;
+            if (P == 0 && q == 0) {
+                D->bands_w[j] = wsum;
+                D->bands_m[j] = (long long)__hip_atomic_load(&D->bands_m_count[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                D->bands_nan[j] = (long long)__hip_atomic_load(&D->bands_nan_count[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&D->bands_m_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&D->bands_nan_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (P == RH_BANDS_PASSES - 1) {
+                const unsigned long long u = (prefix >> 63) ? prefix ^ (1ull << 63) : ~prefix;
+                D->bands[(size_t)slot * ni * np + j * np + q] = D->bands_m[j] ? __longlong_as_double((long long)u) : __builtin_nan("");
+            }
+        }
+    }
+    __syncthreads();   // (in pass 0 the pairs of an item read one histogram)
+    for (int b = threadIdx.x; b < ni * nh * NB; b += RH_BLOCK) {
+        const int jq = b / NB;
+        __hip_atomic_store(D->bands_whist + (size_t)((jq / nh) * RH_BANDS_MAX_PROBS + jq % nh) * RH_BANDS_NBINS + b % NB, 0ull, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&D->bands_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (P == RH_BANDS_PASSES - 1) {
+            long long *hd = D->bands_hdr + (size_t)slot * (2 + 2 * ni), *ws = D->bands_wsum + (size_t)slot * ni;
+            hd[0] = c.k;
+            hd[1] = c.t1;
+            for (int j = 0; j < ni; ++j) {
+                hd[2 + 2 * j] = D->bands_m[j];
+                hd[3 + 2 * j] = D->bands_nan[j];
+                ws[j] = D->bands_w[j];
+            }
+            D->bands_rows = row + 1;
+        }
+    }
 }

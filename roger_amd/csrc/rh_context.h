@@ -171,6 +171,11 @@ struct rh_ctx {
     DevBuf<long long> bands_counts_buf;
     DevBuf<int> bands_zone_buf;
     int bands_nzones = 0;            // 0: the plain configuration (k_bands_select); else k_bands_zonal on (bands_nzones, bands_nitems)
+    // ... likelihood-weighted (rh_bands_configure_weighted): the weight plane (held: k_bands_select_w takes the place of k_bands_select),
+    // the 64-bit digit histograms and the ring of the rows' weight sums (bands_nitems int64 a row)
+    DevBuf<unsigned short> bands_weight_buf;
+    DevBuf<unsigned long long> bands_whist_buf;
+    DevBuf<long long> bands_wsum_buf;
     // carrying the four through a restart (ABI version 18, rh_*_restore): an observer is FRESH from its configure call until the first
     // step that launches the observers -- only then may its state be replaced; scores_interval is the host copy the restore checks a
     // carried t_first against

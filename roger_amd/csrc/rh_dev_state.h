@@ -211,6 +211,15 @@ struct DevState {
     // bands_done on are the plain selection's alone.
     long long *bands_counts;
     const int *bands_zone_off, *bands_zone_cols;
+    // ... likelihood-weighted (rh_bands_configure_weighted; k_bands_select_w): bands_weight (n) uint16, 0: the column takes no part
+    // (bands_mask is w != 0); bands_whist [item][8][2048] uint64: the digit histograms as sums of weights, all zeros between two launches;
+    // bands_wsum (row, item) int64: W of every row, a ring beside bands_hdr; bands_m_count: the keys of numbers pass 0 met, 0 between two
+    // launches; bands_w: W per item, fixed by pass 0.  Null without weights.
+    const unsigned short *bands_weight;
+    unsigned long long *bands_whist;
+    long long *bands_wsum;
+    unsigned bands_m_count[8];
+    long long bands_w[8];
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

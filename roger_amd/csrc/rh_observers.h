@@ -2,7 +2,8 @@
 // (rh_points_*), the catchment totals (rh_totals_*), the zonal totals (rh_zonal_*), the scores against observed series
 // (rh_scores_*), the event outputs (rh_events_*), the duration curves (rh_durations_*) and the ensemble bands (rh_bands_*).  Part of the
 // one translation unit roger_hip.hip, behind rh_context.h.  ABI version 18: the last four are carried through a restart by plain copies
-// (rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore); no kernel is involved.
+// (rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore); no kernel is involved.  ABI version
+// 19: rh_bands_configure_weighted / rh_bands_weight_sums, the likelihood-weighted bands (k_bands_select_w in rh_bands.h).
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure, rh_scores_configure,
 // rh_events_configure, rh_durations_configure, rh_bands_configure): what the fused kernel must leave in memory after every step, from
@@ -51,7 +52,8 @@ static int observers_changed(rh_ctx *ctx) {
 // (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h) -- then the duration curves, on the same grid
 // (rh_durations.h) -- then the ensemble bands: the keys on the same grid, and the six passes of the selection on at most
 // RH_BANDS_MAX_GRID workgroups that stride over the tiles -- per zone instead ONE launch with a workgroup per (zone, item) and a
-// one-thread launch for the row's header (rh_bands.h).  after_fused: rh_control.h, k_diag.
+// one-thread launch for the row's header; with a weight plane the six passes of the weighted selection on bands_weighted_grid
+// workgroups (rh_bands.h).  after_fused: rh_control.h, k_diag.
 static bool has_observers(const rh_ctx *ctx) {
     return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems ||
            ctx->durations_nitems || ctx->bands_nitems;
@@ -79,6 +81,14 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
         if (ctx->bands_nzones) {   // per zone: one launch for the selection, one thread for the row's header
             hipLaunchKernelGGL(k_bands_zonal, dim3(ctx->bands_nzones, ctx->bands_nitems), block, 0, ctx->stream, ctx->dev, (long long)ctx->n, after_fused);
             hipLaunchKernelGGL(k_bands_zonal_row, dim3(1), dim3(1), 0, ctx->stream, ctx->dev, after_fused);
+        } else if (ctx->bands_weight_buf) {   // likelihood-weighted: the grid bounds what a workgroup's uint32 LDS bins can hold
+            const dim3 sel(bands_weighted_grid((long long)ctx->n));
+            hipLaunchKernelGGL(k_bands_select_w<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select_w<1>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select_w<2>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select_w<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select_w<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            hipLaunchKernelGGL(k_bands_select_w<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
         } else {
             const dim3 sel(std::min<unsigned>(grid_for(ctx->n), RH_BANDS_MAX_GRID));
             hipLaunchKernelGGL(k_bands_select<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
@@ -934,8 +944,10 @@ struct BandsZones {
     std::vector<int> index;
 };
 // the buffers: the ring, the accumulators at +0.0, every key "masked out" (a masked-in column stores its key on every counted step), the
-// histograms at 0 (the plain selection's alone); per zone the counts and the column lists
-static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned char *mask, const BandsZones &zones, int64_t capacity) {
+// histograms at 0 (the plain selection's alone); per zone the counts and the column lists; with weights the weight plane, the 64-bit
+// histograms at 0 in place of the 32-bit ones, and the ring of the rows' weight sums
+static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned char *mask, const BandsZones &zones, const uint16_t *weight,
+                       int64_t capacity) {
     const size_t n = (size_t)ctx->n, ab = (size_t)n_items * n * sizeof(double),
                  hb = (size_t)n_items * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS * sizeof(unsigned), nz = (size_t)zones.n_zones,
                  blocks = (size_t)n_items * (nz ? nz : 1);
@@ -950,6 +962,12 @@ static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned cha
         HIPCHK(ctx, ctx->bands_zone_buf.alloc(zones.index.size() * sizeof(int)));
         HIPCHK(ctx, hipMemcpyAsync(ctx->bands_zone_buf, zones.index.data(), zones.index.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         mask = zones.mask.data();
+    } else if (weight) {
+        HIPCHK(ctx, ctx->bands_weight_buf.alloc(n * sizeof(uint16_t)));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->bands_weight_buf, weight, n * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, ctx->bands_whist_buf.alloc(2 * hb));
+        HIPCHK(ctx, hipMemsetAsync(ctx->bands_whist_buf, 0, 2 * hb, ctx->stream));
+        HIPCHK(ctx, ctx->bands_wsum_buf.alloc((size_t)capacity * n_items * sizeof(long long)));
     } else {
         HIPCHK(ctx, ctx->bands_hist_buf.alloc(hb));
         HIPCHK(ctx, hipMemsetAsync(ctx->bands_hist_buf, 0, hb, ctx->stream));
@@ -960,10 +978,11 @@ static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned cha
     }
     return RH_OK;
 }
-// rh_bands_configure (zone == nullptr) and rh_bands_configure_zonal (mask == nullptr) under the name `who`
+// rh_bands_configure (zone == nullptr), rh_bands_configure_zonal (mask == nullptr) and rh_bands_configure_weighted (both null; weighted:
+// `weight` is asked for, and its byte mask w != 0 is formed here) under the name `who`
 static int bands_configure(rh_ctx *ctx, const std::string &who, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs,
                            int64_t interval_seconds, int64_t t_first, const unsigned char *mask, const int32_t *zone, int n_zones, bool zonal,
-                           int64_t capacity) {
+                           int64_t capacity, const uint16_t *weight = nullptr, bool weighted = false) {
     if (!ctx) return RH_ERR_ARG;
     if (n_items < 0 || n_items > RH_BANDS_MAX_ITEMS)
         return fail(ctx, RH_ERR_ARG, who + ": n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_BANDS_MAX_ITEMS) + ")");
@@ -971,8 +990,9 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
     int plane_list[RH_BANDS_MAX_ITEMS] = {}, kind_list[RH_BANDS_MAX_ITEMS] = {}, n_sum = 0;
     double prob_list[RH_BANDS_MAX_PROBS] = {};
     BandsZones zones;
+    std::vector<unsigned char> weight_mask;
     if (!off) {
-        if (!planes || !kinds || !probs || (zonal && !zone)) return fail(ctx, RH_ERR_ARG, who + ": null pointer");
+        if (!planes || !kinds || !probs || (zonal && !zone) || (weighted && !weight)) return fail(ctx, RH_ERR_ARG, who + ": null pointer");
         if (n_probs < 1 || n_probs > RH_BANDS_MAX_PROBS)
             return fail(ctx, RH_ERR_ARG, who + ": n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_BANDS_MAX_PROBS) + ")");
         for (int q = 0; q < n_probs; ++q) {
@@ -1018,7 +1038,15 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
                 if (zone[i] >= 0) zones.index[nz + 1 + (size_t)next[(size_t)zone[i]]++] = (int)i;
             }
         }
+        if (weighted) {
+            const size_t n = (size_t)ctx->n;
+            weight_mask.resize(n);
+            for (size_t i = 0; i < n; ++i) weight_mask[i] = weight[i] != 0;
+            if (std::find(weight_mask.begin(), weight_mask.end(), 1) == weight_mask.end()) return fail(ctx, RH_ERR_ARG, who + ": no participating column (every weight is 0)");
+            mask = weight_mask.data();
+        }
     }
+    if (off || !weighted) weight = nullptr;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
     HIPCHK(ctx, ctx->bands.release());
     HIPCHK(ctx, ctx->bands_acc_buf.release());
@@ -1027,9 +1055,12 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
     HIPCHK(ctx, ctx->bands_mask_buf.release());
     HIPCHK(ctx, ctx->bands_counts_buf.release());
     HIPCHK(ctx, ctx->bands_zone_buf.release());
+    HIPCHK(ctx, ctx->bands_weight_buf.release());
+    HIPCHK(ctx, ctx->bands_whist_buf.release());
+    HIPCHK(ctx, ctx->bands_wsum_buf.release());
     ctx->bands_nitems = ctx->bands_nprobs = ctx->bands_nzones = 0;
     ctx->obs_fresh &= ~(unsigned)RH_FRESH_BANDS;
-    if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, zones, capacity)) {   // refused: the observer is off
+    if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, zones, weight, capacity)) {   // refused: the observer is off
         const std::string why = ctx->err;
         (void)bands_configure(ctx, who, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0, false, 0);
         return fail(ctx, rc, why);
@@ -1044,6 +1075,7 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
     std::memcpy(ctx->bands_planes, plane_list, sizeof(plane_list));
     const long long zero = 0, cap = (long long)ctx->bands.cap, iv = off ? 86400 : (long long)interval_seconds, tf = off ? 0 : (long long)t_first;
     const unsigned none = 0, no_nan[RH_BANDS_MAX_ITEMS] = {};
+    const unsigned short *const weight_dev = ctx->bands_weight_buf;
     const unsigned char *const mask_dev = ctx->bands_mask_buf;
     const int *const zone_off = ctx->bands_zone_buf, *const zone_cols = zone_off ? zone_off + zones.n_zones + 1 : nullptr;
     HIPCHK(ctx, dev_put(ctx, &DevState::bands, *ctx->bands.buf.addr()));
@@ -1055,6 +1087,10 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_counts, *ctx->bands_counts_buf.addr()));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_zone_off, zone_off));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_zone_cols, zone_cols));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_weight, weight_dev));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_whist, *ctx->bands_whist_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_wsum, *ctx->bands_wsum_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_m_count, no_nan));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_rows, zero));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_cap, cap));
     HIPCHK(ctx, dev_put(ctx, &DevState::bands_interval, iv));
@@ -1077,6 +1113,11 @@ int rh_bands_configure_zonal(rh_ctx *ctx, const int *planes, const int *kinds, i
                              int64_t t_first, const int32_t *zone, int n_zones, int64_t capacity) {
     return bands_configure(ctx, "rh_bands_configure_zonal", planes, kinds, n_items, probs, n_probs, interval_seconds, t_first, nullptr, zone, n_zones, true,
                            capacity);
+}
+int rh_bands_configure_weighted(rh_ctx *ctx, const int *planes, const int *kinds, int n_items, const double *probs, int n_probs, int64_t interval_seconds,
+                                int64_t t_first, const uint16_t *weight, int64_t capacity) {
+    return bands_configure(ctx, "rh_bands_configure_weighted", planes, kinds, n_items, probs, n_probs, interval_seconds, t_first, nullptr, nullptr, 0, false,
+                           capacity, weight, true);
 }
 int rh_bands_count(rh_ctx *ctx, int64_t *rows_total) {
     if (!ctx) return RH_ERR_ARG;
@@ -1103,6 +1144,8 @@ int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t 
     if (!ctx) return RH_ERR_ARG;
     long long total = 0;
     if (int rc = ring_rows(ctx, "rh_bands_zonal_read", ctx->bands, "rh_bands_configure_zonal", &DevState::bands_rows, &total)) return rc;
+    if (ctx->bands_weight_buf)
+        return fail(ctx, RH_ERR_STATE, "rh_bands_zonal_read: the bands are configured with weights (rh_bands_read and rh_bands_weight_sums read their rows)");
     if (!ctx->bands_nzones) return fail(ctx, RH_ERR_STATE, "rh_bands_zonal_read: the bands are configured without zones (rh_bands_read reads their rows)");
     const size_t blocks = (size_t)ctx->bands_nitems * ctx->bands_nzones, nv = blocks * ctx->bands_nprobs, nc = blocks * 2;
     const std::string why = ring_range_refusal("rh_bands_zonal_read", first_row, n_rows, total, ctx->bands.cap);
@@ -1116,6 +1159,27 @@ int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t 
     });
     if (rc) return rc;
     return ring_download(ctx, ctx->bands, nv, first_row, n_rows, hdr, values, 2);
+}
+// W per item of the rows [first_row, first_row + n_rows) of a weighted configuration: the ring beside the headers
+int rh_bands_weight_sums(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *wsum, size_t bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = ring_rows(ctx, "rh_bands_weight_sums", ctx->bands, "rh_bands_configure_weighted", &DevState::bands_rows, &total)) return rc;
+    if (!ctx->bands_weight_buf)
+        return fail(ctx, RH_ERR_STATE, "rh_bands_weight_sums: the bands are configured without weights (rh_bands_configure_weighted records the weight sums)");
+    const size_t ni = (size_t)ctx->bands_nitems;
+    const std::string why = ring_range_refusal("rh_bands_weight_sums", first_row, n_rows, total, ctx->bands.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
+    if ((n_rows && !wsum) || bytes != (size_t)n_rows * ni * sizeof(int64_t))
+        return fail(ctx, RH_ERR_ARG, "rh_bands_weight_sums: size mismatch (n_rows x n_items int64)");
+    const int rc = ring_pieces(first_row, n_rows, ctx->bands.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
+        HIPCHK(ctx, hipMemcpyAsync(wsum + (size_t)done * ni, ctx->bands_wsum_buf + (size_t)slot * ni, (size_t)m * ni * sizeof(long long),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        return RH_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
 }
 // the SUM accumulators of the interval under way, with or without zones (the ring's rows are the caller's already; the keys and the
 // selection's scratch are rewritten or zero between two launches)
