@@ -158,6 +158,115 @@ def test_shape_boundaries_of_the_selection(n):
     ctx.close()
 
 
+SELECT_UNROLL = 8     # roger_amd/csrc/rh_bands.h: U of k_bands_select / k_bands_select_w, the tiles a thread holds in flight per trip
+SECOND_TRIP = SELECT_GRID * SELECT_UNROLL * 256 + 1
+
+
+def assert_reaches_the_second_trip(n):
+    """Host only: n columns give more tiles than one trip of the whole grid covers, and the last tile holds one key."""
+    ntiles = -(-n // 256)
+    assert ntiles > SELECT_GRID * SELECT_UNROLL and ntiles - 1 == SELECT_GRID * SELECT_UNROLL and n % 256 == 1, (n, ntiles, SELECT_GRID, SELECT_UNROLL)
+
+
+def second_trip_columns(n):
+    """(the column of tile 2048, a column of tile 256 + 255): workgroup 0's second trip, u = 0; workgroup 255's first trip, u = 1."""
+    at = (SELECT_GRID + SELECT_GRID - 1) * 256 + 17
+    assert at // 256 == 2 * SELECT_GRID - 1 and (n - 1) // 256 == SELECT_GRID * SELECT_UNROLL
+    return n - 1, at
+
+
+def test_second_trip_of_the_striding_loop():
+    """The tile loop of k_bands_select is `for (t = blockIdx.x; t < ntiles; t += gridDim.x * U)` with U = 8 tiles in flight and a grid of
+    at most 256 workgroups: one trip of the whole grid covers 256 x 8 = 2048 tiles of 256 keys, so the smallest n at which a workgroup
+    makes a second trip is 2048 x 256 + 1 = 524 289 columns.  Tile 2048 then belongs to workgroup 0 on its second trip (u = 0), holds a
+    single key, and u = 1 ... 7 of that trip lie beyond the last tile (the `i < n` guard); every other workgroup leaves the loop after one
+    trip.  Not a workload size.  Memory: the context holds about 155 planes x 8 B x n = 0.65 GB, the bands one key plane of 4 MB.
+    Day 0 puts the minimum into that last column, day 1 into a column of tile 256 + 255 (u = 1 of the first trip)."""
+    n = SECOND_TRIP
+    assert_reaches_the_second_trip(n)
+    rng = np.random.default_rng(n)
+    probs = (0.0, 1.0 / n, 0.25, 0.5, 0.75, 1.0 - 1.0 / n, 1.0)
+    ctx = dry_ctx(n)
+    ctx.bands_configure([PLANE], [LAST], probs, DAY, 0, None, 4)
+    for day, at in enumerate(second_trip_columns(n)):
+        x = rng.normal(size=n) * 10.0 ** rng.integers(-4, 5, n)
+        x[rng.random(n) < 0.1] = 0.0
+        x[at] = -1e300
+        want = one_day(ctx, x, probs, None, f"n = {n}, day {day}, the minimum in column {at}")
+        assert want[0] == want[1] == -1e300 and want[2] > -1e300        # (p = 1 / n is rank 0 too)
+    ctx.close()
+
+
+# ---- the full width: 8 items x 8 probabilities ----
+FULL_PLANES = ("theta_irr", "sand", "clay", "theta_6", "theta_27", "theta_4", "rew", "tew")
+FULL_PROBS = (0.0, 0.03, 0.25, 0.5, 0.5625, 0.75, 0.97, 1.0)
+
+
+def full_width_values(rng, n, day):
+    """Eight different planes of crafted values for one day.  The first four planes are read by no routine of the step (theta_irr only for
+    the irrigation demand, a pure output; sand, clay and theta_6 only by rh_params_soil at the setup), so they take adversarial values:
+    both signs, -0.0, ties, infinities, NaN.  theta_27, theta_4, rew and tew are read by the crack depth and the evaporation stress, so
+    they keep plausible, ordered ranges (theta_4 < theta_27, rew < tew), with ties."""
+    wild = [rng.normal(size=n) * 10.0 ** rng.integers(-3, 4, n), np.round(rng.normal(size=n) * 4) / 8 + 0.375, rng.choice([-2.5, -0.0, 0.0, 1e-300, 7.0, np.inf, -np.inf], n),
+            (np.float64(1.5).view(np.uint64) + rng.integers(0, 512, n).astype(np.uint64)).view(np.float64) * (-1.0) ** day]
+    wild[0][rng.random(n) < 0.05] = np.nan
+    tame = [0.12 + np.round(rng.random(n) * 64) / 800, 0.02 + np.round(rng.random(n) * 64) / 800, 2.0 + rng.permutation(n) * (6.0 / n), 10.0 + np.round(rng.random(n) * 200) / 10]
+    return [np.ascontiguousarray(v, dtype=np.float64) for v in wild + tame]
+
+
+def full_width_days(n, n_items, host, configure, seed):
+    """Two dry days on a context with the bands (`configure(ctx, names, kinds)`) beside a context WITHOUT observers that gives the planes
+    and the clock after every step to the restatement `host(kinds)`; items alternate SUM and LAST, so the second day's SUM rows hold both
+    days.  Returns (ctx, the restatement); the caller reads, compares and closes."""
+    rng = np.random.default_rng(seed)
+    ctx, bare = dry_ctx(n), dry_ctx(n)
+    names = FULL_PLANES[:n_items]
+    kinds = [(SUM, LAST)[j % 2] for j in range(n_items)]
+    for v in names:
+        assert v in ctx.index and ctx.index[v] < ctx.planes_held and v not in ctx.pure_output_planes(), v
+    configure(ctx, names, kinds)
+    h = host(kinds)
+    for day in range(2):
+        values = full_width_values(rng, n, day)[:n_items]
+        for c in (ctx, bare):
+            for v, x in zip(names, values):
+                c.upload(v, x)
+            c.run_steps(1)
+        s = bare.get_scalars()
+        assert int(s.dt_secs) == DAY
+        seen = [bare.download(v) for v in names]
+        for v, x, got in zip(names, values, seen):
+            assert (got.view(np.uint64) == x.view(np.uint64)).all(), (v, "the step wrote the plane: the crafted values were not what the observer saw")
+        h.add(int(s.time) - int(s.dt_secs), int(s.time), seen)
+    bare.close()
+    return ctx, h
+
+
+def assert_items_differ(values, what):
+    """Host only: the expected rows of the items are pairwise different, so reading item j's prefix or key plane for item j' changes a bit."""
+    ni = values.shape[1]
+    for j in range(ni):
+        for k in range(j + 1, ni):
+            assert (values[:, j].view(np.uint64) != values[:, k].view(np.uint64)).any(), (what, "items", j, k, "have equal expected rows")
+
+
+@pytest.mark.parametrize("n_probs", [1, 8])
+@pytest.mark.parametrize("n_items", [1, 8])
+def test_items_and_probabilities(n_items, n_probs):
+    """1 and 8 items x 1 and 8 probabilities at 600 columns under test_hip_durations.py's mask: 64 (item, probability) pairs over the 4
+    wavefronts of the pick, the 64 KiB LDS histogram, the clear loop over every item's bins."""
+    n = 600
+    probs = (0.5,) if n_probs == 1 else FULL_PROBS
+    mask = mask_of(n)
+    ctx, h = full_width_days(n, n_items, lambda kinds: HostBands(kinds, probs, n, mask, DAY, 0),
+                             lambda c, names, kinds: c.bands_configure(names, kinds, probs, DAY, 0, mask, 4), seed=n_items * 10 + n_probs)
+    want = h.rows()
+    assert want[1].shape == (2, n_items, n_probs) and (want[0][:, 3] > 0).all(), "no NaN was counted"
+    assert_items_differ(want[1], f"{n_items} items x {n_probs} probabilities")
+    assert_rows(read_all(ctx), want, f"{n_items} items x {n_probs} probabilities")
+    ctx.close()
+
+
 def middle_probs(m):
     """0, the 1/m steps around the middle, 1."""
     m = max(int(m), 1)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from bands_reference import LAST, SUM
-from bands_weighted_reference import HostWeightedBands, weighted_quantiles_of
+from bands_weighted_reference import HostWeightedBands, target_of, weighted_quantiles_of
 from test_hip_bands import DAY, GRIDS, KINDS, NAMES, PLANE, PROBS, assert_rows, assert_state, dry_ctx, mask_of, read_all, reference
 from test_hip_points import NDAYS, NSTEPS, make_ctx
 
@@ -213,6 +213,71 @@ def test_crafted_values(n):
     assert (m, n_nan, W) == (0, 3, 0) and np.isnan(want).all()
     hdr, got = ctx.bands_read(0, 1)
     assert np.isnan(got).all() and hdr[0].tolist() == [hdr[0, 0], hdr[0, 1], 0, 3]
+    ctx.close()
+
+
+def prob_of_target(T, W):
+    """A probability whose target ceil(p * W), by target_of's own arithmetic, is exactly T (1 <= T <= W)."""
+    p = float(T) / float(W)
+    while target_of(p, W) > T:
+        p = float(np.nextafter(p, 0.0))
+    assert target_of(p, W) == T, (T, W, p)
+    return p
+
+
+def test_second_trip_of_the_striding_loop():
+    """tests/test_hip_bands.py's second-trip case for k_bands_select_w: n = 2048 x 256 + 1 = 524 289 columns is the smallest n at which a
+    workgroup of the 256 (bands_weighted_grid gives 256 here: 2049 tiles need only 9 workgroups for the LDS bound) walks a second trip
+    of 8 tiles; tile 2048 is workgroup 0's, holds a single key, and the seven tiles behind it lie beyond n.  Workgroup 0 sums nine tiles
+    into its uint32 LDS bins.  Not a workload size; the context holds about 155 planes x 8 B x n = 0.65 GB, the bands a key plane of 4 MB
+    and a weight plane of 1 MB.
+    The last column has weight 65535, so it alone moves the cumulative weight across 65535 targets: with `before` the weight of the
+    columns below it, the targets before + 1 and before + 65535 give its value, before and before + 65536 its neighbours'.  Day 0 puts
+    the minimum there (before = 0), day 1 into a column of tile 256 + 255 (u = 1 of the first trip) with the last column's value
+    somewhere in the middle."""
+    from test_hip_bands import SECOND_TRIP, assert_reaches_the_second_trip, second_trip_columns
+
+    n = SECOND_TRIP
+    assert_reaches_the_second_trip(n)
+    rng = np.random.default_rng(n)
+    last, at = second_trip_columns(n)
+    w = rng.integers(0, 65536, n)
+    w[last], w[at] = 65535, 1
+    w = w.astype(np.uint16)
+    ctx = dry_ctx(n)
+    for day in range(2):
+        x = rng.normal(size=n) * 10.0 ** rng.integers(-4, 5, n)
+        x[at if day else last] = -1e300
+        assert np.unique(x).size == n
+        on = (w != 0) & (x < x[last])
+        before, W = int(w[on].astype(np.int64).sum()), int(w.astype(np.int64).sum())
+        below = x[on].max() if day else None
+        above = x[(w != 0) & (x > x[last])].min()
+        assert (before == 0) == (day == 0) and before + 65536 <= W
+        probs = (0.0, prob_of_target(max(before, 1), W), prob_of_target(before + 1, W), prob_of_target(before + 65535, W), prob_of_target(before + 65536, W), 1.0)
+        ctx.bands_configure([PLANE], [LAST], probs, DAY, 0, None, 2, weights=w)
+        want, m, n_nan, Wd = one_day(ctx, x, w, probs, f"n = {n}, day {day}")
+        assert (m, n_nan, Wd) == (int((w != 0).sum()), 0, W) and want[0] == -1e300
+        assert want[1] == (below if day else x[last]) and want[2] == want[3] == x[last] and want[4] == above
+    ctx.close()
+
+
+@pytest.mark.parametrize("n_probs", [1, 8])
+@pytest.mark.parametrize("n_items", [1, 8])
+def test_items_and_probabilities(n_items, n_probs):
+    """tests/test_hip_bands.py's full width for the weighted selection: 1 and 8 items x 1 and 8 probabilities at 600 columns, eight
+    planes of different crafted values, SUM and LAST items over two dry days; header, values and weight sums against the restatement."""
+    from test_hip_bands import FULL_PROBS, assert_items_differ, full_width_days
+
+    n = 600
+    probs = (0.5,) if n_probs == 1 else FULL_PROBS
+    w = weights_of(n, seed=n_items + n_probs)
+    ctx, h = full_width_days(n, n_items, lambda kinds: HostWeightedBands(kinds, probs, n, w, DAY, 0),
+                             lambda c, names, kinds: c.bands_configure(names, kinds, probs, DAY, 0, None, 4, weights=w), seed=100 + n_items * 10 + n_probs)
+    want = h.rows()
+    assert want[1].shape == (2, n_items, n_probs) and want[2].shape == (2, n_items) and (want[0][:, 3] > 0).all(), "no NaN was counted"
+    assert_items_differ(want[1], f"{n_items} items x {n_probs} probabilities, weighted")
+    assert_weighted_rows(read_weighted(ctx), want, f"{n_items} items x {n_probs} probabilities, weighted")
     ctx.close()
 
 
