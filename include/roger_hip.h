@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 19  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore; 19: rh_bands_configure_weighted / rh_bands_weight_sums */
+#define RH_ABI_VERSION 20  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore; 19: rh_bands_configure_weighted / rh_bands_weight_sums; 20: rh_bands_observations / rh_bands_obs_read */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {
@@ -615,6 +615,29 @@ int rh_bands_zonal_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t 
 int rh_bands_configure_weighted(rh_ctx *ctx, const int *planes, const int *kinds /* 0 SUM, 1 LAST */, int n_items, const double *probs, int n_probs,
                                 int64_t interval_seconds, int64_t t_first, const uint16_t *weight /* [n], 0: takes no part */, int64_t capacity);
 int rh_bands_weight_sums(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *wsum /* (rows, n_items) */, size_t bytes);
+/* ... where the observation falls (ABI version 20): does the band contain the measurement?  Everything is the bands' rule as it stands
+ * -- clock, SUM / LAST aggregation, s = (acc or v) + 0.0, NaN handling, mask / zones / weights, ring numbering -- and on top of it:
+ *   Scope.  An item may carry observations: one float64 series per item without zones, one per zone with zones.  NaN means missing.
+ *   Indexing.  The series is indexed from the request's start, not from the first counted interval: for row interval number k the element
+ *   is o = obs[k + first_index], first_index = (t_first - start) / interval; an index beyond the series means missing.
+ *   The pair.  On a counted step, per item (and zone), an int64 pair (below, equal): o a NaN (missing, or an all-NaN series) gives below =
+ *   equal = -1; else o' = o + 0.0 and, over the participating columns whose s is a number, below = sum c_i [s_i < o'] and equal = sum c_i
+ *   [s_i == o'], c_i = 1 (plain, zonal) or w_i (weighted); with m == 0: (0, 0).  In numpy, x and wx the participants that are numbers:
+ *   below = int(wx[x < o].sum()), equal = int(wx[x == o].sum()).  On the device an unsigned comparison of keys with key(o'), which is
+ *   the float comparison for every value that is not a NaN, +-0.0 and +-inf included.
+ *   Consequences.  T_tot = m (plain, zonal) or W (weighted): 0 <= below, 0 <= equal, below + equal <= T_tot; for a recorded probability
+ *   p with T = clamp(ceil(p T_tot), 1, T_tot) and recorded quantile q: q <= o <=> below + equal >= T, and q < o <=> below >= T.
+ * One more pass over the key planes behind the selection (k_bands_obs and k_bands_obs_row; per zone k_bands_obs_zonal), launched only
+ * while observations are set: integer sums in registers, shuffles and LDS, no atomics (roger_amd/csrc/rh_bands.h).
+ *   rh_bands_observations  obs (n_items, n_series, n_intervals) float64; n_series is 1 on a plain or weighted configuration and n_zones on
+ *                          a zonal one (anything else: RH_ERR_ARG).  Valid behind any rh_bands_configure* call, at any time; RH_ERR_STATE
+ *                          before one.  Allocates the series, the workgroups' partials and the ring (capacity, n_items, n_series, 2)
+ *                          int64, every pair -1.  n_intervals == 0 releases them; so does every rh_bands_configure* call.  Synchronises.
+ *   rh_bands_obs_read      the pairs of the rows [first_row, first_row + n_rows): (n_rows, n_items, n_series, 2) int64; the row range and
+ *                          the size are checked as in rh_bands_read.  RH_ERR_STATE, naming rh_bands_observations, while no observations
+ *                          are set.  Synchronises. */
+int rh_bands_observations(rh_ctx *ctx, const double *obs /* (n_items, n_series, n_intervals) */, int n_series, int64_t n_intervals, int64_t first_index);
+int rh_bands_obs_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *pairs /* (rows, n_items, n_series, 2) {below, equal} */, size_t bytes);
 
 /* ---- carrying the scores, the duration curves, the event outputs and the bands through a restart (ABI version 18) ----
  * What the kernels keep between two launches is planes of plain data; these calls are copies, no kernel.  Reading: rh_scores_read and

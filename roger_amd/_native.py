@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 19  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 20  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -180,6 +180,8 @@ def load():
     lib.rh_bands_zonal_read.argtypes = [vp, i64, i64, vp, vp, C.c_size_t, vp, C.c_size_t]
     lib.rh_bands_configure_weighted.argtypes = [vp, vp, vp, i32, vp, i32, i64, i64, vp, i64]
     lib.rh_bands_weight_sums.argtypes = [vp, i64, i64, vp, C.c_size_t]
+    lib.rh_bands_observations.argtypes = [vp, vp, i32, i64, i64]
+    lib.rh_bands_obs_read.argtypes = [vp, i64, i64, vp, C.c_size_t]
     lib.rh_scores_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i64]
     lib.rh_durations_restore.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
     lib.rh_events_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -650,7 +652,7 @@ DECLARED_SYMBOLS = (
     "rh_events_configure", "rh_events_headers", "rh_events_download", "rh_events_set_drained", "rh_events_lost",
     "rh_durations_configure", "rh_durations_read",
     "rh_bands_configure", "rh_bands_count", "rh_bands_read", "rh_bands_configure_zonal", "rh_bands_zonal_read",
-    "rh_bands_configure_weighted", "rh_bands_weight_sums",
+    "rh_bands_configure_weighted", "rh_bands_weight_sums", "rh_bands_observations", "rh_bands_obs_read",
     "rh_scores_restore", "rh_durations_restore", "rh_events_state", "rh_events_restore", "rh_bands_state", "rh_bands_restore",
 )
 
@@ -1234,6 +1236,34 @@ class Context:
         wsum = np.empty((n, shape[0]), dtype=np.int64)
         self._check(self._lib.rh_bands_weight_sums(self._h, int(first), n, wsum.ctypes.data_as(C.c_void_p), wsum.nbytes), "rh_bands_weight_sums")
         return wsum
+
+    def bands_observations(self, obs, first_index=0):
+        """Observations behind bands_configure: float64 (items, intervals) -- with zones (items, zones, intervals) -- NaN: missing, an
+        all-NaN series: an item without observations.  Row interval k reads element k + first_index; beyond the series: missing.  From
+        then on every counted interval records per item (and zone) the int64 pair (below, equal): the members, or with weights their
+        weights, below and equal to the observation, -1 where it is missing (rh_bands_observations; bands_obs_read).  None, or no
+        intervals: release them.  Every bands_configure drops them."""
+        shape = getattr(self, "_bands_shape", (0, 0))
+        ni, ns = shape[0], (shape[1] if len(shape) == 3 else 1)
+        if obs is None or np.asarray(obs).size == 0:
+            self._check(self._lib.rh_bands_observations(self._h, None, ns, 0, 0), "rh_bands_observations")
+            return
+        o = np.ascontiguousarray(obs, dtype=np.float64)
+        if o.ndim == 2:
+            o = o[:, None, :]
+        if o.ndim != 3 or (ni and o.shape[0] != ni):   # (nothing configured: the call refuses)
+            raise ValueError(f"bands_observations: the observations have shape {np.shape(obs)}, the bands {ni} items ((items, intervals) or (items, series, intervals))")
+        self._check(self._lib.rh_bands_observations(self._h, o.ctypes.data_as(C.c_void_p), int(o.shape[1]), int(o.shape[2]), int(first_index)),
+                    "rh_bands_observations")
+
+    def bands_obs_read(self, first, n):
+        """The pairs of the rows [first, first + n): int64 (n, items, 2) {below, equal} -- with zones (n, items, zones, 2) -- -1 where the
+        observation is missing."""
+        n = int(n)
+        shape = getattr(self, "_bands_shape", (0, 0))
+        pairs = np.empty((n, shape[0]) + ((shape[1],) if len(shape) == 3 else ()) + (2,), dtype=np.int64)
+        self._check(self._lib.rh_bands_obs_read(self._h, int(first), n, pairs.ctypes.data_as(C.c_void_p), pairs.nbytes), "rh_bands_obs_read")
+        return pairs
 
     def bands_zonal_read(self, first, n):
         """Rows [first, first + n) of the ring of a configuration with zones: (hdr int64 (n, 2): k, t1; counts int64 (n, items, zones, 2):

@@ -13,6 +13,7 @@ A setup script fills `state.bands` in `set_diagnostics`:
     state.bands.mask          = None                                  # or (nx, ny) over the GLOBAL interior, 0: column takes no part
     state.bands.zones         = None                                  # or int (nx, ny) over the GLOBAL interior, <= 0: outside every zone
     state.bands.weights       = None                                  # or (nx, ny) over the GLOBAL interior: likelihood weights, the GLUE band
+    state.bands.observations  = {}                                    # or {"q_ss": series}: where the measurement falls in the ensemble
     state.bands.capacity      = 4096                                  # rows resident on the device; with zones at most what 64 MiB hold
     state.bands.base_output_path = ...                                # as for the diagnostics
 
@@ -61,6 +62,23 @@ without weights under mask = (w != 0), and W == m.  `read()` gains "<v>_w", an (
 attribute weights = "integer 0 ... 65535: rint(w / max(w) * 65535)".  Without weights `read()` and the file are byte for byte what
 they were.
 
+Observations.  Does the band contain the measurement?  `observations = {"q_ss": obs}` gives a variable a float series, NaN: missing, of
+shape (n_intervals,) -- with zones (n_zones, n_intervals) in the order of the ascending global zone list, or (n_intervals,) for every
+zone.  The rule (roger_amd/csrc/rh_bands.h) -- everything is the rule above as it stands, and on top of it: the series is indexed from
+`start`, not from the first counted interval: for row interval number k the element is o = obs[k + (t_first - start) / frequency], so a
+continued run without `resume` stays aligned; an index beyond the series means missing.  On a counted step, per variable (and zone), an
+int64 pair (below, equal): o a NaN (missing, or the variable has no observations) gives below = equal = -1; else o' = o + 0.0 and, over
+the participating columns whose s is a number, below = sum c_i [s_i < o'] and equal = sum c_i [s_i == o'], c_i = 1 or, with weights, the
+integer weight w_i; with m == 0: (0, 0).  In numpy, x and wx the participants that are numbers:
+    below = int(wx[x < o].sum());  equal = int(wx[x == o].sum())
+exact integers, like the rest of the row.  With T_tot = m (or W with weights): 0 <= below, 0 <= equal, below + equal <= T_tot, and for a
+recorded probability p with T = clamp(ceil(p * T_tot), 1, T_tot) and recorded quantile q: q <= o <=> below + equal >= T, and q < o <=>
+below >= T -- so o lies inside [q_lo, q_hi] iff below + equal >= T_lo and below < T_hi: `inside`, whose mean over the observed rows is the
+containing ratio.  `read()` gains "<v>_obs" (float64, NaN where missing), "<v>_below" and "<v>_equal" (int64, -1 where missing); the file
+gains `v_obs`, `v_below`, `v_equal` and `v_pit = (below + equal / 2) / T_tot` (`_FillValue` where the observation is missing or the
+total is 0) over (Time) or (Time, zone) -- `rank_histogram` bins it -- and the global attribute `observations`.  Without observations
+nothing new is launched and `read()` and the file are byte for byte what they were.
+
 Several ranks.  With zones a rank computes the bands of its own block over the GLOBAL zone list: a zone without a column in the block has
 v_n = 0 and fill values, and a rank whose block holds no participating column configures nothing and writes no file.  Order statistics
 of blocks do not merge, so there is no `combine`: a rank computes the bands of ITS OWN block and writes
@@ -75,7 +93,8 @@ Resuming.  With `state.bands.resume = True` every restart file that is written h
 interval under way, the start of the first counted interval, the number of rows recorded so far and the request.  The rows themselves do
 not go into the restart file: the ring is drained and `<identifier>.bands.nc` is written at that moment.  A run that reads such a file with
 `resume = True` and the same request -- variables and kinds, probabilities, frequency, start, mask, zone map, grid and, where weights are
-given, their integer map (a file written with weights resumed without them, or the other way round, is the same error) -- configures the
+given, their integer map, and likewise the observations (a file written with weights or observations resumed without them, or the other
+way round, is the same error) -- configures the
 device with the stored start, uploads the accumulators and goes on numbering rows and intervals where the interrupted run stopped: the
 interrupted run's rows followed by the continued run's are the uninterrupted run's, the interval that holds the restart among them, plain
 and per zone.  (The ring, the key planes and the selection's scratch are no state: they are rewritten or zero between two steps.)  A
@@ -93,6 +112,9 @@ MAX_VARIABLES = 8                 # roger_amd/csrc/rh_bands.h: RH_BANDS_MAX_ITEM
 MAX_PROBABILITIES = 8             # ... RH_BANDS_MAX_PROBS
 MAX_WEIGHT = 65535                # the weight plane is uint16
 WEIGHTS_ATTRIBUTE = "integer 0 ... 65535: rint(w / max(w) * 65535)"
+OBSERVATIONS_ATTRIBUTE = ("v_below, v_equal: the members (with weights: their integer weights) whose interval value is < and == v_obs, -1 where it is "
+                          "missing; v_pit = (below + equal / 2) / total; v_obs lies inside [q(p_lo), q(p_hi)] iff below + equal >= T(p_lo) and "
+                          "below < T(p_hi), T(p) = clamp(ceil(p total), 1, total), total = v_n (with weights v_w)")
 FREQUENCIES = (DAY, 3600, 600)    # the step classes
 KINDS = {"sum": 0, "last": 1}
 
@@ -100,7 +122,8 @@ KINDS = {"sum": 0, "last": 1}
 class Bands(RingSeries):
     """`state.bands`: what the script sets (variables, aggregation, probabilities, frequency, start, mask, zones, weights, capacity,
     base_output_path) and the rows drained so far: headers (n, 2 + 2 V) int64 and values (n, V, P) float64 -- with zones headers (n, 2),
-    counts (n, V, Z, 2) int64 and values (n, V, Z, P); with weights the weight sums (n, V) int64 beside the headers."""
+    counts (n, V, Z, 2) int64 and values (n, V, Z, P); with weights the weight sums (n, V) int64 beside the headers; with observations the
+    pairs (n, V, 2) or (n, V, Z, 2) int64 {below, equal}."""
 
     label = attribute = "bands"
     group = "hip_bands"
@@ -115,6 +138,7 @@ class Bands(RingSeries):
         self.mask = None
         self.zones = None
         self.weights = None
+        self.observations = {}
         self.base_output_path = None
         self.output_path = "{identifier}.bands.nc"
         self._state = None
@@ -129,6 +153,8 @@ class Bands(RingSeries):
         self._counts = []        # ... drained counts
         self._weights = None     # weights: the GLOBAL integer map, uint16 (nx, ny), as quantised by `initialize`; None without weights
         self._wsum = []          # ... drained weight sums
+        self._obs = None         # observations: float64 (V, L) or (V, Z, L), NaN: missing, as formed by `initialize`; None without
+        self._pairs = []         # ... drained pairs
 
     @property
     def active(self):
@@ -148,6 +174,7 @@ class Bands(RingSeries):
                 out[v] = values[:, j].copy()              # (n, Z, P)
                 out[f"{v}_n"] = counts[:, j, :, 0].copy()   # (n, Z)
                 out[f"{v}_nan"] = counts[:, j, :, 1].copy()
+            self._read_observations(out, hdr)
             return out
         hdr, values = self._all_rows()
         out = {"interval": hdr[:, 0].copy(), "time": hdr[:, 1].copy()}
@@ -157,7 +184,50 @@ class Bands(RingSeries):
             out[f"{v}_nan"] = hdr[:, 3 + 2 * j].copy()
             if self._weights is not None:
                 out[f"{v}_w"] = self._all_wsum()[:, j].copy()
+        self._read_observations(out, hdr)
         return out
+
+    def _first_index(self):
+        """The element of a series the first counted interval reads: the series is indexed from `start`."""
+        return (int(self._t_first) - int(self.start)) // int(self.frequency)
+
+    def _obs_rows(self, hdr):
+        """The observation of every drained row, (n, V) or (n, V, Z): NaN where missing or beyond the series."""
+        at = hdr[:, 0] + self._first_index()
+        ok = (at >= 0) & (at < self._obs.shape[-1])
+        out = np.full(self._obs.shape[:-1] + (len(at),), np.nan)
+        out[..., ok] = self._obs[..., at[ok]]
+        return np.moveaxis(out, -1, 0)
+
+    def _all_pairs(self):
+        return np.concatenate(self._pairs) if self._pairs else np.empty((0,) + self._obs.shape[:-1] + (2,), dtype=np.int64)
+
+    def _read_observations(self, out, hdr):
+        """`read()`: "<v>_obs", "<v>_below", "<v>_equal" of the observed variables; nothing without observations."""
+        if self._obs is None:
+            return
+        obs, pairs = self._obs_rows(hdr), self._all_pairs()
+        for j, v in enumerate(self._names):
+            if v in self.observations:
+                out[f"{v}_obs"] = obs[:, j].copy()
+                out[f"{v}_below"] = pairs[:, j, ..., 0].copy()
+                out[f"{v}_equal"] = pairs[:, j, ..., 1].copy()
+
+    def _write_observations(self, variables, extra, hdr, totals, dims):
+        """The file: v_obs, v_below, v_equal and v_pit over `dims`, and the global attribute; totals (n, V[, Z]): m, or W with weights."""
+        if self._obs is None:
+            return
+        obs, pairs = self._obs_rows(hdr), self._all_pairs()
+        for j, v in enumerate(self._names):
+            if v not in self.observations:
+                continue
+            o, below, equal, total = obs[:, j], pairs[:, j, ..., 0], pairs[:, j, ..., 1], np.asarray(totals)[:, j]
+            variables[f"{v}_obs"] = (dims, np.where(np.isnan(o), FILL, o), {"_FillValue": np.float64(FILL), "long_name": f"{v}: the observation of the interval", "units": ""})
+            variables[f"{v}_below"] = (dims, np.ascontiguousarray(below), {"long_name": f"{v}: members below the observation (-1: no observation)", "units": ""})
+            variables[f"{v}_equal"] = (dims, np.ascontiguousarray(equal), {"long_name": f"{v}: members equal to the observation (-1: no observation)", "units": ""})
+            variables[f"{v}_pit"] = (dims, pit(below, equal, total, fill=FILL),
+                                     {"_FillValue": np.float64(FILL), "long_name": f"{v}: (below + equal / 2) / total, where the observation sits in the ensemble", "units": ""})
+        extra["observations"] = OBSERVATIONS_ATTRIBUTE
 
     def _request(self, state):
         """What a resumed run must ask for again (observers.check_same_request)."""
@@ -167,6 +237,8 @@ class Bands(RingSeries):
                    "grid": np.asarray([state.settings.nx, state.settings.ny], dtype=np.int64)}
         if self._weights is not None:   # (only then: the groups of runs without weights stay what they were)
             request["weights"] = map_array(self._weights, np.int64)
+        if self._obs is not None:       # (likewise)
+            request["observations"] = map_array(self._obs, np.float64)
         return request
 
     def restart_state(self, state):
@@ -183,20 +255,27 @@ class Bands(RingSeries):
         return ctx.bands_count()
 
     def _rows(self, ctx, first, n):
+        pairs = () if self._obs is None else (ctx.bands_obs_read(first, n),)
         if self._weights is not None:
-            return ctx.bands_read(first, n) + (ctx.bands_weight_sums(first, n),)
-        return ctx.bands_read(first, n) if self._ids is None else ctx.bands_zonal_read(first, n)
+            return ctx.bands_read(first, n) + (ctx.bands_weight_sums(first, n),) + pairs
+        return (ctx.bands_read(first, n) if self._ids is None else ctx.bands_zonal_read(first, n)) + pairs
 
     def _keep(self, state, hdr, *rest):
+        if self._obs is not None:       # (the pairs beside the rows, last)
+            self._pairs.append(rest[-1])
+            return self._keep_rows(state, hdr, *rest[:-1]) + rest[-1].nbytes
+        return self._keep_rows(state, hdr, *rest)
+
+    def _keep_rows(self, state, hdr, *rest):
         if self._weights is not None:
             values, wsum = rest
             self._wsum.append(wsum)
-            return super()._keep(state, hdr, values) + wsum.nbytes
+            return RingSeries._keep(self, state, hdr, values) + wsum.nbytes
         if self._ids is None:
-            return super()._keep(state, hdr, *rest)
+            return RingSeries._keep(self, state, hdr, *rest)
         counts, values = rest
         self._counts.append(counts)
-        return super()._keep(state, hdr, values) + counts.nbytes
+        return RingSeries._keep(self, state, hdr, values) + counts.nbytes
 
     def _all_rows(self):
         nv, npr = len(self._names), len(self._probs)
@@ -238,6 +317,7 @@ class Bands(RingSeries):
         extra = {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}
         if self._weights is not None:
             extra["weights"] = WEIGHTS_ATTRIBUTE
+        self._write_observations(variables, extra, hdr, self._all_wsum() if self._weights is not None else hdr[:, 2::2], ("Time",))
         write_file(self._path, {"Time": None, "probability": len(self._probs)}, variables, global_attributes(
             settings.identifier, "Exact quantiles across the columns of interval values, one record per counted interval.", extra,
             lead={"columns": "this rank's block"}))
@@ -263,15 +343,73 @@ class Bands(RingSeries):
                              "units": _UNITS.get(v, "")})
             variables[f"{v}_n"] = (("Time", "zone"), np.ascontiguousarray(counts[:, j, :, 0]), {"long_name": f"{v}: columns of the zone that took part", "units": ""})
             variables[f"{v}_nan"] = (("Time", "zone"), np.ascontiguousarray(counts[:, j, :, 1]), {"long_name": f"{v}: participating columns of the zone with a NaN", "units": ""})
+        extra = {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}
+        self._write_observations(variables, extra, hdr, counts[..., 0], ("Time", "zone"))
         write_file(self._path, {"Time": None, "zone": len(self._ids), "probability": len(self._probs)}, variables, global_attributes(
             settings.identifier, "Exact quantiles across the columns of every zone of interval values, one record per counted interval.",
-            {"frequency_seconds": int(self.frequency), "first_interval_starts_seconds": int(self._t_first)}, lead={"columns": "this rank's block"}))
+            extra, lead={"columns": "this rank's block"}))
 
 
 def zonal_capacity(capacity, n_variables, n_zones, n_probabilities):
     """The rows of V Z P 8 + V Z 16 + 16 bytes that RING_BYTES (64 MiB) hold, at most `capacity` and at least one."""
     v, z, p = int(n_variables), int(n_zones), int(n_probabilities)
     return int(max(1, min(int(capacity), RING_BYTES // (v * z * p * 8 + v * z * 16 + 16))))
+
+
+def targets(p, total):
+    """T = clamp(ceil(p * total), 1, total) of a probability under totals (m, or W with weights): one double multiplication, one ceil."""
+    total = np.asarray(total, dtype=np.int64)
+    return np.clip(np.ceil(float(p) * total.astype(np.float64)).astype(np.int64), 1, np.maximum(total, 1))
+
+
+def inside(below, equal, total, p_lo, p_hi):
+    """Whether the observation lies inside [q(p_lo), q(p_hi)], from the recorded counts alone: below + equal >= T(p_lo) and below <
+    T(p_hi) -- the same answer as q_lo <= o <= q_hi on the recorded quantiles.  False where the observation is missing (-1) or nothing
+    took part (total == 0).  The containing ratio is its mean over the observed rows."""
+    below, equal, total = (np.asarray(a, dtype=np.int64) for a in (below, equal, total))
+    return (below >= 0) & (total > 0) & (below + equal >= targets(p_lo, total)) & (below < targets(p_hi, total))
+
+
+def pit(below, equal, total, fill=np.nan):
+    """(below + equal / 2) / total, `fill` where the observation is missing (-1) or nothing took part (total == 0)."""
+    below, equal, total = (np.asarray(a, dtype=np.int64) for a in (below, equal, total))
+    ok = (below >= 0) & (total > 0)
+    return np.where(ok, (below + equal / 2.0) / np.where(ok, total, 1), fill)
+
+
+def rank_histogram(pit_values, bins=10, fill=None):
+    """Counts of the PIT values in `bins` equal bins over [0, 1] (1.0 in the last): int64 (bins,).  NaN and `fill` (default: the files'
+    _FillValue) are left out.  A flat histogram: the ensemble spreads as the observations do."""
+    x = np.asarray(pit_values, dtype=np.float64).reshape(-1)
+    x = x[(x == x) & (x != (FILL if fill is None else fill))]
+    if int(bins) < 1:
+        raise ValueError(f"bands.rank_histogram: bins = {bins} (at least one)")
+    if x.size and (x.min() < 0.0 or x.max() > 1.0):
+        raise ValueError(f"bands.rank_histogram: PIT values lie within [0, 1] (got {x.min()} ... {x.max()})")
+    return np.histogram(x, bins=int(bins), range=(0.0, 1.0))[0].astype(np.int64)
+
+
+def check_observations(observations, names, n_zones):
+    """`state.bands.observations` as float64 (V, L) -- with zones (V, Z, L) -- NaN: missing, a variable without observations all NaN, a
+    shorter series NaN behind its end."""
+    series = {}
+    for v, a in dict(observations).items():
+        if v not in names:
+            raise ValueError(f"bands: observations names {v!r}, which is not among the variables")
+        a = np.asarray(a)
+        if a.dtype.kind != "f":
+            raise ValueError(f"bands: the observations of {v!r} have dtype {a.dtype} (a float array, NaN: missing)")
+        if a.ndim != 1 and not (n_zones is not None and a.ndim == 2 and a.shape[0] == n_zones):
+            want = "(n_intervals,)" if n_zones is None else f"(n_intervals,) or ({n_zones}, n_intervals): a series per zone of the ascending zone list"
+            raise ValueError(f"bands: the observations of {v!r} have shape {a.shape} ({want})")
+        if a.shape[-1] == 0:
+            raise ValueError(f"bands: the observations of {v!r} are empty (at least one interval)")
+        series[v] = a.astype(np.float64)
+    out = np.full((len(names),) + (() if n_zones is None else (int(n_zones),)) + (max(a.shape[-1] for a in series.values()),), np.nan)
+    for j, v in enumerate(names):
+        if v in series:
+            out[j, ..., :series[v].shape[-1]] = series[v]
+    return out
 
 
 def check_weights(weights, mask, settings):
@@ -345,6 +483,7 @@ def initialize(state):
         b._ids = ids.astype(np.int64)
         b._index = index if mask is None else np.where(mask, index, -1).astype(np.int32)   # (a zone the mask empties stays in the list)
         b.capacity = zonal_capacity(b.capacity, len(names), ids.size, len(probs))
+    b._obs = check_observations(b.observations, names, None if b._ids is None else b._ids.size) if b.observations else None
     b._names = names
     b._kinds = [KINDS[b.aggregation.get(v, default_kind(v))] for v in names]
     b._probs = probs
@@ -368,6 +507,10 @@ def start(state):
         if b._weights is None and held.get("request_weights") is not None:   # (the other direction is check_same_request's: a key the file lacks)
             raise RuntimeError(f"bands: resume = True, but the restart file {b._restart_file} was written with weights = an array of shape "
                                f"{np.asarray(held['request_weights']).shape} and this run asks for weights = None: a resumed observer takes the same request")
+        if b._obs is None and held.get("request_observations") is not None:   # (likewise)
+            raise RuntimeError(f"bands: resume = True, but the restart file {b._restart_file} was written with observations = an array of shape "
+                               f"{np.asarray(held['request_observations']).shape} and this run asks for observations = {{}}: a resumed observer takes "
+                               "the same request")
         b._t_first = int(held["scalars"][0])
     b._local = None
     if b._ids is not None:
@@ -392,8 +535,10 @@ def start(state):
                 return   # (several ranks: no masked-in column in this rank's block)
         vs.flush_to_device()
         state.backend_context.bands_configure(b._names, b._kinds, b._probs, f, b._t_first, b._local, int(b.capacity))
+    if b._obs is not None:
+        state.backend_context.bands_observations(b._obs, first_index=b._first_index())
     b._begin()
-    b._hdr, b._values, b._counts, b._wsum = [], [], [], []
+    b._hdr, b._values, b._counts, b._wsum, b._pairs = [], [], [], [], []
     if held is not None:
         rows = int(held["scalars"][1])
         state.backend_context.bands_restore(held["acc"], rows)

@@ -64,6 +64,10 @@
 //
 // Likelihood-weighted (rh_bands_configure_weighted): the GLUE band -- column i counts as w_i identical members.  k_bands runs unchanged
 // and k_bands_select_w<P> takes the place of the six k_bands_select<P>: behind k_bands_zonal in this file, the rule with it.
+//
+// Observations (rh_bands_observations): does the band contain the measurement?  Per counted interval, item (and zone) the int64 pair
+// (below, equal) -- the members, or their weights, below and equal to the observation -- counted from the key planes in one more pass
+// behind the selection: k_bands_obs, k_bands_obs_row and k_bands_obs_zonal at the end of this file, the rule with them.
 #pragma once
 
 #define RH_BANDS_MAX_ITEMS 8
@@ -622,5 +626,173 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
             }
             D->bands_rows = row + 1;
         }
+    }
+}
+
+// ---- where the observation falls (rh_bands_observations) ----
+// The rule.  Everything is the bands' rule as it stands: clock, SUM / LAST aggregation, s = (acc or v) + 0.0, NaN handling, mask / zones /
+// weights, ring numbering.  On top of it an item may carry observations: one float64 series per item without zones, one per zone with
+// zones; NaN: missing.
+// Indexing.  The series is indexed from the configuration's `start`, not from the first counted interval: for row interval number k the
+// element is o = obs[k + bands_obs_first], bands_obs_first = (t_first - start) / frequency (the caller's); an index beyond the series
+// means missing.
+// The pair.  On a counted step, per item (and zone), an int64 pair (below, equal) goes into a ring beside the rows: o a NaN -- below =
+// equal = -1; else o' = o + 0.0 and, over the participating columns whose s is a number,
+//     below = sum c_i [s_i < o'],  equal = sum c_i [s_i == o'],  c_i = 1 (plain, zonal) or w_i (weighted);  m == 0: (0, 0).
+// In numpy, x and wx the participants that are numbers: below = int(wx[x < o].sum()), equal = int(wx[x == o].sum()).  On the device an
+// UNSIGNED comparison of the keys k_bands stored with key(o'): because of the + 0.0 on both sides it is the float comparison for every
+// value that is not a NaN, +-0.0 and +-inf included.
+// Consequences.  T_tot = m (plain, zonal) or W (weighted): 0 <= below, 0 <= equal, below + equal <= T_tot; for a recorded probability p
+// with target T = clamp(ceil(p T_tot), 1, T_tot) and recorded quantile q:  q <= o <=> below + equal >= T,  q < o <=> below >= T.
+//
+// k_bands_obs (plain and weighted): grid (min(RH_BANDS_MAX_GRID, ntiles), items) behind the selection's last pass.  A workgroup strides
+// over the tiles of its item's key plane as k_bands_select does (eight tiles in flight per thread); a thread adds 1, or bands_weight[i],
+// into two int64 registers; keys >= RH_BANDS_KEY_NAN are skipped (a zero weight needs no test: that key is RH_BANDS_KEY_MASKED).  The
+// wavefronts reduce by shuffles, the four of a workgroup through LDS, and thread 0 stores the workgroup's pair into bands_obs_part
+// [item][workgroup][2]: plain stores, no atomics, no last-workgroup pattern.  A missing o ends the workgroup after the scalar loads.
+// k_bands_obs_row: grid (items), one wavefront; adds the partials and writes the pair at the slot of the row just recorded -- the
+// selection's last pass has advanced bands_rows, so that is (bands_rows - 1) mod bands_cap.  Stream order stands where the plain path has
+// its completion counter.
+// k_bands_obs_zonal: grid (zones, items) behind k_bands_zonal_row; a workgroup walks its zone's column list as bands_zonal_pass does,
+// reduces likewise and writes its pair itself.
+// All three end after the scalar loads on a step that is not counted, and under after_fused && D->skipped.
+// No sum overflows: a thread, a workgroup and an item add at most n < 2^31 columns of weight <= 65535 -- below 2^47, as W.
+// Cost of a counted step with observations: one more pass of 8 B (+ 2 B with weights) per item and column, on top of the selection's
+// six, and two launches (zonal: one launch, 8 B + 4 B per participating column gathered).
+static inline unsigned bands_obs_grid(long long n) {
+    const long long ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    return (unsigned)(ntiles < RH_BANDS_MAX_GRID ? (ntiles < 1 ? 1 : ntiles) : RH_BANDS_MAX_GRID);
+}
+// the observation of (item j, series z) for the interval the clock closes; NaN: missing, or beyond the series
+RH_DEV double bands_obs_of(const DevState *D, const BandsClock &c, int j, int z, int nseries) {
+    const long long at = c.k + D->bands_obs_first, len = D->bands_obs_n;
+    return at >= 0 && at < len ? D->bands_obs[((size_t)j * nseries + z) * (size_t)len + (size_t)at] : __builtin_nan("");
+}
+// key(o + 0.0): the key expression of k_bands (o is not a NaN)
+RH_DEV unsigned long long bands_obs_key(double o) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(o + 0.0);
+    return u ^ ((u >> 63) ? ~0ull : 1ull << 63);
+}
+// the workgroup's sums of two int64 values: shuffles within a wavefront, LDS across the RH_BLOCK / 64 of them; thread 0 holds the result
+RH_DEV void bands_obs_reduce(long long &below, long long &equal, long long (*s_part)[2]) {
+    for (int off = 32; off; off >>= 1) {
+        below += __shfl_xor(below, off);
+        equal += __shfl_xor(equal, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_part[threadIdx.x >> 6][0] = below;
+        s_part[threadIdx.x >> 6][1] = equal;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        below = equal = 0;
+        for (int w = 0; w < RH_BLOCK / 64; ++w) {
+            below += s_part[w][0];
+            equal += s_part[w][1];
+        }
+    }
+}
+__global__ __launch_bounds__(RH_BLOCK) void k_bands_obs(Arena a, DevState *D, int after_fused) {
+    constexpr int U = 8;
+    __shared__ long long s_part[RH_BLOCK / 64][2];
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;   // (uniform over the grid)
+    const int j = blockIdx.y;
+    const double o = bands_obs_of(D, c, j, 0, 1);
+    if (o != o) return;   // (uniform over the item's workgroups: k_bands_obs_row writes -1, -1 and reads no partial)
+    const unsigned long long ko = bands_obs_key(o);
+    const int64_t n = a.n, ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
+    const unsigned short *wts = D->bands_weight;   // (null: every participating column counts 1)
+    long long below = 0, equal = 0;   // (below 2^47: at most n < 2^31 columns of weight <= 65535)
+    for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
+        unsigned long long key[U];
+        long long w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = (t + (int64_t)u * gridDim.x) * RH_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
+            key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_BANDS_KEY_MASKED;
+            w[u] = wts ? (i < n ? (long long)__builtin_nontemporal_load(wts + i) : 0ll) : 1ll;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (key[u] >= RH_BANDS_KEY_NAN) continue;
+            below += key[u] < ko ? w[u] : 0ll;
+            equal += key[u] == ko ? w[u] : 0ll;
+        }
+    }
+    bands_obs_reduce(below, equal, s_part);
+    if (threadIdx.x == 0) {
+        long long *part = D->bands_obs_part + ((size_t)j * gridDim.x + blockIdx.x) * 2;
+        part[0] = below;
+        part[1] = equal;
+    }
+}
+__global__ __launch_bounds__(64) void k_bands_obs_row(DevState *D, int nparts, int after_fused) {
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;
+    const int j = blockIdx.x, ni = gridDim.x;
+    const double o = bands_obs_of(D, c, j, 0, 1);
+    long long below = 0, equal = 0;
+    if (o == o) {   // (uniform over the wavefront)
+        const long long *part = D->bands_obs_part + (size_t)j * nparts * 2;
+        for (int b = threadIdx.x; b < nparts; b += 64) {
+            below += part[2 * b];
+            equal += part[2 * b + 1];
+        }
+        for (int off = 32; off; off >>= 1) {
+            below += __shfl_xor(below, off);
+            equal += __shfl_xor(equal, off);
+        }
+    } else {
+        below = equal = -1;
+    }
+    if (threadIdx.x == 0) {
+        long long *out = D->bands_obs_ring + ((size_t)((D->bands_rows - 1) % D->bands_cap) * ni + j) * 2;
+        out[0] = below;
+        out[1] = equal;
+    }
+}
+__global__ __launch_bounds__(RH_BLOCK) void k_bands_obs_zonal(DevState *D, long long n, int after_fused) {
+    constexpr int U = 8;
+    __shared__ long long s_part[RH_BLOCK / 64][2];
+    if (after_fused && D->skipped) return;
+    const BandsClock c = bands_clock(D);
+    if (!c.counted) return;   // (uniform over the grid)
+    const int z = blockIdx.x, j = blockIdx.y, nz = gridDim.x, ni = gridDim.y;
+    long long *out = D->bands_obs_ring + (((size_t)((D->bands_rows - 1) % D->bands_cap) * ni + j) * nz + z) * 2;
+    const double o = bands_obs_of(D, c, j, z, nz);
+    if (o != o) {   // (uniform over the workgroup)
+        if (threadIdx.x == 0) out[0] = out[1] = -1;
+        return;
+    }
+    const unsigned long long ko = bands_obs_key(o);
+    const long long beg = D->bands_zone_off[z], end = D->bands_zone_off[z + 1];
+    const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
+    const int *cols = D->bands_zone_cols;
+    long long below = 0, equal = 0;   // (at most n < 2^31)
+    for (long long base = beg; base < end; base += (long long)RH_BLOCK * U) {
+        int col[U];
+        unsigned long long key[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long at = base + (long long)u * RH_BLOCK + threadIdx.x;
+            col[u] = at < end ? cols[at] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) key[u] = col[u] >= 0 ? keys[col[u]] : RH_BANDS_KEY_MASKED;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (key[u] >= RH_BANDS_KEY_NAN) continue;
+            below += key[u] < ko ? 1ll : 0ll;
+            equal += key[u] == ko ? 1ll : 0ll;
+        }
+    }
+    bands_obs_reduce(below, equal, s_part);
+    if (threadIdx.x == 0) {
+        out[0] = below;
+        out[1] = equal;
     }
 }

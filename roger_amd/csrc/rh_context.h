@@ -176,6 +176,10 @@ struct rh_ctx {
     DevBuf<unsigned short> bands_weight_buf;
     DevBuf<unsigned long long> bands_whist_buf;
     DevBuf<long long> bands_wsum_buf;
+    // ... observations (rh_bands_observations): the series (item, series, interval), the workgroups' partial pairs and the ring of the
+    // rows' pairs (bands_nitems x series x 2 int64 a row); held: the k_bands_obs* launches follow the selection's
+    DevBuf<double> bands_obs_buf;
+    DevBuf<long long> bands_obs_part_buf, bands_obs_ring_buf;
     // carrying the four through a restart (ABI version 18, rh_*_restore): an observer is FRESH from its configure call until the first
     // step that launches the observers -- only then may its state be replaced; scores_interval is the host copy the restore checks a
     // carried t_first against

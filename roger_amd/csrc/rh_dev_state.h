@@ -220,6 +220,13 @@ struct DevState {
     long long *bands_wsum;
     unsigned bands_m_count[8];
     long long bands_w[8];
+    // ... observations (rh_bands_observations; k_bands_obs, k_bands_obs_row, k_bands_obs_zonal): bands_obs (item, series, bands_obs_n)
+    // float64, NaN: missing, series: 1, or the zones; row interval k reads element k + bands_obs_first.  bands_obs_part (item, workgroup,
+    // 2) int64: the workgroups' {below, equal} of the step under way (plain and weighted); bands_obs_ring (row, item, series, 2) int64
+    // {below, equal}, a ring beside bands_hdr, -1: no observation.  Null without observations.
+    const double *bands_obs;
+    long long *bands_obs_part, *bands_obs_ring;
+    long long bands_obs_n, bands_obs_first;
 };
 
 // What the host reads after a step, in pinned host memory that the device writes directly (hipHostMallocMapped): k_export copies the

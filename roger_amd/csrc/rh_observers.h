@@ -3,7 +3,8 @@
 // (rh_scores_*), the event outputs (rh_events_*), the duration curves (rh_durations_*) and the ensemble bands (rh_bands_*).  Part of the
 // one translation unit roger_hip.hip, behind rh_context.h.  ABI version 18: the last four are carried through a restart by plain copies
 // (rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore); no kernel is involved.  ABI version
-// 19: rh_bands_configure_weighted / rh_bands_weight_sums, the likelihood-weighted bands (k_bands_select_w in rh_bands.h).
+// 19: rh_bands_configure_weighted / rh_bands_weight_sums, the likelihood-weighted bands (k_bands_select_w in rh_bands.h).  ABI version
+// 20: rh_bands_observations / rh_bands_obs_read, where the observation falls in the ensemble (k_bands_obs* in rh_bands.h).
 #pragma once
 // The observers' planes changed (rh_diag_configure, rh_points_configure, rh_totals_configure, rh_zonal_configure, rh_scores_configure,
 // rh_events_configure, rh_durations_configure, rh_bands_configure): what the fused kernel must leave in memory after every step, from
@@ -53,7 +54,8 @@ static int observers_changed(rh_ctx *ctx) {
 // (rh_durations.h) -- then the ensemble bands: the keys on the same grid, and the six passes of the selection on at most
 // RH_BANDS_MAX_GRID workgroups that stride over the tiles -- per zone instead ONE launch with a workgroup per (zone, item) and a
 // one-thread launch for the row's header; with a weight plane the six passes of the weighted selection on bands_weighted_grid
-// workgroups (rh_bands.h).  after_fused: rh_control.h, k_diag.
+// workgroups (rh_bands.h); and only while observations are set (rh_bands_observations) the pass that counts the keys below and equal to
+// the observation's and a one-wavefront launch per item for the row's pairs -- per zone ONE launch.  after_fused: rh_control.h, k_diag.
 static bool has_observers(const rh_ctx *ctx) {
     return ctx->diag_n || ctx->points_ncells || ctx->totals_nplanes || ctx->zonal_nplanes || ctx->scores_nitems || ctx->events_nitems ||
            ctx->durations_nitems || ctx->bands_nitems;
@@ -97,6 +99,16 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
             hipLaunchKernelGGL(k_bands_select<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
             hipLaunchKernelGGL(k_bands_select<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
             hipLaunchKernelGGL(k_bands_select<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+        }
+        if (ctx->bands_obs_buf) {   // observations: the pairs {below, equal} behind the row, from the key planes the selection read
+            if (ctx->bands_nzones) {
+                hipLaunchKernelGGL(k_bands_obs_zonal, dim3(ctx->bands_nzones, ctx->bands_nitems), block, 0, ctx->stream, ctx->dev, (long long)ctx->n,
+                                   after_fused);
+            } else {
+                const unsigned parts = bands_obs_grid((long long)ctx->n);
+                hipLaunchKernelGGL(k_bands_obs, dim3(parts, ctx->bands_nitems), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+                hipLaunchKernelGGL(k_bands_obs_row, dim3(ctx->bands_nitems), dim3(64), 0, ctx->stream, ctx->dev, (int)parts, after_fused);
+            }
         }
     }
     CHECK_LAUNCH(ctx);
@@ -943,6 +955,21 @@ struct BandsZones {
     std::vector<unsigned char> mask;
     std::vector<int> index;
 };
+// the observations' buffers released and their members of the control block null: no later step launches k_bands_obs*.  (The caller has
+// synchronised the stream; the sources are static.)
+static int bands_obs_release(rh_ctx *ctx) {
+    static const long long *const none = nullptr;
+    static const long long zero = 0;
+    HIPCHK(ctx, ctx->bands_obs_buf.release());
+    HIPCHK(ctx, ctx->bands_obs_part_buf.release());
+    HIPCHK(ctx, ctx->bands_obs_ring_buf.release());
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs, none));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_part, none));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_ring, none));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_n, zero));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_first, zero));
+    return RH_OK;
+}
 // the buffers: the ring, the accumulators at +0.0, every key "masked out" (a masked-in column stores its key on every counted step), the
 // histograms at 0 (the plain selection's alone); per zone the counts and the column lists; with weights the weight plane, the 64-bit
 // histograms at 0 in place of the 32-bit ones, and the ring of the rows' weight sums
@@ -1058,6 +1085,7 @@ static int bands_configure(rh_ctx *ctx, const std::string &who, const int *plane
     HIPCHK(ctx, ctx->bands_weight_buf.release());
     HIPCHK(ctx, ctx->bands_whist_buf.release());
     HIPCHK(ctx, ctx->bands_wsum_buf.release());
+    if (int rc = bands_obs_release(ctx)) return rc;   // (observations belong to the configuration they were set behind)
     ctx->bands_nitems = ctx->bands_nprobs = ctx->bands_nzones = 0;
     ctx->obs_fresh &= ~(unsigned)RH_FRESH_BANDS;
     if (int rc = off ? RH_OK : bands_alloc(ctx, n_items, n_probs, mask, zones, weight, capacity)) {   // refused: the observer is off
@@ -1174,6 +1202,80 @@ int rh_bands_weight_sums(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t
         return fail(ctx, RH_ERR_ARG, "rh_bands_weight_sums: size mismatch (n_rows x n_items int64)");
     const int rc = ring_pieces(first_row, n_rows, ctx->bands.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
         HIPCHK(ctx, hipMemcpyAsync(wsum + (size_t)done * ni, ctx->bands_wsum_buf + (size_t)slot * ni, (size_t)m * ni * sizeof(long long),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        return RH_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RH_OK;
+}
+// Observations behind any rh_bands_configure* call: obs (n_items, n_series, n_intervals) float64, NaN: missing; n_series 1, or n_zones
+// on a zonal configuration; row interval k reads element k + first_index.  Allocates the series, the partials (plain and weighted) and
+// the ring of pairs at -1 (the rows recorded before this call have no pair); n_intervals == 0 releases them.  Synchronises.
+int rh_bands_observations(rh_ctx *ctx, const double *obs, int n_series, int64_t n_intervals, int64_t first_index) {
+    if (!ctx) return RH_ERR_ARG;
+    if (!ctx->bands_nitems) return fail(ctx, RH_ERR_STATE, "rh_bands_observations: rh_bands_configure has not been called");
+    if (n_intervals < 0 || n_intervals >= (int64_t)1 << 31)
+        return fail(ctx, RH_ERR_ARG, "rh_bands_observations: n_intervals = " + std::to_string(n_intervals) + " (0 ... 2^31 - 1; 0 releases the observations)");
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old ring)
+    if (n_intervals == 0) {
+        if (int rc = bands_obs_release(ctx)) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return RH_OK;
+    }
+    const int want = ctx->bands_nzones ? ctx->bands_nzones : 1;
+    if (n_series != want)
+        return fail(ctx, RH_ERR_ARG, "rh_bands_observations: n_series = " + std::to_string(n_series) +
+                                     (ctx->bands_nzones ? " (the bands are configured per zone: n_zones = " + std::to_string(want) + " series per item)"
+                                                        : " (the bands are configured without zones: 1 series per item)"));
+    if (!obs) return fail(ctx, RH_ERR_ARG, "rh_bands_observations: null pointer");
+    if (first_index < 0)
+        return fail(ctx, RH_ERR_ARG, "rh_bands_observations: first_index = " + std::to_string(first_index) + " (the index of the first counted interval, at least 0)");
+    const size_t ni = (size_t)ctx->bands_nitems, ns = (size_t)n_series, ob = ni * ns * (size_t)n_intervals * sizeof(double),
+                 parts = bands_obs_grid((long long)ctx->n), rb = (size_t)ctx->bands.cap * ni * ns * 2 * sizeof(long long);
+    int rc = RH_OK;
+    auto alloc = [&]() -> int {
+        HIPCHK(ctx, ctx->bands_obs_buf.alloc(ob));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->bands_obs_buf, obs, ob, hipMemcpyHostToDevice, ctx->stream));
+        if (!ctx->bands_nzones) {
+            HIPCHK(ctx, ctx->bands_obs_part_buf.alloc(ni * parts * 2 * sizeof(long long)));
+            HIPCHK(ctx, hipMemsetAsync(ctx->bands_obs_part_buf, 0, ni * parts * 2 * sizeof(long long), ctx->stream));
+        }
+        HIPCHK(ctx, ctx->bands_obs_ring_buf.alloc(rb));
+        HIPCHK(ctx, hipMemsetAsync(ctx->bands_obs_ring_buf, 0xff, rb, ctx->stream));   // -1: no observation
+        return RH_OK;
+    };
+    if ((rc = bands_obs_release(ctx))) return rc;
+    if ((rc = alloc())) {   // refused: no observations, the bands go on as they were
+        const std::string why = ctx->err;
+        (void)bands_obs_release(ctx);
+        (void)hipStreamSynchronize(ctx->stream);
+        return fail(ctx, rc, why);
+    }
+    const long long len = (long long)n_intervals, first = (long long)first_index;
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs, *ctx->bands_obs_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_part, *ctx->bands_obs_part_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_ring, *ctx->bands_obs_ring_buf.addr()));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_n, len));
+    HIPCHK(ctx, dev_put(ctx, &DevState::bands_obs_first, first));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's, and stack locals)
+    return RH_OK;
+}
+// the pairs {below, equal} of the rows [first_row, first_row + n_rows): (n_rows, n_items, n_series, 2) int64, -1 where the observation is
+// missing; the row range is checked as in rh_bands_read.  Synchronises.
+int rh_bands_obs_read(rh_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *pairs, size_t bytes) {
+    if (!ctx) return RH_ERR_ARG;
+    long long total = 0;
+    if (int rc = ring_rows(ctx, "rh_bands_obs_read", ctx->bands, "rh_bands_configure", &DevState::bands_rows, &total)) return rc;
+    if (!ctx->bands_obs_buf)
+        return fail(ctx, RH_ERR_STATE, "rh_bands_obs_read: no observations are set (rh_bands_observations has not been called behind rh_bands_configure)");
+    const size_t np = (size_t)ctx->bands_nitems * (ctx->bands_nzones ? ctx->bands_nzones : 1) * 2;
+    const std::string why = ring_range_refusal("rh_bands_obs_read", first_row, n_rows, total, ctx->bands.cap);
+    if (!why.empty()) return fail(ctx, RH_ERR_ARG, why);
+    if ((n_rows && !pairs) || bytes != (size_t)n_rows * np * sizeof(int64_t))
+        return fail(ctx, RH_ERR_ARG, "rh_bands_obs_read: size mismatch (n_rows x n_items x n_series x 2 int64)");
+    const int rc = ring_pieces(first_row, n_rows, ctx->bands.cap, [&](int64_t done, int64_t slot, int64_t m) -> int {
+        HIPCHK(ctx, hipMemcpyAsync(pairs + (size_t)done * np, ctx->bands_obs_ring_buf + (size_t)slot * np, (size_t)m * np * sizeof(long long),
                                    hipMemcpyDeviceToHost, ctx->stream));
         return RH_OK;
     });
