@@ -348,6 +348,49 @@ int rh_sas_scores_record(rh_sas_ctx *ctx, int64_t day);
 int rh_sas_scores_read(rh_sas_ctx *ctx, double *moments, size_t moment_bytes, unsigned char *closed, size_t closed_bytes,
                        int64_t *days_scored);
 
+/* ---- transport bands: exact quantiles ACROSS the columns per sample window, and where the observation falls ---------------------------
+ * The one figure a GLUE study of the SAS parameters is made for: the 5 - 95 % band of the simulated delta-18O around the bottle samples,
+ * and the share of samples the band contains.  After rh_sas_bands_configure, rh_sas_step and every day of rh_sas_run_days enqueue the
+ * day's band work behind the scores' launch (kernels, the rule in full and the bytes moved: roger_amd/csrc/rh_sas_bands.h; the numpy twin
+ * is tests/sas_bands_reference.py).  rh_sas_stages never records; a context without bands enqueues exactly what it enqueued before these
+ * entry points existed.  Points, totals, zonal totals, scores and bands work side by side, configured in any order.
+ *   items    [n_items], at most RH_SAS_BANDS_MAX_ITEMS, each (value, weight, kind) as rh_sas_scores_configure takes them
+ *   probs    [n_probs] float64, 1 ... RH_SAS_BANDS_MAX_PROBS probabilities within [0, 1], shared by the items
+ *   mask     [n_cells] bytes, 0: the cell takes no part; NULL: every cell
+ *   weights  [n_cells] uint16 likelihood weights w_i, 0: the cell takes no part; NULL: w_i = 1
+ *   obs      [n_items][n_samples] float64, NaN: missing; NULL: no observations, nothing is counted
+ *   first_day, last_day  [n_samples] int64: the windows in the context's count of RECORDED days, which starts at 0 at configure -- the
+ *            window rules and the clock of rh_sas_scores_configure: a day outside every window launches nothing, a window whose first day
+ *            was never recorded is never open
+ * The rule.  Per cell that takes part and item, num and den are accumulated over the window's days exactly as k_sas_scores accumulates them
+ * (restart from +0.0 on the first day; eligible iff wd > 0 && v == v; num = num + fl(v * wd), den = den + wd).  On the closing day the window
+ * value is s = den > 0 ? num / den : NaN (BULK / MEAN) or s = v (LAST), then s = s + 0.0.  m = cells with a number, n_nan = cells with a NaN,
+ * W = sum of w_i over the m cells.  For a probability p, T = clamp((int64)ceil(p * (double)W), 1, W) and the result is the smallest s with
+ * sum_{s_i <= s} w_i >= T: the bits of np.sort(np.repeat(s, w))[T - 1]; with m == 0 NaN and W = 0.  With observations the int64 pair (below,
+ * equal) holds the weights of the members below and equal to o + 0.0; a missing o gives (-1, -1), m == 0 gives (0, 0).
+ * Result, no ring (the caller knows n_samples): rows [n_samples][n_items][n_probs] float64, NaN until the window closed; hdr
+ * [n_samples][n_items]{m, n_nan, W} int64, 0 until then; obs_pair [n_samples][n_items][2] int64, (-1, -1) until then and without
+ * observations; closed [n_samples] bytes, 1 exactly when the closing day of an open window was recorded.
+ *
+ * n_items == 0 releases everything and stops the launches.  Every other call starts anew (day count 0).  Everything is checked before
+ * anything is released or allocated; a refused call leaves the previous configuration in place.  RH_ERR_ARG (rh_sas_last_error names the
+ * offender): null pointers; n_items or n_probs beyond the maxima; a probability outside [0, 1] or NaN; the refusals of
+ * rh_sas_scores_configure for an item (unknown id, int32, DAILY input, sas_params_*, age-resolved value; a weight that is not a daily flux
+ * input; BULK without a weight, MEAN / LAST with one; unknown kind; given twice); n_samples < 1; windows out of order or overlapping; a mask
+ * and weights that leave no cell taking part.  RH_ERR_STATE: an array this context does not hold.
+ *   rh_sas_bands_record   records "now", behind what the stream holds, as the next day of the count, with `day` (>= 0) the daily row: for
+ *                         a driver that steps with rh_sas_stages
+ *   rh_sas_bands_read     rows, hdr, obs_pair, closed with their sizes in bytes, days_recorded (may be NULL); synchronises
+ * Both: RH_ERR_STATE before rh_sas_bands_configure (or after it released everything). */
+#define RH_SAS_BANDS_MAX_ITEMS 8
+#define RH_SAS_BANDS_MAX_PROBS 8
+int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                           const unsigned char *mask, const uint16_t *weights, const double *obs, const int64_t *first_day,
+                           const int64_t *last_day, int64_t n_samples);
+int rh_sas_bands_record(rh_sas_ctx *ctx, int64_t day);
+int rh_sas_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair, size_t pair_bytes,
+                      unsigned char *closed, size_t closed_bytes, int64_t *days_recorded);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

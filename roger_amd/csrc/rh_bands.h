@@ -69,6 +69,7 @@
 // (below, equal) -- the members, or their weights, below and equal to the observation -- counted from the key planes in one more pass
 // behind the selection: k_bands_obs, k_bands_obs_row and k_bands_obs_zonal at the end of this file, the rule with them.
 #pragma once
+#include "rh_select.h"   // the pure pieces shared with rh_sas_bands.h: BandsPass, the key and its inverse, bands_rank_of, the weighted grid and pick
 
 #define RH_BANDS_MAX_ITEMS 8
 #define RH_BANDS_MAX_PROBS 8
@@ -78,8 +79,9 @@
 #define RH_BANDS_PASSES 6
 #define RH_BANDS_MAX_GRID 256   // workgroups of k_bands_select
 #define RH_BANDS_MAX_ZONES 1024   // rh_bands_configure_zonal: a workgroup of k_bands_zonal per zone and item
-#define RH_BANDS_KEY_MASKED (~0ull)
-#define RH_BANDS_KEY_NAN (~0ull - 1ull)
+#define RH_BANDS_KEY_MASKED RH_SELECT_KEY_MASKED
+#define RH_BANDS_KEY_NAN RH_SELECT_KEY_NAN
+static_assert(RH_BLOCK == RH_SELECT_BLOCK && RH_BANDS_MAX_GRID == RH_SELECT_MAX_GRID, "rh_select.h states the tile and the grid of the selection");
 
 struct BandsClock {
     bool first, counted;
@@ -118,16 +120,11 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands(Arena a, DevState *D, int af
         }
         if (!c.counted) continue;
         s = s + 0.0;
-        const unsigned long long u = (unsigned long long)__double_as_longlong(s);
-        D->bands_keys[(size_t)j * n + i] = s != s ? RH_BANDS_KEY_NAN : u ^ ((u >> 63) ? ~0ull : 1ull << 63);
+        D->bands_keys[(size_t)j * n + i] = s != s ? RH_BANDS_KEY_NAN : bands_key_of(s);
     }
 }
 
-// pass P of the selection: digit bits [shift, shift + width) of the key; the bits above them are the prefix
-template <int P>
-struct BandsPass {
-    static constexpr int shift = P < 5 ? 53 - 11 * P : 0, width = P < 5 ? 11 : 9, nb = 1 << width, high = shift + width;
-};
+// (pass P of the selection -- digit bits [shift, shift + width) of the key, the bits above them the prefix -- is BandsPass<P> of rh_select.h)
 RH_DEV unsigned bands_wave_scan(unsigned x) {   // inclusive, over the 64 lanes
     const int lane = threadIdx.x & 63;
     for (int off = 1; off < 64; off <<= 1) {
@@ -158,12 +155,7 @@ RH_DEV void bands_pick(const unsigned (&v)[NC], long long r, int &digit, long lo
         base += chunk;
     }
 }
-// the rank of probability p among m values: one double multiplication, one ceil
-RH_DEV long long bands_rank_of(double p, long long m) {
-    long long r = (long long)ceil(p * (double)m) - 1;
-    r = r > m - 1 ? m - 1 : r;
-    return r < 0 ? 0 : r;
-}
+// (the rank of probability p among m values, one double multiplication and one ceil, is bands_rank_of of rh_select.h)
 template <int P>
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D, int after_fused) {
     using PS = BandsPass<P>;
@@ -261,8 +253,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
                 __hip_atomic_store(&D->bands_nan_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (P == RH_BANDS_PASSES - 1) {
-                const unsigned long long u = (prefix >> 63) ? prefix ^ (1ull << 63) : ~prefix;
-                D->bands[(size_t)slot * ni * np + j * np + q] = m ? __longlong_as_double((long long)u) : __builtin_nan("");
+                D->bands[(size_t)slot * ni * np + j * np + q] = m ? bands_value_of(prefix) : __builtin_nan("");
             }
         }
     }
@@ -406,8 +397,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_zonal(DevState *D, long long
     bands_zonal_pass<4>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
     bands_zonal_pass<5>(keys, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, &s_nan);
     if ((int)threadIdx.x < np) {   // after the last pass the prefix IS the key
-        const unsigned long long prefix = s_prefix[threadIdx.x], u = (prefix >> 63) ? prefix ^ (1ull << 63) : ~prefix;
-        out[threadIdx.x] = __longlong_as_double((long long)u);
+        out[threadIdx.x] = bands_value_of(s_prefix[threadIdx.x]);
     }
 }
 __global__ void k_bands_zonal_row(DevState *D, int after_fused) {
@@ -458,42 +448,9 @@ __global__ void k_bands_zonal_row(DevState *D, int after_fused) {
 // No counter overflows for any configuration the configure call accepts (n < 2^31): LDS bins by the bound above, the global bins and W
 // below 2^31 x 65535 < 2^47, m and n_nan below 2^31, bands_done at most 2^15 workgroups.  Integer atomics only.
 // Cost of a counted step: the plain path's, plus 2 B per column, item and pass of weights, plus 64-bit merges (8 B a bin, not 4).
-#define RH_BANDS_W_MAX_TILES 256   // tiles of RH_BLOCK columns one workgroup of k_bands_select_w may walk
-static_assert((unsigned long long)RH_BANDS_W_MAX_TILES * RH_BLOCK * 65535ull < (1ull << 32), "a uint32 LDS bin holds a workgroup's weights");
-static inline unsigned bands_weighted_grid(long long n) {
-    const long long ntiles = (n + RH_BLOCK - 1) / RH_BLOCK, few = ntiles < RH_BANDS_MAX_GRID ? ntiles : RH_BANDS_MAX_GRID,
-                    bound = (ntiles + RH_BANDS_W_MAX_TILES - 1) / RH_BANDS_W_MAX_TILES;
-    return (unsigned)(few > bound ? few : bound);
-}
-RH_DEV unsigned long long bands_wave_scan64(unsigned long long x) {   // inclusive, over the 64 lanes
-    const int lane = threadIdx.x & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-// bands_pick over 64-bit bins (sums of weights, below 2^47)
-template <int NC>
-RH_DEV void bands_pick64(const unsigned long long (&v)[NC], long long r, int &digit, long long &below) {
-    long long base = 0;
-    bool found = false;
-    digit = 0;
-    below = 0;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-        const unsigned long long incl = bands_wave_scan64(v[k]);
-        const long long chunk = (long long)__shfl(incl, 63);
-        if (!found && base + chunk > r) {
-            const unsigned long long hit = __ballot(base + (long long)incl > r);
-            const int l = __ffsll((long long)hit) - 1;
-            digit = k * 64 + l;
-            below = base + (long long)__shfl(incl - v[k], l);
-            found = true;
-        }
-        base += chunk;
-    }
-}
+#define RH_BANDS_W_MAX_TILES RH_SELECT_W_MAX_TILES   // tiles of RH_BLOCK columns one workgroup of k_bands_select_w may walk
+// (bands_weighted_grid with its static_assert, bands_wave_scan64 and bands_pick64 -- the 64-bit forms of bands_wave_scan and bands_pick above --
+// are rh_select.h's)
 template <int P>
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *D, int after_fused) {
     using PS = BandsPass<P>;
@@ -602,8 +559,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
                 __hip_atomic_store(&D->bands_nan_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (P == RH_BANDS_PASSES - 1) {
-                const unsigned long long u = (prefix >> 63) ? prefix ^ (1ull << 63) : ~prefix;
-                D->bands[(size_t)slot * ni * np + j * np + q] = D->bands_m[j] ? __longlong_as_double((long long)u) : __builtin_nan("");
+                D->bands[(size_t)slot * ni * np + j * np + q] = D->bands_m[j] ? bands_value_of(prefix) : __builtin_nan("");
             }
         }
     }
@@ -670,8 +626,7 @@ RH_DEV double bands_obs_of(const DevState *D, const BandsClock &c, int j, int z,
 }
 // key(o + 0.0): the key expression of k_bands (o is not a NaN)
 RH_DEV unsigned long long bands_obs_key(double o) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(o + 0.0);
-    return u ^ ((u >> 63) ? ~0ull : 1ull << 63);
+    return bands_key_of(o + 0.0);
 }
 // the workgroup's sums of two int64 values: shuffles within a wavefront, LDS across the RH_BLOCK / 64 of them; thread 0 holds the result
 RH_DEV void bands_obs_reduce(long long &below, long long &equal, long long (*s_part)[2]) {

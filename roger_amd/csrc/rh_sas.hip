@@ -34,6 +34,7 @@
 #include "rh_sas_totals.h"
 #include "rh_sas_zonal.h"
 #include "rh_sas_scores.h"
+#include "rh_sas_bands.h"
 
 #include <algorithm>
 #include <memory>
@@ -137,6 +138,21 @@ struct rh_sas_ctx {
     int scores_items = 0;            // 0: not configured, no launches
     bool scores_accumulate = false;  // an item is BULK or MEAN: the days before a window's last are launched too
     int64_t scores_days = 0, scores_k = 0, scores_open = -1;
+    // transport bands (rh_sas_bands_configure): num / den, the key planes, the global histograms, the selection's few words (prefixes,
+    // ranks, counts: SasBandsWords), the result and what the kernels are told on the device; the windows, the day count, the window the
+    // count stands in or before, the closed flags and the observations' copy are the host's (rh_sas_bands.h)
+    DevBuf<double> bands_acc, bands_rows, bands_obs;
+    DevBuf<unsigned long long> bands_keys, bands_hist;
+    DevBuf<long long> bands_words, bands_hdr, bands_pair, bands_part;
+    DevBuf<unsigned char> bands_mask;
+    DevBuf<unsigned short> bands_weight;
+    DevBuf<SasBandsDev> bands_cfg;
+    std::vector<int64_t> bands_first, bands_last;
+    std::vector<unsigned char> bands_closed;
+    std::vector<double> bands_obs_host;   // [item][sample]; empty: no observations
+    int bands_items = 0, bands_probs = 0;   // 0: not configured, no launches
+    bool bands_accumulate = false;          // an item is BULK or MEAN: the days before a window's last are launched too
+    int64_t bands_days = 0, bands_k = 0, bands_open = -1;
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -194,6 +210,14 @@ static int sas_ring_read(rh_sas_ctx *ctx, const char *who, const SasRing &r, int
         return RH_OK;
     });
     return rc ? rc : rh_sas_sync(ctx);
+}
+
+// pass P of the transport bands' selection (rh_sas_bands.h): the histograms over the key planes, then the pick of one workgroup
+template <int P>
+static void sas_bands_pass(rh_sas_ctx *ctx, unsigned grid, int64_t k) {
+    const SasBandsDev *cfg = ctx->bands_cfg.get();
+    hipLaunchKernelGGL(k_sas_bands_hist<P>, dim3(grid), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg);
+    hipLaunchKernelGGL(k_sas_bands_pick<P>, dim3(1), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, k);
 }
 
 extern "C" {
@@ -446,14 +470,16 @@ static int sas_points_enqueue(rh_sas_ctx *ctx, int64_t tag) {
 static int sas_totals_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
 static int sas_zonal_enqueue(rh_sas_ctx *ctx, int64_t tag, int64_t day);
 static int sas_scores_enqueue(rh_sas_ctx *ctx, int64_t day);
+static int sas_bands_enqueue(rh_sas_ctx *ctx, int64_t day);
 
-// a whole day and, with points, totals, zonal totals or scores configured, their rows and the day's scoring
+// a whole day and, with points, totals, zonal totals, scores or bands configured, their rows, the day's scoring and its band work
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
     if (!rc && ctx->points.on()) rc = sas_points_enqueue(ctx, day);
     if (!rc && ctx->totals.on()) rc = sas_totals_enqueue(ctx, day, day);
     if (!rc && ctx->zonal.on()) rc = sas_zonal_enqueue(ctx, day, day);
     if (!rc && ctx->scores_items) rc = sas_scores_enqueue(ctx, day);
+    if (!rc && ctx->bands_items) rc = sas_bands_enqueue(ctx, day);
     return rc;
 }
 
@@ -1007,6 +1033,232 @@ int rh_sas_scores_read(rh_sas_ctx *ctx, double *moments, size_t moment_bytes, un
     SHIPCHK(ctx, hipMemcpyAsync(moments, ctx->scores_buf, moment_bytes, hipMemcpyDeviceToHost, ctx->stream));
     std::copy(ctx->scores_closed.begin(), ctx->scores_closed.end(), closed);
     if (days_scored) *days_scored = ctx->scores_days;
+    return rh_sas_sync(ctx);
+}
+
+// ---- transport bands (include/roger_hip_sas.h; the kernels and the rule: rh_sas_bands.h) ----
+// the selection's words on the device, one allocation of int64: where each part starts
+enum SasBandsWords {
+    SBW_PREFIX = 0,
+    SBW_RANK = SBW_PREFIX + RH_SAS_BANDS_MAX_ITEMS * RH_SAS_BANDS_MAX_PROBS,
+    SBW_M = SBW_RANK + RH_SAS_BANDS_MAX_ITEMS * RH_SAS_BANDS_MAX_PROBS,
+    SBW_NAN = SBW_M + RH_SAS_BANDS_MAX_ITEMS,
+    SBW_W = SBW_NAN + RH_SAS_BANDS_MAX_ITEMS,
+    SBW_M_COUNT = SBW_W + RH_SAS_BANDS_MAX_ITEMS,                 // uint32 [items]
+    SBW_NAN_COUNT = SBW_M_COUNT + RH_SAS_BANDS_MAX_ITEMS / 2,     // uint32 [items]
+    SBW_WORDS = SBW_NAN_COUNT + RH_SAS_BANDS_MAX_ITEMS / 2
+};
+// the next day of the count, behind what the stream holds so far: the clock of sas_scores_enqueue; on a closing day the six passes of the
+// selection follow the day's kernel, and the two kernels of the observations where window k has one
+static int sas_bands_enqueue(rh_sas_ctx *ctx, int64_t day) {
+    const int64_t t = ctx->bands_days++, K = (int64_t)ctx->bands_first.size(), n = ctx->cfg.n_cells;
+    int64_t &k = ctx->bands_k;
+    while (k < K && ctx->bands_last[(size_t)k] < t) ++k;   // (windows that passed without being open)
+    if (k >= K || t < ctx->bands_first[(size_t)k]) return RH_OK;
+    const bool first = t == ctx->bands_first[(size_t)k], closes = t == ctx->bands_last[(size_t)k];
+    if (first) ctx->bands_open = k;
+    if (ctx->bands_open != k) return RH_OK;                // (its first day was never recorded)
+    const SasBandsDev *cfg = ctx->bands_cfg.get();
+    if (closes || ctx->bands_accumulate)
+        hipLaunchKernelGGL(k_sas_bands_day, dim3((unsigned)((n + SAS_BANDS_BLOCK - 1) / SAS_BANDS_BLOCK)), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg,
+                           first ? 1 : 0, closes ? 1 : 0, (day % ctx->cfg.forcing_days) * n);
+    if (closes) {
+        const unsigned grid = bands_weighted_grid((long long)n);
+        sas_bands_pass<0>(ctx, grid, k);
+        sas_bands_pass<1>(ctx, grid, k);
+        sas_bands_pass<2>(ctx, grid, k);
+        sas_bands_pass<3>(ctx, grid, k);
+        sas_bands_pass<4>(ctx, grid, k);
+        sas_bands_pass<5>(ctx, grid, k);
+        bool observed = false;
+        for (int j = 0; j < ctx->bands_items && !ctx->bands_obs_host.empty(); ++j) {
+            const double o = ctx->bands_obs_host[(size_t)j * (size_t)K + (size_t)k];
+            observed = observed || o == o;
+        }
+        if (observed) {   // (an item without one ends after the scalar loads: its pair stays (-1, -1), as configure wrote it)
+            const unsigned parts = sas_bands_obs_grid((long long)n);
+            hipLaunchKernelGGL(k_sas_bands_obs, dim3(parts, (unsigned)ctx->bands_items), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, k);
+            hipLaunchKernelGGL(k_sas_bands_obs_row, dim3((unsigned)ctx->bands_items), dim3(64), 0, ctx->stream, cfg, k, (int)parts);
+        }
+        ctx->bands_closed[(size_t)k] = 1;
+        ctx->bands_open = -1;
+        ++k;
+    }
+    SHIPCHK(ctx, hipGetLastError());
+    return RH_OK;
+}
+
+int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                           const unsigned char *mask, const uint16_t *weights, const double *obs, const int64_t *first_day,
+                           const int64_t *last_day, int64_t n_samples) {
+    const std::string who = "rh_sas_bands_configure: ";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_SAS_BANDS_MAX_ITEMS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_BANDS_MAX_ITEMS) + ")");
+    const int64_t n = ctx->cfg.n_cells;
+    SasBandsDev P = {};
+    bool accumulate = false;
+    if (n_items) {
+        if (!items || !probs || !first_day || !last_day) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+        if (n_probs < 1 || n_probs > RH_SAS_BANDS_MAX_PROBS)
+            return sfail(ctx, RH_ERR_ARG, who + "n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_SAS_BANDS_MAX_PROBS) + ")");
+        for (int q = 0; q < n_probs; ++q) {
+            if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+                return sfail(ctx, RH_ERR_ARG, who + "probability " + std::to_string(q) + " is " + std::to_string(probs[q]) + " (within [0, 1])");
+            P.probs[q] = probs[q];
+        }
+        if (n_samples < 1 || n_samples > ((int64_t)1 << 31) / ((int64_t)n_items * n_probs * (int64_t)sizeof(double)))
+            return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one; rows of " + std::to_string(n_items) + " x " +
+                                              std::to_string(n_probs) + " float64 within 2 GiB)");
+        static const char *const KIND[] = {"BULK", "MEAN", "LAST"};
+        for (int j = 0; j < n_items; ++j) {
+            const int a = items[j].value, w = items[j].weight, kind = items[j].kind;
+            if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
+            if (w < -1 || w >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown weight id " + std::to_string(w));
+            const std::string name = std::string("array ") + SAS_NAMES[a];
+            if (kind < RH_SAS_SCORES_BULK || kind > RH_SAS_SCORES_LAST)
+                return sfail(ctx, RH_ERR_ARG, who + "kind " + std::to_string(kind) + " of " + name + " (0: BULK, 1: MEAN, 2: LAST)");
+            for (int q = 0; q < j; ++q)
+                if (items[q].value == a && items[q].weight == w && items[q].kind == kind)
+                    return sfail(ctx, RH_ERR_ARG, who + name + " is given twice with the same weight and kind");
+            if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
+            if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* have no band)");
+            if (SAS_KIND[a] == K_DAILY) return sfail(ctx, RH_ERR_ARG, who + name + " is a daily input of the step, not a result (daily inputs are weights here)");
+            if (SAS_KIND[a] != K_CELL) return sfail(ctx, RH_ERR_ARG, who + name + " is age-resolved (a band is over one value per cell)");
+            if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
+                return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
+            if (kind == RH_SAS_SCORES_BULK && w < 0) return sfail(ctx, RH_ERR_ARG, who + name + " is BULK and has no weight");
+            if (kind != RH_SAS_SCORES_BULK && w >= 0)
+                return sfail(ctx, RH_ERR_ARG, who + name + " is " + KIND[kind] + " and has the weight " + SAS_NAMES[w] + " (only BULK takes one)");
+            if (!ctx->arr[a])
+                return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
+            P.val[j] = (const double *)ctx->arr[a].get();
+            P.wgt[j] = w >= 0 ? (const double *)ctx->arr[w].get() : nullptr;
+            P.kind[j] = kind;
+            accumulate = accumulate || kind != RH_SAS_SCORES_LAST;
+        }
+        if (mask || weights) {
+            int64_t part = 0;
+            for (int64_t c = 0; c < n; ++c) part += (!mask || mask[c]) && (!weights || weights[c]);
+            if (!part)
+                return sfail(ctx, RH_ERR_ARG, who + "no cell takes part (0 of " + std::to_string(n) + " cells have mask != 0 and a weight > 0)");
+        }
+        for (int64_t k = 0; k < n_samples; ++k) {
+            if (first_day[k] > last_day[k])
+                return sfail(ctx, RH_ERR_ARG, who + "window " + std::to_string(k) + " is [" + std::to_string(first_day[k]) + ", " +
+                                                  std::to_string(last_day[k]) + "]: its last day lies before its first");
+            if (k && first_day[k] <= last_day[k - 1])
+                return sfail(ctx, RH_ERR_ARG, who + "window " + std::to_string(k) + " starts on day " + std::to_string(first_day[k]) + ", window " +
+                                                  std::to_string(k - 1) + " ends on day " + std::to_string(last_day[k - 1]) +
+                                                  " (windows are in increasing order and do not overlap)");
+        }
+    }
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old result)
+    for (DevBuf<double> *b : {&ctx->bands_acc, &ctx->bands_rows, &ctx->bands_obs}) SHIPCHK(ctx, b->release());
+    for (DevBuf<unsigned long long> *b : {&ctx->bands_keys, &ctx->bands_hist}) SHIPCHK(ctx, b->release());
+    for (DevBuf<long long> *b : {&ctx->bands_words, &ctx->bands_hdr, &ctx->bands_pair, &ctx->bands_part}) SHIPCHK(ctx, b->release());
+    SHIPCHK(ctx, ctx->bands_mask.release());
+    SHIPCHK(ctx, ctx->bands_weight.release());
+    SHIPCHK(ctx, ctx->bands_cfg.release());
+    ctx->bands_first.clear();
+    ctx->bands_last.clear();
+    ctx->bands_closed.clear();
+    ctx->bands_obs_host.clear();
+    ctx->bands_items = ctx->bands_probs = 0;
+    ctx->bands_accumulate = false;
+    ctx->bands_days = ctx->bands_k = 0;
+    ctx->bands_open = -1;
+    if (!n_items) return RH_OK;
+    const size_t K = (size_t)n_samples, ni = (size_t)n_items, np = (size_t)n_probs;
+    const size_t acc_b = ni * 2 * (size_t)n * sizeof(double), key_b = ni * (size_t)n * sizeof(unsigned long long);
+    const size_t hist_b = ni * RH_SAS_BANDS_MAX_PROBS * SAS_BANDS_NBINS * sizeof(unsigned long long);
+    const size_t row_b = K * ni * np * sizeof(double), hdr_b = K * ni * SAS_BANDS_HDR * sizeof(long long), pair_b = K * ni * 2 * sizeof(long long);
+    SHIPCHK(ctx, ctx->bands_acc.alloc(acc_b));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->bands_acc, 0, acc_b, ctx->stream));
+    SHIPCHK(ctx, ctx->bands_keys.alloc(key_b));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->bands_keys, 0xff, key_b, ctx->stream));   // RH_SELECT_KEY_MASKED: every byte set
+    SHIPCHK(ctx, ctx->bands_hist.alloc(hist_b));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->bands_hist, 0, hist_b, ctx->stream));
+    SHIPCHK(ctx, ctx->bands_words.alloc(SBW_WORDS * sizeof(long long)));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->bands_words, 0, SBW_WORDS * sizeof(long long), ctx->stream));
+    const std::vector<double> nans(K * ni * np, std::nan(""));
+    SHIPCHK(ctx, ctx->bands_rows.alloc(row_b));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_rows, nans.data(), row_b, hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, ctx->bands_hdr.alloc(hdr_b));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->bands_hdr, 0, hdr_b, ctx->stream));
+    SHIPCHK(ctx, ctx->bands_pair.alloc(pair_b));
+    SHIPCHK(ctx, hipMemsetAsync(ctx->bands_pair, 0xff, pair_b, ctx->stream));   // (-1, -1): every byte set
+    if (mask) {
+        SHIPCHK(ctx, ctx->bands_mask.alloc((size_t)n));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_mask, mask, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (weights) {
+        SHIPCHK(ctx, ctx->bands_weight.alloc((size_t)n * sizeof(unsigned short)));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_weight, weights, (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (obs) {
+        SHIPCHK(ctx, ctx->bands_obs.alloc(ni * K * sizeof(double)));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_obs, obs, ni * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        SHIPCHK(ctx, ctx->bands_part.alloc(ni * sas_bands_obs_grid((long long)n) * 2 * sizeof(long long)));
+    }
+    long long *words = ctx->bands_words.get();
+    P.n_items = n_items;
+    P.n_probs = n_probs;
+    P.n = n;
+    P.n_samples = n_samples;
+    P.mask = ctx->bands_mask.get();
+    P.weight = ctx->bands_weight.get();
+    P.obs = ctx->bands_obs.get();
+    P.acc = ctx->bands_acc.get();
+    P.keys = ctx->bands_keys.get();
+    P.hist = ctx->bands_hist.get();
+    P.prefix = (unsigned long long *)(words + SBW_PREFIX);
+    P.rank = words + SBW_RANK;
+    P.m = words + SBW_M;
+    P.nan = words + SBW_NAN;
+    P.w = words + SBW_W;
+    P.m_count = (unsigned *)(words + SBW_M_COUNT);
+    P.nan_count = (unsigned *)(words + SBW_NAN_COUNT);
+    P.obs_part = ctx->bands_part.get();
+    P.rows = ctx->bands_rows.get();
+    P.hdr = ctx->bands_hdr.get();
+    P.obs_pair = ctx->bands_pair.get();
+    SHIPCHK(ctx, ctx->bands_cfg.alloc(sizeof(SasBandsDev)));
+    SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_cfg, &P, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and locals)
+    ctx->bands_first.assign(first_day, first_day + n_samples);
+    ctx->bands_last.assign(last_day, last_day + n_samples);
+    ctx->bands_closed.assign(K, 0);
+    if (obs) ctx->bands_obs_host.assign(obs, obs + ni * K);
+    ctx->bands_accumulate = accumulate;
+    ctx->bands_probs = n_probs;
+    ctx->bands_items = n_items;
+    return RH_OK;
+}
+
+static int sas_bands_on(rh_sas_ctx *ctx, const char *who) {
+    return ctx ? sas_on(ctx, ctx->bands_items != 0, who, "rh_sas_bands_configure") : RH_ERR_ARG;
+}
+
+int rh_sas_bands_record(rh_sas_ctx *ctx, int64_t day) {
+    if (int rc = sas_bands_on(ctx, "rh_sas_bands_record")) return rc;
+    if (day < 0) return sfail(ctx, RH_ERR_ARG, "rh_sas_bands_record: day = " + std::to_string(day) + " (the row of the daily inputs, >= 0)");
+    return sas_bands_enqueue(ctx, day);
+}
+
+int rh_sas_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair, size_t pair_bytes,
+                      unsigned char *closed, size_t closed_bytes, int64_t *days_recorded) {
+    if (int rc = sas_bands_on(ctx, "rh_sas_bands_read")) return rc;
+    const size_t K = ctx->bands_closed.size(), ni = (size_t)ctx->bands_items, np = (size_t)ctx->bands_probs;
+    if (!rows || !hdr || !obs_pair || !closed || row_bytes != K * ni * np * sizeof(double) || hdr_bytes != K * ni * SAS_BANDS_HDR * sizeof(int64_t) ||
+        pair_bytes != K * ni * 2 * sizeof(int64_t) || closed_bytes != K)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_bands_read: size mismatch (n_samples x n_items x n_probs float64, n_samples x n_items x 3 and x 2 int64, "
+                                      "n_samples bytes)");
+    SHIPCHK(ctx, hipMemcpyAsync(rows, ctx->bands_rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(hdr, ctx->bands_hdr, hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(obs_pair, ctx->bands_pair, pair_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    std::copy(ctx->bands_closed.begin(), ctx->bands_closed.end(), closed);
+    if (days_recorded) *days_recorded = ctx->bands_days;
     return rh_sas_sync(ctx);
 }
 
