@@ -391,6 +391,35 @@ int rh_sas_bands_record(rh_sas_ctx *ctx, int64_t day);
 int rh_sas_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair, size_t pair_bytes,
                       unsigned char *closed, size_t closed_bytes, int64_t *days_recorded);
 
+/* ---- transport bands per zone: the bands above for every zone of a zone map in one run, each zone with its own observations ---------------
+ * The lysimeters of a SAS parameter study, the land uses or sub-catchments of a catchment map (kernels, the rule and the bytes moved:
+ * roger_amd/csrc/rh_sas_bands_zonal.h; the numpy twin is tests/sas_bands_zonal_reference.py).
+ * The promise, which is the whole specification: block (item, zone z) of window k is bit for bit what rh_sas_bands_configure records for that
+ * item with mask = (zone == z) & mask, the same weights, probabilities and windows and obs = obs[item][z].  A zone with m == 0 gives NaN rows,
+ * W = 0 and, with an observation that is not missing, the pair (0, 0); a missing observation gives (-1, -1).  A cell with zone == -1,
+ * mask == 0 or weight 0 takes no part and is in no zone's counts.
+ *   zone     [n_cells] int32: -1 outside every zone, else 0 ... n_zones - 1
+ *   n_zones  1 ... RH_SAS_BANDS_MAX_ZONES
+ *   obs      [n_items][n_zones][n_samples] float64, NaN: missing; NULL: no observations
+ *   everything else as rh_sas_bands_configure takes it
+ * Result: rows [n_samples][n_items][n_zones][n_probs] float64, hdr [n_samples][n_items][n_zones]{m, n_nan, W} int64, obs_pair
+ * [n_samples][n_items][n_zones][2] int64, closed [n_samples] bytes, read with rh_sas_bands_zonal_read (which synchronises).
+ * rh_sas_bands_record, rh_sas_step and rh_sas_run_days serve both configurations; a closing day is 2 launches (3 with an observation)
+ * instead of 13 (15).  rh_sas_bands_configure_zonal replaces a plain configuration and rh_sas_bands_configure replaces it; n_items == 0
+ * releases.  rh_sas_bands_read is RH_ERR_STATE while the bands are per zone, rh_sas_bands_zonal_read is RH_ERR_STATE while they are not.
+ * Everything is checked before anything is released or allocated.  RH_ERR_ARG beyond the refusals of rh_sas_bands_configure: n_zones outside
+ * 1 ... RH_SAS_BANDS_MAX_ZONES; a zone index outside -1 ... n_zones - 1 (the message names the cell); rows of n_items x n_zones x n_probs
+ * float64 x n_samples beyond 2 GiB; and THE BOUND: one workgroup selects a zone in uint32 LDS bins, which hold at most (participating cells
+ * of the zone) x 65535, so with a weight plane a zone of more than 65536 participating cells is refused (the message names the zone): such
+ * a zone belongs to the mask of rh_sas_bands_configure.  Without weights any zone size is exact.
+ * Load balance: one workgroup walks a zone, so the largest zone sets the time of a closing day. */
+#define RH_SAS_BANDS_MAX_ZONES 1024
+int rh_sas_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                                 const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const double *obs,
+                                 const int64_t *first_day, const int64_t *last_day, int64_t n_samples);
+int rh_sas_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair,
+                            size_t pair_bytes, unsigned char *closed, size_t closed_bytes, int64_t *days_recorded);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

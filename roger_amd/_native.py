@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 21  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 22  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -281,6 +281,8 @@ def _declare_sas(lib):
     lib.rh_sas_bands_configure.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
     lib.rh_sas_bands_record.argtypes = [vp, i64]
     lib.rh_sas_bands_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
+    lib.rh_sas_bands_configure_zonal.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
+    lib.rh_sas_bands_zonal_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
 
 
 SAS_DECLARED_SYMBOLS = (
@@ -292,7 +294,7 @@ SAS_DECLARED_SYMBOLS = (
     "rh_sas_totals_configure", "rh_sas_totals_record", "rh_sas_totals_count", "rh_sas_totals_row_elems", "rh_sas_totals_read",
     "rh_sas_zonal_configure", "rh_sas_zonal_record", "rh_sas_zonal_count", "rh_sas_zonal_row_elems", "rh_sas_zonal_read",
     "rh_sas_scores_configure", "rh_sas_scores_record", "rh_sas_scores_read",
-    "rh_sas_bands_configure", "rh_sas_bands_record", "rh_sas_bands_read",
+    "rh_sas_bands_configure", "rh_sas_bands_record", "rh_sas_bands_read", "rh_sas_bands_configure_zonal", "rh_sas_bands_zonal_read",
 )
 
 # RH_SAS_SCORES_*: how a sample's window is aggregated (include/roger_hip_sas.h)
@@ -605,15 +607,19 @@ class SasContext:
         return moments, closed, days.value
 
     # -- transport bands: quantiles across the cells per sample window (rh_sas_bands_*) --------------
-    def bands_configure(self, items, probs=(), windows=None, mask=None, weights=None, obs=None):
+    def bands_configure(self, items, probs=(), windows=None, mask=None, weights=None, obs=None, zones=None, n_zones=None):
         """The exact quantiles `probs` (each within [0, 1]) ACROSS the cells of the window values of `items` -- (value, weight or None,
         kind) as scores_configure takes them -- over the windows (first_day, last_day), int (K,) each, inclusive, in the context's count
         of recorded days, which restarts at 0 here.  `mask`: (n,), 0: the cell takes no part; `weights`: (n,) integers 0 ... 65535, the
         likelihood weight of every cell, 0: no part; `obs`: (n_items, K) float64, NaN: missing -- where the observation falls is counted
-        too.  No items: release everything and stop."""
+        too.  No items: release everything and stop.
+        `zones`: (n,) integers, -1: outside every zone, else 0 ... n_zones - 1 (default: the largest index + 1) -- the bands of every zone in
+        one run, block z bit for bit what mask = (zones == z) & mask gives; `obs` is then (n_items, n_zones, K), and bands_read returns
+        the zone axis behind the items' (rh_sas_bands_configure_zonal).  With weights a zone holds at most 65536 participating cells."""
         items = [(v, w, SAS_SCORES_KINDS[k] if isinstance(k, str) else int(k)) for v, w, k in items]
         flat = np.array([[self.index(v), -1 if w is None else self.index(w), k] for v, w, k in items], dtype=np.int32).reshape(-1, 3)
-        pr = first = last = mk = wt = o = None
+        pr = first = last = mk = wt = o = zn = None
+        nz = 0
         if items:
             if windows is None or len(windows) != 2:
                 raise ValueError("bands_configure: windows = (first_day, last_day), two integer arrays (K,)")
@@ -621,7 +627,7 @@ class SasContext:
             first, last = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in windows)
             if first.size != last.size:
                 raise ValueError(f"bands_configure: windows of {first.size} and {last.size} days")
-            for name, a in (("mask", mask), ("weights", weights)):
+            for name, a in (("mask", mask), ("weights", weights), ("zones", zones)):
                 if a is not None and np.asarray(a).size != self.n:
                     raise ValueError(f"bands_configure: the {name} have {np.asarray(a).size} cells, the context {self.n}")
             if mask is not None:
@@ -631,11 +637,24 @@ class SasContext:
                 if wt.dtype.kind not in "iu" or (wt.size and (int(wt.min()) < 0 or int(wt.max()) > 65535)):
                     raise ValueError(f"bands_configure: weights of dtype {wt.dtype} (integers within 0 ... 65535)")
                 wt = np.ascontiguousarray(wt, dtype=np.uint16)
+            if zones is not None:
+                zn = np.asarray(zones).reshape(-1)
+                if zn.dtype.kind not in "iu":
+                    raise ValueError(f"bands_configure: zones of dtype {zn.dtype} (integers: -1 or 0 ... n_zones - 1)")
+                nz = int(n_zones) if n_zones is not None else int(zn.max()) + 1 if zn.size else 0
+                zn = np.ascontiguousarray(np.clip(zn, -2, 2 ** 31 - 1), dtype=np.int32)   # (out of range stays out of range: the library refuses it)
             if obs is not None:
                 o = np.ascontiguousarray(obs, dtype=np.float64)
-                if o.shape != (len(items), first.size):
-                    raise ValueError(f"bands_configure: observations of shape {o.shape} for {len(items)} items and {first.size} windows")
+                want = (len(items), first.size) if zn is None else (len(items), nz, first.size)
+                if o.shape != want:
+                    raise ValueError(f"bands_configure: observations of shape {o.shape} for {len(items)} items{'' if zn is None else f', {nz} zones'} and "
+                                     f"{first.size} windows")
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        if zn is not None:
+            self._check(self._lib.rh_sas_bands_configure_zonal(self._h, ptr(flat), len(items), ptr(pr), pr.size, ptr(zn), nz, ptr(mk), ptr(wt), ptr(o),
+                                                               ptr(first), ptr(last), first.size), "rh_sas_bands_configure_zonal")
+            self._bands_shape = (first.size, len(items), nz, pr.size)   # (a refused configuration leaves the previous one)
+            return
         self._check(self._lib.rh_sas_bands_configure(self._h, ptr(flat), len(items), ptr(pr), 0 if pr is None else pr.size, ptr(mk), ptr(wt), ptr(o),
                                                      ptr(first), ptr(last), 0 if first is None else first.size), "rh_sas_bands_configure")
         # (a refused configuration leaves the previous one)
@@ -647,16 +666,19 @@ class SasContext:
 
     def bands_read(self):
         """(rows float64 (K, n_items, n_probs), NaN until the window closed; hdr int64 (K, n_items, 3): m, n_nan, W; pairs int64
-        (K, n_items, 2): below, equal, -1 without an observation; closed uint8 (K,); days recorded since bands_configure).  Synchronises."""
-        nk, ni, npr = getattr(self, "_bands_shape", (0, 0, 0))
-        rows = np.empty((nk, ni, npr), dtype=np.float64)
-        hdr = np.empty((nk, ni, 3), dtype=np.int64)
-        pairs = np.empty((nk, ni, 2), dtype=np.int64)
+        (K, n_items, 2): below, equal, -1 without an observation; closed uint8 (K,); days recorded since bands_configure).  Configured with
+        zones: rows (K, n_items, n_zones, n_probs), hdr (K, n_items, n_zones, 3), pairs (K, n_items, n_zones, 2).  Synchronises."""
+        *lead, npr = getattr(self, "_bands_shape", (0, 0, 0))
+        nk, zonal = lead[0], len(lead) == 3
+        rows = np.empty((*lead, npr), dtype=np.float64)
+        hdr = np.empty((*lead, 3), dtype=np.int64)
+        pairs = np.empty((*lead, 2), dtype=np.int64)
         closed = np.empty(nk, dtype=np.uint8)
         days = C.c_int64()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-        self._check(self._lib.rh_sas_bands_read(self._h, vp(rows), rows.nbytes, vp(hdr), hdr.nbytes, vp(pairs), pairs.nbytes, vp(closed), closed.nbytes,
-                                                C.byref(days)), "rh_sas_bands_read")
+        name = "rh_sas_bands_zonal_read" if zonal else "rh_sas_bands_read"
+        self._check(getattr(self._lib, name)(self._h, vp(rows), rows.nbytes, vp(hdr), hdr.nbytes, vp(pairs), pairs.nbytes, vp(closed), closed.nbytes,
+                                             C.byref(days)), name)
         return rows, hdr, pairs, closed, days.value
 
 

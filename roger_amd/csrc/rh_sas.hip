@@ -35,6 +35,7 @@
 #include "rh_sas_zonal.h"
 #include "rh_sas_scores.h"
 #include "rh_sas_bands.h"
+#include "rh_sas_bands_zonal.h"
 
 #include <algorithm>
 #include <memory>
@@ -153,6 +154,11 @@ struct rh_sas_ctx {
     int bands_items = 0, bands_probs = 0;   // 0: not configured, no launches
     bool bands_accumulate = false;          // an item is BULK or MEAN: the days before a window's last are launched too
     int64_t bands_days = 0, bands_k = 0, bands_open = -1;
+    // ... per zone (rh_sas_bands_configure_zonal, rh_sas_bands_zonal.h): the result gains the zone axis behind the item's, the observations'
+    // copy is [item][zone][sample]; the zones' column lists
+    int bands_zones = 0;                    // 0: the plain configuration (k_sas_bands_hist / _pick); else k_sas_bands_zonal on (zones, items)
+    DevBuf<long long> bands_zone_off;
+    DevBuf<int> bands_zone_cols;
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -1062,7 +1068,24 @@ static int sas_bands_enqueue(rh_sas_ctx *ctx, int64_t day) {
     if (closes || ctx->bands_accumulate)
         hipLaunchKernelGGL(k_sas_bands_day, dim3((unsigned)((n + SAS_BANDS_BLOCK - 1) / SAS_BANDS_BLOCK)), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg,
                            first ? 1 : 0, closes ? 1 : 0, (day % ctx->cfg.forcing_days) * n);
-    if (closes) {
+    if (closes && ctx->bands_zones) {   // per zone: one launch in place of the twelve, one more where window k has an observation
+        const size_t nz = (size_t)ctx->bands_zones;
+        const SasBandsZonalDev Z = {ctx->bands_zone_off.get(), ctx->bands_zone_cols.get()};
+        const dim3 grid((unsigned)nz, (unsigned)ctx->bands_items);
+        if (ctx->bands_weight)
+            hipLaunchKernelGGL(k_sas_bands_zonal<true>, grid, dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, Z, k);
+        else
+            hipLaunchKernelGGL(k_sas_bands_zonal<false>, grid, dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, Z, k);
+        bool observed = false;
+        for (size_t jz = 0; jz < (size_t)ctx->bands_items * nz && !ctx->bands_obs_host.empty() && !observed; ++jz) {
+            const double o = ctx->bands_obs_host[jz * (size_t)K + (size_t)k];
+            observed = o == o;
+        }
+        if (observed) hipLaunchKernelGGL(k_sas_bands_obs_zonal, grid, dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, Z, k);
+        ctx->bands_closed[(size_t)k] = 1;
+        ctx->bands_open = -1;
+        ++k;
+    } else if (closes) {
         const unsigned grid = bands_weighted_grid((long long)n);
         sas_bands_pass<0>(ctx, grid, k);
         sas_bands_pass<1>(ctx, grid, k);
@@ -1088,18 +1111,24 @@ static int sas_bands_enqueue(rh_sas_ctx *ctx, int64_t day) {
     return RH_OK;
 }
 
-int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
-                           const unsigned char *mask, const uint16_t *weights, const double *obs, const int64_t *first_day,
-                           const int64_t *last_day, int64_t n_samples) {
-    const std::string who = "rh_sas_bands_configure: ";
+// rh_sas_bands_configure (zone == nullptr, n_zones == 0) and rh_sas_bands_configure_zonal, for the function `name`: with zones the result and
+// the observations gain the zone axis behind the item's, the byte mask becomes (zone >= 0) & mask, and the zones' column lists are built
+static int sas_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                               const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const double *obs,
+                               const int64_t *first_day, const int64_t *last_day, int64_t n_samples) {
+    const std::string who = std::string(name) + ": ";
+    const bool zonal = n_zones != 0;
     if (!ctx) return RH_ERR_ARG;
     if (n_items < 0 || n_items > RH_SAS_BANDS_MAX_ITEMS)
         return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_BANDS_MAX_ITEMS) + ")");
     const int64_t n = ctx->cfg.n_cells;
     SasBandsDev P = {};
     bool accumulate = false;
+    std::vector<unsigned char> folded;          // per zone: (zone >= 0) & mask
+    std::vector<long long> zone_off;            // per zone: [n_zones + 1] into ...
+    std::vector<int> zone_cols;                 // ... the participating columns, ascending within a zone
     if (n_items) {
-        if (!items || !probs || !first_day || !last_day) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+        if (!items || !probs || !first_day || !last_day || (zonal && !zone)) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
         if (n_probs < 1 || n_probs > RH_SAS_BANDS_MAX_PROBS)
             return sfail(ctx, RH_ERR_ARG, who + "n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_SAS_BANDS_MAX_PROBS) + ")");
         for (int q = 0; q < n_probs; ++q) {
@@ -1107,6 +1136,9 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
                 return sfail(ctx, RH_ERR_ARG, who + "probability " + std::to_string(q) + " is " + std::to_string(probs[q]) + " (within [0, 1])");
             P.probs[q] = probs[q];
         }
+        if (zonal && (n_samples < 1 || n_samples > ((int64_t)1 << 31) / ((int64_t)n_items * n_zones * n_probs * (int64_t)sizeof(double))))
+            return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one; rows of " + std::to_string(n_items) + " x " +
+                                              std::to_string(n_zones) + " x " + std::to_string(n_probs) + " float64 within 2 GiB)");
         if (n_samples < 1 || n_samples > ((int64_t)1 << 31) / ((int64_t)n_items * n_probs * (int64_t)sizeof(double)))
             return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one; rows of " + std::to_string(n_items) + " x " +
                                               std::to_string(n_probs) + " float64 within 2 GiB)");
@@ -1137,6 +1169,28 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
             P.kind[j] = kind;
             accumulate = accumulate || kind != RH_SAS_SCORES_LAST;
         }
+        if (zonal) {   // the zones' sizes, the bound of a weighted zone, then the stable counting sort over the participating columns
+            zone_off.assign((size_t)n_zones + 1, 0);
+            folded.assign((size_t)n, 0);
+            for (int64_t c = 0; c < n; ++c) {
+                if (zone[c] < -1 || zone[c] >= n_zones)
+                    return sfail(ctx, RH_ERR_ARG, who + "zone[" + std::to_string(c) + "] = " + std::to_string(zone[c]) + " (-1: outside every zone, else 0 ... " +
+                                                      std::to_string(n_zones - 1) + ")");
+                folded[(size_t)c] = zone[c] >= 0 && (!mask || mask[c]);
+                if (folded[(size_t)c] && (!weights || weights[c])) ++zone_off[(size_t)zone[c] + 1];
+            }
+            for (int z = 0; z < n_zones && weights; ++z)
+                if (zone_off[(size_t)z + 1] > SAS_BANDS_ZONAL_MAX_WEIGHTED)
+                    return sfail(ctx, RH_ERR_ARG, who + "zone " + std::to_string(z) + " has " + std::to_string(zone_off[(size_t)z + 1]) +
+                                                      " participating cells under a weight plane (at most " + std::to_string(SAS_BANDS_ZONAL_MAX_WEIGHTED) +
+                                                      ": a uint32 LDS bin holds a zone's weights; a larger zone belongs to the mask of rh_sas_bands_configure)");
+            for (int z = 0; z < n_zones; ++z) zone_off[(size_t)z + 1] += zone_off[(size_t)z];
+            zone_cols.resize((size_t)zone_off[(size_t)n_zones]);
+            std::vector<long long> at(zone_off.begin(), zone_off.end() - 1);
+            for (int64_t c = 0; c < n; ++c)
+                if (folded[(size_t)c] && (!weights || weights[c])) zone_cols[(size_t)at[(size_t)zone[c]]++] = (int)c;
+            mask = folded.data();
+        }
         if (mask || weights) {
             int64_t part = 0;
             for (int64_t c = 0; c < n; ++c) part += (!mask || mask[c]) && (!weights || weights[c]);
@@ -1160,6 +1214,9 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
     SHIPCHK(ctx, ctx->bands_mask.release());
     SHIPCHK(ctx, ctx->bands_weight.release());
     SHIPCHK(ctx, ctx->bands_cfg.release());
+    SHIPCHK(ctx, ctx->bands_zone_off.release());
+    SHIPCHK(ctx, ctx->bands_zone_cols.release());
+    ctx->bands_zones = 0;
     ctx->bands_first.clear();
     ctx->bands_last.clear();
     ctx->bands_closed.clear();
@@ -1169,10 +1226,10 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
     ctx->bands_days = ctx->bands_k = 0;
     ctx->bands_open = -1;
     if (!n_items) return RH_OK;
-    const size_t K = (size_t)n_samples, ni = (size_t)n_items, np = (size_t)n_probs;
+    const size_t K = (size_t)n_samples, ni = (size_t)n_items, np = (size_t)n_probs, nb = zonal ? (size_t)n_zones : 1;   // nb: blocks per item
     const size_t acc_b = ni * 2 * (size_t)n * sizeof(double), key_b = ni * (size_t)n * sizeof(unsigned long long);
     const size_t hist_b = ni * RH_SAS_BANDS_MAX_PROBS * SAS_BANDS_NBINS * sizeof(unsigned long long);
-    const size_t row_b = K * ni * np * sizeof(double), hdr_b = K * ni * SAS_BANDS_HDR * sizeof(long long), pair_b = K * ni * 2 * sizeof(long long);
+    const size_t row_b = K * ni * nb * np * sizeof(double), hdr_b = K * ni * nb * SAS_BANDS_HDR * sizeof(long long), pair_b = K * ni * nb * 2 * sizeof(long long);
     SHIPCHK(ctx, ctx->bands_acc.alloc(acc_b));
     SHIPCHK(ctx, hipMemsetAsync(ctx->bands_acc, 0, acc_b, ctx->stream));
     SHIPCHK(ctx, ctx->bands_keys.alloc(key_b));
@@ -1181,7 +1238,7 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
     SHIPCHK(ctx, hipMemsetAsync(ctx->bands_hist, 0, hist_b, ctx->stream));
     SHIPCHK(ctx, ctx->bands_words.alloc(SBW_WORDS * sizeof(long long)));
     SHIPCHK(ctx, hipMemsetAsync(ctx->bands_words, 0, SBW_WORDS * sizeof(long long), ctx->stream));
-    const std::vector<double> nans(K * ni * np, std::nan(""));
+    const std::vector<double> nans(K * ni * nb * np, std::nan(""));
     SHIPCHK(ctx, ctx->bands_rows.alloc(row_b));
     SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_rows, nans.data(), row_b, hipMemcpyHostToDevice, ctx->stream));
     SHIPCHK(ctx, ctx->bands_hdr.alloc(hdr_b));
@@ -1197,9 +1254,15 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
         SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_weight, weights, (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
     }
     if (obs) {
-        SHIPCHK(ctx, ctx->bands_obs.alloc(ni * K * sizeof(double)));
-        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_obs, obs, ni * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        SHIPCHK(ctx, ctx->bands_part.alloc(ni * sas_bands_obs_grid((long long)n) * 2 * sizeof(long long)));
+        SHIPCHK(ctx, ctx->bands_obs.alloc(ni * nb * K * sizeof(double)));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_obs, obs, ni * nb * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (!zonal) SHIPCHK(ctx, ctx->bands_part.alloc(ni * sas_bands_obs_grid((long long)n) * 2 * sizeof(long long)));
+    }
+    if (zonal) {
+        SHIPCHK(ctx, ctx->bands_zone_off.alloc(zone_off.size() * sizeof(long long)));
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_zone_off, zone_off.data(), zone_off.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        SHIPCHK(ctx, ctx->bands_zone_cols.alloc((zone_cols.size() + 1) * sizeof(int)));   // (+ 1: never an empty allocation)
+        SHIPCHK(ctx, hipMemcpyAsync(ctx->bands_zone_cols, zone_cols.data(), zone_cols.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     }
     long long *words = ctx->bands_words.get();
     P.n_items = n_items;
@@ -1229,11 +1292,28 @@ int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int
     ctx->bands_first.assign(first_day, first_day + n_samples);
     ctx->bands_last.assign(last_day, last_day + n_samples);
     ctx->bands_closed.assign(K, 0);
-    if (obs) ctx->bands_obs_host.assign(obs, obs + ni * K);
+    if (obs) ctx->bands_obs_host.assign(obs, obs + ni * nb * K);
     ctx->bands_accumulate = accumulate;
     ctx->bands_probs = n_probs;
     ctx->bands_items = n_items;
+    ctx->bands_zones = zonal ? n_zones : 0;
     return RH_OK;
+}
+
+int rh_sas_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                           const unsigned char *mask, const uint16_t *weights, const double *obs, const int64_t *first_day,
+                           const int64_t *last_day, int64_t n_samples) {
+    return sas_bands_configure(ctx, "rh_sas_bands_configure", items, n_items, probs, n_probs, nullptr, 0, mask, weights, obs, first_day, last_day, n_samples);
+}
+
+int rh_sas_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                                 const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const double *obs,
+                                 const int64_t *first_day, const int64_t *last_day, int64_t n_samples) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items && (n_zones < 1 || n_zones > RH_SAS_BANDS_MAX_ZONES))
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_bands_configure_zonal: n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_SAS_BANDS_MAX_ZONES) + ")");
+    return sas_bands_configure(ctx, "rh_sas_bands_configure_zonal", items, n_items, probs, n_probs, zone, n_items ? n_zones : 0, mask, weights, obs, first_day,
+                               last_day, n_samples);
 }
 
 static int sas_bands_on(rh_sas_ctx *ctx, const char *who) {
@@ -1249,11 +1329,29 @@ int rh_sas_bands_record(rh_sas_ctx *ctx, int64_t day) {
 int rh_sas_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair, size_t pair_bytes,
                       unsigned char *closed, size_t closed_bytes, int64_t *days_recorded) {
     if (int rc = sas_bands_on(ctx, "rh_sas_bands_read")) return rc;
+    if (ctx->bands_zones) return sfail(ctx, RH_ERR_STATE, "rh_sas_bands_read: the bands are configured per zone (read them with rh_sas_bands_zonal_read)");
     const size_t K = ctx->bands_closed.size(), ni = (size_t)ctx->bands_items, np = (size_t)ctx->bands_probs;
     if (!rows || !hdr || !obs_pair || !closed || row_bytes != K * ni * np * sizeof(double) || hdr_bytes != K * ni * SAS_BANDS_HDR * sizeof(int64_t) ||
         pair_bytes != K * ni * 2 * sizeof(int64_t) || closed_bytes != K)
         return sfail(ctx, RH_ERR_ARG, "rh_sas_bands_read: size mismatch (n_samples x n_items x n_probs float64, n_samples x n_items x 3 and x 2 int64, "
                                       "n_samples bytes)");
+    SHIPCHK(ctx, hipMemcpyAsync(rows, ctx->bands_rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(hdr, ctx->bands_hdr, hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(obs_pair, ctx->bands_pair, pair_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    std::copy(ctx->bands_closed.begin(), ctx->bands_closed.end(), closed);
+    if (days_recorded) *days_recorded = ctx->bands_days;
+    return rh_sas_sync(ctx);
+}
+
+int rh_sas_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair, size_t pair_bytes,
+                            unsigned char *closed, size_t closed_bytes, int64_t *days_recorded) {
+    if (!ctx) return RH_ERR_ARG;
+    if (int rc = sas_on(ctx, ctx->bands_items != 0 && ctx->bands_zones != 0, "rh_sas_bands_zonal_read", "rh_sas_bands_configure_zonal")) return rc;
+    const size_t K = ctx->bands_closed.size(), blocks = (size_t)ctx->bands_items * (size_t)ctx->bands_zones, np = (size_t)ctx->bands_probs;
+    if (!rows || !hdr || !obs_pair || !closed || row_bytes != K * blocks * np * sizeof(double) || hdr_bytes != K * blocks * SAS_BANDS_HDR * sizeof(int64_t) ||
+        pair_bytes != K * blocks * 2 * sizeof(int64_t) || closed_bytes != K)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_bands_zonal_read: size mismatch (n_samples x n_items x n_zones x n_probs float64, n_samples x n_items x n_zones "
+                                      "x 3 and x 2 int64, n_samples bytes)");
     SHIPCHK(ctx, hipMemcpyAsync(rows, ctx->bands_rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SHIPCHK(ctx, hipMemcpyAsync(hdr, ctx->bands_hdr, hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SHIPCHK(ctx, hipMemcpyAsync(obs_pair, ctx->bands_pair, pair_bytes, hipMemcpyDeviceToHost, ctx->stream));
