@@ -439,6 +439,39 @@ class SasContext:
                                                                values.ctypes.data_as(C.c_void_p), values.nbytes), f"rh_sas_{what}_read")
         return n, tags, values
 
+    def _weighted_items(self, items):
+        """(the items as (value, weight or None), their ids int32 (n_items, 2): -1 for no weight) of what the totals take: an array's
+        name or (array, weight)."""
+        items = [(it, None) if isinstance(it, str) else (it[0], it[1]) for it in items]
+        return items, np.array([[self.index(v), -1 if w is None else self.index(w)] for v, w in items], dtype=np.int32).reshape(-1, 2)
+
+    def _window_items(self, items):
+        """(the items as (value, weight or None, kind int), their ids int32 (n_items, 3)) of what the scores and the bands take: the kind
+        by its name or its number."""
+        items = [(v, w, SAS_SCORES_KINDS[k] if isinstance(k, str) else int(k)) for v, w, k in items]
+        return items, np.array([[self.index(v), -1 if w is None else self.index(w), k] for v, w, k in items], dtype=np.int32).reshape(-1, 3)
+
+    def _totals_layout(self, items):
+        """[(an item's key in rows and files, its width)] of the (value, weight) items of an accepted totals configuration."""
+        return [(totals_item_name(v, w), 1 if v in DAILY_INPUTS else int(np.prod(self.shape(v)[1:], dtype=np.int64))) for v, w in items]
+
+    @staticmethod
+    def _totals_rows(values, layout, one_zone=False):
+        """{item: {"wsum", "count", "sum"[, "min", "max"]}} of rows (n, Z, elements of a zone's part), every statistic a copy (n, Z) and
+        "sum" of an age item (n, Z, width); one_zone: Z is 1 and the axis is dropped."""
+        cut = (lambda a: a[:, 0].copy()) if one_zone else (lambda a: a.copy())
+        out, off = {}, 0
+        for key, w in layout:
+            d = {"wsum": cut(values[:, :, off]), "count": cut(values[:, :, off + 1])}
+            if w == 1:
+                d.update(sum=cut(values[:, :, off + 2]), min=cut(values[:, :, off + 3]), max=cut(values[:, :, off + 4]))
+                off += 5
+            else:
+                d["sum"] = cut(values[:, :, off + 2:off + 2 + w])
+                off += 2 + w
+            out[key] = d
+        return out
+
     # -- time series at observation columns (rh_sas_points_*) -----------------------------------
     def points_configure(self, cells, names, capacity=4096):
         """Record `names` (arrays of the registry) at the local cells `cells` after every day into a ring of `capacity` rows; empty
@@ -478,8 +511,7 @@ class SasContext:
     def totals_configure(self, items, mask=None, capacity=4096):
         """Reduce `items` over the cells where `mask` is set (None: all) after every day into a ring of `capacity` rows.  An item is
         an array's name or (array, weight) with a daily flux input as weight; no items switch the recorder off."""
-        items = [(it, None) if isinstance(it, str) else (it[0], it[1]) for it in items]
-        flat = np.array([[self.index(v), -1 if w is None else self.index(w)] for v, w in items], dtype=np.int32).reshape(-1, 2)
+        items, flat = self._weighted_items(items)
         m = None
         if mask is not None:
             m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
@@ -488,8 +520,7 @@ class SasContext:
         self._check(self._lib.rh_sas_totals_configure(self._h, None if m is None else m.ctypes.data_as(C.c_void_p),
                                                       flat.ctypes.data_as(C.c_void_p), len(items), int(capacity)), "rh_sas_totals_configure")
         # (a refused configuration leaves the previous one)
-        self._totals_items = [(totals_item_name(v, w), 1 if v in DAILY_INPUTS else int(np.prod(self.shape(v)[1:], dtype=np.int64)))
-                              for v, w in items]
+        self._totals_items = self._totals_layout(items)
 
     def totals_record(self, tag=0, day=-1):
         """One row now (the initial values; a driver that steps by stage).  day < 0: no daily row, so an item with a weight or a daily
@@ -506,24 +537,13 @@ class SasContext:
         """(tags (n,) int64, {item: {"wsum", "count", "sum"[, "min", "max"]}}) of the rows [first, first + n) that are still resident;
         an item's key is `<array>` or `<array>_by_<weight>`, its statistics are (n,) float64, "sum" of an age item (n, width)."""
         n, tags, values = self._ring_read("totals", first, n)
-        out, off = {}, 0
-        for key, w in self._totals_items:
-            d = {"wsum": values[:, off].copy(), "count": values[:, off + 1].copy()}
-            if w == 1:
-                d.update(sum=values[:, off + 2].copy(), min=values[:, off + 3].copy(), max=values[:, off + 4].copy())
-                off += 5
-            else:
-                d["sum"] = values[:, off + 2:off + 2 + w].copy()
-                off += 2 + w
-            out[key] = d
-        return tags, out
+        return tags, self._totals_rows(values[:, None, :], self._totals_items, one_zone=True)
 
     # -- zonal totals (rh_sas_zonal_*) ------------------------------------------------------------
     def zonal_configure(self, items, zones=None, n_zones=0, capacity=4096):
         """Reduce `items` (as totals_configure) over the cells of every zone of `zones` -- an index per cell, -1: outside, else
         0 ... n_zones - 1 -- after every day into a ring of `capacity` rows; no items switch the recorder off."""
-        items = [(it, None) if isinstance(it, str) else (it[0], it[1]) for it in items]
-        flat = np.array([[self.index(v), -1 if w is None else self.index(w)] for v, w in items], dtype=np.int32).reshape(-1, 2)
+        items, flat = self._weighted_items(items)
         z = None
         if zones is not None:
             z = np.ascontiguousarray(np.asarray(zones).reshape(-1), dtype=np.int32)
@@ -532,8 +552,7 @@ class SasContext:
         self._check(self._lib.rh_sas_zonal_configure(self._h, None if z is None else z.ctypes.data_as(C.c_void_p), int(n_zones),
                                                      flat.ctypes.data_as(C.c_void_p), len(items), int(capacity)), "rh_sas_zonal_configure")
         # (a refused configuration leaves the previous one)
-        self._zonal_items = [(totals_item_name(v, w), 1 if v in DAILY_INPUTS else int(np.prod(self.shape(v)[1:], dtype=np.int64)))
-                             for v, w in items]
+        self._zonal_items = self._totals_layout(items)
         self._zonal_nzones = int(n_zones) if items else 0
 
     def zonal_record(self, tag=0, day=-1):
@@ -552,18 +571,7 @@ class SasContext:
         """(tags (n,) int64, {item: {"wsum", "count", "sum"[, "min", "max"]}}) of the rows [first, first + n) that are still resident;
         the statistics are (n, Z) float64, "sum" of an age item (n, Z, width)."""
         n, tags, values = self._ring_read("zonal", first, n)
-        values = values.reshape(n, self._zonal_nzones, values.shape[1] // self._zonal_nzones)
-        out, off = {}, 0
-        for key, w in self._zonal_items:
-            d = {"wsum": values[:, :, off].copy(), "count": values[:, :, off + 1].copy()}
-            if w == 1:
-                d.update(sum=values[:, :, off + 2].copy(), min=values[:, :, off + 3].copy(), max=values[:, :, off + 4].copy())
-                off += 5
-            else:
-                d["sum"] = values[:, :, off + 2:off + 2 + w].copy()
-                off += 2 + w
-            out[key] = d
-        return tags, out
+        return tags, self._totals_rows(values.reshape(n, self._zonal_nzones, values.shape[1] // self._zonal_nzones), self._zonal_items)
 
     # -- scores against observed samples (rh_sas_scores_*) ----------------------------------------
     def scores_configure(self, items, obs=None, windows=None, series=None):
@@ -571,8 +579,7 @@ class SasContext:
         each, inclusive, in the context's count of scored days, which restarts at 0 here.  An item is (value, weight or None, kind)
         with kind "bulk" (flux-weighted mean over the window, needs a weight), "mean" or "last".  `series`: the series of every cell
         (< 0: not scored), None: every cell series 0.  No items: release everything and stop."""
-        items = [(v, w, SAS_SCORES_KINDS[k] if isinstance(k, str) else int(k)) for v, w, k in items]
-        flat = np.array([[self.index(v), -1 if w is None else self.index(w), k] for v, w, k in items], dtype=np.int32).reshape(-1, 3)
+        items, flat = self._window_items(items)
         o = first = last = sr = None
         shape = (0, 0, 0)
         if items:
@@ -616,8 +623,7 @@ class SasContext:
         `zones`: (n,) integers, -1: outside every zone, else 0 ... n_zones - 1 (default: the largest index + 1) -- the bands of every zone in
         one run, block z bit for bit what mask = (zones == z) & mask gives; `obs` is then (n_items, n_zones, K), and bands_read returns
         the zone axis behind the items' (rh_sas_bands_configure_zonal).  With weights a zone holds at most 65536 participating cells."""
-        items = [(v, w, SAS_SCORES_KINDS[k] if isinstance(k, str) else int(k)) for v, w, k in items]
-        flat = np.array([[self.index(v), -1 if w is None else self.index(w), k] for v, w, k in items], dtype=np.int32).reshape(-1, 3)
+        items, flat = self._window_items(items)
         pr = first = last = mk = wt = o = zn = None
         nz = 0
         if items:

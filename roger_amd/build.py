@@ -25,7 +25,8 @@ UNITS = {
     "roger_hip": ("rh_host.h", "rh_physics.h", "rh_pow.h", "rh_col.h", "rh_sets.inc", "include/roger_hip.h", "include/rh_fields.def",
                   "rh_dev_state.h", "rh_control.h", "rh_zonal.h", "rh_scores.h", "rh_events.h", "rh_durations.h", "rh_bands.h", "rh_select.h", "rh_step.h", "rh_routing.h", "rh_host_kernels.h", "rh_context.h", "rh_rccl.h", "rh_observers.h", "rh_setup.h", "rh_forcing.h",
                   "rh_routing_host.h", "rh_stepping.h", "rh_tools.h"),
-    "rh_sas": _SAS_DEPS + ("rh_host.h", "rh_sas_points.h", "rh_sas_totals.h", "rh_sas_zonal.h", "rh_sas_scores.h", "rh_sas_bands.h", "rh_sas_bands_zonal.h", "rh_select.h"),   # the SAS C ABI, the points', the totals', the zonal, the scores and the bands kernels
+    "rh_sas": _SAS_DEPS + ("rh_host.h", "rh_sas_points.h", "rh_sas_totals.h", "rh_sas_zonal.h", "rh_sas_scores.h", "rh_sas_bands.h", "rh_sas_bands_zonal.h", "rh_select.h",
+               "rh_sas_context.h", "rh_sas_observers.h"),   # the SAS C ABI, the points', the totals', the zonal, the scores and the bands kernels, the host side
     "rh_sas_det_iso": _SAS_DEPS + ("rh_sas_kernels.h",),            # the deterministic SAS kernels: isotopes ...
     "rh_sas_det_anion": _SAS_DEPS + ("rh_sas_kernels.h",),          # ... and anions
     "rh_sas_euler_iso": _SAS_DEPS + ("rh_sas_solvers_impl.h",),     # the explicit solvers

@@ -1,9 +1,13 @@
 """GPU: the refusals that the observers' host code shares, text for text, and the ring's read across its wrap.
 
 Six rings -- points, catchment totals and zonal totals of the step context (rh_*_read: rh_observers.h) and of the SAS context
-(rh_sas_*_read: rh_sas.hip) -- refuse a range with the same two sentences and copy a resident range in at most two pieces; five configure
-calls of the step context refuse a plane id with the same two sentences.  The texts below are written out as the C sources spelled them
-when every function carried its own copy, so they hold whoever forms them now.
+(rh_sas_*_read: rh_sas_observers.h) -- refuse a range with the same two sentences and copy a resident range in at most two pieces; five
+configure calls of the step context refuse a plane id with the same two sentences.  The texts below are written out as the C sources
+spelled them when every function carried its own copy, so they hold whoever forms them now.
+
+The transport context's part (at the end): the item and window rules that rh_sas_scores_configure, rh_sas_bands_configure and
+rh_sas_bands_configure_zonal share, the "has not been called" answer of every call of the five transport observers, and the window clock
+that the scores and the bands share, on a context of 5 cells that is never stepped.
 
 The smallest set-up that wraps: 257 columns (two tiles of 256), a capacity of 3 rows, five rows recorded: rows 2, 3, 4 are resident in
 slots 2, 0, 1."""
@@ -184,3 +188,191 @@ def test_an_int32_plane(step_ctx, who):
     tail = " (plane ids must name float64 planes)" if TAIL[who] else " (float64 planes only)"
     assert (rc, err) == (RH_ERR_ARG, f"{who}: plane {name} is int32{tail}")
     assert_still_configured(step_ctx)
+
+
+# ---- the transport context: what rh_sas_scores_configure and the two bands calls share, text for text ----
+SAS_N = 5
+SAS_C = np.arange(SAS_N, dtype=np.float64) - 7.5
+SAS_ZONES = np.array([0, 1, -1, 1, 0], dtype=np.int32)
+SAS_WINDOW_CALLS = ("rh_sas_scores_configure", "rh_sas_bands_configure", "rh_sas_bands_configure_zonal")
+BULK, MEAN, LAST = 0, 1, 2
+RH_ERR_STATE = -3
+
+
+def small_sas():
+    from roger_amd._native import SasContext
+
+    ctx = SasContext(SAS_N, 30, forcing_days=2)
+    ctx.upload("C_rz", SAS_C)
+    return ctx
+
+
+def sas_error(ctx, rc):
+    return rc, ctx._lib.rh_sas_last_error(ctx._h).decode()
+
+
+def configure_windows_raw(ctx, who, items, first=(0, 2), last=(0, 3)):
+    """The configure call `who` through the C ABI with an int32 item array (value, weight, kind) and otherwise valid arguments
+    -> (rc, error text)."""
+    lib, h = ctx._lib, ctx._h
+    it = np.array(items, dtype=np.int32).reshape(-1, 3)
+    first, last = np.array(first, dtype=np.int64), np.array(last, dtype=np.int64)
+    probs = np.array([0.0, 0.5, 1.0])
+    if who == "rh_sas_scores_configure":
+        obs = np.full((len(it), 1, first.size), -6.0)
+        return sas_error(ctx, lib.rh_sas_scores_configure(h, vp(it), len(it), None, 1, vp(obs), vp(first), vp(last), first.size))
+    if who == "rh_sas_bands_configure":
+        return sas_error(ctx, lib.rh_sas_bands_configure(h, vp(it), len(it), vp(probs), probs.size, None, None, None, vp(first), vp(last), first.size))
+    return sas_error(ctx, lib.rh_sas_bands_configure_zonal(h, vp(it), len(it), vp(probs), probs.size, vp(SAS_ZONES), 2, None, None, None, vp(first),
+                                                           vp(last), first.size))
+
+
+def configure_windows_valid(ctx, who, items=(("C_rz", None, "last"),), windows=((0, 2), (0, 3))):
+    """A valid configuration through the wrapper, and the function that reads it."""
+    items, windows = list(items), tuple(np.array(w) for w in windows)
+    if who == "rh_sas_scores_configure":
+        ctx.scores_configure(items, obs=np.full((len(items), 1, windows[0].size), -6.0), windows=windows)
+        return ctx.scores_read
+    zonal = who == "rh_sas_bands_configure_zonal"
+    ctx.bands_configure(items, probs=(0.0, 0.5, 1.0), windows=windows, zones=SAS_ZONES if zonal else None, n_zones=2 if zonal else None)
+    return ctx.bands_read
+
+
+def same_reading(a, b):
+    return len(a) == len(b) and all(same_bits(x, y) if getattr(x, "dtype", None) == np.float64 else np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("who", SAS_WINDOW_CALLS)
+def test_the_item_and_window_rules_of_the_transport_windows(who):
+    """Every shared refusal of the three calls with its whole text and code, the two phrases that differ per caller, which rule speaks
+    first for an age-resolved BULK item without a weight; the configuration that was running reads afterwards what it read before."""
+    ctx = small_sas()
+    read = configure_windows_valid(ctx, who)
+    record = ctx.scores_record if who == "rh_sas_scores_configure" else ctx.bands_record
+    record(0)
+    before = read()
+    ix = ctx.index
+    scored = who == "rh_sas_scores_configure"
+    params_are = "are not scored" if scored else "have no band"
+    one_value = "a sample is compared with one value per cell" if scored else "a band is over one value per cell"
+    C_rz = ix("C_rz")
+    cases = (
+        ([(9999, -1, LAST)], {}, RH_ERR_ARG, "unknown array id 9999"),
+        ([(C_rz, 9999, BULK)], {}, RH_ERR_ARG, "unknown weight id 9999"),
+        ([(C_rz, -1, 3)], {}, RH_ERR_ARG, "kind 3 of array C_rz (0: BULK, 1: MEAN, 2: LAST)"),
+        ([(C_rz, -1, LAST), (C_rz, -1, MEAN), (C_rz, -1, LAST)], {}, RH_ERR_ARG, "array C_rz is given twice with the same weight and kind"),
+        ([(ix("maskCatch"), -1, MEAN)], {}, RH_ERR_ARG, "array maskCatch is int32 (float64 arrays only)"),
+        ([(ix("sas_params_q_ss"), -1, MEAN)], {}, RH_ERR_ARG,
+         f"array sas_params_q_ss is a parameter block of the step (sas_params_* {params_are})"),
+        ([(ix("q_ss"), -1, MEAN)], {}, RH_ERR_ARG, "array q_ss is a daily input of the step, not a result (daily inputs are weights here)"),
+        ([(ix("sa_rz"), -1, MEAN)], {}, RH_ERR_ARG, f"array sa_rz is age-resolved ({one_value})"),
+        ([(C_rz, ix("C_in"), BULK)], {}, RH_ERR_ARG, "weight C_in is not a daily flux input (inf_mat_rz ... cpr_rz)"),
+        ([(C_rz, -1, BULK)], {}, RH_ERR_ARG, "array C_rz is BULK and has no weight"),
+        ([(C_rz, ix("q_ss"), MEAN)], {}, RH_ERR_ARG, "array C_rz is MEAN and has the weight q_ss (only BULK takes one)"),
+        ([(ix("tt50_q_ss"), -1, MEAN)], {}, RH_ERR_STATE,
+         "array tt50_q_ss is not held by this context (age_statistics / keep_distributions / tracer)"),
+        ([(C_rz, -1, LAST)], dict(first=(0, 3), last=(0, 2)), RH_ERR_ARG, "window 1 is [3, 2]: its last day lies before its first"),
+        ([(C_rz, -1, LAST)], dict(first=(0, 2), last=(2, 3)), RH_ERR_ARG,
+         "window 1 starts on day 2, window 0 ends on day 2 (windows are in increasing order and do not overlap)"),
+        # precedence: age-resolved is said before BULK without a weight
+        ([(ix("sa_rz"), -1, BULK)], {}, RH_ERR_ARG, f"array sa_rz is age-resolved ({one_value})"),
+    )
+    for items, windows, code, text in cases:
+        assert configure_windows_raw(ctx, who, items, **windows) == (code, f"{who}: {text}"), text
+    assert same_reading(read(), before)
+    ctx.close()
+
+
+
+
+def sas_observer_calls(ctx):
+    """Every _record, _count, _row_elems and _read of the five transport observers, with arguments that ask for no rows and give no bytes:
+    [(function, its configure function, call -> rc)]."""
+    lib, h = ctx._lib, ctx._h
+    i64, buf, byte, cells = C.c_int64(), np.zeros(64), np.zeros(8, dtype=np.uint8), np.zeros(8, dtype=np.int64)
+    n, p64 = C.byref(i64), C.cast(vp(cells), C.POINTER(C.c_int64))
+    no_rows = (0, 0, vp(cells), vp(buf), 0)
+    no_bands = (vp(buf), 0, vp(cells), 0, vp(cells), 0, vp(byte), 0, n)
+    P, T, Z, S, B = (f"rh_sas_{o}_configure" for o in ("points", "totals", "zonal", "scores", "bands"))
+    return [("rh_sas_points_record", P, lambda: lib.rh_sas_points_record(h, 0)),
+            ("rh_sas_points_count", P, lambda: lib.rh_sas_points_count(h, n)),
+            ("rh_sas_points_row_elems", P, lambda: lib.rh_sas_points_row_elems(h, n)),
+            ("rh_sas_points_read", P, lambda: lib.rh_sas_points_read(h, *no_rows)),
+            ("rh_sas_totals_record", T, lambda: lib.rh_sas_totals_record(h, 0, -1)),
+            ("rh_sas_totals_count", T, lambda: lib.rh_sas_totals_count(h, n, p64)),
+            ("rh_sas_totals_row_elems", T, lambda: lib.rh_sas_totals_row_elems(h, n)),
+            ("rh_sas_totals_read", T, lambda: lib.rh_sas_totals_read(h, *no_rows)),
+            ("rh_sas_zonal_record", Z, lambda: lib.rh_sas_zonal_record(h, 0, -1)),
+            ("rh_sas_zonal_count", Z, lambda: lib.rh_sas_zonal_count(h, n, vp(cells))),
+            ("rh_sas_zonal_row_elems", Z, lambda: lib.rh_sas_zonal_row_elems(h, n)),
+            ("rh_sas_zonal_read", Z, lambda: lib.rh_sas_zonal_read(h, *no_rows)),
+            ("rh_sas_scores_record", S, lambda: lib.rh_sas_scores_record(h, 0)),
+            ("rh_sas_scores_read", S, lambda: lib.rh_sas_scores_read(h, vp(buf), 0, vp(byte), 0, n)),
+            ("rh_sas_bands_record", B, lambda: lib.rh_sas_bands_record(h, 0)),
+            ("rh_sas_bands_read", B, lambda: lib.rh_sas_bands_read(h, *no_bands)),
+            ("rh_sas_bands_zonal_read", "rh_sas_bands_configure_zonal", lambda: lib.rh_sas_bands_zonal_read(h, *no_bands))]
+
+
+def test_the_transport_observers_calls_before_configure_and_after_a_release():
+    """`<function>: <configure function> has not been called`, RH_ERR_STATE, from every call of the five observers: on a new context and
+    after each observer was configured and released; the zonal read on plain bands, and the plain read's own text on bands per zone."""
+    ctx = small_sas()
+
+    def assert_all_off():
+        for name, conf, call in sas_observer_calls(ctx):
+            assert sas_error(ctx, call()) == (RH_ERR_STATE, f"{name}: {conf} has not been called"), name
+
+    assert_all_off()
+    ctx.points_configure([0, 4], ["C_rz"], capacity=2)
+    ctx.totals_configure(["C_rz"], None, capacity=2)
+    ctx.zonal_configure(["C_rz"], SAS_ZONES, 2, capacity=2)
+    configure_windows_valid(ctx, "rh_sas_scores_configure")
+    configure_windows_valid(ctx, "rh_sas_bands_configure")
+    for name, conf, call in sas_observer_calls(ctx):
+        rc, text = sas_error(ctx, call())
+        if name == "rh_sas_bands_zonal_read":
+            assert (rc, text) == (RH_ERR_STATE, "rh_sas_bands_zonal_read: rh_sas_bands_configure_zonal has not been called")
+        else:   # (every observer is on: the call succeeds, or a read says that it got no bytes for its windows)
+            assert rc == 0 or (rc == RH_ERR_ARG and text.startswith(f"{name}: size mismatch")), (name, rc, text)
+    configure_windows_valid(ctx, "rh_sas_bands_configure_zonal")
+    plain_read = dict((name, call) for name, _, call in sas_observer_calls(ctx))["rh_sas_bands_read"]
+    assert sas_error(ctx, plain_read()) == (RH_ERR_STATE,
+                                            "rh_sas_bands_read: the bands are configured per zone (read them with rh_sas_bands_zonal_read)")
+    ctx.points_configure([], [])
+    ctx.totals_configure([])
+    ctx.zonal_configure([])
+    ctx.scores_configure([])
+    ctx.bands_configure([])
+    assert_all_off()
+    ctx.close()
+
+
+@pytest.mark.parametrize("kind", [LAST, MEAN], ids=["last", "mean"])
+def test_the_clock_that_scores_and_bands_share(kind):
+    """Nine days over the windows [-1, 1], [2, 2], [3, 4], [6, 7]: window 0 starts before the count and is never open, window 1 is a single
+    day, days 5 and 8 lie outside every window.  A LAST item launches on closing days only, a MEAN item on every day of an open window;
+    both observers close the windows 1 ... 3, count 9 days and hold what their host restatements hold, bit for bit."""
+    import sas_bands_reference as B
+    import sas_scores_reference as S
+
+    ctx = small_sas()
+    windows = (np.array([-1, 2, 3, 6]), np.array([1, 2, 4, 7]))
+    items, probs = [("C_rz", None, kind)], (0.0, 0.5, 1.0)
+    obs = np.array([[[-6.0, -5.5, np.nan, -7.5]]])
+    ctx.scores_configure(items, obs=obs, windows=windows)
+    ctx.bands_configure(items, probs=probs, windows=windows, obs=obs[:, 0])
+    want_s = S.HostSasScores(items, obs, windows, SAS_N)
+    want_b = B.HostSasBands(items, probs, windows, SAS_N, obs=obs[:, 0])
+    for _ in range(9):
+        assert ctx._lib.rh_sas_scores_record(ctx._h, 0) == 0 and ctx._lib.rh_sas_bands_record(ctx._h, 0) == 0
+        want_s.add({"C_rz": SAS_C})
+        want_b.add({"C_rz": SAS_C})
+    moments, closed_s, days_s = ctx.scores_read()
+    rows, hdr, pairs, closed_b, days_b = ctx.bands_read()
+    assert list(closed_s) == [0, 1, 1, 1] and list(closed_b) == [0, 1, 1, 1] and days_s == 9 and days_b == 9
+    assert list(want_s.closed) == [0, 1, 1, 1] and list(want_b.closed) == [0, 1, 1, 1]
+    assert np.isnan(rows[0]).all() and not hdr[0].any() and (pairs[0] == -1).all()
+    assert not np.isnan(rows[1:]).any() and (hdr[1:, 0, 0] == SAS_N).all()
+    assert same_bits(rows, want_b.rows) and np.array_equal(hdr, want_b.hdr) and np.array_equal(pairs, want_b.pairs)
+    assert same_bits(moments, want_s.moments) and list(moments[0, 2]) == [2.0] * SAS_N   # (the windows 1 and 3 have an observation)
+    ctx.close()
