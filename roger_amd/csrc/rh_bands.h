@@ -27,12 +27,12 @@
 // Keys.  k_bands (a workgroup per RH_BLOCK columns, after every step) does the SUM accumulation -- 24 B per SUM item and column; it ends
 // after the scalar loads when the step is not counted and there is no SUM item -- and on a counted step stores the order-preserving
 // key of s into the item's key plane: u = bits(s), key = u ^ (u >> 63 ? ~0 : 1 << 63); unsigned comparison of keys is < on the values.
-// Validity is part of the key plane, not a plane of its own: a NaN s stores RH_BANDS_KEY_NAN (~0 - 1), and a masked-out column keeps
-// RH_BANDS_KEY_MASKED (~0), which the configuration wrote once.  Both are the keys of NaN bit patterns, so no value's key equals them
-// (the largest value's key, +inf's, is 0xfff0000000000000); the selection skips every key >= RH_BANDS_KEY_NAN and counts the first.
+// Validity is part of the key plane, not a plane of its own: a NaN s stores RH_SELECT_KEY_NAN (~0 - 1), and a masked-out column keeps
+// RH_SELECT_KEY_MASKED (~0), which the configuration wrote once.  Both are the keys of NaN bit patterns, so no value's key equals them
+// (the largest value's key, +inf's, is 0xfff0000000000000); the selection skips every key >= RH_SELECT_KEY_NAN and counts the first.
 //
 // Selection.  A radix selection on the keys, most significant digit first, for all (item, probability) pairs at once, in
-// RH_BANDS_PASSES launches of k_bands_select<P> behind k_bands.  The host cannot know whether a step closes an interval (dt is the
+// RH_SELECT_PASSES launches of k_bands_select<P> behind k_bands.  The host cannot know whether a step closes an interval (dt is the
 // device's), so the launches follow every step and end after the scalar loads on a step that is not counted.
 //   digits     11 bits: six passes over 11, 11, 11, 11, 11 and 9 bits.  8 bits would need eight passes.  A launch-bound grid (80 x 53
 //              columns, 21 us per step) pays per launch, a large grid per pass over the keys (8 B per column): both favour fewer
@@ -44,7 +44,7 @@
 //   merge      the workgroup adds its NON-ZERO bins to the global histogram bands_hist [item][probability][2048] with integer atomic
 //              adds at device scope.  Integer adds commute: the sum does not depend on their order.  This is the one place where the
 //              project's "no atomics" habit, which is about floating-point sums, does not apply.  Device-scope atomics on one cache
-//              line are served one after the other (~ 25 ns each), so the grid is at most RH_BANDS_MAX_GRID
+//              line are served one after the other (~ 25 ns each), so the grid is at most RH_SELECT_MAX_GRID
 //              workgroups (one per CU) however many tiles there are, and after pass 0 nearly every bin is empty.
 //   pick       the work of the workgroup that finishes last (k_step's tail pattern, one counter: the grid is small).  Its invariant
 //              is kept: a thread's adds are RETURNING atomics whose results feed an LDS add in front of the workgroup's barrier, and
@@ -69,19 +69,14 @@
 // (below, equal) -- the members, or their weights, below and equal to the observation -- counted from the key planes in one more pass
 // behind the selection: k_bands_obs, k_bands_obs_row and k_bands_obs_zonal at the end of this file, the rule with them.
 #pragma once
-#include "rh_select.h"   // the pure pieces shared with rh_sas_bands.h: BandsPass, the key and its inverse, bands_rank_of, the weighted grid and pick
+#include "rh_select.h"   // the selection's pieces shared with rh_sas_bands.h: keys, passes, grids, the walks, the count, the pick, the pair
 
 #define RH_BANDS_MAX_ITEMS 8
 #define RH_BANDS_MAX_PROBS 8
 #define RH_BANDS_SUM 0
 #define RH_BANDS_LAST 1
-#define RH_BANDS_NBINS 2048   // 11-bit digits
-#define RH_BANDS_PASSES 6
-#define RH_BANDS_MAX_GRID 256   // workgroups of k_bands_select
 #define RH_BANDS_MAX_ZONES 1024   // rh_bands_configure_zonal: a workgroup of k_bands_zonal per zone and item
-#define RH_BANDS_KEY_MASKED RH_SELECT_KEY_MASKED
-#define RH_BANDS_KEY_NAN RH_SELECT_KEY_NAN
-static_assert(RH_BLOCK == RH_SELECT_BLOCK && RH_BANDS_MAX_GRID == RH_SELECT_MAX_GRID, "rh_select.h states the tile and the grid of the selection");
+static_assert(RH_BLOCK == RH_SELECT_BLOCK && RH_BANDS_MAX_PROBS == RH_SELECT_MAX_PROBS, "rh_select.h states the tile and the histograms of the selection");
 
 struct BandsClock {
     bool first, counted;
@@ -120,53 +115,22 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands(Arena a, DevState *D, int af
         }
         if (!c.counted) continue;
         s = s + 0.0;
-        D->bands_keys[(size_t)j * n + i] = s != s ? RH_BANDS_KEY_NAN : bands_key_of(s);
+        D->bands_keys[(size_t)j * n + i] = s != s ? RH_SELECT_KEY_NAN : bands_key_of(s);
     }
 }
 
-// (pass P of the selection -- digit bits [shift, shift + width) of the key, the bits above them the prefix -- is BandsPass<P> of rh_select.h)
-RH_DEV unsigned bands_wave_scan(unsigned x) {   // inclusive, over the 64 lanes
-    const int lane = threadIdx.x & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-// The pick of one wavefront: bin k * 64 + lane of a histogram in v[k]; the digit at which the cumulative count passes the rank r, and the
-// count below it.  (No bin passes it only where the histogram is empty: digit 0, below 0.)
-template <int NC>
-RH_DEV void bands_pick(const unsigned (&v)[NC], long long r, int &digit, long long &below) {
-    long long base = 0;
-    bool found = false;
-    digit = 0;
-    below = 0;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-        const unsigned incl = bands_wave_scan(v[k]);
-        const long long chunk = (long long)__shfl(incl, 63);
-        if (!found && base + chunk > r) {
-            const unsigned long long hit = __ballot(base + (long long)incl > r);
-            const int l = __ffsll((long long)hit) - 1;
-            digit = k * 64 + l;
-            below = base + (long long)__shfl(incl - v[k], l);
-            found = true;
-        }
-        base += chunk;
-    }
-}
-// (the rank of probability p among m values, one double multiplication and one ceil, is bands_rank_of of rh_select.h)
+// The walk over the tiles, the digit count of a key and the pick step of a wavefront are rh_select.h's (select_walk_tiles, select_count,
+// select_pick_step); the kernel is the shell around them: the clock, the merge, the completion pattern and the row.
 template <int P>
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D, int after_fused) {
-    using PS = BandsPass<P>;
-    constexpr int NB = PS::nb, NC = NB / 64, U = 8;
-    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_BANDS_NBINS];
+    constexpr int NB = BandsPass<P>::nb, NC = NB / 64;
+    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_SELECT_NBINS];
     __shared__ unsigned nan_count, posted, is_last;
     if (after_fused && D->skipped) return;
     const BandsClock c = bands_clock(D);
     if (!c.counted) return;   // (uniform over the grid)
     const int ni = D->bands_nitems, np = D->bands_nprobs, nh = P == 0 ? 1 : np;
-    const int64_t n = a.n, ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    const int64_t n = a.n;
     unsigned dep = 0;
     if (threadIdx.x == 0) posted = 0;
     for (int j = 0; j < ni; ++j) {
@@ -177,34 +141,14 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
 #pragma unroll
         for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q) pre[q] = (P > 0 && q < np) ? D->bands_prefix[j * RH_BANDS_MAX_PROBS + q] : 0ull;
         const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
-        for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
-            unsigned long long key[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = (t + (int64_t)u * gridDim.x) * RH_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
-                key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_BANDS_KEY_MASKED;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (key[u] >= RH_BANDS_KEY_NAN) {
-                    if (P == 0 && key[u] == RH_BANDS_KEY_NAN) atomicAdd(&nan_count, 1u);
-                    continue;
-                }
-                const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
-                if (P == 0) {
-                    atomicAdd(&hist[d], 1u);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q)
-                        if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], 1u);
-                }
-            }
-        }
+        unsigned mine = 0, mine_nan = 0;   // pass 0: the NaNs this thread met (the numbers are the histogram's total)
+        select_walk_tiles<false>(keys, nullptr, n, [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<P>(key, w, np, pre, hist, mine, mine_nan); });
+        if (P == 0 && mine_nan) atomicAdd(&nan_count, mine_nan);
         __syncthreads();
-        unsigned *g = D->bands_hist + (size_t)j * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS;
+        unsigned *g = D->bands_hist + (size_t)j * RH_BANDS_MAX_PROBS * RH_SELECT_NBINS;
         for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) {
             const unsigned cnt = hist[b];
-            if (cnt) dep |= __hip_atomic_fetch_add(g + (b / NB) * RH_BANDS_NBINS + (b % NB), cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
+            if (cnt) dep |= __hip_atomic_fetch_add(g + (b / NB) * RH_SELECT_NBINS + (b % NB), cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
         }
         if (P == 0 && threadIdx.x == 0 && nan_count)
             dep |= __hip_atomic_fetch_add(&D->bands_nan_count[j], nan_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31;
@@ -224,35 +168,22 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
     const long long slot = row % D->bands_cap;
     for (int pair = threadIdx.x >> 6; pair < ni * np; pair += RH_BLOCK / 64) {   // (uniform over the wavefront)
         const int j = pair / np, q = pair - j * np, at = j * RH_BANDS_MAX_PROBS + q;
-        const unsigned *h = D->bands_hist + (size_t)(j * RH_BANDS_MAX_PROBS + (P == 0 ? 0 : q)) * RH_BANDS_NBINS;
+        const unsigned *h = D->bands_hist + (size_t)(j * RH_BANDS_MAX_PROBS + (P == 0 ? 0 : q)) * RH_SELECT_NBINS;
         unsigned v[NC];
 #pragma unroll
         for (int k = 0; k < NC; ++k) v[k] = __hip_atomic_load(h + k * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        long long m, r;
-        if (P == 0) {
-            unsigned tot = 0;
-#pragma unroll
-            for (int k = 0; k < NC; ++k) tot += v[k];
-            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
-            m = (long long)tot;
-            r = bands_rank_of(D->bands_probs[q], m);
-        } else {
-            m = D->bands_m[j];
-            r = D->bands_rank[at];
-        }
-        long long below;
-        int digit;
-        bands_pick<NC>(v, r, digit, below);
-        const unsigned long long prefix = (P == 0 ? 0ull : D->bands_prefix[at] << PS::width) | (unsigned long long)digit;
+        const SelectPick pk = select_pick_step<P>(v, D->bands_probs[q], &D->bands_prefix[at], &D->bands_rank[at]);
+        const unsigned long long prefix = pk.prefix;
+        const long long m = P == 0 ? pk.total : D->bands_m[j];
         if (lane == 0) {
             D->bands_prefix[at] = prefix;
-            D->bands_rank[at] = r - below;
+            D->bands_rank[at] = pk.rank;
             if (P == 0 && q == 0) {
                 D->bands_m[j] = m;
                 D->bands_nan[j] = (long long)__hip_atomic_load(&D->bands_nan_count[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&D->bands_nan_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (P == RH_BANDS_PASSES - 1) {
+            if (P == RH_SELECT_PASSES - 1) {
                 D->bands[(size_t)slot * ni * np + j * np + q] = m ? bands_value_of(prefix) : __builtin_nan("");
             }
         }
@@ -260,12 +191,12 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
     __syncthreads();   // (in pass 0 the pairs of an item read one histogram)
     for (int b = threadIdx.x; b < ni * nh * NB; b += RH_BLOCK) {
         const int jq = b / NB;
-        __hip_atomic_store(D->bands_hist + (size_t)((jq / nh) * RH_BANDS_MAX_PROBS + jq % nh) * RH_BANDS_NBINS + b % NB, 0u, __ATOMIC_RELAXED,
+        __hip_atomic_store(D->bands_hist + (size_t)((jq / nh) * RH_BANDS_MAX_PROBS + jq % nh) * RH_SELECT_NBINS + b % NB, 0u, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x == 0) {
         __hip_atomic_store(&D->bands_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (P == RH_BANDS_PASSES - 1) {
+        if (P == RH_SELECT_PASSES - 1) {
             long long *hd = D->bands_hdr + (size_t)slot * (2 + 2 * ni);
             hd[0] = c.k;
             hd[1] = c.t1;
@@ -285,7 +216,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
 // Column lists.  A stable counting sort on the host: bands_zone_off [n_zones + 1] and bands_zone_cols (int32 column indices, ascending
 // within a zone), uploaded once.
 // k_bands_zonal, ONE launch behind k_bands in place of the six k_bands_select: grid (n_zones, n_items).  A workgroup walks its zone's list
-// (eight columns in flight per thread), gathers keys[j * n + col] and runs all RH_BANDS_PASSES digit passes itself: one LDS histogram per
+// (eight columns in flight per thread), gathers keys[j * n + col] and runs all RH_SELECT_PASSES digit passes itself: one LDS histogram per
 // probability at the widths of BandsPass<P>; pass 0 is shared by the probabilities and yields m and n_nan; a wavefront per probability
 // picks the digit (bands_pick); prefixes and ranks stay in LDS between the passes.  The later passes read the keys again: L2 serves them.
 // LDS atomics only -- no device-scope atomic, no completion counter.  It writes its (item, zone) block of row bands_rows % bands_cap:
@@ -299,8 +230,7 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select(Arena a, DevState *D,
 template <int P>
 RH_DEV void bands_zonal_pass(const unsigned long long *keys, const int *cols, long long beg, long long end, int np, const double *probs, unsigned *hist,
                              unsigned long long *s_prefix, long long *s_rank, long long *s_count, unsigned *s_nan) {
-    using PS = BandsPass<P>;
-    constexpr int NB = PS::nb, NC = NB / 64, U = 8;
+    constexpr int NB = BandsPass<P>::nb, NC = NB / 64;
     const int nh = P == 0 ? 1 : np;
     for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) hist[b] = 0;
     if (P == 0 && threadIdx.x == 0) *s_nan = 0;
@@ -308,32 +238,9 @@ RH_DEV void bands_zonal_pass(const unsigned long long *keys, const int *cols, lo
     unsigned long long pre[RH_BANDS_MAX_PROBS];
 #pragma unroll
     for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q) pre[q] = (P > 0 && q < np) ? s_prefix[q] : 0ull;
-    for (long long base = beg; base < end; base += (long long)RH_BLOCK * U) {
-        int col[U];
-        unsigned long long key[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long at = base + (long long)u * RH_BLOCK + threadIdx.x;
-            col[u] = at < end ? cols[at] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) key[u] = col[u] >= 0 ? keys[col[u]] : RH_BANDS_KEY_MASKED;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_BANDS_KEY_NAN) {
-                if (P == 0 && key[u] == RH_BANDS_KEY_NAN) atomicAdd(s_nan, 1u);
-                continue;
-            }
-            const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
-            if (P == 0) {
-                atomicAdd(&hist[d], 1u);
-            } else {
-#pragma unroll
-                for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q)
-                    if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], 1u);
-            }
-        }
-    }
+    unsigned mine = 0, mine_nan = 0;   // pass 0: the NaNs this thread met (the numbers are the histogram's total)
+    select_walk_list<false>(keys, nullptr, cols, beg, end, [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<P>(key, w, np, pre, hist, mine, mine_nan); });
+    if (P == 0 && mine_nan) atomicAdd(s_nan, mine_nan);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     for (int q = threadIdx.x >> 6; q < np; q += RH_BLOCK / 64) {   // (uniform over the wavefront)
@@ -341,32 +248,20 @@ RH_DEV void bands_zonal_pass(const unsigned long long *keys, const int *cols, lo
         unsigned v[NC];
 #pragma unroll
         for (int k = 0; k < NC; ++k) v[k] = h[k * 64 + lane];
-        long long r;
-        if (P == 0) {
-            unsigned tot = 0;
-#pragma unroll
-            for (int k = 0; k < NC; ++k) tot += v[k];
-            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
-            r = bands_rank_of(probs[q], (long long)tot);
-            if (q == 0 && lane == 0) {
-                s_count[0] = (long long)tot;
+        const SelectPick pk = select_pick_step<P>(v, probs[q], &s_prefix[q], &s_rank[q]);
+        if (lane == 0) {
+            s_prefix[q] = pk.prefix;
+            s_rank[q] = pk.rank;
+            if (P == 0 && q == 0) {
+                s_count[0] = pk.total;
                 s_count[1] = (long long)*s_nan;
             }
-        } else {
-            r = s_rank[q];
-        }
-        long long below;
-        int digit;
-        bands_pick<NC>(v, r, digit, below);
-        if (lane == 0) {
-            s_prefix[q] = (P == 0 ? 0ull : s_prefix[q] << PS::width) | (unsigned long long)digit;
-            s_rank[q] = r - below;
         }
     }
     __syncthreads();   // (the next pass clears the histograms and reads the prefixes)
 }
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_zonal(DevState *D, long long n, int after_fused) {
-    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_BANDS_NBINS];
+    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_SELECT_NBINS];
     __shared__ unsigned long long s_prefix[RH_BANDS_MAX_PROBS];
     __shared__ long long s_rank[RH_BANDS_MAX_PROBS], s_count[2];
     __shared__ unsigned s_nan;
@@ -416,7 +311,7 @@ __global__ void k_bands_zonal_row(DevState *D, int after_fused) {
 // handling, keys.
 // Weights.  Integer weights w_i, one uint16 per column, in 0 ... 65535: the type is the bound.  A column with w_i == 0 takes no part,
 // exactly as a masked-out column: it loads and stores nothing in k_bands (whose byte mask is w != 0, written at the configuration, as
-// the zonal path writes zone >= 0), it is in neither m nor n_nan, and its key stays RH_BANDS_KEY_MASKED.
+// the zonal path writes zone >= 0), it is in neither m nor n_nan, and its key stays RH_SELECT_KEY_MASKED.
 // Counts.  m is the number of participating columns whose s is not a NaN, n_nan the number whose s is a NaN: column counts, as in the
 // plain rule.  New: W = sum of w_i over the m columns, an int64.  W < 2^47, since n < 2^31, so (double)W is exact.
 // Target and result.  For a probability p: T = clamp((int64)ceil(p * (double)W), 1, W) -- one double multiplication, one ceil, the same
@@ -431,37 +326,33 @@ __global__ void k_bands_zonal_row(DevState *D, int after_fused) {
 // k_bands_select_w<P>: six launches, the digit widths of BandsPass<P>, the last-workgroup completion pattern of k_bands_select with its
 // invariant.  What differs:
 //   histogram  a key's bin gains w_i, not 1.  The weight plane (bands_weight, 2 B per column) is read in every pass, non-temporal, issued
-//              with the key loads.  A zero weight needs no test: such a column's key is RH_BANDS_KEY_MASKED.
+//              with the key loads.  A zero weight needs no test: such a column's key is RH_SELECT_KEY_MASKED.
 //   LDS bins   stay uint32 (64 KiB for eight probabilities).  A bin holds at most (columns the workgroup walks) x 65535, so a workgroup
-//              walks at most RH_BANDS_W_MAX_TILES = 256 tiles of RH_BLOCK = 256 columns: 65536 x 65535 < 2^32.  bands_weighted_grid
-//              derives the grid from that bound -- max(min(RH_BANDS_MAX_GRID, ntiles), ceil(ntiles / 256)) -- and is the one place that
+//              walks at most RH_SELECT_W_MAX_TILES = 256 tiles of RH_BLOCK = 256 columns: 65536 x 65535 < 2^32.  bands_weighted_grid
+//              derives the grid from that bound -- max(min(RH_SELECT_MAX_GRID, ntiles), ceil(ntiles / 256)) -- and is the one place that
 //              does; beyond 16.7 x 10^6 columns the grid grows past one workgroup per CU.  (The tile loop gives workgroup b the tiles
 //              t = b mod grid: ceil(ntiles / grid) of them at most.)
 //   merge      into bands_whist, uint64 [item][probability][2048] (1 MiB), with returning 64-bit device-scope integer adds of the non-zero
 //              bins (dep |= ret >> 63; a sum stays below 2^47).  The last workgroup clears it.
-//   counts     m is no longer the histogram's total: pass 0 counts the keys below RH_BANDS_KEY_NAN per item in LDS beside nan_count, and
+//   counts     m is no longer the histogram's total: pass 0 counts the keys below RH_SELECT_KEY_NAN per item in LDS beside nan_count, and
 //              one returning device-scope add per workgroup and item takes it to bands_m_count.  W is the pass-0 histogram's total.
-//   pick       bands_wave_scan64 / bands_pick64 over unsigned long long bins: the 32-bit forms above, which k_bands_select and
-//              k_bands_zonal call, are as they were.
+//   pick       select_pick_step over unsigned long long bins: k_bands_select and k_bands_zonal instantiate it over unsigned bins, with
+//              32-bit lane arithmetic.
 //   row        header {k, t1, m, n_nan per item} as in the plain path; W per item goes into a ring of its own, bands_wsum [cap][items]
 //              int64, written with the header before bands_rows advances.
 // No counter overflows for any configuration the configure call accepts (n < 2^31): LDS bins by the bound above, the global bins and W
 // below 2^31 x 65535 < 2^47, m and n_nan below 2^31, bands_done at most 2^15 workgroups.  Integer atomics only.
 // Cost of a counted step: the plain path's, plus 2 B per column, item and pass of weights, plus 64-bit merges (8 B a bin, not 4).
-#define RH_BANDS_W_MAX_TILES RH_SELECT_W_MAX_TILES   // tiles of RH_BLOCK columns one workgroup of k_bands_select_w may walk
-// (bands_weighted_grid with its static_assert, bands_wave_scan64 and bands_pick64 -- the 64-bit forms of bands_wave_scan and bands_pick above --
-// are rh_select.h's)
 template <int P>
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *D, int after_fused) {
-    using PS = BandsPass<P>;
-    constexpr int NB = PS::nb, NC = NB / 64, U = 8;
-    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_BANDS_NBINS];
+    constexpr int NB = BandsPass<P>::nb, NC = NB / 64;
+    __shared__ unsigned hist[RH_BANDS_MAX_PROBS * RH_SELECT_NBINS];
     __shared__ unsigned nan_count, num_count, posted, is_last;
     if (after_fused && D->skipped) return;
     const BandsClock c = bands_clock(D);
     if (!c.counted) return;   // (uniform over the grid)
     const int ni = D->bands_nitems, np = D->bands_nprobs, nh = P == 0 ? 1 : np;
-    const int64_t n = a.n, ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    const int64_t n = a.n;
     const unsigned short *wts = D->bands_weight;
     unsigned dep = 0;
     if (threadIdx.x == 0) posted = 0;
@@ -473,40 +364,16 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
 #pragma unroll
         for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q) pre[q] = (P > 0 && q < np) ? D->bands_prefix[j * RH_BANDS_MAX_PROBS + q] : 0ull;
         const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
-        unsigned mine = 0;   // pass 0: the keys of numbers this thread met
-        for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
-            unsigned long long key[U];
-            unsigned w[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = (t + (int64_t)u * gridDim.x) * RH_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
-                key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_BANDS_KEY_MASKED;
-                w[u] = i < n ? (unsigned)__builtin_nontemporal_load(wts + i) : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (key[u] >= RH_BANDS_KEY_NAN) {
-                    if (P == 0 && key[u] == RH_BANDS_KEY_NAN) atomicAdd(&nan_count, 1u);
-                    continue;
-                }
-                const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
-                if (P == 0) {
-                    ++mine;
-                    atomicAdd(&hist[d], w[u]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < RH_BANDS_MAX_PROBS; ++q)
-                        if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], w[u]);
-                }
-            }
-        }
+        unsigned mine = 0, mine_nan = 0;   // pass 0: the numbers and the NaNs this thread met
+        select_walk_tiles<true>(keys, wts, n, [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<P>(key, w, np, pre, hist, mine, mine_nan); });
         if (P == 0 && mine) atomicAdd(&num_count, mine);
+        if (P == 0 && mine_nan) atomicAdd(&nan_count, mine_nan);
         __syncthreads();
-        unsigned long long *g = D->bands_whist + (size_t)j * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS;
+        unsigned long long *g = D->bands_whist + (size_t)j * RH_BANDS_MAX_PROBS * RH_SELECT_NBINS;
         for (int b = threadIdx.x; b < nh * NB; b += RH_BLOCK) {
             const unsigned cnt = hist[b];
             if (cnt)
-                dep |= (unsigned)(__hip_atomic_fetch_add(g + (b / NB) * RH_BANDS_NBINS + (b % NB), (unsigned long long)cnt, __ATOMIC_RELAXED,
+                dep |= (unsigned)(__hip_atomic_fetch_add(g + (b / NB) * RH_SELECT_NBINS + (b % NB), (unsigned long long)cnt, __ATOMIC_RELAXED,
                                                          __HIP_MEMORY_SCOPE_AGENT) >> 63);
         }
         if (P == 0 && threadIdx.x == 0) {
@@ -529,36 +396,23 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
     const long long slot = row % D->bands_cap;
     for (int pair = threadIdx.x >> 6; pair < ni * np; pair += RH_BLOCK / 64) {   // (uniform over the wavefront)
         const int j = pair / np, q = pair - j * np, at = j * RH_BANDS_MAX_PROBS + q;
-        const unsigned long long *h = D->bands_whist + (size_t)(j * RH_BANDS_MAX_PROBS + (P == 0 ? 0 : q)) * RH_BANDS_NBINS;
+        const unsigned long long *h = D->bands_whist + (size_t)(j * RH_BANDS_MAX_PROBS + (P == 0 ? 0 : q)) * RH_SELECT_NBINS;
         unsigned long long v[NC];
 #pragma unroll
         for (int k = 0; k < NC; ++k) v[k] = __hip_atomic_load(h + k * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        long long wsum = 0, r;
-        if (P == 0) {
-            unsigned long long tot = 0;
-#pragma unroll
-            for (int k = 0; k < NC; ++k) tot += v[k];
-            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
-            wsum = (long long)tot;
-            r = bands_rank_of(D->bands_probs[q], wsum);   // T - 1
-        } else {
-            r = D->bands_rank[at];
-        }
-        long long below;
-        int digit;
-        bands_pick64<NC>(v, r, digit, below);
-        const unsigned long long prefix = (P == 0 ? 0ull : D->bands_prefix[at] << PS::width) | (unsigned long long)digit;
+        const SelectPick pk = select_pick_step<P>(v, D->bands_probs[q], &D->bands_prefix[at], &D->bands_rank[at]);   // (pass 0: the rank is T - 1)
+        const unsigned long long prefix = pk.prefix;
         if (lane == 0) {
             D->bands_prefix[at] = prefix;
-            D->bands_rank[at] = r - below;
+            D->bands_rank[at] = pk.rank;
             if (P == 0 && q == 0) {
-                D->bands_w[j] = wsum;
+                D->bands_w[j] = pk.total;
                 D->bands_m[j] = (long long)__hip_atomic_load(&D->bands_m_count[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 D->bands_nan[j] = (long long)__hip_atomic_load(&D->bands_nan_count[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&D->bands_m_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&D->bands_nan_count[j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (P == RH_BANDS_PASSES - 1) {
+            if (P == RH_SELECT_PASSES - 1) {
                 D->bands[(size_t)slot * ni * np + j * np + q] = D->bands_m[j] ? bands_value_of(prefix) : __builtin_nan("");
             }
         }
@@ -566,12 +420,12 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
     __syncthreads();   // (in pass 0 the pairs of an item read one histogram)
     for (int b = threadIdx.x; b < ni * nh * NB; b += RH_BLOCK) {
         const int jq = b / NB;
-        __hip_atomic_store(D->bands_whist + (size_t)((jq / nh) * RH_BANDS_MAX_PROBS + jq % nh) * RH_BANDS_NBINS + b % NB, 0ull, __ATOMIC_RELAXED,
+        __hip_atomic_store(D->bands_whist + (size_t)((jq / nh) * RH_BANDS_MAX_PROBS + jq % nh) * RH_SELECT_NBINS + b % NB, 0ull, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x == 0) {
         __hip_atomic_store(&D->bands_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (P == RH_BANDS_PASSES - 1) {
+        if (P == RH_SELECT_PASSES - 1) {
             long long *hd = D->bands_hdr + (size_t)slot * (2 + 2 * ni), *ws = D->bands_wsum + (size_t)slot * ni;
             hd[0] = c.k;
             hd[1] = c.t1;
@@ -601,9 +455,9 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
 // Consequences.  T_tot = m (plain, zonal) or W (weighted): 0 <= below, 0 <= equal, below + equal <= T_tot; for a recorded probability p
 // with target T = clamp(ceil(p T_tot), 1, T_tot) and recorded quantile q:  q <= o <=> below + equal >= T,  q < o <=> below >= T.
 //
-// k_bands_obs (plain and weighted): grid (min(RH_BANDS_MAX_GRID, ntiles), items) behind the selection's last pass.  A workgroup strides
+// k_bands_obs (plain and weighted): grid (min(RH_SELECT_MAX_GRID, ntiles), items) behind the selection's last pass.  A workgroup strides
 // over the tiles of its item's key plane as k_bands_select does (eight tiles in flight per thread); a thread adds 1, or bands_weight[i],
-// into two int64 registers; keys >= RH_BANDS_KEY_NAN are skipped (a zero weight needs no test: that key is RH_BANDS_KEY_MASKED).  The
+// into two int64 registers; keys >= RH_SELECT_KEY_NAN are skipped (a zero weight needs no test: that key is RH_SELECT_KEY_MASKED).  The
 // wavefronts reduce by shuffles, the four of a workgroup through LDS, and thread 0 stores the workgroup's pair into bands_obs_part
 // [item][workgroup][2]: plain stores, no atomics, no last-workgroup pattern.  A missing o ends the workgroup after the scalar loads.
 // k_bands_obs_row: grid (items), one wavefront; adds the partials and writes the pair at the slot of the row just recorded -- the
@@ -615,10 +469,6 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_select_w(Arena a, DevState *
 // No sum overflows: a thread, a workgroup and an item add at most n < 2^31 columns of weight <= 65535 -- below 2^47, as W.
 // Cost of a counted step with observations: one more pass of 8 B (+ 2 B with weights) per item and column, on top of the selection's
 // six, and two launches (zonal: one launch, 8 B + 4 B per participating column gathered).
-static inline unsigned bands_obs_grid(long long n) {
-    const long long ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
-    return (unsigned)(ntiles < RH_BANDS_MAX_GRID ? (ntiles < 1 ? 1 : ntiles) : RH_BANDS_MAX_GRID);
-}
 // the observation of (item j, series z) for the interval the clock closes; NaN: missing, or beyond the series
 RH_DEV double bands_obs_of(const DevState *D, const BandsClock &c, int j, int z, int nseries) {
     const long long at = c.k + D->bands_obs_first, len = D->bands_obs_n;
@@ -628,27 +478,9 @@ RH_DEV double bands_obs_of(const DevState *D, const BandsClock &c, int j, int z,
 RH_DEV unsigned long long bands_obs_key(double o) {
     return bands_key_of(o + 0.0);
 }
-// the workgroup's sums of two int64 values: shuffles within a wavefront, LDS across the RH_BLOCK / 64 of them; thread 0 holds the result
-RH_DEV void bands_obs_reduce(long long &below, long long &equal, long long (*s_part)[2]) {
-    for (int off = 32; off; off >>= 1) {
-        below += __shfl_xor(below, off);
-        equal += __shfl_xor(equal, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_part[threadIdx.x >> 6][0] = below;
-        s_part[threadIdx.x >> 6][1] = equal;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        below = equal = 0;
-        for (int w = 0; w < RH_BLOCK / 64; ++w) {
-            below += s_part[w][0];
-            equal += s_part[w][1];
-        }
-    }
-}
+// (the pair of a key, the workgroup's sums and the sum of the partials are select_pair_add, select_pair_reduce and select_pair_partials of
+// rh_select.h)
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_obs(Arena a, DevState *D, int after_fused) {
-    constexpr int U = 8;
     __shared__ long long s_part[RH_BLOCK / 64][2];
     if (after_fused && D->skipped) return;
     const BandsClock c = bands_clock(D);
@@ -657,27 +489,16 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_obs(Arena a, DevState *D, in
     const double o = bands_obs_of(D, c, j, 0, 1);
     if (o != o) return;   // (uniform over the item's workgroups: k_bands_obs_row writes -1, -1 and reads no partial)
     const unsigned long long ko = bands_obs_key(o);
-    const int64_t n = a.n, ntiles = (n + RH_BLOCK - 1) / RH_BLOCK;
+    const int64_t n = a.n;
     const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
-    const unsigned short *wts = D->bands_weight;   // (null: every participating column counts 1)
+    const unsigned short *wts = D->bands_weight;   // (null: every participating column counts 1; uniform, tested once outside the walk)
     long long below = 0, equal = 0;   // (below 2^47: at most n < 2^31 columns of weight <= 65535)
-    for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
-        unsigned long long key[U];
-        long long w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = (t + (int64_t)u * gridDim.x) * RH_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
-            key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_BANDS_KEY_MASKED;
-            w[u] = wts ? (i < n ? (long long)__builtin_nontemporal_load(wts + i) : 0ll) : 1ll;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_BANDS_KEY_NAN) continue;
-            below += key[u] < ko ? w[u] : 0ll;
-            equal += key[u] == ko ? w[u] : 0ll;
-        }
-    }
-    bands_obs_reduce(below, equal, s_part);
+    const auto add = [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_pair_add(key, w, ko, below, equal); };
+    if (wts)
+        select_walk_tiles<true>(keys, wts, n, add);
+    else
+        select_walk_tiles<false>(keys, wts, n, add);
+    select_pair_reduce(below, equal, s_part);
     if (threadIdx.x == 0) {
         long long *part = D->bands_obs_part + ((size_t)j * gridDim.x + blockIdx.x) * 2;
         part[0] = below;
@@ -690,20 +511,8 @@ __global__ __launch_bounds__(64) void k_bands_obs_row(DevState *D, int nparts, i
     if (!c.counted) return;
     const int j = blockIdx.x, ni = gridDim.x;
     const double o = bands_obs_of(D, c, j, 0, 1);
-    long long below = 0, equal = 0;
-    if (o == o) {   // (uniform over the wavefront)
-        const long long *part = D->bands_obs_part + (size_t)j * nparts * 2;
-        for (int b = threadIdx.x; b < nparts; b += 64) {
-            below += part[2 * b];
-            equal += part[2 * b + 1];
-        }
-        for (int off = 32; off; off >>= 1) {
-            below += __shfl_xor(below, off);
-            equal += __shfl_xor(equal, off);
-        }
-    } else {
-        below = equal = -1;
-    }
+    long long below = -1, equal = -1;
+    if (o == o) select_pair_partials(D->bands_obs_part + (size_t)j * nparts * 2, nparts, below, equal);   // (uniform over the wavefront)
     if (threadIdx.x == 0) {
         long long *out = D->bands_obs_ring + ((size_t)((D->bands_rows - 1) % D->bands_cap) * ni + j) * 2;
         out[0] = below;
@@ -711,7 +520,6 @@ __global__ __launch_bounds__(64) void k_bands_obs_row(DevState *D, int nparts, i
     }
 }
 __global__ __launch_bounds__(RH_BLOCK) void k_bands_obs_zonal(DevState *D, long long n, int after_fused) {
-    constexpr int U = 8;
     __shared__ long long s_part[RH_BLOCK / 64][2];
     if (after_fused && D->skipped) return;
     const BandsClock c = bands_clock(D);
@@ -728,24 +536,8 @@ __global__ __launch_bounds__(RH_BLOCK) void k_bands_obs_zonal(DevState *D, long 
     const unsigned long long *keys = D->bands_keys + (size_t)j * (size_t)n;
     const int *cols = D->bands_zone_cols;
     long long below = 0, equal = 0;   // (at most n < 2^31)
-    for (long long base = beg; base < end; base += (long long)RH_BLOCK * U) {
-        int col[U];
-        unsigned long long key[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long at = base + (long long)u * RH_BLOCK + threadIdx.x;
-            col[u] = at < end ? cols[at] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) key[u] = col[u] >= 0 ? keys[col[u]] : RH_BANDS_KEY_MASKED;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_BANDS_KEY_NAN) continue;
-            below += key[u] < ko ? 1ll : 0ll;
-            equal += key[u] == ko ? 1ll : 0ll;
-        }
-    }
-    bands_obs_reduce(below, equal, s_part);
+    select_walk_list<false>(keys, nullptr, cols, beg, end, [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_pair_add(key, w, ko, below, equal); });
+    select_pair_reduce(below, equal, s_part);
     if (threadIdx.x == 0) {
         out[0] = below;
         out[1] = equal;

@@ -52,7 +52,7 @@ static int observers_changed(rh_ctx *ctx) {
 // workgroup per RH_BLOCK columns and one per zone (rh_zonal.h) -- then the scores' moments over all columns, on the accumulators' grid
 // (rh_scores.h) -- then the event outputs, on the same grid (rh_events.h) -- then the duration curves, on the same grid
 // (rh_durations.h) -- then the ensemble bands: the keys on the same grid, and the six passes of the selection on at most
-// RH_BANDS_MAX_GRID workgroups that stride over the tiles -- per zone instead ONE launch with a workgroup per (zone, item) and a
+// RH_SELECT_MAX_GRID workgroups that stride over the tiles -- per zone instead ONE launch with a workgroup per (zone, item) and a
 // one-thread launch for the row's header; with a weight plane the six passes of the weighted selection on bands_weighted_grid
 // workgroups (rh_bands.h); and only while observations are set (rh_bands_observations) the pass that counts the keys below and equal to
 // the observation's and a one-wavefront launch per item for the row's pairs -- per zone ONE launch.  after_fused: rh_control.h, k_diag.
@@ -62,6 +62,14 @@ static bool has_observers(const rh_ctx *ctx) {
 }
 // What rh_*_restore may still replace: set by the observer's configure call, cleared by the first step behind it (launch_observers).
 enum { RH_FRESH_SCORES = 1, RH_FRESH_EVENTS = 2, RH_FRESH_DURATIONS = 4, RH_FRESH_BANDS = 8 };
+// the passes P... of the bands' selection, one launch each, in order: k_bands_select_w<P> with a weight plane, else k_bands_select<P>
+template <bool WEIGHTED, int... P>
+static void launch_bands_select(rh_ctx *ctx, dim3 grid, int after_fused, std::integer_sequence<int, P...>) {
+    const auto launch = [&](void (*kernel)(Arena, DevState *, int)) {
+        hipLaunchKernelGGL(kernel, grid, dim3(RH_BLOCK), 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+    };
+    (launch(WEIGHTED ? k_bands_select_w<P> : k_bands_select<P>), ...);
+}
 static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
     const dim3 cells(grid ? grid : grid_for(ctx->n)), block(RH_BLOCK);
     ctx->obs_fresh = 0;   // (a step is enqueued: the observers' state is the run's from here on)
@@ -84,28 +92,17 @@ static int launch_observers(rh_ctx *ctx, int after_fused, unsigned grid = 0) {
             hipLaunchKernelGGL(k_bands_zonal, dim3(ctx->bands_nzones, ctx->bands_nitems), block, 0, ctx->stream, ctx->dev, (long long)ctx->n, after_fused);
             hipLaunchKernelGGL(k_bands_zonal_row, dim3(1), dim3(1), 0, ctx->stream, ctx->dev, after_fused);
         } else if (ctx->bands_weight_buf) {   // likelihood-weighted: the grid bounds what a workgroup's uint32 LDS bins can hold
-            const dim3 sel(bands_weighted_grid((long long)ctx->n));
-            hipLaunchKernelGGL(k_bands_select_w<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select_w<1>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select_w<2>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select_w<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select_w<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select_w<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            launch_bands_select<true>(ctx, dim3(bands_weighted_grid((long long)ctx->n)), after_fused, std::make_integer_sequence<int, RH_SELECT_PASSES>{});
         } else {
-            const dim3 sel(std::min<unsigned>(grid_for(ctx->n), RH_BANDS_MAX_GRID));
-            hipLaunchKernelGGL(k_bands_select<0>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select<1>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select<2>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select<3>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select<4>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
-            hipLaunchKernelGGL(k_bands_select<5>, sel, block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
+            launch_bands_select<false>(ctx, dim3(std::min<unsigned>(grid_for(ctx->n), RH_SELECT_MAX_GRID)), after_fused,
+                                       std::make_integer_sequence<int, RH_SELECT_PASSES>{});
         }
         if (ctx->bands_obs_buf) {   // observations: the pairs {below, equal} behind the row, from the key planes the selection read
             if (ctx->bands_nzones) {
                 hipLaunchKernelGGL(k_bands_obs_zonal, dim3(ctx->bands_nzones, ctx->bands_nitems), block, 0, ctx->stream, ctx->dev, (long long)ctx->n,
                                    after_fused);
             } else {
-                const unsigned parts = bands_obs_grid((long long)ctx->n);
+                const unsigned parts = select_obs_grid((long long)ctx->n);
                 hipLaunchKernelGGL(k_bands_obs, dim3(parts, ctx->bands_nitems), block, 0, ctx->stream, ctx->arena, ctx->dev, after_fused);
                 hipLaunchKernelGGL(k_bands_obs_row, dim3(ctx->bands_nitems), dim3(64), 0, ctx->stream, ctx->dev, (int)parts, after_fused);
             }
@@ -976,14 +973,14 @@ static int bands_obs_release(rh_ctx *ctx) {
 static int bands_alloc(rh_ctx *ctx, int n_items, int n_probs, const unsigned char *mask, const BandsZones &zones, const uint16_t *weight,
                        int64_t capacity) {
     const size_t n = (size_t)ctx->n, ab = (size_t)n_items * n * sizeof(double),
-                 hb = (size_t)n_items * RH_BANDS_MAX_PROBS * RH_BANDS_NBINS * sizeof(unsigned), nz = (size_t)zones.n_zones,
+                 hb = (size_t)n_items * RH_BANDS_MAX_PROBS * RH_SELECT_NBINS * sizeof(unsigned), nz = (size_t)zones.n_zones,
                  blocks = (size_t)n_items * (nz ? nz : 1);
     HIPCHK(ctx, ctx->bands.buf.alloc((size_t)capacity * blocks * n_probs * sizeof(double)));
     HIPCHK(ctx, ctx->bands.hdr_buf.alloc((size_t)capacity * (nz ? 2 : 2 + 2 * (size_t)n_items) * sizeof(long long)));
     HIPCHK(ctx, ctx->bands_acc_buf.alloc(ab));
     HIPCHK(ctx, hipMemsetAsync(ctx->bands_acc_buf, 0, ab, ctx->stream));
     HIPCHK(ctx, ctx->bands_keys_buf.alloc(ab));
-    HIPCHK(ctx, hipMemsetAsync(ctx->bands_keys_buf, 0xff, ab, ctx->stream));   // RH_BANDS_KEY_MASKED
+    HIPCHK(ctx, hipMemsetAsync(ctx->bands_keys_buf, 0xff, ab, ctx->stream));   // RH_SELECT_KEY_MASKED
     if (nz) {
         HIPCHK(ctx, ctx->bands_counts_buf.alloc((size_t)capacity * blocks * 2 * sizeof(long long)));
         HIPCHK(ctx, ctx->bands_zone_buf.alloc(zones.index.size() * sizeof(int)));
@@ -1232,7 +1229,7 @@ int rh_bands_observations(rh_ctx *ctx, const double *obs, int n_series, int64_t 
     if (first_index < 0)
         return fail(ctx, RH_ERR_ARG, "rh_bands_observations: first_index = " + std::to_string(first_index) + " (the index of the first counted interval, at least 0)");
     const size_t ni = (size_t)ctx->bands_nitems, ns = (size_t)n_series, ob = ni * ns * (size_t)n_intervals * sizeof(double),
-                 parts = bands_obs_grid((long long)ctx->n), rb = (size_t)ctx->bands.cap * ni * ns * 2 * sizeof(long long);
+                 parts = select_obs_grid((long long)ctx->n), rb = (size_t)ctx->bands.cap * ni * ns * 2 * sizeof(long long);
     int rc = RH_OK;
     auto alloc = [&]() -> int {
         HIPCHK(ctx, ctx->bands_obs_buf.alloc(ob));

@@ -47,11 +47,8 @@
 #include "rh_select.h"
 #include "roger_hip_sas.h"
 
-#define SAS_BANDS_BLOCK RH_SELECT_BLOCK
-#define SAS_BANDS_NBINS 2048   // 11-bit digits
-#define SAS_BANDS_PASSES 6
-#define SAS_BANDS_U 8          // tiles a thread holds in flight
 #define SAS_BANDS_HDR 3        // m, n_nan, W
+static_assert(RH_SAS_BANDS_MAX_PROBS == RH_SELECT_MAX_PROBS, "rh_select.h states the histograms of the selection");
 
 struct SasBandsDev {
     const double *val[RH_SAS_BANDS_MAX_ITEMS];   // the width-1 value
@@ -76,8 +73,8 @@ struct SasBandsDev {
     long long *obs_pair;                         // [sample][item][2]
 };
 
-__global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_day(const SasBandsDev *__restrict__ P, int first, int closes, int64_t day_off) {
-    const int64_t i = (int64_t)blockIdx.x * SAS_BANDS_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_day(const SasBandsDev *__restrict__ P, int first, int closes, int64_t day_off) {
+    const int64_t i = (int64_t)blockIdx.x * RH_SELECT_BLOCK + threadIdx.x;
     const size_t n = (size_t)P->n;
     if (i >= P->n) return;
     if (P->mask && !P->mask[i]) return;
@@ -114,75 +111,39 @@ __global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_day(const SasBand
     }
 }
 
-// The keys of one item counted into the workgroup's LDS histogram(s): tile t of SAS_BANDS_BLOCK keys belongs to workgroup t mod grid,
-// eight tiles in flight per thread.  WEIGHTED: the 2-byte weight plane is read with the keys; else every key counts 1.
-template <int PASS, bool WEIGHTED>
-RH_SELECT_DEV void sas_bands_count(const unsigned long long *keys, const unsigned short *wts, int64_t n, int np, const unsigned long long (&pre)[RH_SAS_BANDS_MAX_PROBS],
-                                   unsigned *hist, unsigned *nan_count, unsigned *num_count) {
-    using PS = BandsPass<PASS>;
-    constexpr int NB = PS::nb, U = SAS_BANDS_U;
-    const int64_t ntiles = (n + SAS_BANDS_BLOCK - 1) / SAS_BANDS_BLOCK;
-    unsigned mine = 0, mine_nan = 0;   // pass 0: the numbers and the NaNs this thread met
-    for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
-        unsigned long long key[U];
-        unsigned w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = (t + (int64_t)u * gridDim.x) * SAS_BANDS_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
-            key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_SELECT_KEY_MASKED;
-            w[u] = WEIGHTED ? (i < n ? (unsigned)__builtin_nontemporal_load(wts + i) : 0u) : 1u;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_SELECT_KEY_NAN) {
-                if (PASS == 0 && key[u] == RH_SELECT_KEY_NAN) ++mine_nan;
-                continue;
-            }
-            const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
-            if (PASS == 0) {
-                ++mine;
-                atomicAdd(&hist[d], w[u]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < RH_SAS_BANDS_MAX_PROBS; ++q)
-                    if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], w[u]);
-            }
-        }
-    }
-    if (PASS == 0 && mine) atomicAdd(num_count, mine);
-    if (PASS == 0 && mine_nan) atomicAdd(nan_count, mine_nan);
-}
-
-// Pass PASS, the histograms: grid bands_weighted_grid(n).  A workgroup takes the items one after the other: an LDS histogram (uint32, LDS
-// atomics) per probability -- in pass 0 one for all of them, there is no prefix yet -- then its NON-ZERO bins go to the global uint64
-// histogram with device-scope integer adds whose results nobody takes: integer adds commute, the sum does not depend on their order,
-// and only k_sas_bands_pick<PASS>, the next kernel in the stream, reads it.
+// Pass PASS, the histograms: grid bands_weighted_grid(n).  A workgroup takes the items one after the other: select_walk_tiles and
+// select_count of rh_select.h fill an LDS histogram per probability -- with a weight plane a key counts its weight, else 1 -- then its
+// NON-ZERO bins go to the global uint64 histogram with device-scope integer adds whose results nobody takes: integer adds commute, the
+// sum does not depend on their order, and only k_sas_bands_pick<PASS>, the next kernel in the stream, reads it.
 template <int PASS>
-__global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_hist(const SasBandsDev *__restrict__ P) {
-    using PS = BandsPass<PASS>;
-    constexpr int NB = PS::nb;
-    __shared__ unsigned hist[RH_SAS_BANDS_MAX_PROBS * SAS_BANDS_NBINS];
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_hist(const SasBandsDev *__restrict__ P) {
+    constexpr int NB = BandsPass<PASS>::nb;
+    __shared__ unsigned hist[RH_SAS_BANDS_MAX_PROBS * RH_SELECT_NBINS];
     __shared__ unsigned nan_count, num_count;
     const int ni = P->n_items, np = P->n_probs, nh = PASS == 0 ? 1 : np;
     const int64_t n = P->n;
     const unsigned short *wts = P->weight;   // (uniform: tested once per workgroup and item, outside the loop over the keys)
     for (int j = 0; j < ni; ++j) {
-        for (int b = threadIdx.x; b < nh * NB; b += SAS_BANDS_BLOCK) hist[b] = 0;
+        for (int b = threadIdx.x; b < nh * NB; b += RH_SELECT_BLOCK) hist[b] = 0;
         if (threadIdx.x == 0) nan_count = num_count = 0;
         __syncthreads();
         unsigned long long pre[RH_SAS_BANDS_MAX_PROBS];
 #pragma unroll
         for (int q = 0; q < RH_SAS_BANDS_MAX_PROBS; ++q) pre[q] = (PASS > 0 && q < np) ? P->prefix[j * RH_SAS_BANDS_MAX_PROBS + q] : 0ull;
         const unsigned long long *keys = P->keys + (size_t)j * (size_t)n;
+        unsigned mine = 0, mine_nan = 0;   // pass 0: the numbers and the NaNs this thread met
+        const auto count = [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<PASS>(key, w, np, pre, hist, mine, mine_nan); };
         if (wts)
-            sas_bands_count<PASS, true>(keys, wts, n, np, pre, hist, &nan_count, &num_count);
+            select_walk_tiles<true>(keys, wts, n, count);
         else
-            sas_bands_count<PASS, false>(keys, wts, n, np, pre, hist, &nan_count, &num_count);
+            select_walk_tiles<false>(keys, wts, n, count);
+        if (PASS == 0 && mine) atomicAdd(&num_count, mine);
+        if (PASS == 0 && mine_nan) atomicAdd(&nan_count, mine_nan);
         __syncthreads();
-        unsigned long long *g = P->hist + (size_t)j * RH_SAS_BANDS_MAX_PROBS * SAS_BANDS_NBINS;
-        for (int b = threadIdx.x; b < nh * NB; b += SAS_BANDS_BLOCK) {
+        unsigned long long *g = P->hist + (size_t)j * RH_SAS_BANDS_MAX_PROBS * RH_SELECT_NBINS;
+        for (int b = threadIdx.x; b < nh * NB; b += RH_SELECT_BLOCK) {
             const unsigned cnt = hist[b];
-            if (cnt) (void)__hip_atomic_fetch_add(g + (b / NB) * SAS_BANDS_NBINS + (b % NB), (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cnt) (void)__hip_atomic_fetch_add(g + (b / NB) * RH_SELECT_NBINS + (b % NB), (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (PASS == 0 && threadIdx.x == 0) {
             if (nan_count) (void)__hip_atomic_fetch_add(&P->nan_count[j], nan_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -197,43 +158,29 @@ __global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_hist(const SasBan
 // pair's prefix and subtracts the weight below it from the rank.  Pass 0 fixes m, n_nan, W and T - 1.  Behind a workgroup barrier the
 // bins that were read are cleared.  After the last pass the prefix IS the key: row k of the result.
 template <int PASS>
-__global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_pick(const SasBandsDev *__restrict__ P, int64_t k) {
-    using PS = BandsPass<PASS>;
-    constexpr int NB = PS::nb, NC = NB / 64;
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_pick(const SasBandsDev *__restrict__ P, int64_t k) {
+    constexpr int NB = BandsPass<PASS>::nb, NC = NB / 64;
     const int ni = P->n_items, np = P->n_probs, nh = PASS == 0 ? 1 : np;
     const int lane = threadIdx.x & 63;
-    for (int pair = threadIdx.x >> 6; pair < ni * np; pair += SAS_BANDS_BLOCK / 64) {   // (uniform over the wavefront)
+    for (int pair = threadIdx.x >> 6; pair < ni * np; pair += RH_SELECT_BLOCK / 64) {   // (uniform over the wavefront)
         const int j = pair / np, q = pair - j * np, at = j * RH_SAS_BANDS_MAX_PROBS + q;
-        const unsigned long long *h = P->hist + (size_t)(j * RH_SAS_BANDS_MAX_PROBS + (PASS == 0 ? 0 : q)) * SAS_BANDS_NBINS;
+        const unsigned long long *h = P->hist + (size_t)(j * RH_SAS_BANDS_MAX_PROBS + (PASS == 0 ? 0 : q)) * RH_SELECT_NBINS;
         unsigned long long v[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) v[c] = h[c * 64 + lane];
-        long long wsum = 0, r;
-        if (PASS == 0) {
-            unsigned long long tot = 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) tot += v[c];
-            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
-            wsum = (long long)tot;
-            r = bands_rank_of(P->probs[q], wsum);   // T - 1
-        } else {
-            r = P->rank[at];
-        }
-        long long below;
-        int digit;
-        bands_pick64<NC>(v, r, digit, below);
-        const unsigned long long prefix = (PASS == 0 ? 0ull : P->prefix[at] << PS::width) | (unsigned long long)digit;
+        const SelectPick pk = select_pick_step<PASS>(v, P->probs[q], &P->prefix[at], &P->rank[at]);   // (pass 0: the rank is T - 1)
+        const unsigned long long prefix = pk.prefix;
         if (lane == 0) {
             P->prefix[at] = prefix;
-            P->rank[at] = r - below;
+            P->rank[at] = pk.rank;
             if (PASS == 0 && q == 0) {
-                P->w[j] = wsum;
+                P->w[j] = pk.total;
                 P->m[j] = (long long)P->m_count[j];
                 P->nan[j] = (long long)P->nan_count[j];
                 P->m_count[j] = 0u;
                 P->nan_count[j] = 0u;
             }
-            if (PASS == SAS_BANDS_PASSES - 1) {
+            if (PASS == RH_SELECT_PASSES - 1) {
                 const long long m = P->m[j];
                 P->rows[((size_t)k * ni + j) * np + q] = m ? bands_value_of(prefix) : __builtin_nan("");
                 if (q == 0) {
@@ -246,65 +193,36 @@ __global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_pick(const SasBan
         }
     }
     __syncthreads();   // (in pass 0 the pairs of an item read one histogram)
-    for (int b = threadIdx.x; b < ni * nh * NB; b += SAS_BANDS_BLOCK) {
+    for (int b = threadIdx.x; b < ni * nh * NB; b += RH_SELECT_BLOCK) {
         const int jq = b / NB;
-        P->hist[(size_t)((jq / nh) * RH_SAS_BANDS_MAX_PROBS + jq % nh) * SAS_BANDS_NBINS + b % NB] = 0ull;
+        P->hist[(size_t)((jq / nh) * RH_SAS_BANDS_MAX_PROBS + jq % nh) * RH_SELECT_NBINS + b % NB] = 0ull;
     }
 }
 
 // ---- where the observation falls ----
-// k_sas_bands_obs: grid (sas_bands_obs_grid(n), items) behind the last pick.  A workgroup strides over the tiles of its item's key plane as
+// k_sas_bands_obs: grid (select_obs_grid(n), items) behind the last pick.  A workgroup strides over the tiles of its item's key plane as
 // k_sas_bands_hist does; a thread adds 1, or the column's weight, into two int64 registers; keys >= KEY_NAN are skipped (a zero weight
 // needs no test: that key is KEY_MASKED).  The wavefronts reduce by shuffles, the four of a workgroup through LDS, and thread 0 stores the
 // workgroup's pair into obs_part: plain stores, no atomics.  k_sas_bands_obs_row: grid (items), one wavefront; adds the partials in a
 // fixed order into obs_pair[k].  An item whose observation of window k is missing ends both after the scalar loads: its pair stays
 // (-1, -1).
-static inline unsigned sas_bands_obs_grid(long long n) {
-    const long long ntiles = (n + SAS_BANDS_BLOCK - 1) / SAS_BANDS_BLOCK;
-    return (unsigned)(ntiles < RH_SELECT_MAX_GRID ? (ntiles < 1 ? 1 : ntiles) : RH_SELECT_MAX_GRID);
-}
-__global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_obs(const SasBandsDev *__restrict__ P, int64_t k) {
-    constexpr int U = SAS_BANDS_U;
-    __shared__ long long s_part[SAS_BANDS_BLOCK / 64][2];
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_obs(const SasBandsDev *__restrict__ P, int64_t k) {
+    __shared__ long long s_part[RH_SELECT_BLOCK / 64][2];
     const int j = blockIdx.y;
     const double o = P->obs[(size_t)j * (size_t)P->n_samples + (size_t)k];
     if (o != o) return;   // (uniform over the item's workgroups)
     const unsigned long long ko = bands_key_of(o + 0.0);
-    const int64_t n = P->n, ntiles = (n + SAS_BANDS_BLOCK - 1) / SAS_BANDS_BLOCK;
+    const int64_t n = P->n;
     const unsigned long long *keys = P->keys + (size_t)j * (size_t)n;
-    const unsigned short *wts = P->weight;
+    const unsigned short *wts = P->weight;   // (uniform: tested once, outside the walk)
     long long below = 0, equal = 0;   // (below 2^47: at most n < 2^31 columns of weight <= 65535)
-    for (int64_t t = blockIdx.x; t < ntiles; t += (int64_t)gridDim.x * U) {
-        unsigned long long key[U];
-        long long w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = (t + (int64_t)u * gridDim.x) * SAS_BANDS_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
-            key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_SELECT_KEY_MASKED;
-            w[u] = wts ? (i < n ? (long long)__builtin_nontemporal_load(wts + i) : 0ll) : 1ll;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_SELECT_KEY_NAN) continue;
-            below += key[u] < ko ? w[u] : 0ll;
-            equal += key[u] == ko ? w[u] : 0ll;
-        }
-    }
-    for (int off = 32; off; off >>= 1) {
-        below += __shfl_xor(below, off);
-        equal += __shfl_xor(equal, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_part[threadIdx.x >> 6][0] = below;
-        s_part[threadIdx.x >> 6][1] = equal;
-    }
-    __syncthreads();
+    const auto add = [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_pair_add(key, w, ko, below, equal); };
+    if (wts)
+        select_walk_tiles<true>(keys, wts, n, add);
+    else
+        select_walk_tiles<false>(keys, wts, n, add);
+    select_pair_reduce(below, equal, s_part);
     if (threadIdx.x == 0) {
-        below = equal = 0;
-        for (int w = 0; w < SAS_BANDS_BLOCK / 64; ++w) {
-            below += s_part[w][0];
-            equal += s_part[w][1];
-        }
         long long *part = P->obs_part + ((size_t)j * gridDim.x + blockIdx.x) * 2;
         part[0] = below;
         part[1] = equal;
@@ -314,16 +232,8 @@ __global__ __launch_bounds__(64) void k_sas_bands_obs_row(const SasBandsDev *__r
     const int j = blockIdx.x, ni = gridDim.x;
     const double o = P->obs[(size_t)j * (size_t)P->n_samples + (size_t)k];
     if (o != o) return;   // (uniform over the wavefront)
-    const long long *part = P->obs_part + (size_t)j * nparts * 2;
-    long long below = 0, equal = 0;
-    for (int b = threadIdx.x; b < nparts; b += 64) {
-        below += part[2 * b];
-        equal += part[2 * b + 1];
-    }
-    for (int off = 32; off; off >>= 1) {
-        below += __shfl_xor(below, off);
-        equal += __shfl_xor(equal, off);
-    }
+    long long below, equal;
+    select_pair_partials(P->obs_part + (size_t)j * nparts * 2, nparts, below, equal);
     if (threadIdx.x == 0) {
         long long *out = P->obs_pair + ((size_t)k * ni + j) * 2;
         out[0] = below;

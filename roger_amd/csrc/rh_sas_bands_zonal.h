@@ -17,8 +17,8 @@
 //   k_sas_bands_zonal<WEIGHTED>  grid (n_zones, n_items), in place of the twelve k_sas_bands_hist<P> / k_sas_bands_pick<P>.  A workgroup
 //                     walks its zone's list, eight columns in flight per thread, gathers keys[j * n + col] and, WEIGHTED, weight[col], and
 //                     runs all six digit passes of BandsPass<P> itself: uint32 LDS histograms [probability][2048], pass 0 shared by the
-//                     probabilities and yielding m, n_nan and W; a wavefront per probability widens the bins into bands_pick64 and picks
-//                     the digit over 64-bit cumulative sums; prefixes and ranks stay in LDS between the passes.  The later passes read
+//                     probabilities and yielding m, n_nan and W; a wavefront per probability widens the bins to 64 bit and picks the
+//                     digit over 64-bit cumulative sums (select_pick_step); prefixes and ranks stay in LDS between the passes.  The later passes read
 //                     the keys again: L2 serves them.  It writes its block of rows[k] and hdr[k].
 //   k_sas_bands_obs_zonal  grid (n_zones, n_items), only when observations are configured and window k has one.  A workgroup whose
 //                     observation is NaN ends after its scalar loads: the pair stays (-1, -1), written at configure.  Otherwise it walks
@@ -49,85 +49,42 @@ struct SasBandsZonalDev {
 template <int PASS, bool WEIGHTED>
 RH_SELECT_DEV void sas_bands_zonal_pass(const unsigned long long *keys, const unsigned short *wts, const int *cols, long long beg, long long end, int np,
                                         const double *probs, unsigned *hist, unsigned long long *s_prefix, long long *s_rank, long long *s_count, unsigned *s_cnt) {
-    using PS = BandsPass<PASS>;
-    constexpr int NB = PS::nb, NC = NB / 64, U = SAS_BANDS_U;
+    constexpr int NB = BandsPass<PASS>::nb, NC = NB / 64;
     const int nh = PASS == 0 ? 1 : np;
-    for (int b = threadIdx.x; b < nh * NB; b += SAS_BANDS_BLOCK) hist[b] = 0;
+    for (int b = threadIdx.x; b < nh * NB; b += RH_SELECT_BLOCK) hist[b] = 0;
     if (PASS == 0 && threadIdx.x == 0) s_cnt[0] = s_cnt[1] = 0;
     __syncthreads();
     unsigned long long pre[RH_SAS_BANDS_MAX_PROBS];
 #pragma unroll
     for (int q = 0; q < RH_SAS_BANDS_MAX_PROBS; ++q) pre[q] = (PASS > 0 && q < np) ? s_prefix[q] : 0ull;
     unsigned mine = 0, mine_nan = 0;   // pass 0: the numbers and the NaNs this thread met
-    for (long long base = beg; base < end; base += (long long)SAS_BANDS_BLOCK * U) {
-        int col[U];
-        unsigned long long key[U];
-        unsigned w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long at = base + (long long)u * SAS_BANDS_BLOCK + threadIdx.x;
-            col[u] = at < end ? cols[at] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            key[u] = col[u] >= 0 ? keys[col[u]] : RH_SELECT_KEY_MASKED;
-            w[u] = WEIGHTED ? (col[u] >= 0 ? (unsigned)wts[col[u]] : 0u) : 1u;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_SELECT_KEY_NAN) {
-                if (PASS == 0 && key[u] == RH_SELECT_KEY_NAN) ++mine_nan;
-                continue;
-            }
-            const unsigned d = (unsigned)(key[u] >> PS::shift) & (unsigned)(NB - 1);
-            if (PASS == 0) {
-                ++mine;
-                atomicAdd(&hist[d], w[u]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < RH_SAS_BANDS_MAX_PROBS; ++q)
-                    if (q < np && (key[u] >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * NB + d], w[u]);
-            }
-        }
-    }
+    select_walk_list<WEIGHTED>(keys, wts, cols, beg, end, [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<PASS>(key, w, np, pre, hist, mine, mine_nan); });
     if (PASS == 0 && mine) atomicAdd(&s_cnt[0], mine);
     if (PASS == 0 && mine_nan) atomicAdd(&s_cnt[1], mine_nan);
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    for (int q = threadIdx.x >> 6; q < np; q += SAS_BANDS_BLOCK / 64) {   // (uniform over the wavefront)
+    for (int q = threadIdx.x >> 6; q < np; q += RH_SELECT_BLOCK / 64) {   // (uniform over the wavefront)
         const unsigned *h = hist + (PASS == 0 ? 0 : q) * NB;
         unsigned long long v[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) v[c] = (unsigned long long)h[c * 64 + lane];
-        long long r;
-        if (PASS == 0) {
-            unsigned long long tot = 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) tot += v[c];
-            for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
-            r = bands_rank_of(probs[q], (long long)tot);   // T - 1
-            if (q == 0 && lane == 0) {
+        const SelectPick pk = select_pick_step<PASS>(v, probs[q], &s_prefix[q], &s_rank[q]);   // (pass 0: the rank is T - 1)
+        if (lane == 0) {
+            s_prefix[q] = pk.prefix;
+            s_rank[q] = pk.rank;
+            if (PASS == 0 && q == 0) {
                 s_count[0] = (long long)s_cnt[0];
                 s_count[1] = (long long)s_cnt[1];
-                s_count[2] = (long long)tot;
+                s_count[2] = pk.total;
             }
-        } else {
-            r = s_rank[q];
-        }
-        long long below;
-        int digit;
-        bands_pick64<NC>(v, r, digit, below);
-        if (lane == 0) {
-            s_prefix[q] = (PASS == 0 ? 0ull : s_prefix[q] << PS::width) | (unsigned long long)digit;
-            s_rank[q] = r - below;
         }
     }
     __syncthreads();   // (the next pass clears the histograms and reads the prefixes)
 }
 
 template <bool WEIGHTED>
-__global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_zonal(const SasBandsDev *__restrict__ P, SasBandsZonalDev Z, int64_t k) {
-    __shared__ unsigned hist[RH_SAS_BANDS_MAX_PROBS * SAS_BANDS_NBINS];
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_zonal(const SasBandsDev *__restrict__ P, SasBandsZonalDev Z, int64_t k) {
+    __shared__ unsigned hist[RH_SAS_BANDS_MAX_PROBS * RH_SELECT_NBINS];
     __shared__ unsigned long long s_prefix[RH_SAS_BANDS_MAX_PROBS];
     __shared__ long long s_rank[RH_SAS_BANDS_MAX_PROBS], s_count[SAS_BANDS_HDR];
     __shared__ unsigned s_cnt[2];
@@ -160,54 +117,24 @@ __global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_zonal(const SasBa
 }
 
 // where the observation falls, per zone: obs is [item][zone][sample]
-__global__ __launch_bounds__(SAS_BANDS_BLOCK) void k_sas_bands_obs_zonal(const SasBandsDev *__restrict__ P, SasBandsZonalDev Z, int64_t k) {
-    constexpr int U = SAS_BANDS_U;
-    __shared__ long long s_part[SAS_BANDS_BLOCK / 64][2];
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_obs_zonal(const SasBandsDev *__restrict__ P, SasBandsZonalDev Z, int64_t k) {
+    __shared__ long long s_part[RH_SELECT_BLOCK / 64][2];
     const int z = blockIdx.x, j = blockIdx.y, nz = gridDim.x, ni = gridDim.y;
     const double o = P->obs[((size_t)j * nz + z) * (size_t)P->n_samples + (size_t)k];
     if (o != o) return;   // (uniform over the workgroup)
     const unsigned long long ko = bands_key_of(o + 0.0);
     const long long beg = Z.zone_off[z], end = Z.zone_off[z + 1];
     const unsigned long long *keys = P->keys + (size_t)j * (size_t)P->n;
-    const unsigned short *wts = P->weight;
+    const unsigned short *wts = P->weight;   // (uniform: tested once, outside the walk)
     const int *cols = Z.zone_cols;
     long long below = 0, equal = 0;   // (below 2^47: fewer than 2^31 columns of weight <= 65535)
-    for (long long base = beg; base < end; base += (long long)SAS_BANDS_BLOCK * U) {
-        int col[U];
-        unsigned long long key[U];
-        long long w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long at = base + (long long)u * SAS_BANDS_BLOCK + threadIdx.x;
-            col[u] = at < end ? cols[at] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            key[u] = col[u] >= 0 ? keys[col[u]] : RH_SELECT_KEY_MASKED;
-            w[u] = wts ? (col[u] >= 0 ? (long long)wts[col[u]] : 0ll) : 1ll;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (key[u] >= RH_SELECT_KEY_NAN) continue;
-            below += key[u] < ko ? w[u] : 0ll;
-            equal += key[u] == ko ? w[u] : 0ll;
-        }
-    }
-    for (int off = 32; off; off >>= 1) {
-        below += __shfl_xor(below, off);
-        equal += __shfl_xor(equal, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_part[threadIdx.x >> 6][0] = below;
-        s_part[threadIdx.x >> 6][1] = equal;
-    }
-    __syncthreads();
+    const auto add = [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_pair_add(key, w, ko, below, equal); };
+    if (wts)
+        select_walk_list<true>(keys, wts, cols, beg, end, add);
+    else
+        select_walk_list<false>(keys, wts, cols, beg, end, add);
+    select_pair_reduce(below, equal, s_part);
     if (threadIdx.x == 0) {
-        below = equal = 0;
-        for (int w = 0; w < SAS_BANDS_BLOCK / 64; ++w) {
-            below += s_part[w][0];
-            equal += s_part[w][1];
-        }
         long long *out = P->obs_pair + (((size_t)k * ni + j) * nz + z) * 2;
         out[0] = below;
         out[1] = equal;

@@ -405,8 +405,12 @@ enum SasBandsWords {
 template <int P>
 static void sas_bands_pass(rh_sas_ctx *ctx, unsigned grid, int64_t k) {
     const SasBandsDev *cfg = ctx->bands.cfg.get();
-    hipLaunchKernelGGL(k_sas_bands_hist<P>, dim3(grid), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg);
-    hipLaunchKernelGGL(k_sas_bands_pick<P>, dim3(1), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, k);
+    hipLaunchKernelGGL(k_sas_bands_hist<P>, dim3(grid), dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg);
+    hipLaunchKernelGGL(k_sas_bands_pick<P>, dim3(1), dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg, k);
+}
+template <int... P>   // ... and the passes P..., in order
+static void sas_bands_passes(rh_sas_ctx *ctx, unsigned grid, int64_t k, std::integer_sequence<int, P...>) {
+    (sas_bands_pass<P>(ctx, grid, k), ...);
 }
 
 // the next day of the count, behind what the stream holds so far: the day's kernel; on a closing day the selection follows it -- per zone
@@ -417,27 +421,21 @@ static int sas_bands_enqueue(rh_sas_ctx *ctx, int64_t day) {
     if (!now.launch) return RH_OK;
     const int64_t n = ctx->cfg.n_cells, k = now.k;
     const SasBandsDev *cfg = S.cfg.get();
-    hipLaunchKernelGGL(k_sas_bands_day, dim3((unsigned)((n + SAS_BANDS_BLOCK - 1) / SAS_BANDS_BLOCK)), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg,
+    hipLaunchKernelGGL(k_sas_bands_day, dim3((unsigned)((n + RH_SELECT_BLOCK - 1) / RH_SELECT_BLOCK)), dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg,
                        now.first ? 1 : 0, now.closes ? 1 : 0, (day % ctx->cfg.forcing_days) * n);
     if (now.closes && S.zones) {   // per zone: one launch in place of the twelve, one more where window k has an observation
         const SasBandsZonalDev Z = {S.zone_off.get(), S.zone_cols.get()};
         const dim3 grid((unsigned)S.zones, (unsigned)S.n_items);
         if (S.weight)
-            hipLaunchKernelGGL(k_sas_bands_zonal<true>, grid, dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, Z, k);
+            hipLaunchKernelGGL(k_sas_bands_zonal<true>, grid, dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg, Z, k);
         else
-            hipLaunchKernelGGL(k_sas_bands_zonal<false>, grid, dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, Z, k);
-        if (S.observed(k)) hipLaunchKernelGGL(k_sas_bands_obs_zonal, grid, dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, Z, k);
+            hipLaunchKernelGGL(k_sas_bands_zonal<false>, grid, dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg, Z, k);
+        if (S.observed(k)) hipLaunchKernelGGL(k_sas_bands_obs_zonal, grid, dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg, Z, k);
     } else if (now.closes) {
-        const unsigned grid = bands_weighted_grid((long long)n);
-        sas_bands_pass<0>(ctx, grid, k);
-        sas_bands_pass<1>(ctx, grid, k);
-        sas_bands_pass<2>(ctx, grid, k);
-        sas_bands_pass<3>(ctx, grid, k);
-        sas_bands_pass<4>(ctx, grid, k);
-        sas_bands_pass<5>(ctx, grid, k);
+        sas_bands_passes(ctx, bands_weighted_grid((long long)n), k, std::make_integer_sequence<int, RH_SELECT_PASSES>{});
         if (S.observed(k)) {   // (an item without one ends after the scalar loads: its pair stays (-1, -1), as configure wrote it)
-            const unsigned parts = sas_bands_obs_grid((long long)n);
-            hipLaunchKernelGGL(k_sas_bands_obs, dim3(parts, (unsigned)S.n_items), dim3(SAS_BANDS_BLOCK), 0, ctx->stream, cfg, k);
+            const unsigned parts = select_obs_grid((long long)n);
+            hipLaunchKernelGGL(k_sas_bands_obs, dim3(parts, (unsigned)S.n_items), dim3(RH_SELECT_BLOCK), 0, ctx->stream, cfg, k);
             hipLaunchKernelGGL(k_sas_bands_obs_row, dim3((unsigned)S.n_items), dim3(64), 0, ctx->stream, cfg, k, (int)parts);
         }
     }
@@ -514,7 +512,7 @@ static int sas_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_sas_s
     if (!n_items) return RH_OK;
     const size_t K = (size_t)n_samples, ni = (size_t)n_items, np = (size_t)n_probs, nb = zonal ? (size_t)n_zones : 1;   // nb: blocks per item
     const size_t acc_b = ni * 2 * (size_t)n * sizeof(double), key_b = ni * (size_t)n * sizeof(unsigned long long);
-    const size_t hist_b = ni * RH_SAS_BANDS_MAX_PROBS * SAS_BANDS_NBINS * sizeof(unsigned long long);
+    const size_t hist_b = ni * RH_SAS_BANDS_MAX_PROBS * RH_SELECT_NBINS * sizeof(unsigned long long);
     const size_t row_b = K * ni * nb * np * sizeof(double), hdr_b = K * ni * nb * SAS_BANDS_HDR * sizeof(long long), pair_b = K * ni * nb * 2 * sizeof(long long);
     SHIPCHK(ctx, S.acc.alloc(acc_b));
     SHIPCHK(ctx, hipMemsetAsync(S.acc, 0, acc_b, ctx->stream));
@@ -542,7 +540,7 @@ static int sas_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_sas_s
     if (obs) {
         SHIPCHK(ctx, S.obs.alloc(ni * nb * K * sizeof(double)));
         SHIPCHK(ctx, hipMemcpyAsync(S.obs, obs, ni * nb * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        if (!zonal) SHIPCHK(ctx, S.part.alloc(ni * sas_bands_obs_grid((long long)n) * 2 * sizeof(long long)));
+        if (!zonal) SHIPCHK(ctx, S.part.alloc(ni * select_obs_grid((long long)n) * 2 * sizeof(long long)));
     }
     if (zonal) {
         SHIPCHK(ctx, S.zone_off.alloc(zone_off.size() * sizeof(long long)));

@@ -1,14 +1,21 @@
-// rh_select.h -- the pure pieces of the radix selection on order-preserving keys that the ensemble bands of the SVAT / oneD step
-// (rh_bands.h, in roger_hip.hip) and the bands of the offline transport model (rh_sas_bands.h, in rh_sas.hip) share: the key of a double
-// and its inverse, the digits of the six passes, the rank of a probability, the grid whose workgroups cannot overflow a uint32 LDS bin,
-// and the pick of a wavefront over 64-bit bins.  Functions of their arguments only: no kernel, no device state, no memory access.
+// rh_select.h -- the pieces of the radix selection on order-preserving keys that the ensemble bands of the SVAT / oneD step (rh_bands.h, in
+// roger_hip.hip) and the bands of the offline transport model (rh_sas_bands.h and rh_sas_bands_zonal.h, in rh_sas.hip) share, each stated
+// once: the key of a double and its inverse, the digits of the six passes, the rank of a probability, the grids, the two walks over the
+// keys, the digit count of a key, the pick of a wavefront over the bins, and the pair (below, equal) of an observation.  No kernel, no
+// DevState / SasBandsDev: device functions that take pointers.  What differs between the kernels -- the clocks, the merge into global
+// bins, the completion pattern, where prefix and rank live, the ring and row writes -- is theirs.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #define RH_SELECT_DEV __device__ __forceinline__
+#define RH_SELECT_BODY __attribute__((always_inline))   // on the lambda a walk calls per key: U call sites, one loop body
 #define RH_SELECT_BLOCK 256         // keys of a tile, threads of a workgroup
+#define RH_SELECT_U 8               // tiles (list entries) a thread holds in flight per trip
 #define RH_SELECT_MAX_GRID 256      // workgroups of a pass (one per CU), unless the LDS bound asks for more
 #define RH_SELECT_W_MAX_TILES 256   // tiles one workgroup may walk with weights up to 65535 in uint32 LDS bins
+#define RH_SELECT_MAX_PROBS 8       // probabilities of an item: LDS histograms of a workgroup
+#define RH_SELECT_NBINS 2048        // 11-bit digits: bins of a histogram in memory
+#define RH_SELECT_PASSES 6
 #define RH_SELECT_KEY_MASKED (~0ull)
 #define RH_SELECT_KEY_NAN (~0ull - 1ull)
 
@@ -42,25 +49,101 @@ static inline unsigned bands_weighted_grid(long long n) {
                     bound = (ntiles + RH_SELECT_W_MAX_TILES - 1) / RH_SELECT_W_MAX_TILES;
     return (unsigned)(few > bound ? few : bound);
 }
-RH_SELECT_DEV unsigned long long bands_wave_scan64(unsigned long long x) {   // inclusive, over the 64 lanes
+// the workgroups per item of the pass that counts an observation's pair: min(MAX_GRID, max(1, ntiles))
+static inline unsigned select_obs_grid(long long n) {
+    const long long ntiles = (n + RH_SELECT_BLOCK - 1) / RH_SELECT_BLOCK;
+    return (unsigned)(ntiles < RH_SELECT_MAX_GRID ? (ntiles < 1 ? 1 : ntiles) : RH_SELECT_MAX_GRID);
+}
+
+// ---- the walks: body(key, w) for every key of the workgroup's share, U loads requested before the first use ----
+// A key plane of n keys: tile t of RH_SELECT_BLOCK keys belongs to workgroup t mod grid; non-temporal loads.  WEIGHTED: the 2-byte weight
+// plane is read with the keys; else w is the constant 1.  Beyond n the key is KEY_MASKED (and the weight 0).
+template <bool WEIGHTED, class Body>
+RH_SELECT_DEV void select_walk_tiles(const unsigned long long *keys, const unsigned short *wts, long long n, Body body) {
+    constexpr int U = RH_SELECT_U;
+    const long long ntiles = (n + RH_SELECT_BLOCK - 1) / RH_SELECT_BLOCK;
+    for (long long t = blockIdx.x; t < ntiles; t += (long long)gridDim.x * U) {
+        unsigned long long key[U];
+        unsigned w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long i = (t + (long long)u * gridDim.x) * RH_SELECT_BLOCK + threadIdx.x;   // (beyond the last tile: beyond n)
+            key[u] = i < n ? __builtin_nontemporal_load(keys + i) : RH_SELECT_KEY_MASKED;
+            w[u] = WEIGHTED ? (i < n ? (unsigned)__builtin_nontemporal_load(wts + i) : 0u) : 1u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) body(key[u], w[u]);
+    }
+}
+// The entries [beg, end) of a column list, walked by ONE workgroup: cols[at], then the gathers keys[col] and, WEIGHTED, wts[col]; plain
+// loads.  Beyond end the key is KEY_MASKED (and the weight 0).
+template <bool WEIGHTED, class Body>
+RH_SELECT_DEV void select_walk_list(const unsigned long long *keys, const unsigned short *wts, const int *cols, long long beg, long long end, Body body) {
+    constexpr int U = RH_SELECT_U;
+    for (long long base = beg; base < end; base += (long long)RH_SELECT_BLOCK * U) {
+        int col[U];
+        unsigned long long key[U];
+        unsigned w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long at = base + (long long)u * RH_SELECT_BLOCK + threadIdx.x;
+            col[u] = at < end ? cols[at] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            key[u] = col[u] >= 0 ? keys[col[u]] : RH_SELECT_KEY_MASKED;
+            w[u] = WEIGHTED ? (col[u] >= 0 ? (unsigned)wts[col[u]] : 0u) : 1u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) body(key[u], w[u]);
+    }
+}
+
+// ---- the count: one key into the workgroup's LDS histograms (uint32, LDS atomics) ----
+// Keys >= KEY_NAN take no part; pass 0 counts the NaN and the numbers this thread met in registers (one LDS add per thread behind the
+// walk is the caller's).  Pass 0 has one histogram for all probabilities -- there is no prefix yet; a later pass adds w into the
+// histogram of every probability q < np whose prefix pre[q] the key's higher digits equal.
+template <int PASS>
+RH_SELECT_DEV void select_count(unsigned long long key, unsigned w, int np, const unsigned long long (&pre)[RH_SELECT_MAX_PROBS], unsigned *hist,
+                                unsigned &mine, unsigned &mine_nan) {
+    using PS = BandsPass<PASS>;
+    if (key >= RH_SELECT_KEY_NAN) {
+        if (PASS == 0 && key == RH_SELECT_KEY_NAN) ++mine_nan;
+        return;
+    }
+    const unsigned d = (unsigned)(key >> PS::shift) & (unsigned)(PS::nb - 1);
+    if (PASS == 0) {
+        ++mine;
+        atomicAdd(&hist[d], w);
+    } else {
+#pragma unroll
+        for (int q = 0; q < RH_SELECT_MAX_PROBS; ++q)
+            if (q < np && (key >> (PS::high & 63)) == pre[q]) atomicAdd(&hist[q * PS::nb + d], w);
+    }
+}
+
+// ---- the pick of one wavefront: bin k * 64 + lane of a histogram in v[k]; T the bins' type (uint32 counts, or uint64 sums of weights
+// below 2^47), and the lane arithmetic of the scan is T's ----
+template <class T>
+RH_SELECT_DEV T bands_wave_scan(T x) {   // inclusive, over the 64 lanes
     const int lane = threadIdx.x & 63;
     for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long y = __shfl_up(x, off);
+        const T y = __shfl_up(x, off);
         if (lane >= off) x += y;
     }
     return x;
 }
-// The pick of one wavefront over 64-bit bins (sums of weights, below 2^47): bin k * 64 + lane of a histogram in v[k]; the digit at which
-// the cumulative sum passes the rank r, and the sum below it.  (No bin passes it only where the histogram is empty: digit 0, below 0.)
-template <int NC>
-RH_SELECT_DEV void bands_pick64(const unsigned long long (&v)[NC], long long r, int &digit, long long &below) {
+// the digit at which the cumulative sum passes the rank r, and the sum below it.  (No bin passes it only where the histogram is empty:
+// digit 0, below 0.)
+template <int NC, class T>
+RH_SELECT_DEV void bands_pick(const T (&v)[NC], long long r, int &digit, long long &below) {
     long long base = 0;
     bool found = false;
     digit = 0;
     below = 0;
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
-        const unsigned long long incl = bands_wave_scan64(v[k]);
+        const T incl = bands_wave_scan(v[k]);
         const long long chunk = (long long)__shfl(incl, 63);
         if (!found && base + chunk > r) {
             const unsigned long long hit = __ballot(base + (long long)incl > r);
@@ -71,4 +154,68 @@ RH_SELECT_DEV void bands_pick64(const unsigned long long (&v)[NC], long long r, 
         }
         base += chunk;
     }
+}
+// One pass of one (item, probability) pair, the bins in registers.  Pass 0 forms the histogram's total and from it the rank of p; a later
+// pass reads the rank and the prefix where the pass before stored them (device memory or LDS), the prefix only behind the pick.  The
+// digit picked is appended to the prefix, the sum below it leaves the rank; storing both is the caller's.
+struct SelectPick {
+    unsigned long long prefix;
+    long long rank, total;   // total: pass 0 only
+};
+template <int PASS, class T>
+RH_SELECT_DEV SelectPick select_pick_step(const T (&v)[BandsPass<PASS>::nb / 64], double p, const unsigned long long *prefix, const long long *rank) {
+    constexpr int NC = BandsPass<PASS>::nb / 64;
+    long long total = 0, r;
+    if (PASS == 0) {
+        T tot = 0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) tot += v[k];
+        for (int off = 32; off; off >>= 1) tot += __shfl_xor(tot, off);
+        total = (long long)tot;
+        r = bands_rank_of(p, total);
+    } else {
+        r = *rank;
+    }
+    long long below;
+    int digit;
+    bands_pick<NC>(v, r, digit, below);
+    return {(PASS == 0 ? 0ull : *prefix << BandsPass<PASS>::width) | (unsigned long long)digit, r - below, total};
+}
+
+// ---- the pair of an observation with key ko: the weights of the keys below and equal to it (below 2^47) ----
+RH_SELECT_DEV void select_pair_add(unsigned long long key, unsigned w, unsigned long long ko, long long &below, long long &equal) {
+    if (key >= RH_SELECT_KEY_NAN) return;
+    below += key < ko ? (long long)w : 0ll;
+    equal += key == ko ? (long long)w : 0ll;
+}
+RH_SELECT_DEV void select_pair_wave(long long &below, long long &equal) {   // every lane holds the wavefront's sums
+    for (int off = 32; off; off >>= 1) {
+        below += __shfl_xor(below, off);
+        equal += __shfl_xor(equal, off);
+    }
+}
+// the workgroup's sums: shuffles within a wavefront, LDS across the RH_SELECT_BLOCK / 64 of them; thread 0 holds the result
+RH_SELECT_DEV void select_pair_reduce(long long &below, long long &equal, long long (*s_part)[2]) {
+    select_pair_wave(below, equal);
+    if ((threadIdx.x & 63) == 0) {
+        s_part[threadIdx.x >> 6][0] = below;
+        s_part[threadIdx.x >> 6][1] = equal;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        below = equal = 0;
+        for (int w = 0; w < RH_SELECT_BLOCK / 64; ++w) {
+            below += s_part[w][0];
+            equal += s_part[w][1];
+        }
+    }
+}
+// the sums of nparts workgroups' pairs, by one wavefront, in a fixed order
+RH_SELECT_DEV void select_pair_partials(const long long *part, int nparts, long long &below, long long &equal) {
+    below = equal = 0;
+    for (int b = threadIdx.x; b < nparts; b += 64) {
+        below += part[2 * b];
+        equal += part[2 * b + 1];
+    }
+    select_pair_wave(below, equal);
 }

@@ -24,7 +24,7 @@ PROBS = (0.0, 0.05, 0.5, 0.95, 1.0)
 DAY = 86400
 GRIDS = [(257, 1), (40, 25)]
 PLANE = "theta_irr"
-SELECT_GRID = 256     # roger_amd/csrc/rh_bands.h: RH_BANDS_MAX_GRID, the workgroups that stride over the tiles of 256 keys
+SELECT_GRID = 256     # roger_amd/csrc/rh_select.h: RH_SELECT_MAX_GRID, the workgroups that stride over the tiles of 256 keys
 
 
 def mask_of(n):
@@ -158,7 +158,7 @@ def test_shape_boundaries_of_the_selection(n):
     ctx.close()
 
 
-SELECT_UNROLL = 8     # roger_amd/csrc/rh_bands.h: U of k_bands_select / k_bands_select_w, the tiles a thread holds in flight per trip
+SELECT_UNROLL = 8     # roger_amd/csrc/rh_select.h: RH_SELECT_U of select_walk_tiles, the tiles a thread holds in flight per trip
 SECOND_TRIP = SELECT_GRID * SELECT_UNROLL * 256 + 1
 
 
