@@ -420,6 +420,52 @@ int rh_sas_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *item
 int rh_sas_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, int64_t *obs_pair,
                             size_t pair_bytes, unsigned char *closed, size_t closed_bytes, int64_t *days_recorded);
 
+/* ---- transport bands by age: the bands above for every age class of an age-resolved array ---------------------------------------------------
+ * The other figure a SAS parameter study is made for: the travel time distribution of the percolate, TT_q_ss(T) or tt_q_ss(T), or the storage
+ * by age sa_s(T), with its 5 - 50 - 95 % band over the behavioural parameter sets -- without downloading the (n_cells, ages) array (kernels,
+ * the rule and the bytes moved: roger_amd/csrc/rh_sas_age_bands.h; the numpy twin is tests/sas_age_bands_reference.py).
+ * The promise, which is the whole specification: block (item j, age class a) of window k is bit for bit what rh_sas_bands_configure would
+ * record for the width-1 values A_j[:, a] with kind LAST under the same mask, weights, probabilities and windows: s = v + 0.0; a NaN element
+ * is counted in that age class's n_nan and takes no further part; +-inf are values; a cell with mask == 0 or weight 0 takes no part;
+ * T = clamp((int64)ceil(p * (double)W), 1, W) and the result is the smallest s with sum_{s_i <= s} w_i >= T; m == 0 gives NaN rows and W = 0.
+ * m, n_nan and W are per age class.
+ *   items    [n_items], at most RH_SAS_AGE_BANDS_MAX_ITEMS, each (value, weight, kind): value a per-cell float64 array of width ages or
+ *            ages + 1 this context holds (always: sa_rz, sa_ss, msa_*; with keep_distributions: tt_*, mtt_*, TT_*, sa_s, msa_s); weight -1
+ *            and kind RH_SAS_SCORES_LAST.  The kind is part of the ABI so that window means can follow without changing it; BULK and MEAN
+ *            are refused today with a message that says so
+ *   probs, mask, weights, first_day, last_day, n_samples   as rh_sas_bands_configure takes them; the count of recorded days is this
+ *            recorder's own and starts at 0 at configure
+ * After rh_sas_age_bands_configure, rh_sas_step and every day of rh_sas_run_days that closes an open window enqueue, behind the bands'
+ * launches, two launches per item (a transpose of the participating columns into a key plane, the selection of every age class by a
+ * workgroup of its own); every other day enqueues nothing.  rh_sas_stages never records; a context without bands by age enqueues exactly
+ * what it enqueued before these entry points existed.  Points, totals, zonal totals, scores, either kind of bands and the bands by age
+ * work side by side, configured in any order.
+ * Result, no ring: rows [n_samples][sum_j W_j][n_probs] float64, item j's block (W_j, n_probs) in configured order, NaN until the window
+ * closed; hdr [n_samples][sum_j W_j]{m, n_nan, W} int64, 0 until then; closed [n_samples] bytes.
+ * n_items == 0 releases everything and stops the launches.  Every other call starts anew (day count 0).  Everything is checked, and the new
+ * buffers are allocated, before the previous configuration is released: a refused call or a failed allocation leaves the previous
+ * configuration in place.  RH_ERR_ARG (rh_sas_last_error names the offender): null pointers; n_items or n_probs beyond the maxima; a
+ * probability outside [0, 1] or NaN; an unknown id; an int32 array, a DAILY input or sas_params_*; a width-1 array (it belongs to
+ * rh_sas_bands_configure); a weight, or a kind other than LAST; an item given twice; n_samples < 1; windows out of order or overlapping; a
+ * mask and weights that leave no cell taking part; rows of sum_j W_j x n_probs float64 x n_samples, or hdr of sum_j W_j x 3 int64 x
+ * n_samples (the larger buffer below three probabilities), beyond 2 GiB; and THE BOUND: one
+ * workgroup selects an age class in uint32 LDS bins, which hold at most (participating cells) x 65535, so with a weight plane more than
+ * 65536 participating cells are refused.  Without weights any n_cells < 2^31 is exact.  RH_ERR_STATE: an array this context does not hold.
+ * Device memory: one key plane of max_j W_j x (participating cells) x 8 bytes, shared by the items.
+ *   rh_sas_age_bands_record     records "now", behind what the stream holds, as the next day of the count; `day` (>= 0) is the daily row
+ *                               (unused while every item is LAST): for a driver that steps with rh_sas_stages
+ *   rh_sas_age_bands_row_elems  sum_j W_j
+ *   rh_sas_age_bands_read       rows, hdr, closed with their sizes in bytes, days_recorded (may be NULL); synchronises
+ * All three: RH_ERR_STATE before rh_sas_age_bands_configure (or after it released everything). */
+#define RH_SAS_AGE_BANDS_MAX_ITEMS 4
+int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                               const unsigned char *mask, const uint16_t *weights, const int64_t *first_day, const int64_t *last_day,
+                               int64_t n_samples);
+int rh_sas_age_bands_record(rh_sas_ctx *ctx, int64_t day);
+int rh_sas_age_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total);
+int rh_sas_age_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed,
+                          size_t closed_bytes, int64_t *days_recorded);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

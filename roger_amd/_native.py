@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROGER_HIP_LIB", os.path.join(PKG, "libroger_hip.so"))  # override: kernel experiments
 
 
-ABI_VERSION = 22  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 23  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -283,6 +283,10 @@ def _declare_sas(lib):
     lib.rh_sas_bands_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
     lib.rh_sas_bands_configure_zonal.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64]
     lib.rh_sas_bands_zonal_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
+    lib.rh_sas_age_bands_configure.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i64]
+    lib.rh_sas_age_bands_record.argtypes = [vp, i64]
+    lib.rh_sas_age_bands_row_elems.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.rh_sas_age_bands_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int64)]
 
 
 SAS_DECLARED_SYMBOLS = (
@@ -295,6 +299,7 @@ SAS_DECLARED_SYMBOLS = (
     "rh_sas_zonal_configure", "rh_sas_zonal_record", "rh_sas_zonal_count", "rh_sas_zonal_row_elems", "rh_sas_zonal_read",
     "rh_sas_scores_configure", "rh_sas_scores_record", "rh_sas_scores_read",
     "rh_sas_bands_configure", "rh_sas_bands_record", "rh_sas_bands_read", "rh_sas_bands_configure_zonal", "rh_sas_bands_zonal_read",
+    "rh_sas_age_bands_configure", "rh_sas_age_bands_record", "rh_sas_age_bands_row_elems", "rh_sas_age_bands_read",
 )
 
 # RH_SAS_SCORES_*: how a sample's window is aggregated (include/roger_hip_sas.h)
@@ -686,6 +691,63 @@ class SasContext:
         self._check(getattr(self._lib, name)(self._h, vp(rows), rows.nbytes, vp(hdr), hdr.nbytes, vp(pairs), pairs.nbytes, vp(closed), closed.nbytes,
                                              C.byref(days)), name)
         return rows, hdr, pairs, closed, days.value
+
+    # -- transport bands by age: the bands of every age class of an age-resolved array (rh_sas_age_bands_*) --------------
+    def age_bands_configure(self, items, probs=(), windows=None, mask=None, weights=None):
+        """The exact quantiles `probs` ACROSS the cells for EVERY age class of the age-resolved arrays `items` -- an array's name, or
+        (value, None, "last") as bands_configure takes an item; window means are not built -- on the closing day of each of the windows
+        (first_day, last_day), int (K,) each, inclusive, in this recorder's own count of recorded days, which restarts at 0 here.  `mask`
+        and `weights` as bands_configure takes them; with weights at most 65536 cells take part.  Block (item, age class a) is bit for
+        bit what bands_configure records for the width-1 values A[:, a] with kind "last".  No items: release everything and stop."""
+        items, flat = self._window_items([(it, None, "last") if isinstance(it, str) else it for it in items])
+        pr = first = last = mk = wt = None
+        if items:
+            if windows is None or len(windows) != 2:
+                raise ValueError("age_bands_configure: windows = (first_day, last_day), two integer arrays (K,)")
+            pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+            first, last = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in windows)
+            if first.size != last.size:
+                raise ValueError(f"age_bands_configure: windows of {first.size} and {last.size} days")
+            for name, a in (("mask", mask), ("weights", weights)):
+                if a is not None and np.asarray(a).size != self.n:
+                    raise ValueError(f"age_bands_configure: the {name} have {np.asarray(a).size} cells, the context {self.n}")
+            if mask is not None:
+                mk = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if weights is not None:
+                wt = np.asarray(weights).reshape(-1)
+                if wt.dtype.kind not in "iu" or (wt.size and (int(wt.min()) < 0 or int(wt.max()) > 65535)):
+                    raise ValueError(f"age_bands_configure: weights of dtype {wt.dtype} (integers within 0 ... 65535)")
+                wt = np.ascontiguousarray(wt, dtype=np.uint16)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self._lib.rh_sas_age_bands_configure(self._h, ptr(flat), len(items), ptr(pr), 0 if pr is None else pr.size, ptr(mk), ptr(wt),
+                                                         ptr(first), ptr(last), 0 if first is None else first.size), "rh_sas_age_bands_configure")
+        # (a refused configuration leaves the previous one)
+        self._age_bands_items = [(v, int(np.prod(self.shape(v)[1:], dtype=np.int64))) for v, _, _ in items]
+        self._age_bands_shape = (0 if first is None else first.size, 0 if pr is None else pr.size)
+
+    def age_bands_record(self, day=0):
+        """Record now as the next day of the count (a driver that steps by stage).  `day` (>= 0) is the row of the daily inputs, as for
+        bands_record; it is checked and otherwise ignored today, because every item is "last" and reads no daily input."""
+        self._check(self._lib.rh_sas_age_bands_record(self._h, int(day)), "rh_sas_age_bands_record")
+
+    def age_bands_read(self):
+        """(rows {name: float64 (K, W, n_probs)}, NaN until the window closed; hdr {name: int64 (K, W, 3)}: m, n_nan, W per age class;
+        closed uint8 (K,); days recorded since age_bands_configure), W the item's width (ages or ages + 1).  Synchronises."""
+        total = C.c_int64()
+        self._check(self._lib.rh_sas_age_bands_row_elems(self._h, C.byref(total)), "rh_sas_age_bands_row_elems")
+        nk, npr = self._age_bands_shape
+        rows = np.empty((nk, total.value, npr), dtype=np.float64)
+        hdr = np.empty((nk, total.value, 3), dtype=np.int64)
+        closed = np.empty(nk, dtype=np.uint8)
+        days = C.c_int64()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self._lib.rh_sas_age_bands_read(self._h, vp(rows), rows.nbytes, vp(hdr), hdr.nbytes, vp(closed), closed.nbytes, C.byref(days)),
+                    "rh_sas_age_bands_read")
+        out_rows, out_hdr, off = {}, {}, 0
+        for v, w in self._age_bands_items:
+            out_rows[v], out_hdr[v] = rows[:, off:off + w].copy(), hdr[:, off:off + w].copy()
+            off += w
+        return out_rows, out_hdr, closed, days.value
 
 
 def totals_item_name(value, weight=None):

@@ -36,6 +36,7 @@
 #include "rh_sas_scores.h"
 #include "rh_sas_bands.h"
 #include "rh_sas_bands_zonal.h"
+#include "rh_sas_age_bands.h"
 
 #include <algorithm>
 #include <memory>
@@ -316,7 +317,7 @@ int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
 
 #include "rh_sas_observers.h"
 
-// a whole day and, with points, totals, zonal totals, scores or bands configured, their rows, the day's scoring and its band work
+// a whole day and, with points, totals, zonal totals, scores, bands or bands by age configured, their rows, the day's scoring and its band work
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
     if (!rc && ctx->points.on()) rc = sas_points_enqueue(ctx, day);
@@ -324,6 +325,7 @@ static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     if (!rc && ctx->zonal.on()) rc = sas_zonal_enqueue(ctx, day, day);
     if (!rc && ctx->scores.on()) rc = sas_scores_enqueue(ctx, day);
     if (!rc && ctx->bands.on()) rc = sas_bands_enqueue(ctx, day);
+    if (!rc && ctx->age_bands.on()) rc = sas_age_bands_enqueue(ctx);
     return rc;
 }
 

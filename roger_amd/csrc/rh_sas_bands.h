@@ -48,7 +48,7 @@
 #include "roger_hip_sas.h"
 
 #define SAS_BANDS_HDR 3        // m, n_nan, W
-static_assert(RH_SAS_BANDS_MAX_PROBS == RH_SELECT_MAX_PROBS, "rh_select.h states the histograms of the selection");
+static_assert(RH_SAS_BANDS_MAX_PROBS == RH_SELECT_MAX_PROBS && SAS_BANDS_HDR == RH_SELECT_HDR, "rh_select.h states the histograms of the selection");
 
 struct SasBandsDev {
     const double *val[RH_SAS_BANDS_MAX_ITEMS];   // the width-1 value

@@ -19,7 +19,8 @@
 //                     runs all six digit passes of BandsPass<P> itself: uint32 LDS histograms [probability][2048], pass 0 shared by the
 //                     probabilities and yielding m, n_nan and W; a wavefront per probability widens the bins to 64 bit and picks the
 //                     digit over 64-bit cumulative sums (select_pick_step); prefixes and ranks stay in LDS between the passes.  The later passes read
-//                     the keys again: L2 serves them.  It writes its block of rows[k] and hdr[k].
+//                     the keys again: L2 serves them.  It writes its block of rows[k] and hdr[k].  The pass body is select_lds_pass<P> /
+//                     select_lds_block of rh_select.h, which k_sas_age_bands (rh_sas_age_bands.h) runs over a contiguous run.
 //   k_sas_bands_obs_zonal  grid (n_zones, n_items), only when observations are configured and window k has one.  A workgroup whose
 //                     observation is NaN ends after its scalar loads: the pair stays (-1, -1), written at configure.  Otherwise it walks
 //                     the list and adds 1 or w_i into two int64 registers by the unsigned comparison with key(o + 0.0), reduces by
@@ -44,76 +45,18 @@ struct SasBandsZonalDev {
     const int *zone_cols;        // the participating columns, ascending within a zone
 };
 
-// Pass PASS of one (zone, item) workgroup over the list entries [beg, end): the histograms, then the pick.  s_cnt: {numbers, NaNs} of
-// pass 0; s_count: {m, n_nan, W} fixed by pass 0.
-template <int PASS, bool WEIGHTED>
-RH_SELECT_DEV void sas_bands_zonal_pass(const unsigned long long *keys, const unsigned short *wts, const int *cols, long long beg, long long end, int np,
-                                        const double *probs, unsigned *hist, unsigned long long *s_prefix, long long *s_rank, long long *s_count, unsigned *s_cnt) {
-    constexpr int NB = BandsPass<PASS>::nb, NC = NB / 64;
-    const int nh = PASS == 0 ? 1 : np;
-    for (int b = threadIdx.x; b < nh * NB; b += RH_SELECT_BLOCK) hist[b] = 0;
-    if (PASS == 0 && threadIdx.x == 0) s_cnt[0] = s_cnt[1] = 0;
-    __syncthreads();
-    unsigned long long pre[RH_SAS_BANDS_MAX_PROBS];
-#pragma unroll
-    for (int q = 0; q < RH_SAS_BANDS_MAX_PROBS; ++q) pre[q] = (PASS > 0 && q < np) ? s_prefix[q] : 0ull;
-    unsigned mine = 0, mine_nan = 0;   // pass 0: the numbers and the NaNs this thread met
-    select_walk_list<WEIGHTED>(keys, wts, cols, beg, end, [&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<PASS>(key, w, np, pre, hist, mine, mine_nan); });
-    if (PASS == 0 && mine) atomicAdd(&s_cnt[0], mine);
-    if (PASS == 0 && mine_nan) atomicAdd(&s_cnt[1], mine_nan);
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    for (int q = threadIdx.x >> 6; q < np; q += RH_SELECT_BLOCK / 64) {   // (uniform over the wavefront)
-        const unsigned *h = hist + (PASS == 0 ? 0 : q) * NB;
-        unsigned long long v[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) v[c] = (unsigned long long)h[c * 64 + lane];
-        const SelectPick pk = select_pick_step<PASS>(v, probs[q], &s_prefix[q], &s_rank[q]);   // (pass 0: the rank is T - 1)
-        if (lane == 0) {
-            s_prefix[q] = pk.prefix;
-            s_rank[q] = pk.rank;
-            if (PASS == 0 && q == 0) {
-                s_count[0] = (long long)s_cnt[0];
-                s_count[1] = (long long)s_cnt[1];
-                s_count[2] = pk.total;
-            }
-        }
-    }
-    __syncthreads();   // (the next pass clears the histograms and reads the prefixes)
-}
-
+// One (zone, item) workgroup: the whole selection in its own LDS (select_lds_block of rh_select.h) over the zone's list entries.
 template <bool WEIGHTED>
 __global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_bands_zonal(const SasBandsDev *__restrict__ P, SasBandsZonalDev Z, int64_t k) {
-    __shared__ unsigned hist[RH_SAS_BANDS_MAX_PROBS * RH_SELECT_NBINS];
-    __shared__ unsigned long long s_prefix[RH_SAS_BANDS_MAX_PROBS];
-    __shared__ long long s_rank[RH_SAS_BANDS_MAX_PROBS], s_count[SAS_BANDS_HDR];
-    __shared__ unsigned s_cnt[2];
+    RH_SELECT_LDS(L);
     const int z = blockIdx.x, j = blockIdx.y, nz = gridDim.x, ni = gridDim.y, np = P->n_probs;
     const long long beg = Z.zone_off[z], end = Z.zone_off[z + 1];
     const unsigned long long *keys = P->keys + (size_t)j * (size_t)P->n;
     const unsigned short *wts = P->weight;
     const int *cols = Z.zone_cols;
-    const double *probs = P->probs;
     const size_t block = ((size_t)k * ni + j) * nz + z;
-    double *out = P->rows + block * np;
-    long long *hd = P->hdr + block * SAS_BANDS_HDR;
-    sas_bands_zonal_pass<0, WEIGHTED>(keys, wts, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, s_cnt);
-    const long long m = s_count[0];
-    if (threadIdx.x == 0) {
-        hd[0] = m;
-        hd[1] = s_count[1];
-        hd[2] = s_count[2];
-    }
-    if (m == 0) {   // (uniform over the workgroup)
-        if ((int)threadIdx.x < np) out[threadIdx.x] = __builtin_nan("");
-        return;
-    }
-    sas_bands_zonal_pass<1, WEIGHTED>(keys, wts, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, s_cnt);
-    sas_bands_zonal_pass<2, WEIGHTED>(keys, wts, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, s_cnt);
-    sas_bands_zonal_pass<3, WEIGHTED>(keys, wts, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, s_cnt);
-    sas_bands_zonal_pass<4, WEIGHTED>(keys, wts, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, s_cnt);
-    sas_bands_zonal_pass<5, WEIGHTED>(keys, wts, cols, beg, end, np, probs, hist, s_prefix, s_rank, s_count, s_cnt);
-    if ((int)threadIdx.x < np) out[threadIdx.x] = bands_value_of(s_prefix[threadIdx.x]);   // after the last pass the prefix IS the key
+    select_lds_block([&](auto body) RH_SELECT_BODY { select_walk_list<WEIGHTED>(keys, wts, cols, beg, end, body); }, np, P->probs, L, P->rows + block * np,
+                     P->hdr + block * SAS_BANDS_HDR);
 }
 
 // where the observation falls, per zone: obs is [item][zone][sample]

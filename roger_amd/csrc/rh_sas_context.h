@@ -199,6 +199,29 @@ struct SasBands {
     }
 };
 
+// transport bands by age (rh_sas_age_bands_configure, rh_sas_age_bands.h): ONE key plane [Wmax][n_part] that the items share, the
+// participating columns and their compacted weights, the probabilities and the result on the device; the items' arrays and widths, the
+// windows and their clock are the host's.  On while it has windows.
+struct SasAgeBands {
+    static constexpr const char *configure = "rh_sas_age_bands_configure";
+    DevBuf<double> rows, probs;
+    DevBuf<long long> hdr;
+    DevBuf<unsigned long long> keys;
+    DevBuf<int> part_cols;
+    DevBuf<unsigned short> wts_c;   // null: every participating column counts 1
+    SasWindows win;
+    const double *src[RH_SAS_AGE_BANDS_MAX_ITEMS] = {};
+    int width[RH_SAS_AGE_BANDS_MAX_ITEMS] = {};
+    int n_items = 0, n_probs = 0;
+    int64_t n_part = 0, ages_total = 0;   // ages_total: the sum of the items' widths
+    bool on() const { return win.on(); }
+    hipError_t release() {
+        const hipError_t e = first_error({rows.release(), probs.release(), hdr.release(), keys.release(), part_cols.release(), wts_c.release()});
+        *this = SasAgeBands();
+        return e;
+    }
+};
+
 struct rh_sas_ctx {
     Stream stream;                   // first member: destroyed last, after everything that was enqueued on it has been released
     rh_sas_config cfg = {};
@@ -212,6 +235,7 @@ struct rh_sas_ctx {
     SasZonal zonal;
     SasScores scores;
     SasBands bands;
+    SasAgeBands age_bands;
     std::string err;
 };
 static std::string g_sas_create_err;

@@ -1,6 +1,6 @@
 // rh_sas_observers.h -- what follows every day of the transport model: the time series at observation columns (rh_sas_points_*), the
 // catchment totals (rh_sas_totals_*), the zonal totals (rh_sas_zonal_*), the scores against observed samples (rh_sas_scores_*) and the
-// transport bands, plain and per zone (rh_sas_bands_*).  Each has its launch sequence (sas_*_enqueue, which the day calls), its configure
+// transport bands, plain and per zone (rh_sas_bands_*) and by age (rh_sas_age_bands_*).  Each has its launch sequence (sas_*_enqueue, which the day calls), its configure
 // call and its reads.  Part of the one translation unit rh_sas.hip, behind rh_sas_context.h; the entry points get their C linkage from
 // their declarations in roger_hip_sas.h.
 #pragma once
@@ -634,4 +634,138 @@ int rh_sas_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int
     if (int rc = sas_on(ctx, ctx->bands.on() && ctx->bands.zones != 0, "rh_sas_bands_zonal_read", "rh_sas_bands_configure_zonal")) return rc;
     return sas_bands_read(ctx, "rh_sas_bands_zonal_read", (size_t)ctx->bands.zones, "n_samples x n_items x n_zones", rows, row_bytes, hdr, hdr_bytes, obs_pair,
                           pair_bytes, closed, closed_bytes, days_recorded);
+}
+
+// ---- transport bands by age (include/roger_hip_sas.h; the kernels and the rule: rh_sas_age_bands.h) ----
+// the next day of the count, behind what the stream holds so far: nothing unless it closes an open window; then per item the transpose
+// into the ONE key plane and the selection of every age class, item after item in stream order
+static int sas_age_bands_enqueue(rh_sas_ctx *ctx) {
+    SasAgeBands &S = ctx->age_bands;
+    const SasWindows::Tick now = S.win.tick();
+    if (!now.launch) return RH_OK;   // (every item is LAST: launch == closes)
+    const size_t np = (size_t)S.n_probs;
+    size_t block = (size_t)now.k * (size_t)S.ages_total;
+    for (int j = 0; j < S.n_items; ++j) {
+        const int W = S.width[j];
+        rh_sas_age_launch(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.probs.get(), S.n_probs,
+                          S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
+        block += (size_t)W;
+    }
+    SHIPCHK(ctx, hipGetLastError());
+    return RH_OK;
+}
+
+int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                               const unsigned char *mask, const uint16_t *weights, const int64_t *first_day, const int64_t *last_day,
+                               int64_t n_samples) {
+    const std::string who = "rh_sas_age_bands_configure: ";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items < 0 || n_items > RH_SAS_AGE_BANDS_MAX_ITEMS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_AGE_BANDS_MAX_ITEMS) + ")");
+    SasAgeBands &S = ctx->age_bands;
+    if (!n_items) {
+        SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old result)
+        SHIPCHK(ctx, S.release());
+        return RH_OK;
+    }
+    const int64_t n = ctx->cfg.n_cells;
+    SasAgeBands N;   // the new configuration: checked and allocated in full before the previous one is released
+    if (!items || !probs || !first_day || !last_day) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+    if (n_probs < 1 || n_probs > RH_SAS_BANDS_MAX_PROBS)
+        return sfail(ctx, RH_ERR_ARG, who + "n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_SAS_BANDS_MAX_PROBS) + ")");
+    for (int q = 0; q < n_probs; ++q)
+        if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+            return sfail(ctx, RH_ERR_ARG, who + "probability " + std::to_string(q) + " is " + std::to_string(probs[q]) + " (within [0, 1])");
+    int wmax = 0;
+    for (int j = 0; j < n_items; ++j) {
+        const int a = items[j].value, w = items[j].weight, kind = items[j].kind;
+        if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
+        const std::string name = std::string("array ") + SAS_NAMES[a];
+        if (kind < RH_SAS_SCORES_BULK || kind > RH_SAS_SCORES_LAST)
+            return sfail(ctx, RH_ERR_ARG, who + "kind " + std::to_string(kind) + " of " + name + " (0: BULK, 1: MEAN, 2: LAST)");
+        if (kind != RH_SAS_SCORES_LAST)
+            return sfail(ctx, RH_ERR_ARG, who + name + " is " + (kind == RH_SAS_SCORES_BULK ? "BULK" : "MEAN") +
+                                              " (only LAST is built: a window mean of an age-resolved value needs an (n, ages) accumulator per item)");
+        if (w != -1) return sfail(ctx, RH_ERR_ARG, who + name + " has the weight id " + std::to_string(w) + " (LAST takes none: -1)");
+        for (int q = 0; q < j; ++q)
+            if (items[q].value == a) return sfail(ctx, RH_ERR_ARG, who + name + " is given twice");
+        if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
+        if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* have no band)");
+        if (SAS_KIND[a] == K_DAILY) return sfail(ctx, RH_ERR_ARG, who + name + " is a daily input of the step, not a result");
+        if (SAS_KIND[a] == K_CELL) return sfail(ctx, RH_ERR_ARG, who + name + " has width 1 (it belongs to rh_sas_bands_configure)");
+        if (!ctx->arr[a])
+            return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
+        N.src[j] = (const double *)ctx->arr[a].get();
+        N.width[j] = (int)(ctx->elems[a] / n);
+        N.ages_total += N.width[j];
+        wmax = std::max(wmax, N.width[j]);
+    }
+    const int64_t block_b = std::max<int64_t>(n_probs * (int64_t)sizeof(double), SAS_BANDS_HDR * (int64_t)sizeof(int64_t));   // rows or hdr, the larger
+    if (n_samples < 1 || n_samples > ((int64_t)1 << 31) / (N.ages_total * block_b))
+        return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one; rows of " + std::to_string(N.ages_total) +
+                                          " age classes x " + std::to_string(n_probs) + " float64 and headers of 3 int64, each within 2 GiB)");
+    if (int rc = sas_check_windows(ctx, who, first_day, last_day, n_samples)) return rc;
+    std::vector<int> part_cols;          // the participating columns, ascending ...
+    std::vector<unsigned short> wts_c;   // ... and their weights, at the same index
+    for (int64_t c = 0; c < n; ++c)
+        if ((!mask || mask[c]) && (!weights || weights[c])) {
+            part_cols.push_back((int)c);
+            if (weights) wts_c.push_back(weights[c]);
+        }
+    N.n_part = (int64_t)part_cols.size();
+    if (!N.n_part) return sfail(ctx, RH_ERR_ARG, who + "no cell takes part (0 of " + std::to_string(n) + " cells have mask != 0 and a weight > 0)");
+    if (weights && N.n_part > SAS_AGE_BANDS_MAX_WEIGHTED)
+        return sfail(ctx, RH_ERR_ARG, who + std::to_string(N.n_part) + " participating cells under a weight plane (at most " +
+                                          std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) + ": a uint32 LDS bin holds an age class's weights; without weights any size is exact)");
+    const size_t K = (size_t)n_samples, np = (size_t)n_probs, blocks = K * (size_t)N.ages_total, npart = (size_t)N.n_part;
+    const size_t row_b = blocks * np * sizeof(double), hdr_b = blocks * SAS_BANDS_HDR * sizeof(long long);
+    const std::vector<double> nans(blocks * np, std::nan(""));
+    SHIPCHK(ctx, N.keys.alloc((size_t)wmax * npart * sizeof(unsigned long long)));
+    SHIPCHK(ctx, N.rows.alloc(row_b));
+    SHIPCHK(ctx, hipMemcpyAsync(N.rows, nans.data(), row_b, hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, N.hdr.alloc(hdr_b));
+    SHIPCHK(ctx, hipMemsetAsync(N.hdr, 0, hdr_b, ctx->stream));
+    SHIPCHK(ctx, N.probs.alloc(np * sizeof(double)));
+    SHIPCHK(ctx, hipMemcpyAsync(N.probs, probs, np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, N.part_cols.alloc(npart * sizeof(int)));
+    SHIPCHK(ctx, hipMemcpyAsync(N.part_cols, part_cols.data(), npart * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (weights) {
+        SHIPCHK(ctx, N.wts_c.alloc(npart * sizeof(unsigned short)));
+        SHIPCHK(ctx, hipMemcpyAsync(N.wts_c, wts_c.data(), npart * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
+    }
+    SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and locals; launches that write the old result)
+    N.n_items = n_items;
+    N.n_probs = n_probs;
+    N.win.set(first_day, last_day, n_samples, false);
+    SHIPCHK(ctx, S.release());
+    S = std::move(N);
+    return RH_OK;
+}
+
+int rh_sas_age_bands_record(rh_sas_ctx *ctx, int64_t day) {
+    if (int rc = sas_on(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_record")) return rc;
+    if (day < 0) return sfail(ctx, RH_ERR_ARG, "rh_sas_age_bands_record: day = " + std::to_string(day) + " (the row of the daily inputs, >= 0)");
+    return sas_age_bands_enqueue(ctx);
+}
+
+int rh_sas_age_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total) {
+    if (int rc = sas_on(const_cast<rh_sas_ctx *>(ctx), &rh_sas_ctx::age_bands, "rh_sas_age_bands_row_elems")) return rc;
+    if (!ages_total) return RH_ERR_ARG;
+    *ages_total = ctx->age_bands.ages_total;
+    return RH_OK;
+}
+
+int rh_sas_age_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed, size_t closed_bytes,
+                          int64_t *days_recorded) {
+    if (int rc = sas_on(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_read")) return rc;
+    const SasAgeBands &S = ctx->age_bands;
+    const size_t K = S.win.closed.size(), blocks = K * (size_t)S.ages_total;
+    if (!rows || !hdr || !closed || row_bytes != blocks * (size_t)S.n_probs * sizeof(double) || hdr_bytes != blocks * SAS_BANDS_HDR * sizeof(int64_t) ||
+        closed_bytes != K)
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_age_bands_read: size mismatch (n_samples x ages_total x n_probs float64, n_samples x ages_total x 3 int64, n_samples bytes)");
+    SHIPCHK(ctx, hipMemcpyAsync(rows, S.rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(hdr, S.hdr, hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    std::copy(S.win.closed.begin(), S.win.closed.end(), closed);
+    if (days_recorded) *days_recorded = S.win.days;
+    return rh_sas_sync(ctx);
 }

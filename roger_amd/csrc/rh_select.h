@@ -1,7 +1,8 @@
 // rh_select.h -- the pieces of the radix selection on order-preserving keys that the ensemble bands of the SVAT / oneD step (rh_bands.h, in
-// roger_hip.hip) and the bands of the offline transport model (rh_sas_bands.h and rh_sas_bands_zonal.h, in rh_sas.hip) share, each stated
-// once: the key of a double and its inverse, the digits of the six passes, the rank of a probability, the grids, the two walks over the
-// keys, the digit count of a key, the pick of a wavefront over the bins, and the pair (below, equal) of an observation.  No kernel, no
+// roger_hip.hip) and the bands of the offline transport model (rh_sas_bands.h, rh_sas_bands_zonal.h and rh_sas_age_bands.h, in rh_sas.hip)
+// share, each stated once: the key of a double and its inverse, the digits of the six passes, the rank of a probability, the grids, the
+// three walks over the keys, the digit count of a key, the pick of a wavefront over the bins, the whole selection of one workgroup in its
+// own LDS (a zone, an age class), and the pair (below, equal) of an observation.  No kernel, no
 // DevState / SasBandsDev: device functions that take pointers.  What differs between the kernels -- the clocks, the merge into global
 // bins, the completion pattern, where prefix and rank live, the ring and row writes -- is theirs.
 #pragma once
@@ -98,6 +99,24 @@ RH_SELECT_DEV void select_walk_list(const unsigned long long *keys, const unsign
         for (int u = 0; u < U; ++u) body(key[u], w[u]);
     }
 }
+// A contiguous run of n keys, walked by ONE workgroup: keys[at] and, WEIGHTED, the weight at the SAME index wts[at]; plain loads.  Beyond
+// the run's end the key is KEY_MASKED (and the weight 0).
+template <bool WEIGHTED, class Body>
+RH_SELECT_DEV void select_walk_run(const unsigned long long *keys, const unsigned short *wts, long long n, Body body) {
+    constexpr int U = RH_SELECT_U;
+    for (long long base = 0; base < n; base += (long long)RH_SELECT_BLOCK * U) {
+        unsigned long long key[U];
+        unsigned w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long at = base + (long long)u * RH_SELECT_BLOCK + threadIdx.x;
+            key[u] = at < n ? keys[at] : RH_SELECT_KEY_MASKED;
+            w[u] = WEIGHTED ? (at < n ? (unsigned)wts[at] : 0u) : 1u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) body(key[u], w[u]);
+    }
+}
 
 // ---- the count: one key into the workgroup's LDS histograms (uint32, LDS atomics) ----
 // Keys >= KEY_NAN take no part; pass 0 counts the NaN and the numbers this thread met in registers (one LDS add per thread behind the
@@ -180,6 +199,82 @@ RH_SELECT_DEV SelectPick select_pick_step(const T (&v)[BandsPass<PASS>::nb / 64]
     int digit;
     bands_pick<NC>(v, r, digit, below);
     return {(PASS == 0 ? 0ull : *prefix << BandsPass<PASS>::width) | (unsigned long long)digit, r - below, total};
+}
+
+// ---- the whole selection by ONE workgroup in its own LDS (a zone of rh_sas_bands_zonal.h, an age class of rh_sas_age_bands.h) ----
+// uint32 histograms [probability][2048], pass 0 shared by the probabilities; the prefixes and the ranks that remain between the passes;
+// count {m, n_nan, W} fixed by pass 0; cnt {numbers, NaNs} of pass 0.  With weights the workgroup's share holds at most
+// RH_SELECT_W_MAX_TILES x RH_SELECT_BLOCK keys (the static_assert above): the caller's configure call enforces it.
+#define RH_SELECT_HDR 3   // m, n_nan, W
+struct SelectLds {
+    unsigned *hist;
+    unsigned long long *prefix;
+    long long *rank, *count;
+    unsigned *cnt;
+};
+#define RH_SELECT_LDS(L)                                                         \
+    __shared__ unsigned L##_hist[RH_SELECT_MAX_PROBS * RH_SELECT_NBINS];         \
+    __shared__ unsigned long long L##_prefix[RH_SELECT_MAX_PROBS];               \
+    __shared__ long long L##_rank[RH_SELECT_MAX_PROBS], L##_count[RH_SELECT_HDR]; \
+    __shared__ unsigned L##_cnt[2];                                              \
+    const SelectLds L = {L##_hist, L##_prefix, L##_rank, L##_count, L##_cnt}
+// Pass PASS: walk(body) calls body(key, w) for every key of the workgroup's share (one of the walks above); the histograms, then a
+// wavefront per probability widens the bins to 64 bit and picks the digit.
+template <int PASS, class Walk>
+RH_SELECT_DEV void select_lds_pass(Walk walk, int np, const double *probs, const SelectLds &L) {
+    constexpr int NB = BandsPass<PASS>::nb, NC = NB / 64;
+    const int nh = PASS == 0 ? 1 : np;
+    for (int b = threadIdx.x; b < nh * NB; b += RH_SELECT_BLOCK) L.hist[b] = 0;
+    if (PASS == 0 && threadIdx.x == 0) L.cnt[0] = L.cnt[1] = 0;
+    __syncthreads();
+    unsigned long long pre[RH_SELECT_MAX_PROBS];
+#pragma unroll
+    for (int q = 0; q < RH_SELECT_MAX_PROBS; ++q) pre[q] = (PASS > 0 && q < np) ? L.prefix[q] : 0ull;
+    unsigned mine = 0, mine_nan = 0;   // pass 0: the numbers and the NaNs this thread met
+    unsigned *hist = L.hist;
+    walk([&](unsigned long long key, unsigned w) RH_SELECT_BODY { select_count<PASS>(key, w, np, pre, hist, mine, mine_nan); });
+    if (PASS == 0 && mine) atomicAdd(&L.cnt[0], mine);
+    if (PASS == 0 && mine_nan) atomicAdd(&L.cnt[1], mine_nan);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int q = threadIdx.x >> 6; q < np; q += RH_SELECT_BLOCK / 64) {   // (uniform over the wavefront)
+        const unsigned *h = L.hist + (PASS == 0 ? 0 : q) * NB;
+        unsigned long long v[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) v[c] = (unsigned long long)h[c * 64 + lane];
+        const SelectPick pk = select_pick_step<PASS>(v, probs[q], &L.prefix[q], &L.rank[q]);   // (pass 0: the rank is T - 1)
+        if (lane == 0) {
+            L.prefix[q] = pk.prefix;
+            L.rank[q] = pk.rank;
+            if (PASS == 0 && q == 0) {
+                L.count[0] = (long long)L.cnt[0];
+                L.count[1] = (long long)L.cnt[1];
+                L.count[2] = pk.total;
+            }
+        }
+    }
+    __syncthreads();   // (the next pass clears the histograms and reads the prefixes)
+}
+// All six passes: hd {m, n_nan, W} and the np values of out, NaN where m == 0.
+template <class Walk>
+RH_SELECT_DEV void select_lds_block(Walk walk, int np, const double *probs, const SelectLds &L, double *out, long long *hd) {
+    select_lds_pass<0>(walk, np, probs, L);
+    const long long m = L.count[0];
+    if (threadIdx.x == 0) {
+        hd[0] = m;
+        hd[1] = L.count[1];
+        hd[2] = L.count[2];
+    }
+    if (m == 0) {   // (uniform over the workgroup)
+        if ((int)threadIdx.x < np) out[threadIdx.x] = __builtin_nan("");
+        return;
+    }
+    select_lds_pass<1>(walk, np, probs, L);
+    select_lds_pass<2>(walk, np, probs, L);
+    select_lds_pass<3>(walk, np, probs, L);
+    select_lds_pass<4>(walk, np, probs, L);
+    select_lds_pass<5>(walk, np, probs, L);
+    if ((int)threadIdx.x < np) out[threadIdx.x] = bands_value_of(L.prefix[threadIdx.x]);   // after the last pass the prefix IS the key
 }
 
 // ---- the pair of an observation with key ko: the weights of the keys below and equal to it (below 2^47) ----

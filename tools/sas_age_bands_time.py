@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""What the transport bands by age (rh_sas_age_bands_*; the kernels of roger_amd/csrc/rh_sas_age_bands.h) cost on a CLOSING day -- every
+other day enqueues nothing -- at 10^5 columns x 1000 ages, for 1 item (TT_q_ss, 1001 age classes) and 4 items (TT_q_ss, tt_q_ss, sa_s,
+sa_rz: 4001 age classes), three probabilities, without weights (every column takes part) and with a weight plane on a mask of 65536
+columns (the bound of a weighted configuration).
+
+BEHIND THE DAY'S KERNEL (`run`).  Milliseconds ADDED per day where it counts: rh_sas_run_days over 14 days (oxygen-18, deterministic
+solver, 6 sub-steps, keep_distributions on in every variant), every day its own window (14 closing days); every figure a process of its
+own, the minimum of three runs after a warm-up run: (n) nothing configured, (a1) / (a4) 1 / 4 items, (a1w) / (a4w) the same with weights.
+
+ALONE (`alone`).  The STAND-ALONE time of a closing day's launches: rh_sas_age_bands_record on a context that holds uploaded values (no
+day kernel), R days enqueued back to back and one synchronisation at the end; 1 and 4 items, without and with weights; and the SLOPE over
+the participating columns, 1 item without weights under masks of 25 000, 50 000 and 100 000 columns (one workgroup walks an age class).
+Beside it THE ALTERNATIVE it replaces, timed in the same process: download the item's (n, ages + 1) array and np.partition on the host
+at the three ranks.  10^6 columns (an 8 GB array per item) are not measured here.
+
+OFF cost (`off`).  `python bench.py --model sas --steps 8 --warmup 2` (nothing configured), ms per day: the parent's library and this
+tree's ALTERNATING, three runs each; the median of this tree against the parent's own range.  Needs
+ROGER_HIP_PARENT=/path/to/parent/libroger_hip.so; ROGER_HIP_OFF_FIRST=tree lets this tree's library open the alternation.
+
+    python3 tools/sas_age_bands_time.py [run] [alone] [off]        (default: all; `off` is skipped without ROGER_HIP_PARENT)"""
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from sas_bands_time import PROBS, RUN_AGES, RUN_DAYS, RUN_N, RUN_SUBSTEPS, bench_ms_per_day  # noqa: E402
+
+R, REPEATS, BOUND = 5, 3, 65536
+ITEMS = ["TT_q_ss", "tt_q_ss", "sa_s", "sa_rz"]
+RUN_VARIANTS = [("n", "(n) nothing configured", 0, False), ("a1", "(a1) 1 item, 1001 age classes, 2 launches a closing day", 1, False),
+                ("a4", "(a4) 4 items, 4001 age classes, 8 launches", 4, False), ("a1w", "(a1w) 1 item, weights on a mask of 65536 columns", 1, True),
+                ("a4w", "(a4w) 4 items, weights on a mask of 65536 columns", 4, True)]
+
+
+def participation(n, weighted, n_part=None):
+    """(mask, weights): every column -- or the first n_part columns of a stride over the domain, with likelihoods 1 ... 65535."""
+    import numpy as np
+
+    if not weighted and n_part is None:
+        return None, None
+    n_part = BOUND if n_part is None else n_part
+    mask = np.zeros(n, dtype=np.uint8)
+    mask[np.round(np.linspace(0, n - 1, n_part)).astype(np.int64)] = 1
+    assert int(mask.sum()) == n_part
+    return mask, np.random.default_rng(n).integers(1, 65536, size=n).astype(np.uint16) if weighted else None
+
+
+def run_child(variant):
+    """ms per day of rh_sas_run_days behind the real day kernel: the minimum of three runs after a warm-up run."""
+    import numpy as np
+
+    from roger_amd import sas as rsas
+
+    _, _, n_items, weighted = next(v for v in RUN_VARIANTS if v[0] == variant)
+    daily = rsas.synthetic_daily_inputs(RUN_N, RUN_DAYS, seed=42)
+    ctx = rsas.create_sas(RUN_N, RUN_AGES, RUN_SUBSTEPS, 90.0, 260.0, daily=daily, keep_distributions=True)
+    windows = (np.arange(RUN_DAYS),) * 2
+    mask, w = participation(RUN_N, weighted)
+    best = None
+    for k in range(4):
+        if n_items:
+            ctx.age_bands_configure(ITEMS[:n_items], PROBS, windows, mask, w)
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.run_days(0, RUN_DAYS)
+        ctx.sync()
+        ms = (time.perf_counter() - t0) / RUN_DAYS * 1e3
+        if k:
+            best = ms if best is None else min(best, ms)
+    if n_items:
+        rows, hdr, closed, days = ctx.age_bands_read()
+        assert closed.all() and days == RUN_DAYS and all(hdr[v][..., 0].any() for v in ITEMS[:n_items])
+    ctx.close()
+    print(json.dumps(best))
+
+
+def behind_the_day():
+    got = {}
+    for v, _, _, _ in RUN_VARIANTS:
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", v], check=True, capture_output=True, text=True, timeout=280).stdout
+        got[v] = float(json.loads(out.strip().splitlines()[-1]))
+    lines = [f"    rh_sas_run_days over {RUN_DAYS} closing days, {RUN_N} columns x {RUN_AGES} ages, {RUN_SUBSTEPS} sub-steps, keep_distributions, "
+             "3 probabilities, ms per day (minimum of 3 runs, a process each):"]
+    for v, text, _, _ in RUN_VARIANTS:
+        lines.append(f"    {text}: {got[v]:.4f}" + ("" if v == "n" else f"   ({got[v] - got['n']:+.4f} ms per closing day against (n))"))
+    return lines
+
+
+def alone():
+    import numpy as np
+
+    from roger_amd._native import SasContext
+
+    n, ages = RUN_N, RUN_AGES
+    rng = np.random.default_rng(7)
+    ctx = SasContext(n, ages, keep_distributions=True)
+    for v in ITEMS:
+        ctx.upload(v, rng.random(ctx.shape(v)))
+    windows = (np.arange(R * (REPEATS + 1)),) * 2
+    lines = []
+
+    def timed(n_items, mask, w, what):
+        ctx.age_bands_configure(ITEMS[:n_items], PROBS, windows, mask, w)
+        for _ in range(R):       # warm-up: first launches, clocks
+            ctx.age_bands_record(0)
+        ctx.sync()
+        ms = []
+        for _ in range(REPEATS):
+            t0 = time.perf_counter()
+            for _ in range(R):
+                ctx.age_bands_record(0)
+            ctx.sync()
+            ms.append((time.perf_counter() - t0) / R * 1e3)
+        assert ctx.age_bands_read()[2].all()
+        lines.append(f"    {what}: {statistics.median(ms):9.4f} ms per closing day (median of {REPEATS} x {R} days; {min(ms):.4f} ... {max(ms):.4f}), back to back")
+        return statistics.median(ms)
+
+    for n_items in (1, 4):
+        for weighted in (False, True):
+            mask, w = participation(n, weighted)
+            timed(n_items, mask, w, f"{n} columns x {ages} ages, {n_items} item(s), " + (f"weights on {BOUND} columns" if weighted else f"no weights, {n} columns take part"))
+    slope = {}
+    for n_part in (25_000, 50_000, 100_000):
+        mask, _ = participation(n, False, n_part) if n_part < n else (None, None)
+        slope[n_part] = timed(1, mask, None, f"slope: 1 item, no weights, {n_part:6d} participating columns")
+    lines.append(f"    slope: {(slope[100_000] - slope[25_000]) / 75.0:.4f} ms per 1000 participating columns and item of 1001 age classes (25 000 -> 100 000)")
+    ctx.age_bands_configure([])
+    # the alternative: the (n, ages + 1) array to the host, np.partition at the three ranks
+    t0 = time.perf_counter()
+    A = ctx.download("TT_q_ss")
+    t1 = time.perf_counter()
+    ranks = sorted({min(max(int(np.ceil(p * n)), 1), n) - 1 for p in PROBS})
+    band = np.partition(A, ranks, axis=0)[ranks]
+    t2 = time.perf_counter()
+    assert band.shape == (len(ranks), ages + 1)
+    lines.append(f"    the alternative, 1 item: download of ({n}, {ages + 1}) float64 {1e3 * (t1 - t0):.1f} ms + np.partition at {len(ranks)} ranks on the host "
+                 f"{1e3 * (t2 - t1):.1f} ms = {1e3 * (t2 - t0):.1f} ms")
+    lines.append("    10^6 columns: not measured")
+    ctx.close()
+    return lines
+
+
+def off_cost():
+    parent = os.environ.get("ROGER_HIP_PARENT")
+    if not parent:
+        return ["    off cost: ROGER_HIP_PARENT is not set, skipped"]
+    old, new, key = [], [], ""
+    first = os.environ.get("ROGER_HIP_OFF_FIRST", "parent")   # which library opens the alternation: an order effect shows when it is swapped
+    for _ in range(3):
+        for lib in ((parent, None) if first == "parent" else (None, parent)):
+            ms, key = bench_ms_per_day(lib)
+            (old if lib else new).append(ms)
+    med = statistics.median(new)
+    verdict = "within or below the parent's range" if med <= max(old) else "ABOVE the parent's range"
+    return [f"    bench.py --model sas --steps 8 --warmup 2, nothing configured, {key} in ms, alternating: parent library "
+            + ", ".join(f"{x:.4f}" for x in old) + f" (range {min(old):.4f} ... {max(old):.4f}); this tree " + ", ".join(f"{x:.4f}" for x in new)
+            + f" (median {med:.4f}): {verdict}"]
+
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["--child"]:
+        run_child(sys.argv[2])
+        sys.exit(0)
+    what = sys.argv[1:] or ["run", "alone", "off"]
+    print("transport bands by age (rh_sas_age_bands_*), measured once on one MI355X", flush=True)
+    if "run" in what:
+        print("\n".join(behind_the_day()), flush=True)
+    if "alone" in what:
+        print("\n".join(alone()), flush=True)
+    if "off" in what:
+        print("\n".join(off_cost()), flush=True)
