@@ -466,6 +466,39 @@ int rh_sas_age_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total);
 int rh_sas_age_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed,
                           size_t closed_bytes, int64_t *days_recorded);
 
+/* ---- transport bands by age per zone: the bands by age above for every zone of a zone map in one run -----------------------------------------
+ * Every lysimeter's, land use's or sub-catchment's travel time band from ONE transport run (kernels, the rule and the bytes moved:
+ * roger_amd/csrc/rh_sas_age_bands.h; the numpy twin is tests/sas_age_bands_zonal_reference.py).
+ * The promise, which is the whole specification: block (item j, zone z, age class a) of window k is bit for bit what
+ * rh_sas_age_bands_configure records for item j and age class a with mask = (zone == z) & mask and the same weights, probabilities and
+ * windows.  A cell with zone == -1, mask == 0 or weight 0 loads and stores nothing and is in no zone's counts; a zone with m == 0 in an age
+ * class gives NaN rows and W = 0 there.  Only kind RH_SAS_SCORES_LAST with weight -1 is accepted, as above.
+ *   zone     [n_cells] int32: -1 outside every zone, else 0 ... n_zones - 1
+ *   n_zones  1 ... RH_SAS_AGE_BANDS_MAX_ZONES
+ *   everything else as rh_sas_age_bands_configure takes it
+ * Result: rows [n_samples][sum_j W_j x n_zones][n_probs] float64, item j's block (n_zones, W_j, n_probs) in configured order -- the zone axis
+ * stands before the age axis, so a zone's distribution is contiguous --, hdr likewise with {m, n_nan, W} int64, closed [n_samples] bytes,
+ * read with rh_sas_age_bands_zonal_read (which synchronises).
+ * rh_sas_age_bands_record, rh_sas_age_bands_row_elems (sum_j W_j, without the zone axis), rh_sas_step and rh_sas_run_days serve both
+ * configurations; a closing day is at most three launches per item: the transpose, the selection of the zones of more than 256
+ * participating cells (six digit passes by a workgroup per zone and age class) and the selection of the zones of 1 ... 256 (one key per
+ * thread, no histogram).  Each configure call replaces the other; n_items == 0 releases.  rh_sas_age_bands_read is RH_ERR_STATE while the
+ * bands by age are per zone, rh_sas_age_bands_zonal_read is RH_ERR_STATE while they are not.  Everything is checked, and the new buffers are
+ * allocated, before the running configuration is released: a refused call leaves it in place.
+ * RH_ERR_ARG beyond the refusals of rh_sas_age_bands_configure: n_zones outside 1 ... RH_SAS_AGE_BANDS_MAX_ZONES; a zone index outside
+ * -1 ... n_zones - 1 (the message names the cell); rows or headers of n_samples x sum_j W_j x n_zones blocks beyond 2 GiB; and THE BOUND,
+ * which is PER ZONE here: one workgroup selects a (zone, age class) in uint32 LDS bins, so with a weight plane a ZONE of more than 65536
+ * participating cells is refused (the message names the zone and its size).  A weighted study of more than 65536 participating cells in
+ * total is accepted when every zone is within the bound -- the one place where this call accepts more than rh_sas_age_bands_configure,
+ * which refuses that total.  Without weights any zone size is exact.
+ * Load balance: one workgroup walks a (zone, age class), so the largest zone sets the time of a closing day. */
+#define RH_SAS_AGE_BANDS_MAX_ZONES 1024
+int rh_sas_age_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                                     const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights,
+                                     const int64_t *first_day, const int64_t *last_day, int64_t n_samples);
+int rh_sas_age_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed,
+                                size_t closed_bytes, int64_t *days_recorded);
+
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);
 int rh_sas_timing_summary(rh_sas_ctx *ctx, double *total_ms, int64_t *launches);

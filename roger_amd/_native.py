@@ -18,7 +18,7 @@ INCLUDE = os.path.join(os.path.dirname(PKG), "include")   # where roger_amd/buil
 
 
 # -- what this binding was written for: the version and the structures are stated by hand, everything else is read from the headers --
-ABI_VERSION = 23  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 24  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -1005,6 +1005,7 @@ class SasContext:
         self._scores_shape = (0, 0)          # (items, samples)
         self._bands_shape = (0, 0, 0)        # (windows, items, probs); with zones (windows, items, zones, probs)
         self._age_bands_items, self._age_bands_shape = [], (0, 0)   # [(name, width)], (windows, probs)
+        self._age_bands_zones = 0                                   # 0: the plain configuration
 
     def _check(self, rc, what):
         if rc != 0:
@@ -1343,22 +1344,38 @@ class SasContext:
         return rows, hdr, pairs, closed, days.value
 
     # -- transport bands by age: the bands of every age class of an age-resolved array (rh_sas_age_bands_*) --------------
-    def age_bands_configure(self, items, probs=(), windows=None, mask=None, weights=None):
+    def age_bands_configure(self, items, probs=(), windows=None, mask=None, weights=None, zones=None, n_zones=None):
         """The exact quantiles `probs` ACROSS the cells for EVERY age class of the age-resolved arrays `items` -- an array's name, or
         (value, None, "last") as bands_configure takes an item; window means are not built -- on the closing day of each of the windows
         (first_day, last_day), int (K,) each, inclusive, in this recorder's own count of recorded days, which restarts at 0 here.  `mask`
         and `weights` as bands_configure takes them; with weights at most 65536 cells take part.  Block (item, age class a) is bit for
-        bit what bands_configure records for the width-1 values A[:, a] with kind "last".  No items: release everything and stop."""
+        bit what bands_configure records for the width-1 values A[:, a] with kind "last".  No items: release everything and stop.
+        `zones`: (n,) integers, -1: outside every zone, else 0 ... n_zones - 1 (default: the largest index + 1) -- the bands by age of every
+        zone in one run, block (zone z, age class a) bit for bit what mask = (zones == z) & mask gives; age_bands_read then returns the
+        zone axis in front of the age axis (rh_sas_age_bands_configure_zonal).  With weights the bound of 65536 participating cells
+        holds per zone, not in total."""
         items, flat = self._window_items([(it, None, "last") if isinstance(it, str) else it for it in items])
-        pr = first = last = mk = wt = None
+        pr = first = last = mk = wt = zn = None
+        nz = 0
         if items:
-            pr, first, last, mk, wt = self._bands_arguments("age_bands_configure", probs, windows, mask, weights)
+            pr, first, last, mk, wt = self._bands_arguments("age_bands_configure", probs, windows, mask, weights, zones)
+            if zones is not None:
+                zn = np.asarray(zones).reshape(-1)
+                if zn.dtype.kind not in "iu":
+                    raise ValueError(f"age_bands_configure: zones of dtype {zn.dtype} (integers: -1 or 0 ... n_zones - 1)")
+                nz = int(n_zones) if n_zones is not None else int(zn.max()) + 1 if zn.size else 0
+                zn = _cell_map("age_bands_configure", "zones", zn, self.n, _CELLS, lowest=-2)
         nk, npr = 0 if first is None else first.size, 0 if pr is None else pr.size
-        self._check(self._lib.rh_sas_age_bands_configure(self._h, _ptr(flat), len(items), _ptr(pr), npr, _ptr(mk), _ptr(wt), _ptr(first), _ptr(last),
-                                                         nk), "rh_sas_age_bands_configure")
+        if zn is not None:
+            self._check(self._lib.rh_sas_age_bands_configure_zonal(self._h, _ptr(flat), len(items), _ptr(pr), npr, _ptr(zn), nz, _ptr(mk), _ptr(wt),
+                                                                   _ptr(first), _ptr(last), nk), "rh_sas_age_bands_configure_zonal")
+        else:
+            self._check(self._lib.rh_sas_age_bands_configure(self._h, _ptr(flat), len(items), _ptr(pr), npr, _ptr(mk), _ptr(wt), _ptr(first),
+                                                             _ptr(last), nk), "rh_sas_age_bands_configure")
         # (a refused configuration leaves the previous one)
         self._age_bands_items = [(v, int(np.prod(self.shape(v)[1:], dtype=np.int64))) for v, _, _ in items]
         self._age_bands_shape = (nk, npr)
+        self._age_bands_zones = 0 if zn is None else nz
 
     def age_bands_record(self, day=0):
         """Record now as the next day of the count (a driver that steps by stage).  `day` (>= 0) is the row of the daily inputs, as for
@@ -1367,18 +1384,22 @@ class SasContext:
 
     def age_bands_read(self):
         """(rows {name: float64 (K, W, n_probs)}, NaN until the window closed; hdr {name: int64 (K, W, 3)}: m, n_nan, W per age class;
-        closed uint8 (K,); days recorded since age_bands_configure), W the item's width (ages or ages + 1).  Synchronises."""
+        closed uint8 (K,); days recorded since age_bands_configure), W the item's width (ages or ages + 1).  Configured with zones: rows
+        {name: (K, n_zones, W, n_probs)}, hdr {name: (K, n_zones, W, 3)}.  Synchronises."""
         total = C.c_int64()
         self._check(self._lib.rh_sas_age_bands_row_elems(self._h, C.byref(total)), "rh_sas_age_bands_row_elems")
         nk, npr = self._age_bands_shape
-        rows = np.empty((nk, total.value, npr), dtype=np.float64)
-        hdr = np.empty((nk, total.value, 3), dtype=np.int64)
+        nz = self._age_bands_zones
+        rows = np.empty((nk, total.value * max(nz, 1), npr), dtype=np.float64)
+        hdr = np.empty((nk, total.value * max(nz, 1), 3), dtype=np.int64)
         closed = np.empty(nk, dtype=np.uint8)
         days = C.c_int64()
-        self._check(self._lib.rh_sas_age_bands_read(self._h, _ptr(rows), rows.nbytes, _ptr(hdr), hdr.nbytes, _ptr(closed), closed.nbytes, C.byref(days)),
-                    "rh_sas_age_bands_read")
+        name = "rh_sas_age_bands_zonal_read" if nz else "rh_sas_age_bands_read"
+        self._check(getattr(self._lib, name)(self._h, _ptr(rows), rows.nbytes, _ptr(hdr), hdr.nbytes, _ptr(closed), closed.nbytes, C.byref(days)), name)
         out_rows, out_hdr, off = {}, {}, 0
         for v, w in self._age_bands_items:
-            out_rows[v], out_hdr[v] = rows[:, off:off + w].copy(), hdr[:, off:off + w].copy()
-            off += w
+            wz = w * max(nz, 1)
+            lead = (nk, nz, w) if nz else (nk, w)
+            out_rows[v], out_hdr[v] = rows[:, off:off + wz].reshape(*lead, npr).copy(), hdr[:, off:off + wz].reshape(*lead, 3).copy()
+            off += wz
         return out_rows, out_hdr, closed, days.value

@@ -34,6 +34,25 @@
 // LOAD BALANCE.  ONE workgroup walks an age class: a closing day's time grows with n_part, and W_j workgroups are in flight.
 // Bytes on a closing day, per item, participating column and age class: 8 B read and 8 B written by the transpose, six passes x (8 B key
 // + 2 B weight) by the selection (a run of 10^5 keys is 0.8 MB: the later passes are served by the caches).
+//
+// PER ZONE (rh_sas_age_bands_configure_zonal; the numpy twin is tests/sas_age_bands_zonal_reference.py).  One more promise: block (item j,
+// zone z, age class a) -- rows [k][j][z][a][probability], hdr [k][j][z][a]{m, n_nan, W}, the zone axis in front of the age axis -- is bit for
+// bit what the plain configuration records for item j and age class a with mask = (zone == z) & mask.  A column with zone == -1, mask == 0
+// or weight 0 is in no zone's counts.  The host orders part_cols and wts_c by zone with a stable counting sort (ascending within a zone)
+// and uploads zone_off [n_zones + 1], so that k_sas_age_keys, unchanged, writes a key plane whose row a holds zone z's keys as the
+// contiguous run [zone_off[z], zone_off[z + 1]).  Per item at most three launches (SasAgeZones lists the zones of each):
+//   k_sas_age_bands_zonal<WEIGHTED>   grid (W_j, long zones), 256 threads: the zones of more than SAS_AGE_SHORT_ZONE = 256 participating
+//                      cells; select_walk_run over the zone's run and select_lds_block, as k_sas_age_bands: a shell, nothing restated.
+//   k_sas_age_bands_small<WEIGHTED>   grid (W_j, short zones), 256 threads: the zones of 1 ... 256 cells.  A zone map multiplies the runs by
+//                      up to 1024 and the six passes cost six clears of up to 64 KiB of LDS and six picks however short the run is; here a
+//                      thread holds ONE key and weight (beyond the run's end KEY_MASKED and 0, so that such a thread counts in no
+//                      reduction and is no candidate), both go to LDS, and behind one barrier c_t = sum of w_j over the run's members with
+//                      key_j <= key_t, read as broadcasts (uint32: 256 x 65535 < 2^32).  m, n_nan and W by a workgroup reduction; per
+//                      probability T - 1 = bands_rank_of(p, W) and the result is the minimum key over the threads with c_t >= T -- a
+//                      shuffle minimum per wavefront, LDS across the four -- turned back by bands_value_of.  No histogram, no digit
+//                      pass, 3376 B of LDS; the same promise and the same bits as the six passes.
+// An empty zone is in neither list: its blocks keep the NaN rows and zero headers configure wrote.  THE BOUND is per zone: with a weight
+// plane a ZONE of more than 65536 participating cells is refused; the total may be larger, which the plain configuration refuses.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +69,24 @@ static_assert(RH_SELECT_BLOCK % SAS_AGE_TILE == 0, "a wavefront of the transpose
 // it lay within it in both alternation orders (DESIGN.md 3.9.3 gives the figures and what the control runs do and do not show).
 void rh_sas_age_launch(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
                        const unsigned short *wts_c, const double *probs, int np, double *rows, long long *hdr);
+
+// Per zone: what the two kernels of a zonal configuration are told.  zone_off [n_zones + 1] into part_cols / wts_c / a row of the key plane,
+// which are in zone order; the zones of 1 ... SAS_AGE_SHORT_ZONE participating cells and the longer ones (an empty zone is in neither list:
+// its blocks keep what configure wrote).
+struct SasAgeZones {
+    const long long *zone_off;
+    const int *short_zones, *long_zones;
+    int n_short, n_long;
+};
+#ifndef SAS_AGE_SHORT_ZONE   // (tools/sas_age_bands_time.py builds a variant with 0: every zone through the six passes, to price the second path)
+#define SAS_AGE_SHORT_ZONE RH_SELECT_BLOCK   // by construction, not tuned: one key per thread of k_sas_age_bands_small
+#endif
+static_assert(SAS_AGE_SHORT_ZONE <= RH_SELECT_BLOCK, "k_sas_age_bands_small holds one key per thread");
+// One item's launches of a zonal configuration on `stream`: the transpose, unchanged, with part_cols in zone order; k_sas_age_bands_zonal
+// where there are long zones, k_sas_age_bands_small where there are short ones; rows [n_zones][W][np] and hdr [n_zones][W][3] are the item's
+// blocks of the window.
+void rh_sas_age_launch_zonal(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
+                             const unsigned short *wts_c, const SasAgeZones &Z, const double *probs, int np, double *rows, long long *hdr);
 
 #ifdef RH_SAS_AGE_UNIT
 // keys[a][i] = key(A[part_cols[i]][a] + 0.0) for i < n_part, a < W
@@ -91,15 +128,122 @@ __global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_age_bands(const unsigne
                      hdr + a * RH_SELECT_HDR);
 }
 
-void rh_sas_age_launch(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
-                       const unsigned short *wts_c, const double *probs, int np, double *rows, long long *hdr) {
+// ---- per zone (rh_sas_age_bands_configure_zonal): one run of the key plane per (age class, zone) ----
+// workgroup (a, l): the selection over the run keys[a][zone_off[z] ... zone_off[z + 1]) of zone z = long_zones[l]; rows and hdr are the
+// item's blocks of window k, [n_zones][W][n_probs] and [n_zones][W][3], W = gridDim.x
+template <bool WEIGHTED>
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_age_bands_zonal(const unsigned long long *__restrict__ keys, const unsigned short *__restrict__ wts_c,
+                                                                         long long n_part, SasAgeZones Z, const double *__restrict__ probs, int np,
+                                                                         double *__restrict__ rows, long long *__restrict__ hdr) {
+    RH_SELECT_LDS(L);
+    const size_t a = blockIdx.x, z = (size_t)Z.long_zones[blockIdx.y], block = z * gridDim.x + a;
+    const long long beg = Z.zone_off[z], len = Z.zone_off[z + 1] - beg;
+    const unsigned long long *run = keys + a * (size_t)n_part + (size_t)beg;
+    const unsigned short *wts = WEIGHTED ? wts_c + beg : nullptr;
+    select_lds_block([&](auto body) RH_SELECT_BODY { select_walk_run<WEIGHTED>(run, wts, len, body); }, np, probs, L, rows + block * (size_t)np,
+                     hdr + block * RH_SELECT_HDR);
+}
+
+// the sum of x over the workgroup, in every thread: shuffles within a wavefront, LDS across the RH_SELECT_BLOCK / 64 of them
+RH_SELECT_DEV unsigned sas_age_block_sum(unsigned x, unsigned *s_part) {
+    for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = x;
+    __syncthreads();
+    x = 0;
+#pragma unroll
+    for (int w = 0; w < RH_SELECT_BLOCK / 64; ++w) x += s_part[w];
+    return x;
+}
+
+// workgroup (a, l): zone z = short_zones[l] has 1 ... RH_SELECT_BLOCK participating cells, so a thread holds ONE key of the run and the
+// selection needs no histogram and no digit pass: c_t, the weight of the members at or below thread t's key, is formed from the run in LDS
+// (every lane of a read asks for the same address: a broadcast), and the result of a probability is the smallest key with c_t >= T.  The
+// same promise and the same bits as select_lds_block: T - 1 is bands_rank_of(p, W), the value is bands_value_of(key).
+template <bool WEIGHTED>
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_age_bands_small(const unsigned long long *__restrict__ keys, const unsigned short *__restrict__ wts_c,
+                                                                         long long n_part, SasAgeZones Z, const double *__restrict__ probs, int np,
+                                                                         double *__restrict__ rows, long long *__restrict__ hdr) {
+    __shared__ unsigned long long s_key[RH_SELECT_BLOCK], s_min[RH_SELECT_MAX_PROBS][RH_SELECT_BLOCK / 64];
+    __shared__ unsigned s_w[RH_SELECT_BLOCK], s_part[3][RH_SELECT_BLOCK / 64];
+    const size_t a = blockIdx.x, z = (size_t)Z.short_zones[blockIdx.y], block = z * gridDim.x + a;
+    const long long beg = Z.zone_off[z];
+    const int len = (int)(Z.zone_off[z + 1] - beg), t = (int)threadIdx.x;   // 1 ... RH_SELECT_BLOCK
+    const bool in = t < len;
+    const unsigned long long key = in ? keys[a * (size_t)n_part + (size_t)(beg + t)] : RH_SELECT_KEY_MASKED;
+    const unsigned w = in ? (WEIGHTED ? (unsigned)wts_c[beg + t] : 1u) : 0u;
+    s_key[t] = key;
+    s_w[t] = w;
+    __syncthreads();
+    const bool number = key < RH_SELECT_KEY_NAN;
+    unsigned c = 0;   // at most RH_SELECT_BLOCK x 65535 < 2^32
+#pragma unroll 4
+    for (int j = 0; j < len; ++j) {   // (the run's members only; the padding beyond its end is for the three reductions below)
+        const unsigned long long kj = s_key[j];
+        c += (kj <= key && kj < RH_SELECT_KEY_NAN) ? s_w[j] : 0u;
+    }
+    const unsigned m = sas_age_block_sum(number ? 1u : 0u, s_part[0]), n_nan = sas_age_block_sum(key == RH_SELECT_KEY_NAN ? 1u : 0u, s_part[1]),
+                   total = sas_age_block_sum(number ? w : 0u, s_part[2]);
+    if (t == 0) {
+        hdr[block * RH_SELECT_HDR] = (long long)m;
+        hdr[block * RH_SELECT_HDR + 1] = (long long)n_nan;
+        hdr[block * RH_SELECT_HDR + 2] = (long long)total;
+    }
+    double *out = rows + block * (size_t)np;
+    if (m == 0) {   // (uniform over the workgroup)
+        if (t < np) out[t] = __builtin_nan("");
+        return;
+    }
+    for (int q = 0; q < np; ++q) {
+        const long long r = bands_rank_of(probs[q], (long long)total);   // T - 1
+        unsigned long long best = (number && (long long)c > r) ? key : RH_SELECT_KEY_MASKED;
+        for (int off = 32; off; off >>= 1) {
+            const unsigned long long other = __shfl_xor(best, off);
+            best = other < best ? other : best;
+        }
+        if ((t & 63) == 0) s_min[q][t >> 6] = best;
+    }
+    __syncthreads();
+    if (t < np) {
+        unsigned long long best = s_min[t][0];
+#pragma unroll
+        for (int wv = 1; wv < RH_SELECT_BLOCK / 64; ++wv) best = s_min[t][wv] < best ? s_min[t][wv] : best;
+        out[t] = bands_value_of(best);
+    }
+}
+
+static void sas_age_launch_keys(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys) {
     const dim3 tiles((unsigned)((n_part + SAS_AGE_TILE - 1) / SAS_AGE_TILE), (unsigned)((W + SAS_AGE_TILE - 1) / SAS_AGE_TILE));
     hipLaunchKernelGGL(k_sas_age_keys, tiles, dim3(RH_SELECT_BLOCK), 0, stream, A, W, part_cols, n_part, keys);
+}
+
+void rh_sas_age_launch(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
+                       const unsigned short *wts_c, const double *probs, int np, double *rows, long long *hdr) {
+    sas_age_launch_keys(stream, A, W, part_cols, n_part, keys);
     if (wts_c)
         hipLaunchKernelGGL(k_sas_age_bands<true>, dim3((unsigned)W), dim3(RH_SELECT_BLOCK), 0, stream, (const unsigned long long *)keys, wts_c, n_part, probs, np,
                            rows, hdr);
     else
         hipLaunchKernelGGL(k_sas_age_bands<false>, dim3((unsigned)W), dim3(RH_SELECT_BLOCK), 0, stream, (const unsigned long long *)keys, wts_c, n_part, probs, np,
                            rows, hdr);
+}
+
+template <bool WEIGHTED>
+static void sas_age_launch_zones(hipStream_t stream, int W, long long n_part, const unsigned long long *keys, const unsigned short *wts_c, const SasAgeZones &Z,
+                                 const double *probs, int np, double *rows, long long *hdr) {
+    if (Z.n_long)
+        hipLaunchKernelGGL(k_sas_age_bands_zonal<WEIGHTED>, dim3((unsigned)W, (unsigned)Z.n_long), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, Z, probs,
+                           np, rows, hdr);
+    if (Z.n_short)
+        hipLaunchKernelGGL(k_sas_age_bands_small<WEIGHTED>, dim3((unsigned)W, (unsigned)Z.n_short), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, Z, probs,
+                           np, rows, hdr);
+}
+
+void rh_sas_age_launch_zonal(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
+                             const unsigned short *wts_c, const SasAgeZones &Z, const double *probs, int np, double *rows, long long *hdr) {
+    sas_age_launch_keys(stream, A, W, part_cols, n_part, keys);
+    if (wts_c)
+        sas_age_launch_zones<true>(stream, W, n_part, keys, wts_c, Z, probs, np, rows, hdr);
+    else
+        sas_age_launch_zones<false>(stream, W, n_part, keys, wts_c, Z, probs, np, rows, hdr);
 }
 #endif   // RH_SAS_AGE_UNIT

@@ -214,9 +214,17 @@ struct SasAgeBands {
     int width[RH_SAS_AGE_BANDS_MAX_ITEMS] = {};
     int n_items = 0, n_probs = 0;
     int64_t n_part = 0, ages_total = 0;   // ages_total: the sum of the items' widths
+    // ... per zone (rh_sas_age_bands_configure_zonal): part_cols and wts_c are in zone order, the result gains the zone axis behind the
+    // item's and in front of the age axis; where each zone's run starts and the lists of the short and of the long zones
+    int zones = 0;                        // 0: the plain configuration (k_sas_age_bands); else k_sas_age_bands_zonal / _small
+    DevBuf<long long> zone_off;
+    DevBuf<int> zone_lists;               // [n_short] short zones, then [n_long] long ones
+    int n_short = 0, n_long = 0;
+    SasAgeZones dev_zones() const { return {zone_off.get(), zone_lists.get(), zone_lists.get() + n_short, n_short, n_long}; }
     bool on() const { return win.on(); }
     hipError_t release() {
-        const hipError_t e = first_error({rows.release(), probs.release(), hdr.release(), keys.release(), part_cols.release(), wts_c.release()});
+        const hipError_t e = first_error({rows.release(), probs.release(), hdr.release(), keys.release(), part_cols.release(), wts_c.release(),
+                                          zone_off.release(), zone_lists.release()});
         *this = SasAgeBands();
         return e;
     }

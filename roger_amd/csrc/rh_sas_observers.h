@@ -643,23 +643,30 @@ static int sas_age_bands_enqueue(rh_sas_ctx *ctx) {
     SasAgeBands &S = ctx->age_bands;
     const SasWindows::Tick now = S.win.tick();
     if (!now.launch) return RH_OK;   // (every item is LAST: launch == closes)
-    const size_t np = (size_t)S.n_probs;
-    size_t block = (size_t)now.k * (size_t)S.ages_total;
+    const size_t np = (size_t)S.n_probs, nb = S.zones ? (size_t)S.zones : 1;   // nb: blocks per age class
+    size_t block = (size_t)now.k * (size_t)S.ages_total * nb;
     for (int j = 0; j < S.n_items; ++j) {
         const int W = S.width[j];
-        rh_sas_age_launch(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.probs.get(), S.n_probs,
-                          S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
-        block += (size_t)W;
+        if (S.zones)   // per zone: the transpose, then the long zones' selection and the short zones', at most three launches
+            rh_sas_age_launch_zonal(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.dev_zones(),
+                                    S.probs.get(), S.n_probs, S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
+        else
+            rh_sas_age_launch(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.probs.get(), S.n_probs,
+                              S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
+        block += (size_t)W * nb;
     }
     SHIPCHK(ctx, hipGetLastError());
     return RH_OK;
 }
 
-int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
-                               const unsigned char *mask, const uint16_t *weights, const int64_t *first_day, const int64_t *last_day,
-                               int64_t n_samples) {
-    const std::string who = "rh_sas_age_bands_configure: ";
-    if (!ctx) return RH_ERR_ARG;
+// rh_sas_age_bands_configure (zone == nullptr, n_zones == 0) and rh_sas_age_bands_configure_zonal, for the function `name`: with zones the
+// result gains the zone axis in front of the age axis, a cell takes part where (zone >= 0) & mask and its weight say so, part_cols and
+// wts_c are in zone order (a stable counting sort, as sas_bands_configure does it) and the bound of a weight plane holds per zone
+static int sas_age_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                                   const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const int64_t *first_day,
+                                   const int64_t *last_day, int64_t n_samples) {
+    const std::string who = std::string(name) + ": ";
+    const bool zonal = n_zones != 0;
     if (n_items < 0 || n_items > RH_SAS_AGE_BANDS_MAX_ITEMS)
         return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_AGE_BANDS_MAX_ITEMS) + ")");
     SasAgeBands &S = ctx->age_bands;
@@ -670,7 +677,7 @@ int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items,
     }
     const int64_t n = ctx->cfg.n_cells;
     SasAgeBands N;   // the new configuration: checked and allocated in full before the previous one is released
-    if (!items || !probs || !first_day || !last_day) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
+    if (!items || !probs || !first_day || !last_day || (zonal && !zone)) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
     if (n_probs < 1 || n_probs > RH_SAS_BANDS_MAX_PROBS)
         return sfail(ctx, RH_ERR_ARG, who + "n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_SAS_BANDS_MAX_PROBS) + ")");
     for (int q = 0; q < n_probs; ++q)
@@ -701,23 +708,58 @@ int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items,
         wmax = std::max(wmax, N.width[j]);
     }
     const int64_t block_b = std::max<int64_t>(n_probs * (int64_t)sizeof(double), SAS_BANDS_HDR * (int64_t)sizeof(int64_t));   // rows or hdr, the larger
-    if (n_samples < 1 || n_samples > ((int64_t)1 << 31) / (N.ages_total * block_b))
-        return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one; rows of " + std::to_string(N.ages_total) +
-                                          " age classes x " + std::to_string(n_probs) + " float64 and headers of 3 int64, each within 2 GiB)");
+    if (n_samples < 1 || n_samples > ((int64_t)1 << 31) / (N.ages_total * (zonal ? n_zones : 1) * block_b))
+        return sfail(ctx, RH_ERR_ARG, who + "n_samples = " + std::to_string(n_samples) + " (at least one; rows of " +
+                                          (zonal ? std::to_string(n_zones) + " zones x " : std::string()) + std::to_string(N.ages_total) + " age classes x " +
+                                          std::to_string(n_probs) + " float64 and headers of 3 int64, each within 2 GiB)");
     if (int rc = sas_check_windows(ctx, who, first_day, last_day, n_samples)) return rc;
-    std::vector<int> part_cols;          // the participating columns, ascending ...
+    std::vector<int> part_cols;          // the participating columns, ascending (per zone: in zone order, ascending within a zone) ...
     std::vector<unsigned short> wts_c;   // ... and their weights, at the same index
-    for (int64_t c = 0; c < n; ++c)
-        if ((!mask || mask[c]) && (!weights || weights[c])) {
-            part_cols.push_back((int)c);
-            if (weights) wts_c.push_back(weights[c]);
+    std::vector<long long> zone_off;     // per zone: [n_zones + 1] into both
+    std::vector<int> zone_lists;         // per zone: the short zones, then the long ones
+    const auto takes_part = [&](int64_t c) { return (!zonal || zone[c] >= 0) && (!mask || mask[c]) && (!weights || weights[c]); };
+    if (zonal) {   // the zones' sizes, the bound of a weighted zone, then the stable counting sort over the participating columns
+        zone_off.assign((size_t)n_zones + 1, 0);
+        for (int64_t c = 0; c < n; ++c) {
+            if (zone[c] < -1 || zone[c] >= n_zones)
+                return sfail(ctx, RH_ERR_ARG, who + "zone[" + std::to_string(c) + "] = " + std::to_string(zone[c]) + " (-1: outside every zone, else 0 ... " +
+                                                  std::to_string(n_zones - 1) + ")");
+            if (takes_part(c)) ++zone_off[(size_t)zone[c] + 1];
         }
+        for (int z = 0; z < n_zones && weights; ++z)
+            if (zone_off[(size_t)z + 1] > SAS_AGE_BANDS_MAX_WEIGHTED)
+                return sfail(ctx, RH_ERR_ARG, who + "zone " + std::to_string(z) + " has " + std::to_string(zone_off[(size_t)z + 1]) +
+                                                  " participating cells under a weight plane (at most " + std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) +
+                                                  ": a uint32 LDS bin holds the weights of a zone's age class; without weights any size is exact)");
+        for (int z = 0; z < n_zones; ++z)   // (short: 1 ... SAS_AGE_SHORT_ZONE cells; an empty zone is in neither list)
+            if (zone_off[(size_t)z + 1] > 0 && zone_off[(size_t)z + 1] <= SAS_AGE_SHORT_ZONE) zone_lists.push_back(z);
+        N.n_short = (int)zone_lists.size();
+        for (int z = 0; z < n_zones; ++z)
+            if (zone_off[(size_t)z + 1] > SAS_AGE_SHORT_ZONE) zone_lists.push_back(z);
+        N.n_long = (int)zone_lists.size() - N.n_short;
+        for (int z = 0; z < n_zones; ++z) zone_off[(size_t)z + 1] += zone_off[(size_t)z];
+        part_cols.resize((size_t)zone_off[(size_t)n_zones]);
+        if (weights) wts_c.resize(part_cols.size());
+        std::vector<long long> at(zone_off.begin(), zone_off.end() - 1);
+        for (int64_t c = 0; c < n; ++c)
+            if (takes_part(c)) {
+                const size_t i = (size_t)at[(size_t)zone[c]]++;
+                part_cols[i] = (int)c;
+                if (weights) wts_c[i] = weights[c];
+            }
+    } else {
+        for (int64_t c = 0; c < n; ++c)
+            if (takes_part(c)) {
+                part_cols.push_back((int)c);
+                if (weights) wts_c.push_back(weights[c]);
+            }
+    }
     N.n_part = (int64_t)part_cols.size();
     if (!N.n_part) return sfail(ctx, RH_ERR_ARG, who + "no cell takes part (0 of " + std::to_string(n) + " cells have mask != 0 and a weight > 0)");
-    if (weights && N.n_part > SAS_AGE_BANDS_MAX_WEIGHTED)
+    if (!zonal && weights && N.n_part > SAS_AGE_BANDS_MAX_WEIGHTED)
         return sfail(ctx, RH_ERR_ARG, who + std::to_string(N.n_part) + " participating cells under a weight plane (at most " +
                                           std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) + ": a uint32 LDS bin holds an age class's weights; without weights any size is exact)");
-    const size_t K = (size_t)n_samples, np = (size_t)n_probs, blocks = K * (size_t)N.ages_total, npart = (size_t)N.n_part;
+    const size_t K = (size_t)n_samples, np = (size_t)n_probs, blocks = K * (size_t)N.ages_total * (zonal ? (size_t)n_zones : 1), npart = (size_t)N.n_part;
     const size_t row_b = blocks * np * sizeof(double), hdr_b = blocks * SAS_BANDS_HDR * sizeof(long long);
     const std::vector<double> nans(blocks * np, std::nan(""));
     SHIPCHK(ctx, N.keys.alloc((size_t)wmax * npart * sizeof(unsigned long long)));
@@ -733,13 +775,38 @@ int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items,
         SHIPCHK(ctx, N.wts_c.alloc(npart * sizeof(unsigned short)));
         SHIPCHK(ctx, hipMemcpyAsync(N.wts_c, wts_c.data(), npart * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
     }
+    if (zonal) {
+        SHIPCHK(ctx, N.zone_off.alloc(zone_off.size() * sizeof(long long)));
+        SHIPCHK(ctx, hipMemcpyAsync(N.zone_off, zone_off.data(), zone_off.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        SHIPCHK(ctx, N.zone_lists.alloc(zone_lists.size() * sizeof(int)));   // (never empty: a cell takes part)
+        SHIPCHK(ctx, hipMemcpyAsync(N.zone_lists, zone_lists.data(), zone_lists.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and locals; launches that write the old result)
     N.n_items = n_items;
     N.n_probs = n_probs;
+    N.zones = zonal ? n_zones : 0;
     N.win.set(first_day, last_day, n_samples, false);
     SHIPCHK(ctx, S.release());
     S = std::move(N);
     return RH_OK;
+}
+
+int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                               const unsigned char *mask, const uint16_t *weights, const int64_t *first_day, const int64_t *last_day,
+                               int64_t n_samples) {
+    if (!ctx) return RH_ERR_ARG;
+    return sas_age_bands_configure(ctx, "rh_sas_age_bands_configure", items, n_items, probs, n_probs, nullptr, 0, mask, weights, first_day, last_day, n_samples);
+}
+
+int rh_sas_age_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                                     const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const int64_t *first_day,
+                                     const int64_t *last_day, int64_t n_samples) {
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items && (n_zones < 1 || n_zones > RH_SAS_AGE_BANDS_MAX_ZONES))
+        return sfail(ctx, RH_ERR_ARG, "rh_sas_age_bands_configure_zonal: n_zones = " + std::to_string(n_zones) + " (1 ... " +
+                                          std::to_string(RH_SAS_AGE_BANDS_MAX_ZONES) + ")");
+    return sas_age_bands_configure(ctx, "rh_sas_age_bands_configure_zonal", items, n_items, probs, n_probs, zone, n_items ? n_zones : 0, mask, weights,
+                                   first_day, last_day, n_samples);
 }
 
 int rh_sas_age_bands_record(rh_sas_ctx *ctx, int64_t day) {
@@ -755,17 +822,34 @@ int rh_sas_age_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total) {
     return RH_OK;
 }
 
-int rh_sas_age_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed, size_t closed_bytes,
-                          int64_t *days_recorded) {
-    if (int rc = sas_on(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_read")) return rc;
+// What both reads of the bands by age copy out, for the function `who` of bands that are on: `nb` blocks per age class; `lead` names the axes
+// in front of a block's values in the size check's text.  Synchronises.
+static int sas_age_bands_read(rh_sas_ctx *ctx, const char *who, size_t nb, const char *lead, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes,
+                              unsigned char *closed, size_t closed_bytes, int64_t *days_recorded) {
     const SasAgeBands &S = ctx->age_bands;
-    const size_t K = S.win.closed.size(), blocks = K * (size_t)S.ages_total;
+    const size_t K = S.win.closed.size(), blocks = K * (size_t)S.ages_total * nb;
     if (!rows || !hdr || !closed || row_bytes != blocks * (size_t)S.n_probs * sizeof(double) || hdr_bytes != blocks * SAS_BANDS_HDR * sizeof(int64_t) ||
         closed_bytes != K)
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_age_bands_read: size mismatch (n_samples x ages_total x n_probs float64, n_samples x ages_total x 3 int64, n_samples bytes)");
+        return sfail(ctx, RH_ERR_ARG, std::string(who) + ": size mismatch (" + lead + " x n_probs float64, " + lead + " x 3 int64, n_samples bytes)");
     SHIPCHK(ctx, hipMemcpyAsync(rows, S.rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SHIPCHK(ctx, hipMemcpyAsync(hdr, S.hdr, hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
     std::copy(S.win.closed.begin(), S.win.closed.end(), closed);
     if (days_recorded) *days_recorded = S.win.days;
     return rh_sas_sync(ctx);
+}
+
+int rh_sas_age_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed, size_t closed_bytes,
+                          int64_t *days_recorded) {
+    if (int rc = sas_on(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_read")) return rc;
+    if (ctx->age_bands.zones)
+        return sfail(ctx, RH_ERR_STATE, "rh_sas_age_bands_read: the bands by age are configured per zone (read them with rh_sas_age_bands_zonal_read)");
+    return sas_age_bands_read(ctx, "rh_sas_age_bands_read", 1, "n_samples x ages_total", rows, row_bytes, hdr, hdr_bytes, closed, closed_bytes, days_recorded);
+}
+
+int rh_sas_age_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed, size_t closed_bytes,
+                                int64_t *days_recorded) {
+    if (!ctx) return RH_ERR_ARG;
+    if (int rc = sas_on(ctx, ctx->age_bands.on() && ctx->age_bands.zones != 0, "rh_sas_age_bands_zonal_read", "rh_sas_age_bands_configure_zonal")) return rc;
+    return sas_age_bands_read(ctx, "rh_sas_age_bands_zonal_read", (size_t)ctx->age_bands.zones, "n_samples x n_zones x ages_total", rows, row_bytes, hdr,
+                              hdr_bytes, closed, closed_bytes, days_recorded);
 }

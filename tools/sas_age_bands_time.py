@@ -18,7 +18,15 @@ OFF cost (`off`).  `python bench.py --model sas --steps 8 --warmup 2` (nothing c
 tree's ALTERNATING, three runs each; the median of this tree against the parent's own range.  Needs
 ROGER_HIP_PARENT=/path/to/parent/libroger_hip.so; ROGER_HIP_OFF_FIRST=tree lets this tree's library open the alternation.
 
-    python3 tools/sas_age_bands_time.py [run] [alone] [off]        (default: all; `off` is skipped without ROGER_HIP_PARENT)"""
+PER ZONE (`zonal`; not part of the default).  rh_sas_age_bands_configure_zonal, 1 item (TT_q_ss), no weights, every column in a zone: the
+plain configuration, 1, 8, 64 and 1024 equal contiguous zones, and one map with a zone of 90 % of the columns beside 63 small ones --
+stand-alone (R closing days back to back) and behind the day's kernel (14 closing days), every figure a process of its own, the minimum
+of three runs after a warm-up run.  THE ALTERNATIVE, stand-alone: the plain call once per zone with mask = zones == z, the sum over the
+zones of a closing day each (8 and 64 zones and the 90 % map: every zone; 1024 zones: 16 zones, times 64).  ROGER_HIP_NO_SMALL=/path/to/a/library built
+with -DSAS_AGE_SHORT_ZONE=0 (tools/build_variant.py nosmall --unit rh_sas -DSAS_AGE_SHORT_ZONE=0) adds the 1024 zones with every zone
+through the six passes: the price of the second path as a measured pair.
+
+    python3 tools/sas_age_bands_time.py [run] [alone] [off] [zonal]   (default: run alone off; `off` is skipped without ROGER_HIP_PARENT)"""
 import json
 import os
 import statistics
@@ -146,6 +154,105 @@ def alone():
     return lines
 
 
+ZONAL_VARIANTS = [("plain", "the plain configuration (no zones)"), ("z1", "1 zone"), ("z8", "8 equal zones"), ("z64", "64 equal zones"),
+                  ("z1024", "1024 equal zones (97 or 98 columns each: the one-key-per-thread kernel)"),
+                  ("z90", "64 zones, one of 90 % of the columns")]
+
+
+def zone_map(variant, n):
+    """int32 (n,) zone indices of a variant, None for the plain configuration; contiguous zones, every column in one."""
+    import numpy as np
+
+    if variant == "plain":
+        return None
+    c = np.arange(n, dtype=np.int64)
+    if variant == "z90":
+        big = n * 9 // 10
+        return np.where(c < big, 0, 1 + (c - big) * 63 // (n - big)).astype(np.int32)
+    return (c * int(variant[1:]) // n).astype(np.int32)
+
+
+def zonal_child(mode, variant):
+    """ms per closing day of one variant: `alone` (record back to back), `run` (behind the day's kernel; `none`: nothing configured) or
+    `per_zone` (the plain call once per zone, summed); the minimum of three runs after a warm-up run."""
+    import numpy as np
+
+    from roger_amd import sas as rsas
+    from roger_amd._native import SasContext
+
+    n, ages = RUN_N, RUN_AGES
+    zones = None if variant == "none" else zone_map(variant, n)
+    if mode == "run":
+        daily = rsas.synthetic_daily_inputs(n, RUN_DAYS, seed=42)
+        ctx = rsas.create_sas(n, ages, RUN_SUBSTEPS, 90.0, 260.0, daily=daily, keep_distributions=True)
+        windows = (np.arange(RUN_DAYS),) * 2
+        best = []
+        for k in range(4):
+            if variant != "none":
+                ctx.age_bands_configure(ITEMS[:1], PROBS, windows, zones=zones)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ctx.run_days(0, RUN_DAYS)
+            ctx.sync()
+            best.append((time.perf_counter() - t0) / RUN_DAYS * 1e3)
+        if variant != "none":
+            assert ctx.age_bands_read()[2].all()
+        ctx.close()
+        print(json.dumps(min(best[1:])))
+        return
+    ctx = SasContext(n, ages, keep_distributions=True)
+    ctx.upload(ITEMS[0], np.random.default_rng(7).random(ctx.shape(ITEMS[0])))
+    windows = (np.arange(R * 4),) * 2
+
+    def closing_day(**kw):
+        ctx.age_bands_configure(ITEMS[:1], PROBS, windows, **kw)
+        ms = []
+        for k in range(4):
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(R):
+                ctx.age_bands_record(0)
+            ctx.sync()
+            ms.append((time.perf_counter() - t0) / R * 1e3)
+        assert ctx.age_bands_read()[2].all()
+        return min(ms[1:])
+
+    if mode == "alone":
+        out = closing_day(zones=zones)
+    else:   # per_zone: the plain call under the mask of every zone (1024 zones: 16 of them, scaled)
+        nz = int(zones.max()) + 1
+        sample = range(nz) if nz <= 64 else range(0, nz, nz // 16)
+        out = sum(closing_day(mask=zones == z) for z in sample) * (nz / len(sample))
+    ctx.close()
+    print(json.dumps(out))
+
+
+def zonal_cost():
+    def child(mode, variant, lib=None):
+        env = dict(os.environ, **({"ROGER_HIP_LIB": lib} if lib else {}))
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--zonal-child", mode, variant], check=True, capture_output=True, text=True,
+                             timeout=280, env=env).stdout
+        return float(json.loads(out.strip().splitlines()[-1]))
+
+    lines = [f"    per zone: {RUN_N} columns x {RUN_AGES} ages, 1 item (1001 age classes), 3 probabilities, no weights, ms per closing day "
+             "(minimum of 3 runs, a process each)"]
+    none = child("run", "none")
+    lines.append(f"    behind the day's kernel, nothing configured: {none:.4f} ms per day")
+    for v, text in ZONAL_VARIANTS:
+        alone, run = child("alone", v), child("run", v)
+        lines.append(f"    {text}: stand-alone {alone:.4f}; behind the day's kernel {run:.4f} ({run - none:+.4f} against nothing configured)")
+    for v in ("z8", "z64", "z90", "z1024"):
+        lines.append(f"    the alternative, the plain call once per zone, {'64 zones with one of 90 % of the columns' if v == 'z90' else v[1:] + ' zones'}, stand-alone, summed"
+                     + (" (16 zones x 64)" if v == "z1024" else "") + f": {child('per_zone', v):.4f}")
+    lib = os.environ.get("ROGER_HIP_NO_SMALL")
+    if lib:
+        lines.append(f"    1024 equal zones with every zone through the six passes (a build with SAS_AGE_SHORT_ZONE=0): stand-alone {child('alone', 'z1024', lib):.4f}; "
+                     f"behind the day's kernel {child('run', 'z1024', lib):.4f}")
+    else:
+        lines.append("    ROGER_HIP_NO_SMALL is not set: the 1024 zones through the six passes were not measured")
+    return lines
+
+
 def off_cost():
     parent = os.environ.get("ROGER_HIP_PARENT")
     if not parent:
@@ -167,6 +274,9 @@ if __name__ == "__main__":
     if sys.argv[1:2] == ["--child"]:
         run_child(sys.argv[2])
         sys.exit(0)
+    if sys.argv[1:2] == ["--zonal-child"]:
+        zonal_child(sys.argv[2], sys.argv[3])
+        sys.exit(0)
     what = sys.argv[1:] or ["run", "alone", "off"]
     print("transport bands by age (rh_sas_age_bands_*), measured once on one MI355X", flush=True)
     if "run" in what:
@@ -175,3 +285,5 @@ if __name__ == "__main__":
         print("\n".join(alone()), flush=True)
     if "off" in what:
         print("\n".join(off_cost()), flush=True)
+    if "zonal" in what:
+        print("\n".join(zonal_cost()), flush=True)
