@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define RH_ABI_VERSION 24  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore; 19: rh_bands_configure_weighted / rh_bands_weight_sums; 20: rh_bands_observations / rh_bands_obs_read; 21: rh_sas_bands_* (roger_hip_sas.h); 22: rh_sas_bands_configure_zonal / rh_sas_bands_zonal_read (roger_hip_sas.h); 23: rh_sas_age_bands_* (roger_hip_sas.h); 24: rh_sas_age_bands_configure_zonal / rh_sas_age_bands_zonal_read (roger_hip_sas.h) */
+#define RH_ABI_VERSION 25  /* 2: rh_config gained enable_routing_1D + dy, rh_sas_config.solver (round 2); 3: rh_comm_info (round 3); 4: rh_svat_step_scalars (round 4); 5: rh_comm_set_grid; 6: rh_points_configure / _count / _read; 7: rh_sas_points_* (roger_hip_sas.h); 8: rh_totals_configure / _count / _read; 9: rh_sas_totals_* (roger_hip_sas.h); 10: rh_zonal_configure / _count / _read; 11: rh_sas_zonal_* (roger_hip_sas.h); 12: rh_scores_configure / _read; 13: rh_sas_scores_configure / _record / _read (roger_hip_sas.h); 14: rh_events_configure / _headers / _download / _set_drained / _lost; 15: rh_durations_configure / _read; 16: rh_bands_configure / _count / _read; 17: rh_bands_configure_zonal / rh_bands_zonal_read; 18: rh_scores_restore, rh_durations_restore, rh_events_state / _restore, rh_bands_state / _restore; 19: rh_bands_configure_weighted / rh_bands_weight_sums; 20: rh_bands_observations / rh_bands_obs_read; 21: rh_sas_bands_* (roger_hip_sas.h); 22: rh_sas_bands_configure_zonal / rh_sas_bands_zonal_read (roger_hip_sas.h); 23: rh_sas_age_bands_* (roger_hip_sas.h); 24: rh_sas_age_bands_configure_zonal / rh_sas_age_bands_zonal_read (roger_hip_sas.h); 25: rh_sas_age_window_bands_* (roger_hip_sas.h) */
 #define RH_SLOTS_PER_DAY 144 /* roger/variables.py:109 "timesteps_day": 6 * 24 */
 
 typedef enum rh_status {

@@ -431,8 +431,8 @@ int rh_sas_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int
  * m, n_nan and W are per age class.
  *   items    [n_items], at most RH_SAS_AGE_BANDS_MAX_ITEMS, each (value, weight, kind): value a per-cell float64 array of width ages or
  *            ages + 1 this context holds (always: sa_rz, sa_ss, msa_*; with keep_distributions: tt_*, mtt_*, TT_*, sa_s, msa_s); weight -1
- *            and kind RH_SAS_SCORES_LAST.  The kind is part of the ABI so that window means can follow without changing it; BULK and MEAN
- *            are refused today with a message that says so
+ *            and kind RH_SAS_SCORES_LAST.  These calls record the band of a SNAPSHOT and stay LAST-only: BULK and MEAN are refused with a
+ *            message that says so; the window means of the same arrays are an observer of their own, rh_sas_age_window_bands_* below
  *   probs, mask, weights, first_day, last_day, n_samples   as rh_sas_bands_configure takes them; the count of recorded days is this
  *            recorder's own and starts at 0 at configure
  * After rh_sas_age_bands_configure, rh_sas_step and every day of rh_sas_run_days that closes an open window enqueue, behind the bands'
@@ -498,6 +498,50 @@ int rh_sas_age_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *
                                      const int64_t *first_day, const int64_t *last_day, int64_t n_samples);
 int rh_sas_age_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed,
                                 size_t closed_bytes, int64_t *days_recorded);
+
+/* ---- window means of the bands by age: the band of a BULK SAMPLE's age-resolved value, plain or per zone --------------------------------------
+ * A bottle is a bulk sample over its window, and its travel time distribution is the flux-weighted mean sum_d q_ss(d) tt_q_ss(T, d) /
+ * sum_d q_ss(d) over the window's days.  The bands by age above record the snapshot of the closing day; these record the band of that mean
+ * (or of the plain mean over the days), for every age class, without downloading the (n_cells, ages) array on any day (kernels, the rule
+ * and the bytes moved: roger_amd/csrc/rh_sas_age_bands.h; the numpy twin is tests/sas_age_window_bands_reference.py).
+ * The promise, which is the whole specification: block (item j, [zone z,] age class a) of window k is bit for bit what rh_sas_bands_configure
+ * records for the width-1 values A_j[:, a] with the same item weight and kind, under the same mask, weights, probabilities and windows; with
+ * zones, mask = (zone == z) & mask.  So per participating cell, age class and recorded day of an open window: wd is the cell's value in row
+ * `day` of the daily weight (BULK) or 1.0 (MEAN); the element is eligible iff wd > 0 && v == v; then num = num + fl(v * wd), den = den + wd;
+ * both restart from +0.0 on the window's first day; on the closing day s = den > 0 ? num / den : NaN, then s + 0.0; a NaN s is counted in
+ * that block's n_nan.  den is per ELEMENT: a NaN in one age class on one day does not touch its neighbours.
+ *   items    [n_items], at most RH_SAS_AGE_BANDS_MAX_ITEMS, each (value, weight, kind): value as rh_sas_age_bands_configure takes it; kind
+ *            RH_SAS_SCORES_BULK with a daily flux input as weight, or RH_SAS_SCORES_MEAN with weight -1.  LAST is refused: it belongs to
+ *            rh_sas_age_bands_configure
+ *   zone, n_zones   NULL and 0: the plain form; else as rh_sas_age_bands_configure_zonal takes them
+ *   probs, mask, weights, first_day, last_day, n_samples   as rh_sas_age_bands_configure takes them; the count of recorded days is this
+ *            observer's own and starts at 0 at configure
+ * After the call, rh_sas_step and every day of rh_sas_run_days enqueue, behind the bands by age, on every day of an open window one launch
+ * per item that updates the accumulators; on the closing day one launch per item that does the day's update in registers and writes the key
+ * plane, and the selection launches of the bands by age.  A day outside every window enqueues nothing; rh_sas_stages never records; a context
+ * without this observer enqueues exactly what it enqueued before these entry points existed.  Both observers by age may be configured at once:
+ * each has its own key plane, participating set, clock and result.
+ * Result, no ring: rows [n_samples][sum_j W_j][n_probs] and hdr [n_samples][sum_j W_j]{m, n_nan, W}, as rh_sas_age_bands_read returns them;
+ * with zones rows [n_samples][sum_j W_j x n_zones][n_probs], item j's block (n_zones, W_j, n_probs), as rh_sas_age_bands_zonal_read returns
+ * them.  ONE read serves both forms.
+ * Device memory: the key plane of the bands by age, and 16 bytes per participating cell and age class of every item (num and den, float64),
+ * zero at configure.  They are not part of a restart file.
+ * n_items == 0 releases.  Everything is checked, and the new buffers are allocated, before the running configuration is released.  The
+ * refusals are those of rh_sas_age_bands_configure and _zonal, word for word behind the function's name -- the array checks, an item given
+ * twice, n_samples and the 2 GiB bound of the rows, the windows, no participating cell, the bound of a weight plane (per zone with zones),
+ * zone indices and n_zones -- and for the item's weight those of rh_sas_bands_configure (not a daily flux input; BULK without a weight;
+ * MEAN with one).
+ *   rh_sas_age_window_bands_record     records "now" as the next day of the count, with `day` (>= 0) the row of the daily weights
+ *   rh_sas_age_window_bands_row_elems  sum_j W_j
+ *   rh_sas_age_window_bands_read       rows, hdr, closed with their sizes in bytes, days_recorded (may be NULL); synchronises
+ * All three: RH_ERR_STATE before rh_sas_age_window_bands_configure (or after it released everything). */
+int rh_sas_age_window_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                                      const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights,
+                                      const int64_t *first_day, const int64_t *last_day, int64_t n_samples);
+int rh_sas_age_window_bands_record(rh_sas_ctx *ctx, int64_t day);
+int rh_sas_age_window_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total);
+int rh_sas_age_window_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed,
+                                 size_t closed_bytes, int64_t *days_recorded);
 
 /* HIP-event timing of the step kernel (same protocol as rh_enable_timing / rh_timing_summary). */
 int rh_sas_enable_timing(rh_sas_ctx *ctx, int on);

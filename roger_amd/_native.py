@@ -18,7 +18,7 @@ INCLUDE = os.path.join(os.path.dirname(PKG), "include")   # where roger_amd/buil
 
 
 # -- what this binding was written for: the version and the structures are stated by hand, everything else is read from the headers --
-ABI_VERSION = 24  # include/roger_hip.h: RH_ABI_VERSION
+ABI_VERSION = 25  # include/roger_hip.h: RH_ABI_VERSION
 
 
 class RhConfig(C.Structure):
@@ -1006,6 +1006,7 @@ class SasContext:
         self._bands_shape = (0, 0, 0)        # (windows, items, probs); with zones (windows, items, zones, probs)
         self._age_bands_items, self._age_bands_shape = [], (0, 0)   # [(name, width)], (windows, probs)
         self._age_bands_zones = 0                                   # 0: the plain configuration
+        self._age_window_items, self._age_window_shape, self._age_window_zones = [], (0, 0), 0   # the same of age_window_bands_configure
 
     def _check(self, rc, what):
         if rc != 0:
@@ -1355,16 +1356,7 @@ class SasContext:
         zone axis in front of the age axis (rh_sas_age_bands_configure_zonal).  With weights the bound of 65536 participating cells
         holds per zone, not in total."""
         items, flat = self._window_items([(it, None, "last") if isinstance(it, str) else it for it in items])
-        pr = first = last = mk = wt = zn = None
-        nz = 0
-        if items:
-            pr, first, last, mk, wt = self._bands_arguments("age_bands_configure", probs, windows, mask, weights, zones)
-            if zones is not None:
-                zn = np.asarray(zones).reshape(-1)
-                if zn.dtype.kind not in "iu":
-                    raise ValueError(f"age_bands_configure: zones of dtype {zn.dtype} (integers: -1 or 0 ... n_zones - 1)")
-                nz = int(n_zones) if n_zones is not None else int(zn.max()) + 1 if zn.size else 0
-                zn = _cell_map("age_bands_configure", "zones", zn, self.n, _CELLS, lowest=-2)
+        pr, first, last, mk, wt, zn, nz = self._age_arguments("age_bands_configure", items, probs, windows, mask, weights, zones, n_zones)
         nk, npr = 0 if first is None else first.size, 0 if pr is None else pr.size
         if zn is not None:
             self._check(self._lib.rh_sas_age_bands_configure_zonal(self._h, _ptr(flat), len(items), _ptr(pr), npr, _ptr(zn), nz, _ptr(mk), _ptr(wt),
@@ -1377,6 +1369,38 @@ class SasContext:
         self._age_bands_shape = (nk, npr)
         self._age_bands_zones = 0 if zn is None else nz
 
+    def _age_arguments(self, method, items, probs, windows, mask, weights, zones, n_zones):
+        """_bands_arguments and (the zone map int32 (n,) or None, n_zones) of what both observers by age take; without items all None and 0."""
+        if not items:
+            return None, None, None, None, None, None, 0
+        pr, first, last, mk, wt = self._bands_arguments(method, probs, windows, mask, weights, zones)
+        zn, nz = None, 0
+        if zones is not None:
+            zn = np.asarray(zones).reshape(-1)
+            if zn.dtype.kind not in "iu":
+                raise ValueError(f"{method}: zones of dtype {zn.dtype} (integers: -1 or 0 ... n_zones - 1)")
+            nz = int(n_zones) if n_zones is not None else int(zn.max()) + 1 if zn.size else 0
+            zn = _cell_map(method, "zones", zn, self.n, _CELLS, lowest=-2)
+        return pr, first, last, mk, wt, zn, nz
+
+    def _age_read(self, prefix, name, layout, shape, nz):
+        """What age_bands_read and age_window_bands_read return: the row count by `prefix`_row_elems, the read by the function `name`."""
+        total = C.c_int64()
+        self._check(getattr(self._lib, prefix + "_row_elems")(self._h, C.byref(total)), prefix + "_row_elems")
+        nk, npr = shape
+        rows = np.empty((nk, total.value * max(nz, 1), npr), dtype=np.float64)
+        hdr = np.empty((nk, total.value * max(nz, 1), 3), dtype=np.int64)
+        closed = np.empty(nk, dtype=np.uint8)
+        days = C.c_int64()
+        self._check(getattr(self._lib, name)(self._h, _ptr(rows), rows.nbytes, _ptr(hdr), hdr.nbytes, _ptr(closed), closed.nbytes, C.byref(days)), name)
+        out_rows, out_hdr, off = {}, {}, 0
+        for v, w in layout:
+            wz = w * max(nz, 1)
+            lead = (nk, nz, w) if nz else (nk, w)
+            out_rows[v], out_hdr[v] = rows[:, off:off + wz].reshape(*lead, npr).copy(), hdr[:, off:off + wz].reshape(*lead, 3).copy()
+            off += wz
+        return out_rows, out_hdr, closed, days.value
+
     def age_bands_record(self, day=0):
         """Record now as the next day of the count (a driver that steps by stage).  `day` (>= 0) is the row of the daily inputs, as for
         bands_record; it is checked and otherwise ignored today, because every item is "last" and reads no daily input."""
@@ -1386,20 +1410,34 @@ class SasContext:
         """(rows {name: float64 (K, W, n_probs)}, NaN until the window closed; hdr {name: int64 (K, W, 3)}: m, n_nan, W per age class;
         closed uint8 (K,); days recorded since age_bands_configure), W the item's width (ages or ages + 1).  Configured with zones: rows
         {name: (K, n_zones, W, n_probs)}, hdr {name: (K, n_zones, W, 3)}.  Synchronises."""
-        total = C.c_int64()
-        self._check(self._lib.rh_sas_age_bands_row_elems(self._h, C.byref(total)), "rh_sas_age_bands_row_elems")
-        nk, npr = self._age_bands_shape
         nz = self._age_bands_zones
-        rows = np.empty((nk, total.value * max(nz, 1), npr), dtype=np.float64)
-        hdr = np.empty((nk, total.value * max(nz, 1), 3), dtype=np.int64)
-        closed = np.empty(nk, dtype=np.uint8)
-        days = C.c_int64()
-        name = "rh_sas_age_bands_zonal_read" if nz else "rh_sas_age_bands_read"
-        self._check(getattr(self._lib, name)(self._h, _ptr(rows), rows.nbytes, _ptr(hdr), hdr.nbytes, _ptr(closed), closed.nbytes, C.byref(days)), name)
-        out_rows, out_hdr, off = {}, {}, 0
-        for v, w in self._age_bands_items:
-            wz = w * max(nz, 1)
-            lead = (nk, nz, w) if nz else (nk, w)
-            out_rows[v], out_hdr[v] = rows[:, off:off + wz].reshape(*lead, npr).copy(), hdr[:, off:off + wz].reshape(*lead, 3).copy()
-            off += wz
-        return out_rows, out_hdr, closed, days.value
+        return self._age_read("rh_sas_age_bands", "rh_sas_age_bands_zonal_read" if nz else "rh_sas_age_bands_read", self._age_bands_items,
+                              self._age_bands_shape, nz)
+
+    # -- window means of the bands by age: the band of a bulk sample's age-resolved value (rh_sas_age_window_bands_*) --------------
+    def age_window_bands_configure(self, items, probs=(), windows=None, mask=None, weights=None, zones=None, n_zones=None):
+        """The exact quantiles `probs` ACROSS the cells for every age class of the WINDOW MEANS of the age-resolved arrays `items`:
+        ("tt_q_ss", "q_ss", "bulk") -- the mean over the window's days weighted by the daily flux, a bottle's travel time distribution --
+        or ("sa_s", None, "mean").  Everything else as age_bands_configure takes it, `zones` included; "last" belongs there.  Block (item,
+        [zone z,] age class a) is bit for bit what bands_configure records for the width-1 values A[:, a] with the same weight and kind.
+        An observer of its own beside age_bands_*: 16 bytes per participating cell and age class stay on the device, and every day of
+        an open window launches.  No items: release everything and stop."""
+        items, flat = self._window_items(items)
+        pr, first, last, mk, wt, zn, nz = self._age_arguments("age_window_bands_configure", items, probs, windows, mask, weights, zones, n_zones)
+        nk, npr = 0 if first is None else first.size, 0 if pr is None else pr.size
+        self._check(self._lib.rh_sas_age_window_bands_configure(self._h, _ptr(flat), len(items), _ptr(pr), npr, _ptr(zn), nz, _ptr(mk), _ptr(wt),
+                                                                _ptr(first), _ptr(last), nk), "rh_sas_age_window_bands_configure")
+        # (a refused configuration leaves the previous one)
+        self._age_window_items = [(v, int(np.prod(self.shape(v)[1:], dtype=np.int64))) for v, _, _ in items]
+        self._age_window_shape = (nk, npr)
+        self._age_window_zones = 0 if zn is None else nz
+
+    def age_window_bands_record(self, day=0):
+        """Record now as the next day of the count, `day` the row of the daily weights (a driver that steps by stage)."""
+        self._check(self._lib.rh_sas_age_window_bands_record(self._h, int(day)), "rh_sas_age_window_bands_record")
+
+    def age_window_bands_read(self):
+        """(rows {name: float64 (K, [n_zones,] W, n_probs)}, hdr {name: int64 (K, [n_zones,] W, 3)}, closed uint8 (K,), days recorded since
+        age_window_bands_configure), as age_bands_read returns them.  Synchronises."""
+        return self._age_read("rh_sas_age_window_bands", "rh_sas_age_window_bands_read", self._age_window_items, self._age_window_shape,
+                              self._age_window_zones)

@@ -40,6 +40,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <type_traits>
 
 __global__ void k_selftest_div(const double *a, const double *d, double *out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -317,7 +318,8 @@ int rh_sas_stages(rh_sas_ctx *ctx, int64_t day, int stages) {
 
 #include "rh_sas_observers.h"
 
-// a whole day and, with points, totals, zonal totals, scores, bands or bands by age configured, their rows, the day's scoring and its band work
+// a whole day and, with points, totals, zonal totals, scores, bands, bands by age or their window means configured, their rows, the day's
+// scoring and its band work
 static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     int rc = rh_sas_stages(ctx, day, RH_SAS_ALL);
     if (!rc && ctx->points.on()) rc = sas_points_enqueue(ctx, day);
@@ -326,6 +328,7 @@ static int sas_day(rh_sas_ctx *ctx, int64_t day) {
     if (!rc && ctx->scores.on()) rc = sas_scores_enqueue(ctx, day);
     if (!rc && ctx->bands.on()) rc = sas_bands_enqueue(ctx, day);
     if (!rc && ctx->age_bands.on()) rc = sas_age_bands_enqueue(ctx);
+    if (!rc && ctx->age_window_bands.on()) rc = sas_age_window_bands_enqueue(ctx, day);
     return rc;
 }
 

@@ -1,7 +1,7 @@
 // rh_sas_age_bands.h -- transport bands by age (rh_sas_age_bands_*, include/roger_hip_sas.h): the exact quantiles of rh_sas_bands.h ACROSS
 // the columns for every age class of an age-resolved array -- the 5 - 50 - 95 % band of the travel time distribution TT_q_ss(T) or of the
 // storage by age sa_s(T) over the behavioural sets of a SAS parameter study -- without downloading the (n, ages) array.  rh_sas.hip includes
-// it for the constants and rh_sas_age_launch; rh_sas_age.hip defines RH_SAS_AGE_UNIT and holds the kernels.  The numpy twin is
+// it for the constants and the rh_sas_age_launch_* functions; rh_sas_age.hip defines RH_SAS_AGE_UNIT and holds the kernels.  The numpy twin is
 // tests/sas_age_bands_reference.py.
 //
 // THE RULE (one promise, the whole specification).  Block (item j, age class a) of window k -- rows [k][j][a][probability], hdr
@@ -13,9 +13,9 @@
 //   T = clamp((int64)ceil(p * (double)W), 1, W), and the result is the smallest s with sum_{s_i <= s} w_i >= T;
 //   m == 0 gives NaN rows and W = 0.
 // m, n_nan and W are per age class: NaN patterns differ along the age axis.
-// Clock and windows are SasWindows, as for the scores and the bands, with an own count of recorded days from 0 at configure.  The ABI takes
-// an item kind so that window means can follow; only RH_SAS_SCORES_LAST with weight -1 is accepted today, and work is enqueued on the
-// closing day of an open window only.  (BULK / MEAN need an (n, W) accumulator and a per-element den per item.)
+// Clock and windows are SasWindows, as for the scores and the bands, with an own count of recorded days from 0 at configure.  These calls
+// record a SNAPSHOT and stay LAST-only: only RH_SAS_SCORES_LAST with weight -1 is accepted, and work is enqueued on the closing day of an
+// open window only.  The window means (BULK / MEAN) are an observer of their own, rh_sas_age_window_bands_*: WINDOW MEANS below.
 //
 // THE LAUNCHES.  At configure the host builds part_cols [n_part], the participating columns in ascending order, and the compacted weights
 // wts_c [n_part] (wts_c[i] = weights[part_cols[i]]), and uploads both once.  On a closing day, per item, one after another on the
@@ -53,6 +53,26 @@
 //                      pass, 3376 B of LDS; the same promise and the same bits as the six passes.
 // An empty zone is in neither list: its blocks keep the NaN rows and zero headers configure wrote.  THE BOUND is per zone: with a weight
 // plane a ZONE of more than 65536 participating cells is refused; the total may be larger, which the plain configuration refuses.
+//
+// WINDOW MEANS (rh_sas_age_window_bands_*; the numpy twin is tests/sas_age_window_bands_reference.py).  One more promise and nothing
+// restated: block (item j, [zone z,] age class a) of window k is bit for bit what THE RULE of rh_sas_bands.h records for the width-1 values
+// A_j[:, a] with the same item weight and kind -- BULK by a daily flux input, or MEAN -- under the same mask, weights, probabilities and
+// windows; with zones, mask = (zone == z) & mask.  Per participating column, age class and recorded day of an open window: wd is the
+// column's value in row `day` of the daily weight (BULK) or 1.0 (MEAN); eligible iff wd > 0 && v == v; num = num + fl(v * wd), den = den + wd,
+// one IEEE operation each; both restart from +0.0 on the window's first day, eligible or not; on the closing day
+// s = den > 0 ? num / den : NaN, then s + 0.0; a NaN s is counted in that block's n_nan.  den is per ELEMENT: a NaN in one age class on one
+// day must not touch its neighbours.  The observer has its own SasWindows (accumulate = true), key plane, participating set and result: it
+// may be configured beside the snapshot observer.  Per item acc = num [n_part][W_j], den [n_part][W_j] in participating order (zone order
+// under zones), the age axis contiguous as in the source rows, indexed in size_t (n_part x W passes 2^31 at 10^7 x 1001), zero at configure.
+//   k_sas_age_acc<BULK>           every day of an open window that does not close it: grid (ceil(n_part / 4)), 256 threads, a wavefront per
+//                      column, lanes along the age axis: source, num and den are unit stride and the column's wd is read once.  An
+//                      eligible element moves 8 B source + 16 B read + 16 B written; a first day reads no accumulator; wd <= 0 touches
+//                      nothing, except that a first day stores the zeros without loading the source; an ineligible element of another day
+//                      stores nothing.
+//   k_sas_age_keys_window<BULK>   the closing day: k_sas_age_keys' transpose with the same tile, padding and guards, whose load side does
+//                      the day's update in registers and forms s and the key; no accumulator is stored, the next window restarts.  24 B
+//                      read (8 B on a one-day window) and 8 B written per element.
+// Behind it the selection launches above, as they are (rh_sas_age_launch_select).  Stream order orders everything.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,14 +81,6 @@
 #define SAS_AGE_TILE 64                                                                     // columns and age classes of a transpose tile
 #define SAS_AGE_BANDS_MAX_WEIGHTED ((long long)RH_SELECT_W_MAX_TILES * RH_SELECT_BLOCK)   // participating cells under a weight plane
 static_assert(RH_SELECT_BLOCK % SAS_AGE_TILE == 0, "a wavefront of the transpose is one row of a tile");
-
-// One item's two launches on `stream`: the transpose into keys [W][n_part], then the selection of the W age classes into the item's blocks
-// rows [W][np] and hdr [W][3] of the window; wts_c null: every participating column counts 1.  Defined in rh_sas_age.hip, the translation
-// unit that holds the kernels below and is linked behind every other unit (LINK_LAST of roger_amd/build.py).  Why: with these kernels
-// inside rh_sas.hip, `bench.py --model sas` with nothing configured lay above the parent's range in two sessions; in a unit of their own
-// it lay within it in both alternation orders (DESIGN.md 3.9.3 gives the figures and what the control runs do and do not show).
-void rh_sas_age_launch(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
-                       const unsigned short *wts_c, const double *probs, int np, double *rows, long long *hdr);
 
 // Per zone: what the two kernels of a zonal configuration are told.  zone_off [n_zones + 1] into part_cols / wts_c / a row of the key plane,
 // which are in zone order; the zones of 1 ... SAS_AGE_SHORT_ZONE participating cells and the longer ones (an empty zone is in neither list:
@@ -82,11 +94,24 @@ struct SasAgeZones {
 #define SAS_AGE_SHORT_ZONE RH_SELECT_BLOCK   // by construction, not tuned: one key per thread of k_sas_age_bands_small
 #endif
 static_assert(SAS_AGE_SHORT_ZONE <= RH_SELECT_BLOCK, "k_sas_age_bands_small holds one key per thread");
-// One item's launches of a zonal configuration on `stream`: the transpose, unchanged, with part_cols in zone order; k_sas_age_bands_zonal
-// where there are long zones, k_sas_age_bands_small where there are short ones; rows [n_zones][W][np] and hdr [n_zones][W][3] are the item's
-// blocks of the window.
-void rh_sas_age_launch_zonal(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
-                             const unsigned short *wts_c, const SasAgeZones &Z, const double *probs, int np, double *rows, long long *hdr);
+
+// The launches of one item on `stream`, each stated once; both observers (the snapshot's sas_age_bands_enqueue and the window means'
+// sas_age_window_bands_enqueue of rh_sas_observers.h) fill a key plane and then call the ONE selection.  Defined in rh_sas_age.hip, the
+// translation unit that holds the kernels below and is linked behind every other unit (LINK_LAST of roger_amd/build.py).  Why: with these
+// kernels inside rh_sas.hip, `bench.py --model sas` with nothing configured lay above the parent's range in two sessions; in a unit of
+// their own it lay within it in both alternation orders (DESIGN.md 3.9.3 gives the figures and what the control runs do and do not show).
+//   rh_sas_age_launch_keys     the snapshot's transpose of A into keys [W][n_part] (part_cols in zone order under zones)
+//   rh_sas_age_launch_select   the selection of the W age classes of a key plane into the item's blocks of the window: Z null, rows [W][np]
+//                              and hdr [W][3] by k_sas_age_bands; else rows [n_zones][W][np] and hdr [n_zones][W][3] by
+//                              k_sas_age_bands_zonal where there are long zones and k_sas_age_bands_small where there are short ones.
+//                              wts_c null: every participating column counts 1
+//   rh_sas_age_launch_window   a day of an open window of the window means (below): k_sas_age_acc, or on the closing day
+//                              k_sas_age_keys_window into keys; wrow the day's row of the daily weight (BULK) or null (MEAN)
+void rh_sas_age_launch_keys(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys);
+void rh_sas_age_launch_select(hipStream_t stream, int W, long long n_part, const unsigned long long *keys, const unsigned short *wts_c, const SasAgeZones *Z,
+                              const double *probs, int np, double *rows, long long *hdr);
+void rh_sas_age_launch_window(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, const double *wrow, bool first, bool closes,
+                              double *num, double *den, unsigned long long *keys);
 
 #ifdef RH_SAS_AGE_UNIT
 // keys[a][i] = key(A[part_cols[i]][a] + 0.0) for i < n_part, a < W
@@ -211,39 +236,139 @@ __global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_age_bands_small(const u
     }
 }
 
-static void sas_age_launch_keys(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys) {
-    const dim3 tiles((unsigned)((n_part + SAS_AGE_TILE - 1) / SAS_AGE_TILE), (unsigned)((W + SAS_AGE_TILE - 1) / SAS_AGE_TILE));
-    hipLaunchKernelGGL(k_sas_age_keys, tiles, dim3(RH_SELECT_BLOCK), 0, stream, A, W, part_cols, n_part, keys);
+// ---- window means (rh_sas_age_window_bands_*): num and den per participating column and age class, [n_part][W] each ----
+// One update of an element, the words of k_sas_bands_day: eligible iff wd > 0 && v == v (the caller has tested wd); the product is rounded
+// before it is added (-ffp-contract=off).
+RH_SELECT_DEV bool sas_age_acc_add(double v, double wd, double &num, double &den) {
+    const bool eligible = v == v;
+    if (eligible) {
+        const double t = v * wd;
+        num = num + t;
+        den = den + wd;
+    }
+    return eligible;
 }
 
-void rh_sas_age_launch(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
-                       const unsigned short *wts_c, const double *probs, int np, double *rows, long long *hdr) {
-    sas_age_launch_keys(stream, A, W, part_cols, n_part, keys);
-    if (wts_c)
-        hipLaunchKernelGGL(k_sas_age_bands<true>, dim3((unsigned)W), dim3(RH_SELECT_BLOCK), 0, stream, (const unsigned long long *)keys, wts_c, n_part, probs, np,
-                           rows, hdr);
-    else
-        hipLaunchKernelGGL(k_sas_age_bands<false>, dim3((unsigned)W), dim3(RH_SELECT_BLOCK), 0, stream, (const unsigned long long *)keys, wts_c, n_part, probs, np,
-                           rows, hdr);
+// A day of an open window that does not close it.  A wavefront per participating column i, lanes along the age axis: the source row
+// A[part_cols[i]][...], num[i][...] and den[i][...] are unit stride, and the column's wd is read once.  wd <= 0 (or NaN): nothing is
+// touched, unless the day is the window's first -- then the zeros are stored and the source is not loaded.  A first day reads no accumulator;
+// an element that is not eligible on another day stores nothing.
+template <bool BULK>
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_age_acc(const double *__restrict__ A, int W, const int *__restrict__ part_cols, long long n_part,
+                                                                 const double *__restrict__ wrow, int first, double *__restrict__ num,
+                                                                 double *__restrict__ den) {
+    const long long i = (long long)blockIdx.x * (RH_SELECT_BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= n_part) return;   // (uniform over the wavefront)
+    const int lane = threadIdx.x & 63, col = part_cols[i];
+    const double wd = BULK ? wrow[col] : 1.0;
+    const size_t at = (size_t)i * (size_t)W;
+    double *pn = num + at, *pd = den + at;
+    if (!(wd > 0.0)) {
+        if (first)
+            for (int a = lane; a < W; a += 64) pn[a] = pd[a] = 0.0;
+        return;
+    }
+    const double *src = A + (size_t)col * (size_t)W;
+#pragma unroll 4
+    for (int a = lane; a < W; a += 64) {
+        double n_ = 0.0, d_ = 0.0;
+        if (!first) {
+            n_ = pn[a];
+            d_ = pd[a];
+        }
+        const bool eligible = sas_age_acc_add(src[a], wd, n_, d_);
+        if (first || eligible) {
+            pn[a] = n_;
+            pd[a] = d_;
+        }
+    }
+}
+
+// The closing day: k_sas_age_keys' transpose -- the same tile, padding and guards on both edges -- whose load side does the day's update in
+// registers, forms s = den > 0 ? num / den : NaN, then s + 0.0, and the key.  A row of a tile is a column and a wavefront, so wd is uniform
+// over it.  No accumulator is stored: the next window restarts.
+template <bool BULK>
+__global__ __launch_bounds__(RH_SELECT_BLOCK) void k_sas_age_keys_window(const double *__restrict__ A, int W, const int *__restrict__ part_cols, long long n_part,
+                                                                         const double *__restrict__ wrow, int first, const double *__restrict__ num,
+                                                                         const double *__restrict__ den, unsigned long long *__restrict__ keys) {
+    __shared__ unsigned long long tile[SAS_AGE_TILE][SAS_AGE_TILE + 1];
+    constexpr int ROWS = RH_SELECT_BLOCK / SAS_AGE_TILE;   // rows of a tile per trip
+    const long long i0 = (long long)blockIdx.x * SAS_AGE_TILE;
+    const int a0 = (int)blockIdx.y * SAS_AGE_TILE, lane = threadIdx.x % SAS_AGE_TILE, row = threadIdx.x / SAS_AGE_TILE;
+#pragma unroll
+    for (int t = 0; t < SAS_AGE_TILE / ROWS; ++t) {   // column i0 + r, lanes along the age axis
+        const int r = row + t * ROWS;
+        const long long i = i0 + r;
+        const int a = a0 + lane;
+        if (i < n_part && a < W) {
+            const int col = part_cols[i];
+            const double wd = BULK ? wrow[col] : 1.0;
+            const size_t at = (size_t)i * (size_t)W + (size_t)a;
+            double n_ = 0.0, d_ = 0.0;
+            if (!first) {
+                n_ = num[at];
+                d_ = den[at];
+            }
+            if (wd > 0.0) (void)sas_age_acc_add(A[(size_t)col * (size_t)W + (size_t)a], wd, n_, d_);
+            const double s = (d_ > 0.0 ? n_ / d_ : __builtin_nan("")) + 0.0;
+            tile[r][lane] = s != s ? RH_SELECT_KEY_NAN : bands_key_of(s);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < SAS_AGE_TILE / ROWS; ++t) {   // age class a0 + r, lanes along the columns
+        const int r = row + t * ROWS;
+        const long long i = i0 + lane;
+        const int a = a0 + r;
+        if (a < W && i < n_part) keys[(size_t)a * (size_t)n_part + (size_t)i] = tile[lane][r];
+    }
+}
+
+static dim3 sas_age_tiles(int W, long long n_part) {
+    return dim3((unsigned)((n_part + SAS_AGE_TILE - 1) / SAS_AGE_TILE), (unsigned)((W + SAS_AGE_TILE - 1) / SAS_AGE_TILE));
+}
+
+void rh_sas_age_launch_keys(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys) {
+    hipLaunchKernelGGL(k_sas_age_keys, sas_age_tiles(W, n_part), dim3(RH_SELECT_BLOCK), 0, stream, A, W, part_cols, n_part, keys);
 }
 
 template <bool WEIGHTED>
-static void sas_age_launch_zones(hipStream_t stream, int W, long long n_part, const unsigned long long *keys, const unsigned short *wts_c, const SasAgeZones &Z,
-                                 const double *probs, int np, double *rows, long long *hdr) {
-    if (Z.n_long)
-        hipLaunchKernelGGL(k_sas_age_bands_zonal<WEIGHTED>, dim3((unsigned)W, (unsigned)Z.n_long), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, Z, probs,
+static void sas_age_launch_select(hipStream_t stream, int W, long long n_part, const unsigned long long *keys, const unsigned short *wts_c, const SasAgeZones *Z,
+                                  const double *probs, int np, double *rows, long long *hdr) {
+    if (!Z)
+        hipLaunchKernelGGL(k_sas_age_bands<WEIGHTED>, dim3((unsigned)W), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, probs, np, rows, hdr);
+    if (Z && Z->n_long)
+        hipLaunchKernelGGL(k_sas_age_bands_zonal<WEIGHTED>, dim3((unsigned)W, (unsigned)Z->n_long), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, *Z, probs,
                            np, rows, hdr);
-    if (Z.n_short)
-        hipLaunchKernelGGL(k_sas_age_bands_small<WEIGHTED>, dim3((unsigned)W, (unsigned)Z.n_short), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, Z, probs,
+    if (Z && Z->n_short)
+        hipLaunchKernelGGL(k_sas_age_bands_small<WEIGHTED>, dim3((unsigned)W, (unsigned)Z->n_short), dim3(RH_SELECT_BLOCK), 0, stream, keys, wts_c, n_part, *Z, probs,
                            np, rows, hdr);
 }
 
-void rh_sas_age_launch_zonal(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, unsigned long long *keys,
-                             const unsigned short *wts_c, const SasAgeZones &Z, const double *probs, int np, double *rows, long long *hdr) {
-    sas_age_launch_keys(stream, A, W, part_cols, n_part, keys);
+void rh_sas_age_launch_select(hipStream_t stream, int W, long long n_part, const unsigned long long *keys, const unsigned short *wts_c, const SasAgeZones *Z,
+                              const double *probs, int np, double *rows, long long *hdr) {
     if (wts_c)
-        sas_age_launch_zones<true>(stream, W, n_part, keys, wts_c, Z, probs, np, rows, hdr);
+        sas_age_launch_select<true>(stream, W, n_part, keys, wts_c, Z, probs, np, rows, hdr);
     else
-        sas_age_launch_zones<false>(stream, W, n_part, keys, wts_c, Z, probs, np, rows, hdr);
+        sas_age_launch_select<false>(stream, W, n_part, keys, wts_c, Z, probs, np, rows, hdr);
+}
+
+template <bool BULK>
+static void sas_age_launch_window(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, const double *wrow, bool first, bool closes,
+                                  double *num, double *den, unsigned long long *keys) {
+    if (closes)
+        hipLaunchKernelGGL(k_sas_age_keys_window<BULK>, sas_age_tiles(W, n_part), dim3(RH_SELECT_BLOCK), 0, stream, A, W, part_cols, n_part, wrow, first ? 1 : 0,
+                           (const double *)num, (const double *)den, keys);
+    else
+        hipLaunchKernelGGL(k_sas_age_acc<BULK>, dim3((unsigned)((n_part + RH_SELECT_BLOCK / 64 - 1) / (RH_SELECT_BLOCK / 64))), dim3(RH_SELECT_BLOCK), 0, stream, A, W,
+                           part_cols, n_part, wrow, first ? 1 : 0, num, den);
+}
+
+void rh_sas_age_launch_window(hipStream_t stream, const double *A, int W, const int *part_cols, long long n_part, const double *wrow, bool first, bool closes,
+                              double *num, double *den, unsigned long long *keys) {
+    if (wrow)
+        sas_age_launch_window<true>(stream, A, W, part_cols, n_part, wrow, first, closes, num, den, keys);
+    else
+        sas_age_launch_window<false>(stream, A, W, part_cols, n_part, wrow, first, closes, num, den, keys);
 }
 #endif   // RH_SAS_AGE_UNIT

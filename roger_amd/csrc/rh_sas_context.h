@@ -230,6 +230,21 @@ struct SasAgeBands {
     }
 };
 
+// window means of the bands by age (rh_sas_age_window_bands_configure, rh_sas_age_bands.h): everything the snapshot observer holds -- a key
+// plane, a participating set, a result and a clock, all of its OWN, since both may be configured -- and per item num [n_part][W_j] and
+// den [n_part][W_j] in ONE allocation, zero at configure, the first row of the item's daily weight (BULK; null: MEAN)
+struct SasAgeWindowBands : SasAgeBands {
+    static constexpr const char *configure = "rh_sas_age_window_bands_configure";
+    DevBuf<double> acc;
+    size_t acc_off[RH_SAS_AGE_BANDS_MAX_ITEMS] = {};     // where item j's num starts; its den follows n_part x W_j later
+    const double *wgt[RH_SAS_AGE_BANDS_MAX_ITEMS] = {};
+    hipError_t release() {
+        const hipError_t e = first_error({SasAgeBands::release(), acc.release()});
+        *this = SasAgeWindowBands();
+        return e;
+    }
+};
+
 struct rh_sas_ctx {
     Stream stream;                   // first member: destroyed last, after everything that was enqueued on it has been released
     rh_sas_config cfg = {};
@@ -244,6 +259,7 @@ struct rh_sas_ctx {
     SasScores scores;
     SasBands bands;
     SasAgeBands age_bands;
+    SasAgeWindowBands age_window_bands;
     std::string err;
 };
 static std::string g_sas_create_err;
@@ -361,12 +377,23 @@ static int sas_totals_items(rh_sas_ctx *ctx, const std::string &who, const rh_sa
     return RH_OK;
 }
 
+// The weight of a (value, weight, kind) item whose ids and kind are known ones: a daily flux input, which BULK has and no other kind does.
+// The one statement of it, for the scores, the bands and the window means of the bands by age; `name` is "array <value>".
+static int sas_window_weight(rh_sas_ctx *ctx, const std::string &who, const std::string &name, int w, int kind) {
+    static const char *const KIND[] = {"BULK", "MEAN", "LAST"};
+    if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
+        return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
+    if (kind == RH_SAS_SCORES_BULK && w < 0) return sfail(ctx, RH_ERR_ARG, who + name + " is BULK and has no weight");
+    if (kind != RH_SAS_SCORES_BULK && w >= 0)
+        return sfail(ctx, RH_ERR_ARG, who + name + " is " + KIND[kind] + " and has the weight " + SAS_NAMES[w] + " (only BULK takes one)");
+    return RH_OK;
+}
+
 // What the (value, weight, kind) items of rh_sas_scores_configure and of the two bands calls are: ids and kinds checked, the arrays and
 // weights on the device, and whether any item accumulates over its window.  `who` opens the message of a refusal; `params_are` says what
 // sas_params_* are to the caller ("are not scored"), `one_value` why an age-resolved array is none of its items.
 static int sas_window_items(rh_sas_ctx *ctx, const std::string &who, const rh_sas_scores_item *items, int n_items, const char *params_are,
                             const char *one_value, const double **val, const double **wgt, int *kinds, bool *accumulate) {
-    static const char *const KIND[] = {"BULK", "MEAN", "LAST"};
     for (int j = 0; j < n_items; ++j) {
         const int a = items[j].value, w = items[j].weight, kind = items[j].kind;
         if (a < 0 || a >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown array id " + std::to_string(a));
@@ -381,11 +408,7 @@ static int sas_window_items(rh_sas_ctx *ctx, const std::string &who, const rh_sa
         if (SAS_KIND[a] == K_PARAM) return sfail(ctx, RH_ERR_ARG, who + name + " is a parameter block of the step (sas_params_* " + params_are + ")");
         if (SAS_KIND[a] == K_DAILY) return sfail(ctx, RH_ERR_ARG, who + name + " is a daily input of the step, not a result (daily inputs are weights here)");
         if (SAS_KIND[a] != K_CELL) return sfail(ctx, RH_ERR_ARG, who + name + " is age-resolved (" + one_value + ")");
-        if (w >= 0 && (SAS_KIND[w] != K_DAILY || w == SA_C_in))
-            return sfail(ctx, RH_ERR_ARG, who + "weight " + SAS_NAMES[w] + " is not a daily flux input (inf_mat_rz ... cpr_rz)");
-        if (kind == RH_SAS_SCORES_BULK && w < 0) return sfail(ctx, RH_ERR_ARG, who + name + " is BULK and has no weight");
-        if (kind != RH_SAS_SCORES_BULK && w >= 0)
-            return sfail(ctx, RH_ERR_ARG, who + name + " is " + KIND[kind] + " and has the weight " + SAS_NAMES[w] + " (only BULK takes one)");
+        if (int rc = sas_window_weight(ctx, who, name, w, kind)) return rc;
         if (!ctx->arr[a])
             return sfail(ctx, RH_ERR_STATE, who + name + " is not held by this context (age_statistics / keep_distributions / tracer)");
         val[j] = (const double *)ctx->arr[a].get();

@@ -1,6 +1,7 @@
 // rh_sas_observers.h -- what follows every day of the transport model: the time series at observation columns (rh_sas_points_*), the
 // catchment totals (rh_sas_totals_*), the zonal totals (rh_sas_zonal_*), the scores against observed samples (rh_sas_scores_*) and the
-// transport bands, plain and per zone (rh_sas_bands_*) and by age (rh_sas_age_bands_*).  Each has its launch sequence (sas_*_enqueue, which the day calls), its configure
+// transport bands, plain and per zone (rh_sas_bands_*), by age (rh_sas_age_bands_*) and the window means by age
+// (rh_sas_age_window_bands_*).  Each has its launch sequence (sas_*_enqueue, which the day calls), its configure
 // call and its reads.  Part of the one translation unit rh_sas.hip, behind rh_sas_context.h; the entry points get their C linkage from
 // their declarations in roger_hip_sas.h.
 #pragma once
@@ -638,45 +639,133 @@ int rh_sas_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int
 
 // ---- transport bands by age (include/roger_hip_sas.h; the kernels and the rule: rh_sas_age_bands.h) ----
 // the next day of the count, behind what the stream holds so far: nothing unless it closes an open window; then per item the transpose
-// into the ONE key plane and the selection of every age class, item after item in stream order
+// into the ONE key plane and the selection of every age class (per zone: of the long zones and of the short ones, at most three launches),
+// item after item in stream order
 static int sas_age_bands_enqueue(rh_sas_ctx *ctx) {
     SasAgeBands &S = ctx->age_bands;
     const SasWindows::Tick now = S.win.tick();
     if (!now.launch) return RH_OK;   // (every item is LAST: launch == closes)
     const size_t np = (size_t)S.n_probs, nb = S.zones ? (size_t)S.zones : 1;   // nb: blocks per age class
+    const SasAgeZones Z = S.dev_zones();
     size_t block = (size_t)now.k * (size_t)S.ages_total * nb;
     for (int j = 0; j < S.n_items; ++j) {
         const int W = S.width[j];
-        if (S.zones)   // per zone: the transpose, then the long zones' selection and the short zones', at most three launches
-            rh_sas_age_launch_zonal(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.dev_zones(),
-                                    S.probs.get(), S.n_probs, S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
-        else
-            rh_sas_age_launch(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.probs.get(), S.n_probs,
-                              S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
+        rh_sas_age_launch_keys(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.keys.get());
+        rh_sas_age_launch_select(ctx->stream, W, (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.zones ? &Z : nullptr, S.probs.get(), S.n_probs,
+                                 S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
         block += (size_t)W * nb;
     }
     SHIPCHK(ctx, hipGetLastError());
     return RH_OK;
 }
 
-// rh_sas_age_bands_configure (zone == nullptr, n_zones == 0) and rh_sas_age_bands_configure_zonal, for the function `name`: with zones the
-// result gains the zone axis in front of the age axis, a cell takes part where (zone >= 0) & mask and its weight say so, part_cols and
-// wts_c are in zone order (a stable counting sort, as sas_bands_configure does it) and the bound of a weight plane holds per zone
-static int sas_age_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
-                                   const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const int64_t *first_day,
-                                   const int64_t *last_day, int64_t n_samples) {
+// ... of the window means: on every day of an open window, per item, k_sas_age_acc; on the closing day k_sas_age_keys_window into the
+// observer's own key plane and the selection that the snapshot observer launches, item after item in stream order
+static int sas_age_window_bands_enqueue(rh_sas_ctx *ctx, int64_t day) {
+    SasAgeWindowBands &S = ctx->age_window_bands;
+    const SasWindows::Tick now = S.win.tick();
+    if (!now.launch) return RH_OK;
+    const int64_t day_off = (day % ctx->cfg.forcing_days) * ctx->cfg.n_cells;
+    const size_t np = (size_t)S.n_probs, nb = S.zones ? (size_t)S.zones : 1, npart = (size_t)S.n_part;
+    const SasAgeZones Z = S.dev_zones();
+    size_t block = (size_t)now.k * (size_t)S.ages_total * nb;
+    for (int j = 0; j < S.n_items; ++j) {
+        const int W = S.width[j];
+        double *num = S.acc + S.acc_off[j], *den = num + npart * (size_t)W;
+        rh_sas_age_launch_window(ctx->stream, S.src[j], W, S.part_cols.get(), (long long)S.n_part, S.wgt[j] ? S.wgt[j] + day_off : nullptr, now.first, now.closes,
+                                 num, den, S.keys.get());
+        if (now.closes)
+            rh_sas_age_launch_select(ctx->stream, W, (long long)S.n_part, S.keys.get(), S.wts_c.get(), S.zones ? &Z : nullptr, S.probs.get(), S.n_probs,
+                                     S.rows + block * np, S.hdr + block * SAS_BANDS_HDR);
+        block += (size_t)W * nb;
+    }
+    SHIPCHK(ctx, hipGetLastError());
+    return RH_OK;
+}
+
+// The participating set of both observers by age, on the host: the columns that take part -- (zone >= 0, with zones) & mask & weight > 0 --
+// ascending, per zone in zone order by a stable counting sort (as sas_bands_configure does it); their weights at the same index; where
+// each zone's run starts; the short zones' list, then the long zones'.  Refuses, for the function whose name opens `who`: a zone index out
+// of range, no participating cell, and THE BOUND of a weight plane (per zone when zonal).
+struct SasAgeSet {
+    std::vector<int> part_cols;
+    std::vector<unsigned short> wts_c;   // empty: no weight plane
+    std::vector<long long> zone_off;     // per zone: [n_zones + 1] into both
+    std::vector<int> zone_lists;
+    int n_short = 0, n_long = 0;
+};
+static int sas_age_participants(rh_sas_ctx *ctx, const std::string &who, const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights,
+                                SasAgeSet &P) {
+    const int64_t n = ctx->cfg.n_cells;
+    const bool zonal = n_zones != 0;
+    const auto takes_part = [&](int64_t c) { return (!zonal || zone[c] >= 0) && (!mask || mask[c]) && (!weights || weights[c]); };
+    if (zonal) {   // the zones' sizes, the bound of a weighted zone, then the stable counting sort over the participating columns
+        std::vector<long long> &zone_off = P.zone_off;
+        zone_off.assign((size_t)n_zones + 1, 0);
+        for (int64_t c = 0; c < n; ++c) {
+            if (zone[c] < -1 || zone[c] >= n_zones)
+                return sfail(ctx, RH_ERR_ARG, who + "zone[" + std::to_string(c) + "] = " + std::to_string(zone[c]) + " (-1: outside every zone, else 0 ... " +
+                                                  std::to_string(n_zones - 1) + ")");
+            if (takes_part(c)) ++zone_off[(size_t)zone[c] + 1];
+        }
+        for (int z = 0; z < n_zones && weights; ++z)
+            if (zone_off[(size_t)z + 1] > SAS_AGE_BANDS_MAX_WEIGHTED)
+                return sfail(ctx, RH_ERR_ARG, who + "zone " + std::to_string(z) + " has " + std::to_string(zone_off[(size_t)z + 1]) +
+                                                  " participating cells under a weight plane (at most " + std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) +
+                                                  ": a uint32 LDS bin holds the weights of a zone's age class; without weights any size is exact)");
+        for (int z = 0; z < n_zones; ++z)   // (short: 1 ... SAS_AGE_SHORT_ZONE cells; an empty zone is in neither list)
+            if (zone_off[(size_t)z + 1] > 0 && zone_off[(size_t)z + 1] <= SAS_AGE_SHORT_ZONE) P.zone_lists.push_back(z);
+        P.n_short = (int)P.zone_lists.size();
+        for (int z = 0; z < n_zones; ++z)
+            if (zone_off[(size_t)z + 1] > SAS_AGE_SHORT_ZONE) P.zone_lists.push_back(z);
+        P.n_long = (int)P.zone_lists.size() - P.n_short;
+        for (int z = 0; z < n_zones; ++z) zone_off[(size_t)z + 1] += zone_off[(size_t)z];
+        P.part_cols.resize((size_t)zone_off[(size_t)n_zones]);
+        if (weights) P.wts_c.resize(P.part_cols.size());
+        std::vector<long long> at(zone_off.begin(), zone_off.end() - 1);
+        for (int64_t c = 0; c < n; ++c)
+            if (takes_part(c)) {
+                const size_t i = (size_t)at[(size_t)zone[c]]++;
+                P.part_cols[i] = (int)c;
+                if (weights) P.wts_c[i] = weights[c];
+            }
+    } else {
+        for (int64_t c = 0; c < n; ++c)
+            if (takes_part(c)) {
+                P.part_cols.push_back((int)c);
+                if (weights) P.wts_c.push_back(weights[c]);
+            }
+    }
+    const int64_t n_part = (int64_t)P.part_cols.size();
+    if (!n_part) return sfail(ctx, RH_ERR_ARG, who + "no cell takes part (0 of " + std::to_string(n) + " cells have mask != 0 and a weight > 0)");
+    if (!zonal && weights && n_part > SAS_AGE_BANDS_MAX_WEIGHTED)
+        return sfail(ctx, RH_ERR_ARG, who + std::to_string(n_part) + " participating cells under a weight plane (at most " +
+                                          std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) + ": a uint32 LDS bin holds an age class's weights; without weights any size is exact)");
+    return RH_OK;
+}
+
+// The configure calls of the observer `obs` by age -- the snapshot's two and the window means' one -- for the function `name`; zone == nullptr,
+// n_zones == 0: the plain form.  With zones the result gains the zone axis in front of the age axis, part_cols and wts_c are in zone order and
+// the bound of a weight plane holds per zone (sas_age_participants).  The observers differ in the kinds they take -- the snapshot LAST
+// without a weight, the window means BULK with a daily weight and MEAN -- and in the accumulators of the means; every other check and its
+// wording is one.
+template <class O>
+static int sas_age_configure(rh_sas_ctx *ctx, O rh_sas_ctx::*obs, const char *name, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
+                             const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const int64_t *first_day,
+                             const int64_t *last_day, int64_t n_samples) {
+    constexpr bool MEANS = std::is_same<O, SasAgeWindowBands>::value;
     const std::string who = std::string(name) + ": ";
     const bool zonal = n_zones != 0;
     if (n_items < 0 || n_items > RH_SAS_AGE_BANDS_MAX_ITEMS)
         return sfail(ctx, RH_ERR_ARG, who + "n_items = " + std::to_string(n_items) + " (0 ... " + std::to_string(RH_SAS_AGE_BANDS_MAX_ITEMS) + ")");
-    SasAgeBands &S = ctx->age_bands;
+    O &S = ctx->*obs;
     if (!n_items) {
         SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (launches that write the old result)
         SHIPCHK(ctx, S.release());
         return RH_OK;
     }
     const int64_t n = ctx->cfg.n_cells;
-    SasAgeBands N;   // the new configuration: checked and allocated in full before the previous one is released
+    O N;   // the new configuration: checked and allocated in full before the previous one is released
     if (!items || !probs || !first_day || !last_day || (zonal && !zone)) return sfail(ctx, RH_ERR_ARG, who + "null pointer");
     if (n_probs < 1 || n_probs > RH_SAS_BANDS_MAX_PROBS)
         return sfail(ctx, RH_ERR_ARG, who + "n_probs = " + std::to_string(n_probs) + " (1 ... " + std::to_string(RH_SAS_BANDS_MAX_PROBS) + ")");
@@ -690,10 +779,18 @@ static int sas_age_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_s
         const std::string name = std::string("array ") + SAS_NAMES[a];
         if (kind < RH_SAS_SCORES_BULK || kind > RH_SAS_SCORES_LAST)
             return sfail(ctx, RH_ERR_ARG, who + "kind " + std::to_string(kind) + " of " + name + " (0: BULK, 1: MEAN, 2: LAST)");
-        if (kind != RH_SAS_SCORES_LAST)
-            return sfail(ctx, RH_ERR_ARG, who + name + " is " + (kind == RH_SAS_SCORES_BULK ? "BULK" : "MEAN") +
-                                              " (only LAST is built: a window mean of an age-resolved value needs an (n, ages) accumulator per item)");
-        if (w != -1) return sfail(ctx, RH_ERR_ARG, who + name + " has the weight id " + std::to_string(w) + " (LAST takes none: -1)");
+        if constexpr (MEANS) {
+            if (kind == RH_SAS_SCORES_LAST)
+                return sfail(ctx, RH_ERR_ARG, who + name + " is LAST (the band of a snapshot belongs to rh_sas_age_bands_configure; here BULK and MEAN)");
+            if (w < -1 || w >= SA_COUNT) return sfail(ctx, RH_ERR_ARG, who + "unknown weight id " + std::to_string(w));
+            if (int rc = sas_window_weight(ctx, who, name, w, kind)) return rc;
+            N.wgt[j] = w >= 0 ? (const double *)ctx->arr[w].get() : nullptr;
+        } else {
+            if (kind != RH_SAS_SCORES_LAST)
+                return sfail(ctx, RH_ERR_ARG, who + name + " is " + (kind == RH_SAS_SCORES_BULK ? "BULK" : "MEAN") +
+                                                  " (only LAST is built: a window mean of an age-resolved value needs an (n, ages) accumulator per item)");
+            if (w != -1) return sfail(ctx, RH_ERR_ARG, who + name + " has the weight id " + std::to_string(w) + " (LAST takes none: -1)");
+        }
         for (int q = 0; q < j; ++q)
             if (items[q].value == a) return sfail(ctx, RH_ERR_ARG, who + name + " is given twice");
         if (SAS_KIND[a] == K_MASK) return sfail(ctx, RH_ERR_ARG, who + name + " is int32 (float64 arrays only)");
@@ -713,52 +810,11 @@ static int sas_age_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_s
                                           (zonal ? std::to_string(n_zones) + " zones x " : std::string()) + std::to_string(N.ages_total) + " age classes x " +
                                           std::to_string(n_probs) + " float64 and headers of 3 int64, each within 2 GiB)");
     if (int rc = sas_check_windows(ctx, who, first_day, last_day, n_samples)) return rc;
-    std::vector<int> part_cols;          // the participating columns, ascending (per zone: in zone order, ascending within a zone) ...
-    std::vector<unsigned short> wts_c;   // ... and their weights, at the same index
-    std::vector<long long> zone_off;     // per zone: [n_zones + 1] into both
-    std::vector<int> zone_lists;         // per zone: the short zones, then the long ones
-    const auto takes_part = [&](int64_t c) { return (!zonal || zone[c] >= 0) && (!mask || mask[c]) && (!weights || weights[c]); };
-    if (zonal) {   // the zones' sizes, the bound of a weighted zone, then the stable counting sort over the participating columns
-        zone_off.assign((size_t)n_zones + 1, 0);
-        for (int64_t c = 0; c < n; ++c) {
-            if (zone[c] < -1 || zone[c] >= n_zones)
-                return sfail(ctx, RH_ERR_ARG, who + "zone[" + std::to_string(c) + "] = " + std::to_string(zone[c]) + " (-1: outside every zone, else 0 ... " +
-                                                  std::to_string(n_zones - 1) + ")");
-            if (takes_part(c)) ++zone_off[(size_t)zone[c] + 1];
-        }
-        for (int z = 0; z < n_zones && weights; ++z)
-            if (zone_off[(size_t)z + 1] > SAS_AGE_BANDS_MAX_WEIGHTED)
-                return sfail(ctx, RH_ERR_ARG, who + "zone " + std::to_string(z) + " has " + std::to_string(zone_off[(size_t)z + 1]) +
-                                                  " participating cells under a weight plane (at most " + std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) +
-                                                  ": a uint32 LDS bin holds the weights of a zone's age class; without weights any size is exact)");
-        for (int z = 0; z < n_zones; ++z)   // (short: 1 ... SAS_AGE_SHORT_ZONE cells; an empty zone is in neither list)
-            if (zone_off[(size_t)z + 1] > 0 && zone_off[(size_t)z + 1] <= SAS_AGE_SHORT_ZONE) zone_lists.push_back(z);
-        N.n_short = (int)zone_lists.size();
-        for (int z = 0; z < n_zones; ++z)
-            if (zone_off[(size_t)z + 1] > SAS_AGE_SHORT_ZONE) zone_lists.push_back(z);
-        N.n_long = (int)zone_lists.size() - N.n_short;
-        for (int z = 0; z < n_zones; ++z) zone_off[(size_t)z + 1] += zone_off[(size_t)z];
-        part_cols.resize((size_t)zone_off[(size_t)n_zones]);
-        if (weights) wts_c.resize(part_cols.size());
-        std::vector<long long> at(zone_off.begin(), zone_off.end() - 1);
-        for (int64_t c = 0; c < n; ++c)
-            if (takes_part(c)) {
-                const size_t i = (size_t)at[(size_t)zone[c]]++;
-                part_cols[i] = (int)c;
-                if (weights) wts_c[i] = weights[c];
-            }
-    } else {
-        for (int64_t c = 0; c < n; ++c)
-            if (takes_part(c)) {
-                part_cols.push_back((int)c);
-                if (weights) wts_c.push_back(weights[c]);
-            }
-    }
-    N.n_part = (int64_t)part_cols.size();
-    if (!N.n_part) return sfail(ctx, RH_ERR_ARG, who + "no cell takes part (0 of " + std::to_string(n) + " cells have mask != 0 and a weight > 0)");
-    if (!zonal && weights && N.n_part > SAS_AGE_BANDS_MAX_WEIGHTED)
-        return sfail(ctx, RH_ERR_ARG, who + std::to_string(N.n_part) + " participating cells under a weight plane (at most " +
-                                          std::to_string(SAS_AGE_BANDS_MAX_WEIGHTED) + ": a uint32 LDS bin holds an age class's weights; without weights any size is exact)");
+    SasAgeSet P;
+    if (int rc = sas_age_participants(ctx, who, zone, n_zones, mask, weights, P)) return rc;
+    N.n_part = (int64_t)P.part_cols.size();
+    N.n_short = P.n_short;
+    N.n_long = P.n_long;
     const size_t K = (size_t)n_samples, np = (size_t)n_probs, blocks = K * (size_t)N.ages_total * (zonal ? (size_t)n_zones : 1), npart = (size_t)N.n_part;
     const size_t row_b = blocks * np * sizeof(double), hdr_b = blocks * SAS_BANDS_HDR * sizeof(long long);
     const std::vector<double> nans(blocks * np, std::nan(""));
@@ -770,22 +826,28 @@ static int sas_age_bands_configure(rh_sas_ctx *ctx, const char *name, const rh_s
     SHIPCHK(ctx, N.probs.alloc(np * sizeof(double)));
     SHIPCHK(ctx, hipMemcpyAsync(N.probs, probs, np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SHIPCHK(ctx, N.part_cols.alloc(npart * sizeof(int)));
-    SHIPCHK(ctx, hipMemcpyAsync(N.part_cols, part_cols.data(), npart * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    SHIPCHK(ctx, hipMemcpyAsync(N.part_cols, P.part_cols.data(), npart * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     if (weights) {
         SHIPCHK(ctx, N.wts_c.alloc(npart * sizeof(unsigned short)));
-        SHIPCHK(ctx, hipMemcpyAsync(N.wts_c, wts_c.data(), npart * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
+        SHIPCHK(ctx, hipMemcpyAsync(N.wts_c, P.wts_c.data(), npart * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
     }
     if (zonal) {
-        SHIPCHK(ctx, N.zone_off.alloc(zone_off.size() * sizeof(long long)));
-        SHIPCHK(ctx, hipMemcpyAsync(N.zone_off, zone_off.data(), zone_off.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-        SHIPCHK(ctx, N.zone_lists.alloc(zone_lists.size() * sizeof(int)));   // (never empty: a cell takes part)
-        SHIPCHK(ctx, hipMemcpyAsync(N.zone_lists, zone_lists.data(), zone_lists.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        SHIPCHK(ctx, N.zone_off.alloc(P.zone_off.size() * sizeof(long long)));
+        SHIPCHK(ctx, hipMemcpyAsync(N.zone_off, P.zone_off.data(), P.zone_off.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        SHIPCHK(ctx, N.zone_lists.alloc(P.zone_lists.size() * sizeof(int)));   // (never empty: a cell takes part)
+        SHIPCHK(ctx, hipMemcpyAsync(N.zone_lists, P.zone_lists.data(), P.zone_lists.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if constexpr (MEANS) {   // num and den of every item, 16 B per participating column and age class, zero
+        const size_t acc_b = 2 * npart * (size_t)N.ages_total * sizeof(double);
+        SHIPCHK(ctx, N.acc.alloc(acc_b));
+        SHIPCHK(ctx, hipMemsetAsync(N.acc, 0, acc_b, ctx->stream));
+        for (int j = 1; j < n_items; ++j) N.acc_off[j] = N.acc_off[j - 1] + 2 * npart * (size_t)N.width[j - 1];
     }
     SHIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the sources are the caller's and locals; launches that write the old result)
     N.n_items = n_items;
     N.n_probs = n_probs;
     N.zones = zonal ? n_zones : 0;
-    N.win.set(first_day, last_day, n_samples, false);
+    N.win.set(first_day, last_day, n_samples, MEANS);
     SHIPCHK(ctx, S.release());
     S = std::move(N);
     return RH_OK;
@@ -795,18 +857,25 @@ int rh_sas_age_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items,
                                const unsigned char *mask, const uint16_t *weights, const int64_t *first_day, const int64_t *last_day,
                                int64_t n_samples) {
     if (!ctx) return RH_ERR_ARG;
-    return sas_age_bands_configure(ctx, "rh_sas_age_bands_configure", items, n_items, probs, n_probs, nullptr, 0, mask, weights, first_day, last_day, n_samples);
+    return sas_age_configure(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_configure", items, n_items, probs, n_probs, nullptr, 0, mask, weights, first_day,
+                             last_day, n_samples);
+}
+
+// n_zones within 1 ... RH_SAS_AGE_BANDS_MAX_ZONES, for the configure call `name` that was given a zone map
+static int sas_age_check_zones(rh_sas_ctx *ctx, const char *name, int n_zones) {
+    if (n_zones < 1 || n_zones > RH_SAS_AGE_BANDS_MAX_ZONES)
+        return sfail(ctx, RH_ERR_ARG, std::string(name) + ": n_zones = " + std::to_string(n_zones) + " (1 ... " + std::to_string(RH_SAS_AGE_BANDS_MAX_ZONES) + ")");
+    return RH_OK;
 }
 
 int rh_sas_age_bands_configure_zonal(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs,
                                      const int32_t *zone, int n_zones, const unsigned char *mask, const uint16_t *weights, const int64_t *first_day,
                                      const int64_t *last_day, int64_t n_samples) {
     if (!ctx) return RH_ERR_ARG;
-    if (n_items && (n_zones < 1 || n_zones > RH_SAS_AGE_BANDS_MAX_ZONES))
-        return sfail(ctx, RH_ERR_ARG, "rh_sas_age_bands_configure_zonal: n_zones = " + std::to_string(n_zones) + " (1 ... " +
-                                          std::to_string(RH_SAS_AGE_BANDS_MAX_ZONES) + ")");
-    return sas_age_bands_configure(ctx, "rh_sas_age_bands_configure_zonal", items, n_items, probs, n_probs, zone, n_items ? n_zones : 0, mask, weights,
-                                   first_day, last_day, n_samples);
+    if (n_items)
+        if (int rc = sas_age_check_zones(ctx, "rh_sas_age_bands_configure_zonal", n_zones)) return rc;
+    return sas_age_configure(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_configure_zonal", items, n_items, probs, n_probs, zone, n_items ? n_zones : 0, mask,
+                             weights, first_day, last_day, n_samples);
 }
 
 int rh_sas_age_bands_record(rh_sas_ctx *ctx, int64_t day) {
@@ -822,11 +891,10 @@ int rh_sas_age_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total) {
     return RH_OK;
 }
 
-// What both reads of the bands by age copy out, for the function `who` of bands that are on: `nb` blocks per age class; `lead` names the axes
-// in front of a block's values in the size check's text.  Synchronises.
-static int sas_age_bands_read(rh_sas_ctx *ctx, const char *who, size_t nb, const char *lead, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes,
-                              unsigned char *closed, size_t closed_bytes, int64_t *days_recorded) {
-    const SasAgeBands &S = ctx->age_bands;
+// What the reads of an observer by age `S` that is on copy out, for the function `who`: `nb` blocks per age class; `lead` names the axes in
+// front of a block's values in the size check's text.  Synchronises.
+static int sas_age_bands_read(rh_sas_ctx *ctx, const SasAgeBands &S, const char *who, size_t nb, const char *lead, double *rows, size_t row_bytes, int64_t *hdr,
+                              size_t hdr_bytes, unsigned char *closed, size_t closed_bytes, int64_t *days_recorded) {
     const size_t K = S.win.closed.size(), blocks = K * (size_t)S.ages_total * nb;
     if (!rows || !hdr || !closed || row_bytes != blocks * (size_t)S.n_probs * sizeof(double) || hdr_bytes != blocks * SAS_BANDS_HDR * sizeof(int64_t) ||
         closed_bytes != K)
@@ -843,13 +911,47 @@ int rh_sas_age_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64
     if (int rc = sas_on(ctx, &rh_sas_ctx::age_bands, "rh_sas_age_bands_read")) return rc;
     if (ctx->age_bands.zones)
         return sfail(ctx, RH_ERR_STATE, "rh_sas_age_bands_read: the bands by age are configured per zone (read them with rh_sas_age_bands_zonal_read)");
-    return sas_age_bands_read(ctx, "rh_sas_age_bands_read", 1, "n_samples x ages_total", rows, row_bytes, hdr, hdr_bytes, closed, closed_bytes, days_recorded);
+    return sas_age_bands_read(ctx, ctx->age_bands, "rh_sas_age_bands_read", 1, "n_samples x ages_total", rows, row_bytes, hdr, hdr_bytes, closed, closed_bytes,
+                              days_recorded);
 }
 
 int rh_sas_age_bands_zonal_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed, size_t closed_bytes,
                                 int64_t *days_recorded) {
     if (!ctx) return RH_ERR_ARG;
     if (int rc = sas_on(ctx, ctx->age_bands.on() && ctx->age_bands.zones != 0, "rh_sas_age_bands_zonal_read", "rh_sas_age_bands_configure_zonal")) return rc;
-    return sas_age_bands_read(ctx, "rh_sas_age_bands_zonal_read", (size_t)ctx->age_bands.zones, "n_samples x n_zones x ages_total", rows, row_bytes, hdr,
-                              hdr_bytes, closed, closed_bytes, days_recorded);
+    return sas_age_bands_read(ctx, ctx->age_bands, "rh_sas_age_bands_zonal_read", (size_t)ctx->age_bands.zones, "n_samples x n_zones x ages_total", rows, row_bytes,
+                              hdr, hdr_bytes, closed, closed_bytes, days_recorded);
+}
+
+// ---- window means of the bands by age (include/roger_hip_sas.h; the kernels and the rule: rh_sas_age_bands.h) ----
+int rh_sas_age_window_bands_configure(rh_sas_ctx *ctx, const rh_sas_scores_item *items, int n_items, const double *probs, int n_probs, const int32_t *zone,
+                                      int n_zones, const unsigned char *mask, const uint16_t *weights, const int64_t *first_day, const int64_t *last_day,
+                                      int64_t n_samples) {
+    const char *name = "rh_sas_age_window_bands_configure";
+    if (!ctx) return RH_ERR_ARG;
+    if (n_items && (zone || n_zones))   // (zone == NULL && n_zones == 0: the plain form)
+        if (int rc = sas_age_check_zones(ctx, name, n_zones)) return rc;
+    return sas_age_configure(ctx, &rh_sas_ctx::age_window_bands, name, items, n_items, probs, n_probs, zone, n_items ? n_zones : 0, mask, weights, first_day,
+                             last_day, n_samples);
+}
+
+int rh_sas_age_window_bands_record(rh_sas_ctx *ctx, int64_t day) {
+    if (int rc = sas_on(ctx, &rh_sas_ctx::age_window_bands, "rh_sas_age_window_bands_record")) return rc;
+    if (day < 0) return sfail(ctx, RH_ERR_ARG, "rh_sas_age_window_bands_record: day = " + std::to_string(day) + " (the row of the daily inputs, >= 0)");
+    return sas_age_window_bands_enqueue(ctx, day);
+}
+
+int rh_sas_age_window_bands_row_elems(const rh_sas_ctx *ctx, int64_t *ages_total) {
+    if (int rc = sas_on(const_cast<rh_sas_ctx *>(ctx), &rh_sas_ctx::age_window_bands, "rh_sas_age_window_bands_row_elems")) return rc;
+    if (!ages_total) return RH_ERR_ARG;
+    *ages_total = ctx->age_window_bands.ages_total;
+    return RH_OK;
+}
+
+int rh_sas_age_window_bands_read(rh_sas_ctx *ctx, double *rows, size_t row_bytes, int64_t *hdr, size_t hdr_bytes, unsigned char *closed, size_t closed_bytes,
+                                 int64_t *days_recorded) {
+    if (int rc = sas_on(ctx, &rh_sas_ctx::age_window_bands, "rh_sas_age_window_bands_read")) return rc;
+    const SasAgeWindowBands &S = ctx->age_window_bands;
+    return sas_age_bands_read(ctx, S, "rh_sas_age_window_bands_read", S.zones ? (size_t)S.zones : 1, S.zones ? "n_samples x n_zones x ages_total" : "n_samples x ages_total",
+                              rows, row_bytes, hdr, hdr_bytes, closed, closed_bytes, days_recorded);
 }

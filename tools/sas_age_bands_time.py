@@ -26,7 +26,14 @@ zones of a closing day each (8 and 64 zones and the 90 % map: every zone; 1024 z
 with -DSAS_AGE_SHORT_ZONE=0 (tools/build_variant.py nosmall --unit rh_sas -DSAS_AGE_SHORT_ZONE=0) adds the 1024 zones with every zone
 through the six passes: the price of the second path as a measured pair.
 
-    python3 tools/sas_age_bands_time.py [run] [alone] [off] [zonal]   (default: run alone off; `off` is skipped without ROGER_HIP_PARENT)"""
+WINDOW MEANS (`window`; not part of the default).  rh_sas_age_window_bands_*, 1 item (tt_q_ss BULK by q_ss, 1000 age classes), no weights,
+every column takes part.  Stand-alone (record back to back on uploaded values): an ACCUMULATING day (k_sas_age_acc on a day that is neither
+a window's first nor its last; 8 B source + 16 B read + 16 B written per element, reported as bytes per second too) and a CLOSING day of
+one-day windows (k_sas_age_keys_window and the selection).  Behind the day's kernel, rh_sas_run_days over 14 days: nothing configured, the
+snapshot observer with 14 windows, the window means with ONE window of 14 days and with 14 windows of one day.  Every figure a process of
+its own, the minimum of three runs after a warm-up run.
+
+    python3 tools/sas_age_bands_time.py [run] [alone] [off] [zonal] [window]   (default: run alone off; `off` is skipped without ROGER_HIP_PARENT)"""
 import json
 import os
 import statistics
@@ -253,6 +260,79 @@ def zonal_cost():
     return lines
 
 
+WINDOW_ITEM = [("tt_q_ss", "q_ss", "bulk")]
+WINDOW_RUNS = [("none", "nothing configured"), ("snapshot", "the snapshot observer, 1 item, 14 windows of one day"),
+               ("w1", "the window means, 1 item, ONE window of 14 days (13 accumulating days, 1 closing day)"),
+               ("w14", "the window means, 1 item, 14 windows of one day (14 closing days)")]
+
+
+def window_child(mode, variant):
+    """ms per day of one variant of the window means: `alone` acc / close (record back to back) or `run` (behind the day's kernel)."""
+    import numpy as np
+
+    from roger_amd import sas as rsas
+    from roger_amd._native import SasContext
+
+    n, ages = RUN_N, RUN_AGES
+    one_long, every_day = (np.array([0]), np.array([RUN_DAYS - 1])), (np.arange(RUN_DAYS),) * 2
+    if mode == "run":
+        daily = rsas.synthetic_daily_inputs(n, RUN_DAYS, seed=42)
+        ctx = rsas.create_sas(n, ages, RUN_SUBSTEPS, 90.0, 260.0, daily=daily, keep_distributions=True)
+        best = []
+        for k in range(4):
+            if variant == "snapshot":
+                ctx.age_bands_configure(["tt_q_ss"], PROBS, every_day)
+            elif variant != "none":
+                ctx.age_window_bands_configure(WINDOW_ITEM, PROBS, one_long if variant == "w1" else every_day)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ctx.run_days(0, RUN_DAYS)
+            ctx.sync()
+            best.append((time.perf_counter() - t0) / RUN_DAYS * 1e3)
+        if variant in ("w1", "w14"):
+            rows, hdr, closed, days = ctx.age_window_bands_read()
+            assert closed.all() and days == RUN_DAYS and hdr["tt_q_ss"][..., 0].any()
+        ctx.close()
+        print(json.dumps(min(best[1:])))
+        return
+    rng = np.random.default_rng(7)
+    ctx = SasContext(n, ages, keep_distributions=True)
+    ctx.upload("tt_q_ss", rng.random(ctx.shape("tt_q_ss")))
+    ctx.upload("q_ss", rng.random(ctx.shape("q_ss")) + 0.1)
+    days = R * 4 + 2
+    # acc: one window that the days below never close; close: every day a window of its own
+    ctx.age_window_bands_configure(WINDOW_ITEM, PROBS, (np.array([0]), np.array([days])) if variant == "acc" else (np.arange(days),) * 2)
+    ctx.age_window_bands_record(0)   # (acc: the window's first day, which reads no accumulator)
+    ms = []
+    for k in range(4):
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(R):
+            ctx.age_window_bands_record(0)
+        ctx.sync()
+        ms.append((time.perf_counter() - t0) / R * 1e3)
+    ctx.close()
+    print(json.dumps(min(ms[1:])))
+
+
+def window_cost():
+    def child(mode, variant):
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--window-child", mode, variant], check=True, capture_output=True, text=True,
+                             timeout=280).stdout
+        return float(json.loads(out.strip().splitlines()[-1]))
+
+    elems = RUN_N * RUN_AGES
+    acc, close = child("alone", "acc"), child("alone", "close")
+    lines = [f"    window means: {RUN_N} columns x {RUN_AGES} ages, 1 item (tt_q_ss BULK by q_ss, {RUN_AGES} age classes), 3 probabilities, no weights, ms per "
+             "day (minimum of 3 runs, a process each)",
+             f"    stand-alone, an accumulating day (k_sas_age_acc): {acc:.4f} ms; {elems} elements x 40 B = {elems * 40 / 1e9:.2f} GB, {elems * 40 / acc / 1e9:.3f} TB/s",
+             f"    stand-alone, a closing day of a one-day window (k_sas_age_keys_window, k_sas_age_bands): {close:.4f} ms"]
+    got = {v: child("run", v) for v, _ in WINDOW_RUNS}
+    for v, text in WINDOW_RUNS:
+        lines.append(f"    behind the day's kernel over {RUN_DAYS} days, {text}: {got[v]:.4f}" + ("" if v == "none" else f" ({got[v] - got['none']:+.4f} against nothing configured)"))
+    return lines
+
+
 def off_cost():
     parent = os.environ.get("ROGER_HIP_PARENT")
     if not parent:
@@ -277,6 +357,9 @@ if __name__ == "__main__":
     if sys.argv[1:2] == ["--zonal-child"]:
         zonal_child(sys.argv[2], sys.argv[3])
         sys.exit(0)
+    if sys.argv[1:2] == ["--window-child"]:
+        window_child(sys.argv[2], sys.argv[3])
+        sys.exit(0)
     what = sys.argv[1:] or ["run", "alone", "off"]
     print("transport bands by age (rh_sas_age_bands_*), measured once on one MI355X", flush=True)
     if "run" in what:
@@ -287,3 +370,5 @@ if __name__ == "__main__":
         print("\n".join(off_cost()), flush=True)
     if "zonal" in what:
         print("\n".join(zonal_cost()), flush=True)
+    if "window" in what:
+        print("\n".join(window_cost()), flush=True)
